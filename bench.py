@@ -2,7 +2,7 @@
 """bench.py — the reference's headline metric on MI355X: shaded Mpixels/s of the 4K deferred frame (BuildHZB +
 CullIndirectArgs + DeferredLighting/Sky) on the Sponza constants, with % of HBM roofline for the dominant kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one frame of BASELINE.json configs[2] on synthetic inputs already resident in HBM:
@@ -84,7 +84,13 @@ def parse():
                          "last exit with the constant 100 MHz clock): per-kernel spans and the gaps between consecutive launches, without a profiler")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the 1M-instance cull and iid side measurements")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed frame computed (HDR frame, HZB chain, the cull's command words and "
+                         "visible list) to DIR/<name>.npy as float32 / float64, at most 64 MB in all (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _self_launch(args) -> int:
@@ -386,6 +392,11 @@ def main():
     dt = time.perf_counter() - t0
     if not args.python_gc:
         gc.enable()
+    # the last timed frame's outputs, read back before anything else runs on its buffers (the untimed passes below render into them)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = sets[(args.warmup + args.steps - 1) % ring]
+        dumped = dump_outputs(Path(args.dump_outputs), last["hdr_full"], last.get("ldr_full"), hzb, d_args, d_vis, d_cnt)
     timeline = None
     if tl is not None:
         hp.debug_timeline(None)
@@ -555,11 +566,60 @@ def main():
         result["timeline"] = timeline
     if gc_on is not None:
         result["with_python_gc_on"] = gc_on
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if rank == 0:
         result["setup_seconds"] = round(gen_s, 1)
         print(json.dumps(result))
     if N > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_FRAME_BYTES = 32 << 20  # ... of which the frame images (HDR, and LDR with --gather-ldr)
+DUMP_HZB_BYTES = 24 << 20    # ... and the HZB chain (with its texel index where it is sampled)
+DUMP_SEED = 20240607         # the fixed seed of every sample taken
+
+
+def dump_outputs(out_dir: Path, hdr_full, ldr_full, hzb, d_args, d_vis, d_cnt) -> dict:
+    """--dump-outputs: what the last timed frame computed, as a caller of the frame receives it, written to out_dir/<name>.npy:
+      hdr.npy              float32 [rows, W, 4]  the RGBA16F frame, decoded
+      ldr.npy              float32 [rows, W, 4]  the tonemapped RGBA8 frame, one value per channel (0..255; --gather-ldr only)
+      frame_rows.npy       float64 [rows]        the frame rows those are: all of them, or a fixed seeded sample of whole rows where
+                                                 the frame would not fit in DUMP_FRAME_BYTES (a 4K frame: 546 of 2160 rows)
+      hzb.npy              float32 [texels]      the HZB chain (all mips, packed as the layout packs them); where it would not fit in
+      hzb_index.npy        float64 [texels]      DUMP_HZB_BYTES, a fixed seeded sample of texels and their offsets in the chain
+      indirect_args.npy    float64 [n, 16]       the command words (uint32 values; InstanceCount is word 11)
+      visible_indices.npy  float64 [count]       the compacted list of visible instances
+      visible_count.npy    float64 [1]
+    N > 1: rank 0's view, i.e. the gathered frame (with --gather-ldr only the LDR frame is gathered: the HDR one holds rank 0's band)
+    and the HZB, with rank 0's share of the cull. Called behind the fence of the timed region. Returns {name: shape}."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    H, W = int(hdr_full.shape[0]), int(hdr_full.shape[1])
+    row_bytes = W * 4 * 4 * (2 if ldr_full is not None else 1)
+    rows = np.arange(H)
+    if H * row_bytes > DUMP_FRAME_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(H, DUMP_FRAME_BYTES // row_bytes, replace=False))
+    arrays = {"hdr": hdr_full.cpu().numpy().view(np.float16)[rows].astype(np.float32)}
+    if ldr_full is not None:
+        arrays["ldr"] = ldr_full.cpu().numpy().view(np.uint8).reshape(H, W, 4)[rows].astype(np.float32)
+    arrays["frame_rows"] = rows.astype(np.float64)
+    h = hzb.cpu().numpy()
+    if h.nbytes > DUMP_HZB_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(h.size, DUMP_HZB_BYTES // (4 + 8), replace=False))
+        arrays["hzb"], arrays["hzb_index"] = h[idx], idx.astype(np.float64)
+    else:
+        arrays["hzb"] = h
+    count = int(d_cnt.cpu().numpy().view(np.uint32)[0])
+    if d_args is not None:
+        arrays["indirect_args"] = d_args.cpu().numpy().view(np.uint32).astype(np.float64)
+    arrays["visible_indices"] = d_vis.cpu().numpy().view(np.uint32)[:count].astype(np.float64)
+    arrays["visible_count"] = np.array([count], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs to dump are {total} B, over {DUMP_MAX_BYTES}"
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def stream_ceiling_leg(hp, torch, nbytes, dev):
