@@ -55,6 +55,12 @@ typedef struct ur_frame_resources {
 #define UR_FRAME_HZB_WITH_LIGHTING 0x4000u /* the WHOLE Build HZB chain rides along with the Lighting launch (ur_defer_hzb_tail(ctx, 2)): its 128x32 pieces are walked by one wave of every lighting workgroup, its tail by an extra workgroup that waits for them; two launches per frame (cull, lighting). Ignored with ASYNC_COMPUTE */
 #define UR_FRAME_TIME_LIGHTING_KERNEL 0x10000u /* time the Lighting pass by a HIP event pair carried on its kernel dispatch (ur_time_next_lighting): from the end of what precedes the kernel to the kernel's end, what rocprofv3's kernel trace reports for the dispatch; no event record behind the kernel; read with ur_frame_lighting_times() */
 #define UR_FRAME_HZB_SHARD 0x20000u /* several ranks (ur_frame_create's world_size > 1): Build HZB builds only this rank's 128x32 pieces of mips 0..4 (ur_build_hzb_band; riding the Lighting launch with HZB_WITH_LIGHTING) and leaves the exchange of the slices and the tail (ur_build_hzb_tail) to the caller, who holds the communicator. One rank: the whole chain as usual */
+/* The rest of the reference's post chain after Tonemap's input (DeferredRenderer.cpp:1363-1573). Each needs UR_FRAME_TONEMAP and a
+ * tonemap_band (else UR_EINVAL), and the WHOLE frame in one call: rows == height, else UR_EUNSUPPORTED (a sharded caller gathers
+ * the HDR frame first and calls ur_auto_exposure / ur_tonemap_cas itself). Resources and parameters: ur_frame_set_post. */
+#define UR_FRAME_AUTO_EXPOSURE 0x40000u /* "AutoExposure" pass before Tonemap: Lighting -> luminance[W] (history luminance[1-W]); Tonemap then applies 2^EV */
+#define UR_FRAME_CAS 0x80000u /* "CAS" pass after Tonemap: Tonemap writes tonemap_scratch, CAS sharpens it into tonemap_band */
+#define UR_FRAME_FUSE_TONEMAP_CAS 0x100000u /* with CAS: Tonemap runs ur_tonemap_cas straight into tonemap_band (same bytes, no scratch); the CAS pass is then culled */
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -75,6 +81,20 @@ uint32_t ur_frame_lighting_times(ur_frame* f, float* out_ms, uint32_t cap);
 uint32_t ur_frame_lighting_times_ex(ur_frame* f, float* out_ms, float* out_record_ms, uint32_t cap);
 int ur_frame_hzb_ready(const ur_frame* f);
 void ur_frame_reset_hzb(ur_frame* f);
+/* Post-chain resources and parameters of the frames that follow (the reference's RendererConfig values in brackets). Without this
+ * call: no luminance textures, no scratch, tonemap 0.9 / 2.2, CAS sharpness 0.5. The pointers must stay valid while frames use them. */
+typedef struct ur_frame_post {
+    float* luminance[2];        /* device, 1 float each: LuminanceA / B (R32_FLOAT 1x1, CreateLuminanceResources); needed by AUTO_EXPOSURE */
+    uint32_t* tonemap_scratch;  /* device, width x rows R8G8B8A8 "TonemapOutput": Tonemap's output when CAS runs as its own pass; unused when fused */
+    float delta_time;           /* RenderFrame's DeltaTime (seconds) */
+    float tonemap_exposure, tonemap_gamma;                      /* [0.9, 2.2] */
+    float ae_key, ae_min, ae_max, ae_speed_up, ae_speed_down;   /* [0.3, 0.1, 5, 3, 1] */
+    float cas_sharpness;                                        /* [0.5] */
+} ur_frame_post;
+int ur_frame_set_post(ur_frame* f, const ur_frame_post* post);
+/* The luminance history becomes invalid (like ur_frame_reset_hzb): the next AutoExposure pass runs with UseHistory = 0. The write
+ * index is kept: a frame whose AutoExposure ran writes luminance[W], then W flips; any other frame invalidates the history. */
+void ur_frame_reset_post(ur_frame* f);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

@@ -346,6 +346,48 @@ int ur_tonemap(ur_ctx* ctx, const ur_tonemap_constants* constants, const ur_half
 int ur_temporal_aa(ur_ctx* ctx, const ur_half4* current_frame, const ur_half4* history_band, ur_half4* output_band, float history_weight,
                    uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
 
+/* ---- AutoExposure and CAS: the rest of the reference's post chain (DeferredRenderer.cpp:1363-1573) ------------ */
+
+/* AutoExposureConstants (Shaders/AutoExposure.hlsl:1-12), 36 bytes */
+typedef struct ur_auto_exposure_constants {
+    float InputSize[2];
+    float DeltaTime;
+    float AdaptationSpeedUp;
+    float AdaptationSpeedDown;
+    uint32_t UseHistory;
+    float AutoExposureKey;
+    float AutoExposureMin;
+    float AutoExposureMax;
+} ur_auto_exposure_constants;
+
+/* CasParams (Shaders/Cas.hlsl:44-49), 16 bytes */
+typedef struct ur_cas_constants {
+    float TexelDelta[2];
+    float Sharpness;
+    float Padding;
+} ur_cas_constants;
+
+/* AutoExposure.hlsl:24-93, one workgroup: 16 x 16 bilinear taps of the full w x h RGBA16F frame (mip 0, clamp; the weights
+ * in fp32 from t = uv * size - 0.5), log2 of their luminance, summed in a fixed order (the same input gives the same bits),
+ * target EV clamped to [log2 AutoExposureMin, log2 AutoExposureMax] and, when UseHistory != 0, adapted from prev_ev[0].
+ * Writes one float, out_ev[0] (the LogAverageLuminance texel Tonemap reads as exposure_ev).
+ * InputSize must be ((float)w, (float)h). prev_ev may be null iff UseHistory == 0; it may equal out_ev. */
+int ur_auto_exposure(ur_ctx* ctx, const ur_auto_exposure_constants* constants, const ur_half4* hdr_full, uint32_t w, uint32_t h,
+                     const float* prev_ev, float* out_ev);
+
+/* Cas.hlsl:67-99 (the reference's own amp / w formula) over rows [row0,row0+rows) of a w x h R8G8B8A8_UNORM image:
+ * ldr_full is the FULL image (a band's edge rows need the rows around it), out_band is band-local. The taps are the pixel
+ * and its 4-neighbours, clamped at the image edges: what the pass samples with TexelDelta = (1/w, 1/h) at pixel centres,
+ * the only value the reference sets (DeferredRenderer.cpp:1533); any other TexelDelta returns UR_EUNSUPPORTED.
+ * Output: saturate, rounded like ur_tonemap, A = 255. 8 B/pixel. */
+int ur_cas(ur_ctx* ctx, const ur_cas_constants* constants, const uint32_t* ldr_full, uint32_t* out_band,
+           uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+
+/* ur_tonemap of the full frame followed by ur_cas of the band in ONE launch, byte for byte: the tonemapped RGBA8 image is
+ * never written (HDR in, final LDR out: 12 B/pixel instead of 20). hdr_full: the FULL w x h RGBA16F frame. */
+int ur_tonemap_cas(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const ur_half4* hdr_full,
+                   const float* exposure_ev, uint32_t* out_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+
 /* ---- multi-GPU: gather the row bands of the HDR frame ------------------------------------------ */
 
 /* comm: an ncclComm_t (RCCL). hdr_full: device, w*h half4 on every rank; rank r has already written

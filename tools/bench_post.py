@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Timing of the post-chain launches on one GPU (development aid; bench.py is the contract benchmark).
+
+    python tools/bench_post.py [--sizes 1080p,4k,8k] [--iters 200] [--batches 7] [--json out.jsonl]
+
+For each frame size: ur_tonemap, ur_cas, ur_tonemap + ur_cas back to back, ur_tonemap_cas and ur_auto_exposure, each timed with
+one device-event pair around a batch of back-to-back launches (per-launch time = batch time / launches), after a warm-up, over
+enough rotating buffer sets that a batch's bytes exceed the 256 MiB memory-side cache. Bytes per pixel: Tonemap 12
+(8 read + 4 written), CAS 8 (4 + 4), the pair 20, fused 12 (8 + 4). Before any time of a size is printed, the fused output is
+checked byte-equal to the two launches. The fraction is bytes / time over 8 TB/s (the HBM peak of MI355X).
+The byte counts above are what must cross HBM at least. The CAS strip kernels (csrc/post.hip) also load the two halo rows of every
+STRIP_ROWS-row strip that the neighbouring strips load too, so they issue more: CAS 4 * 10 / 8 + 4 = 9 B/pixel, fused 8 * 10 / 8 + 4 = 14;
+whether those repeated rows come from L2 / the memory-side cache or from HBM is not measured. Both figures are printed.
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160), "8k": (7680, 4320)}
+PEAK_BPS = 8e12
+STRIP_ROWS = 8  # output rows per wave of csrc/post.hip's strip kernels (kRows): kRows + 2 input rows are loaded per strip
+CACHE_BYTES = 256 << 20
+
+
+def time_batches(torch, fn, nsets, iters, batches, warm=10):
+    for k in range(warm):
+        fn(k % nsets)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(batches):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for k in range(iters):
+            fn(k % nsets)
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1e3 / iters)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1080p,4k,8k")
+    ap.add_argument("--iters", type=int, default=200, help="launches per timed batch")
+    ap.add_argument("--batches", type=int, default=7)
+    ap.add_argument("--sharpness", type=float, default=0.5)
+    ap.add_argument("--json", default="", help="also append one JSON line per measurement to this file")
+    a = ap.parse_args()
+    import torch
+    from unclerenderer_amd.hotpath import HotPath
+    assert torch.cuda.is_available(), "bench_post needs a GPU"
+    hp = HotPath(0)
+    rows_out = []
+    for name in a.sizes.split(","):
+        w, h = SIZES[name]
+        px = w * h
+        set_bytes = px * (8 + 4 + 4 + 4)
+        nsets = max(2, -(-3 * CACHE_BYTES // set_bytes))
+        g = torch.Generator(device="cuda").manual_seed(1)
+        hdr = [(torch.rand((h, w, 4), device="cuda", generator=g) * 3.0).half() for _ in range(nsets)]
+        ldr = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(nsets)]
+        out = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(nsets)]
+        fused = [torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(nsets)]
+        ev = torch.zeros(1, device="cuda")
+        hp.auto_exposure(hdr[0], ev, w, h)
+        kw = dict(exposure=0.9, gamma=2.2, exposure_ev=ev)
+        # the fused launch must give the two launches' bytes at this size
+        hp.tonemap(hdr[0], ldr[0], w, h, **kw)
+        hp.cas(ldr[0], out[0], w, h, sharpness=a.sharpness)
+        hp.tonemap_cas(hdr[0], fused[0], w, h, sharpness=a.sharpness, **kw)
+        torch.cuda.synchronize()
+        assert torch.equal(out[0], fused[0]), f"{name}: ur_tonemap_cas differs from ur_tonemap + ur_cas"
+
+        def two(i):
+            hp.tonemap(hdr[i], ldr[i], w, h, **kw)
+            hp.cas(ldr[i], out[i], w, h, sharpness=a.sharpness)
+
+        halo = (STRIP_ROWS + 2) / STRIP_ROWS
+        # (label, DRAM-floor bytes per pixel, bytes per pixel the launch issues, launch)
+        cases = [
+            ("ur_tonemap", 12, 12, lambda i: hp.tonemap(hdr[i], ldr[i], w, h, **kw)),
+            ("ur_cas", 8, 4 * halo + 4, lambda i: hp.cas(ldr[i], out[i], w, h, sharpness=a.sharpness)),
+            ("ur_tonemap+ur_cas", 20, 12 + 4 * halo + 4, two),
+            ("ur_tonemap_cas", 12, 8 * halo + 4, lambda i: hp.tonemap_cas(hdr[i], fused[i], w, h, sharpness=a.sharpness, **kw)),
+            ("ur_auto_exposure", 0, 0, lambda i: hp.auto_exposure(hdr[i], ev, w, h)),
+        ]
+        for label, bpp, issued, fn in cases:
+            t = time_batches(torch, fn, nsets, a.iters, a.batches)
+            med = float(np.median(t))
+            r = {"size": name, "w": w, "h": h, "op": label, "bytes": px * bpp, "us_median": round(med, 2), "us_min": round(min(t), 2),
+                 "us_max": round(max(t), 2), "frac_8TBps": round(px * bpp / (med * 1e-6) / PEAK_BPS, 3) if bpp else None,
+                 "issued_bytes": int(px * issued), "issued_frac_8TBps": round(px * issued / (med * 1e-6) / PEAK_BPS, 3) if bpp else None, "sets": nsets}
+            rows_out.append(r)
+            frac = f"{r['frac_8TBps']:.3f}" if bpp else "  -  "
+            ifrac = f"{r['issued_frac_8TBps']:.3f}" if bpp else "  -  "
+            print(f"{name:>5} {label:<18} {px * bpp / 1e6:8.1f} MB  {med:8.2f} us  [{min(t):.2f}, {max(t):.2f}]  {frac} of 8 TB/s"
+                  f"  (issued {px * issued / 1e6:6.1f} MB: {ifrac})", flush=True)
+        del hdr, ldr, out, fused
+        torch.cuda.empty_cache()
+    if a.json:
+        with open(a.json, "a") as f:
+            for r in rows_out:
+                f.write(json.dumps(r) + "\n")
+    hp.close()
+
+
+if __name__ == "__main__":
+    main()

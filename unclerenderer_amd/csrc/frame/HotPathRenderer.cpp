@@ -9,10 +9,14 @@
 #include <sstream>
 
 #include "../../../include/ur_frame.h"
+#include "../ur_internal.h"
 
 int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
                                   const FHotPathOptions& Options)
 {
+    // Every call must reach the bookkeeping after Graph.Execute at the end: it hands the luminance history to the next frame
+    // (valid and flipped after an AutoExposure pass that ran, invalid after any other frame, :1612-1620). Errors of passes are
+    // collected in PassError rather than returned early; an early return added above Execute must do that bookkeeping too.
     PassError = UR_OK;
     FRenderGraph Graph;
     Graph.SetDevice(Device);
@@ -164,30 +168,119 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
 
-    // ---- Tonemap (DeferredRenderer.cpp:1449-1513 with TAA, auto exposure and CAS off): Lighting -> LDR band --------------
+    // ---- AutoExposure -> Tonemap -> CAS (DeferredRenderer.cpp:1363-1573; TemporalAA left out, see HotPathRenderer.h) ------------
+    // Without AutoExposure and CAS this is the Tonemap pass alone, Lighting -> LDR band, as before they existed.
+    const bool bAutoExposure = Options.bTonemap && Res.TonemapBand && Options.bAutoExposure;
+    const bool bCas = Options.bTonemap && Res.TonemapBand && Options.bCas;
+    const bool bFuseCas = bCas && Options.bFuseTonemapCas;
+    const uint32 WriteIndex = LuminanceWriteIndex;
+    FRGResourceHandle LuminanceHandles[2];
+    if (bAutoExposure) {
+        LuminanceHandles[0] = Graph.ImportTexture("LuminanceA", Res.Luminance[0], &Res.LuminanceStates[0], {1, 1, RG_FORMAT_R32_FLOAT});
+        LuminanceHandles[1] = Graph.ImportTexture("LuminanceB", Res.Luminance[1], &Res.LuminanceStates[1], {1, 1, RG_FORMAT_R32_FLOAT});
+    }
+
+    struct FAutoExposurePassData
+    {
+        bool bEnabled = false;
+        ur_auto_exposure_constants K = {};
+        uint32 ReadIndex = 0, WriteIndex = 0;
+    };
+    if (bAutoExposure) {
+        Graph.AddPass<FAutoExposurePassData>("AutoExposure", [&](FAutoExposurePassData& Data, FRGPassBuilder& Builder)
+        {
+            Data.bEnabled = true;
+            Data.ReadIndex = 1u - WriteIndex;
+            Data.WriteIndex = WriteIndex;
+            Data.K.InputSize[0] = static_cast<float>(Res.Width);
+            Data.K.InputSize[1] = static_cast<float>(Res.Height);
+            Data.K.DeltaTime = Constants.DeltaTime;
+            Data.K.AdaptationSpeedUp = Constants.AutoExposureSpeedUp;
+            Data.K.AdaptationSpeedDown = Constants.AutoExposureSpeedDown;
+            Data.K.UseHistory = bLuminanceHistoryValid ? 1u : 0u;
+            Data.K.AutoExposureKey = Constants.AutoExposureKey;
+            Data.K.AutoExposureMin = Constants.AutoExposureMin;
+            Data.K.AutoExposureMax = Constants.AutoExposureMax;
+            Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Builder.ReadTexture(LuminanceHandles[Data.ReadIndex], RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Builder.WriteTexture(LuminanceHandles[Data.WriteIndex], RG_STATE_UNORDERED_ACCESS);
+        }, [this, &Res](const FAutoExposurePassData& Data, FHIPCommandContext& Cmd)
+        {
+            const int rc = ur_auto_exposure(Cmd.GetContext(), &Data.K, Res.LightingBand, Res.Width, Res.Height,
+                                            Data.K.UseHistory ? Res.Luminance[Data.ReadIndex] : nullptr, Res.Luminance[Data.WriteIndex]);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
+    }
+
     struct FTonemapPassData
     {
         bool bEnabled = false;
+        bool bFuseCas = false;
         ur_tonemap_constants K;
+        ur_cas_constants Cas;
+        const float* ExposureEv = nullptr;
+        uint32* Output = nullptr;
+    };
+    struct FCasPassData
+    {
+        bool bEnabled = false;
+        ur_cas_constants K;
     };
     if (Options.bTonemap && Res.TonemapBand) {
-        const FRGResourceHandle TonemapHandle = Graph.ImportTexture("TonemapOutput", Res.TonemapBand, &Res.TonemapState, {Res.Width, Res.Rows, RG_FORMAT_R8G8B8A8_UNORM_SRGB});
+        // the back buffer: "TonemapOutput" itself when nothing follows Tonemap
+        const FRGResourceHandle TonemapHandle = bCas ? Graph.ImportTexture("BackBuffer", Res.TonemapBand, &Res.TonemapState, {Res.Width, Res.Rows, RG_FORMAT_R8G8B8A8_UNORM})
+                                                     : Graph.ImportTexture("TonemapOutput", Res.TonemapBand, &Res.TonemapState, {Res.Width, Res.Rows, RG_FORMAT_R8G8B8A8_UNORM_SRGB});
+        const FRGResourceHandle ScratchHandle = bCas && !bFuseCas
+            ? Graph.ImportTexture("TonemapOutput", Res.TonemapScratch, &Res.TonemapScratchState, {Res.Width, Res.Rows, RG_FORMAT_R8G8B8A8_UNORM})
+            : FRGResourceHandle{};
+        const ur_cas_constants CasK = {{1.0f / static_cast<float>(Res.Width), 1.0f / static_cast<float>(Res.Height)}, Constants.CasSharpness, 0.0f}; // :1533
         Graph.AddPass<FTonemapPassData>("Tonemap", [&](FTonemapPassData& Data, FRGPassBuilder& Builder)
         {
             Data.bEnabled = true;
+            Data.bFuseCas = bFuseCas;
             Data.K = Constants.Tonemap;
+            Data.K.EnableAutoExposure = bAutoExposure ? 1u : 0u;
+            Data.Cas = CasK;
+            Data.ExposureEv = bAutoExposure ? Res.Luminance[WriteIndex] : nullptr;
+            Data.Output = bCas && !bFuseCas ? Res.TonemapScratch : Res.TonemapBand;
             Builder.ReadTexture(LightingHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
-            Builder.WriteTexture(TonemapHandle, RG_STATE_RENDER_TARGET);
+            if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
+            Builder.WriteTexture(bCas && !bFuseCas ? ScratchHandle : TonemapHandle, RG_STATE_RENDER_TARGET);
         }, [this, &Res](const FTonemapPassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = ur_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, nullptr, Res.TonemapBand, Res.Width, Res.Rows);
+            const int rc = Data.bFuseCas
+                ? ur_tonemap_cas(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Height, Res.Row0, Res.Rows)
+                : ur_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Rows);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
             Res.LightingState = RG_STATE_RENDER_TARGET; // the reference transitions the lighting buffer back (:1511-1512)
         });
+        if (bCas) {
+            // fused: still in the graph, disabled and culled, like Sky under bFuseLightingAndSky
+            Graph.AddPass<FCasPassData>("CAS", [&](FCasPassData& Data, FRGPassBuilder& Builder)
+            {
+                Data.bEnabled = !bFuseCas;
+                Data.K = CasK;
+                if (!Data.bEnabled) return;
+                Builder.ReadTexture(ScratchHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+                Builder.WriteTexture(TonemapHandle, RG_STATE_RENDER_TARGET);
+            }, [this, &Res](const FCasPassData& Data, FHIPCommandContext& Cmd)
+            {
+                if (!Data.bEnabled) return;
+                const int rc = ur_cas(Cmd.GetContext(), &Data.K, Res.TonemapScratch, Res.TonemapBand, Res.Width, Res.Height, Res.Row0, Res.Rows);
+                if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+            });
+        }
     }
 
     Graph.Execute(Cmd);
     LastReport = Graph.GetLastExecutionReport();
+    // :1612-1620: the luminance written this frame is next frame's history
+    if (bAutoExposure && PassError == UR_OK) {
+        bLuminanceHistoryValid = true;
+        LuminanceWriteIndex = 1u - LuminanceWriteIndex;
+    } else {
+        bLuminanceHistoryValid = false;
+    }
     return PassError;
 }
 
@@ -209,6 +302,7 @@ struct ur_frame
     bool bRecordAfter = false; // this frame's bracket gets the third event (UR_FRAME_TIME_LIGHTING_RECORD_COST)
     bool bKernelEvents = false; // UR_FRAME_TIME_LIGHTING_KERNEL: the pair rides on the Lighting dispatch itself, nothing is recorded around it
     bool bStartOnCull = false;  // ... and this frame's START event was handed to the cull launch directly in front of the Lighting launch
+    ur_frame_post Post = {{nullptr, nullptr}, nullptr, 0.0f, 0.9f, 2.2f, 0.3f, 0.1f, 5.0f, 3.0f, 1.0f, 0.5f}; // ur_frame_set_post
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
 };
 
@@ -293,6 +387,17 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
                     const ur_sky_constants* sky, uint32_t flags)
 {
     if (!f || !r || !culling_constants || !scene || !sky) return UR_EINVAL;
+    const uint32_t post_flags = UR_FRAME_AUTO_EXPOSURE | UR_FRAME_CAS | UR_FRAME_FUSE_TONEMAP_CAS;
+    if (flags & post_flags) {
+        const bool cas_pass = (flags & UR_FRAME_CAS) && !(flags & UR_FRAME_FUSE_TONEMAP_CAS);
+        if (!(flags & UR_FRAME_TONEMAP) || !r->tonemap_band) { ur::set_error("ur_frame_render: AUTO_EXPOSURE / CAS need UR_FRAME_TONEMAP and a tonemap_band"); return UR_EINVAL; }
+        if ((flags & UR_FRAME_AUTO_EXPOSURE) && (!f->Post.luminance[0] || !f->Post.luminance[1])) { ur::set_error("ur_frame_render: AUTO_EXPOSURE needs ur_frame_set_post's luminance[2]"); return UR_EINVAL; }
+        if (cas_pass && !f->Post.tonemap_scratch) { ur::set_error("ur_frame_render: a CAS pass of its own needs ur_frame_set_post's tonemap_scratch"); return UR_EINVAL; }
+        if ((flags & (UR_FRAME_AUTO_EXPOSURE | UR_FRAME_CAS)) && (r->row0 != 0 || r->rows != r->height)) {
+            ur::set_error("ur_frame_render: AutoExposure and CAS need the whole frame (rows == height); a sharded caller gathers first");
+            return UR_EUNSUPPORTED;
+        }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -301,6 +406,9 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.DepthBand = const_cast<float*>(r->depth_band);
     R.LightingBand = r->lighting_band;
     R.TonemapBand = r->tonemap_band;
+    R.TonemapScratch = f->Post.tonemap_scratch;
+    R.Luminance[0] = f->Post.luminance[0];
+    R.Luminance[1] = f->Post.luminance[1];
     R.DepthFull = const_cast<float*>(r->depth_full);
     R.HZB = r->hzb;
     std::memcpy(R.HZBMips, r->hzb_mips, sizeof(R.HZBMips));
@@ -318,6 +426,15 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
     K.Scene = *scene;
     K.Sky = *sky;
+    K.Tonemap.Exposure = f->Post.tonemap_exposure;
+    K.Tonemap.Gamma = f->Post.tonemap_gamma;
+    K.DeltaTime = f->Post.delta_time;
+    K.AutoExposureKey = f->Post.ae_key;
+    K.AutoExposureMin = f->Post.ae_min;
+    K.AutoExposureMax = f->Post.ae_max;
+    K.AutoExposureSpeedUp = f->Post.ae_speed_up;
+    K.AutoExposureSpeedDown = f->Post.ae_speed_down;
+    K.CasSharpness = f->Post.cas_sharpness;
     FHotPathOptions O;
     O.bEnableIndirectDraw = (flags & UR_FRAME_INDIRECT_DRAW) != 0;
     O.bHZBEnabled = (flags & UR_FRAME_HZB) != 0;
@@ -326,6 +443,9 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bSkyEnabled = (flags & UR_FRAME_SKY) != 0;
     O.bFuseLightingAndSky = (flags & UR_FRAME_FUSE_LIGHTING_SKY) != 0;
     O.bTonemap = (flags & UR_FRAME_TONEMAP) != 0;
+    O.bAutoExposure = (flags & UR_FRAME_AUTO_EXPOSURE) != 0;
+    O.bCas = (flags & UR_FRAME_CAS) != 0;
+    O.bFuseTonemapCas = (flags & UR_FRAME_FUSE_TONEMAP_CAS) != 0;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -374,6 +494,15 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
 void ur_frame_join_async(ur_frame* f) { if (f) f->Cmd.JoinAsyncCompute(); }
 int ur_frame_hzb_ready(const ur_frame* f) { return f && f->Renderer.IsHZBReady() ? 1 : 0; }
 void ur_frame_reset_hzb(ur_frame* f) { if (f) f->Renderer.ResetHZB(); }
+
+int ur_frame_set_post(ur_frame* f, const ur_frame_post* post)
+{
+    if (!f || !post) { ur::set_error("ur_frame_set_post: null argument"); return UR_EINVAL; }
+    f->Post = *post;
+    return UR_OK;
+}
+
+void ur_frame_reset_post(ur_frame* f) { if (f) f->Renderer.ResetLuminanceHistory(); }
 
 static uint32_t copy_out(const std::string& s, char* buf, uint32_t cap)
 {

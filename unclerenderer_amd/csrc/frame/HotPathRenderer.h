@@ -1,7 +1,9 @@
 // HotPathRenderer — the four hot passes of FDeferredRenderer::RenderFrame wired onto the render graph.
 //
 // Reference wiring (Source/Render/DeferredRenderer.cpp): "GPU Culling" :508-542 (+ FRenderer::ConfigureHZBOcclusion /
-// DispatchGpuCulling, Renderer.cpp:384-472), "Build HZB" :982-1212, "Lighting" :1214-1255, "Sky" :1257-1296.
+// DispatchGpuCulling, Renderer.cpp:384-472), "Build HZB" :982-1212, "Lighting" :1214-1255, "Sky" :1257-1296, and optionally the
+// post chain "AutoExposure" :1363-1438, "Tonemap" :1440-1513, "CAS" :1515-1573 (TemporalAA is left out: the reference never
+// validates its history, so its pass is a copy of Lighting).
 // Pass names, PassData structs, declared usages/states and pass order are the reference's; the execute lambdas call
 // the C-ABI (include/ur_hotpath.h) instead of recording D3D12 commands. The passes between them (shadow map, depth
 // prepass, G-buffer raster, post FX) are out of scope: their outputs arrive as imported textures.
@@ -26,7 +28,9 @@ struct FHotPathResources
     uint32* GBufferC = nullptr;
     float* DepthBand = nullptr;
     ur_half4* LightingBand = nullptr;
-    uint32* TonemapBand = nullptr;    // optional: R8G8B8A8_UNORM output of the Tonemap pass for this band
+    uint32* TonemapBand = nullptr;    // optional: R8G8B8A8_UNORM output of the Tonemap pass for this band (the back buffer)
+    uint32* TonemapScratch = nullptr; // "TonemapOutput": Tonemap's output when CAS runs as its own pass
+    float* Luminance[2] = {};         // LuminanceA / B: 1x1 R32_FLOAT (CreateLuminanceResources, DeferredRenderer.cpp:2692-2712)
     // full-frame depth for the replicated HZB build, and the HZB itself
     float* DepthFull = nullptr;
     float* HZB = nullptr;
@@ -49,6 +53,8 @@ struct FHotPathResources
     uint32 HZBState = RG_STATE_UNORDERED_ACCESS;
     uint32 LightingState = RG_STATE_RENDER_TARGET;
     uint32 TonemapState = RG_STATE_RENDER_TARGET;
+    uint32 TonemapScratchState = RG_STATE_RENDER_TARGET;
+    uint32 LuminanceStates[2] = {RG_STATE_UNORDERED_ACCESS, RG_STATE_UNORDERED_ACCESS};
 };
 
 struct FHotPathFrameConstants
@@ -57,6 +63,10 @@ struct FHotPathFrameConstants
     ur_scene_constants Scene = {};
     ur_sky_constants Sky = {};
     ur_tonemap_constants Tonemap = {1u, 0u, 0.9f, 2.2f}; // bTonemapEnabled, auto exposure off, TonemapExposure, TonemapGamma (DeferredRenderer.h:193-196)
+    float DeltaTime = 0.0f;                               // RenderFrame's DeltaTime (AutoExposure adaptation)
+    float AutoExposureKey = 0.3f, AutoExposureMin = 0.1f, AutoExposureMax = 5.0f; // RendererConfig.h:28-30
+    float AutoExposureSpeedUp = 3.0f, AutoExposureSpeedDown = 1.0f;              // RendererConfig.h:31-32
+    float CasSharpness = 0.5f;                                                   // RendererConfig.h:26
 };
 
 struct FHotPathOptions
@@ -68,7 +78,10 @@ struct FHotPathOptions
     bool bRenderShadows = true;
     bool bSkyEnabled = true;
     bool bFuseLightingAndSky = false; // MI355X fast path: one pass, same result as Lighting followed by Sky
-    bool bTonemap = false;            // next row: Tonemap pass after Sky (TAA / auto exposure off)
+    bool bTonemap = false;            // next row: Tonemap pass after Sky (TAA off)
+    bool bAutoExposure = false;       // with bTonemap: AutoExposure pass before Tonemap (bAutoExposureEnabled)
+    bool bCas = false;                // with bTonemap: CAS pass after Tonemap (bEnableCas)
+    bool bFuseTonemapCas = false;     // MI355X fast path: Tonemap + CAS in one launch (ur_tonemap_cas), CAS pass culled
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;
@@ -90,11 +103,15 @@ public:
     void SetLightingTimer(std::function<void(hipStream_t, bool /*begin*/)> Fn) { LightingTimer = std::move(Fn); }
     bool IsHZBReady() const { return bHZBReady; }
     void ResetHZB() { bHZBReady = false; }
+    // luminance ping-pong of the AutoExposure pass (LuminanceWriteIndex / bLuminanceHistoryValid, DeferredRenderer.cpp:1612-1620)
+    void ResetLuminanceHistory() { bLuminanceHistoryValid = false; }
     const std::vector<FRenderGraph::FPassReport>& GetLastReport() const { return LastReport; }
 
 private:
     FHIPDevice* Device = nullptr;
     bool bHZBReady = false;
+    bool bLuminanceHistoryValid = false;
+    uint32 LuminanceWriteIndex = 0;
     int PassError = 0;
     std::vector<FRenderGraph::FPassReport> LastReport;
     std::function<void(hipStream_t, bool)> LightingTimer;

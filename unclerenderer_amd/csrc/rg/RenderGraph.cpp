@@ -137,6 +137,7 @@ uint32 RGFormatBytesPerTexel(ERGFormat Format)
 {
     switch (Format) {
     case RG_FORMAT_R16G16B16A16_FLOAT: return 8;
+    case RG_FORMAT_R8G8B8A8_UNORM:
     case RG_FORMAT_R8G8B8A8_UNORM_SRGB:
     case RG_FORMAT_R32_FLOAT:
     case RG_FORMAT_D24_UNORM_S8_UINT:

@@ -55,6 +55,7 @@ enum ERGResourceState : uint32 {
 enum ERGFormat : uint32 {
     RG_FORMAT_UNKNOWN = 0,
     RG_FORMAT_R16G16B16A16_FLOAT = 10,
+    RG_FORMAT_R8G8B8A8_UNORM = 28,  // the back buffer (DX12SwapChain.cpp) and the Tonemap output CAS reads
     RG_FORMAT_R8G8B8A8_UNORM_SRGB = 29,
     RG_FORMAT_R32_FLOAT = 41,       // also what the depth buffer looks like through its SRV
     RG_FORMAT_D24_UNORM_S8_UINT = 45,

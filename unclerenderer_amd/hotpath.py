@@ -275,6 +275,18 @@ class Frame:
     def reset_hzb(self):
         self._L.ur_frame_reset_hzb(self._f)
 
+    def set_post(self, luminance=(None, None), tonemap_scratch=None, delta_time=0.0, tonemap_exposure=0.9, tonemap_gamma=2.2, ae_key=0.3,
+                 ae_min=0.1, ae_max=5.0, ae_speed_up=3.0, ae_speed_down=1.0, cas_sharpness=0.5):
+        """ur_frame_set_post: the AutoExposure / CAS resources (device tensors, kept alive here) and parameters of the frames that follow."""
+        dp = lambda t: t.data_ptr() if t is not None else None
+        p = _lib.FramePost((C.c_void_p * 2)(dp(luminance[0]), dp(luminance[1])), dp(tonemap_scratch), delta_time, tonemap_exposure, tonemap_gamma,
+                           ae_key, ae_min, ae_max, ae_speed_up, ae_speed_down, cas_sharpness)
+        self._post_keep = (luminance, tonemap_scratch)
+        _lib.check(self._L.ur_frame_set_post(self._f, C.byref(p)), "ur_frame_set_post")
+
+    def reset_post(self):
+        self._L.ur_frame_reset_post(self._f)
+
     def report(self):
         """[(pass name, culled, transitions)] of the last executed graph."""
         n = self._L.ur_frame_report(self._f, None, 0)
@@ -317,6 +329,40 @@ def _temporal_aa(self, current_frame, history_band, output_band, history_weight,
 
 
 HotPath.temporal_aa = _temporal_aa
+
+
+def _auto_exposure(self, hdr_full, out_ev, w, h, prev_ev=None, use_history=False, delta_time=0.0, speed_up=3.0, speed_down=1.0,
+                   key=0.3, ev_min=0.1, ev_max=5.0):
+    """AutoExposure (AutoExposure.hlsl) of the full RGBA16F frame: one float (the EV Tonemap applies) into out_ev.
+    Defaults: RendererConfig.h:28-32."""
+    k = _lib.AutoExposureConstants((C.c_float * 2)(w, h), delta_time, speed_up, speed_down, int(use_history), key, ev_min, ev_max)
+    _lib.check(self._L.ur_auto_exposure(self._ctx, C.byref(k), _ptr(hdr_full), w, h, _ptr(prev_ev), _ptr(out_ev)), "ur_auto_exposure")
+
+
+def _cas_constants(w, h, sharpness):
+    return _lib.CasConstants((C.c_float * 2)(1.0 / w, 1.0 / h), sharpness, 0.0)  # TexelDelta as the pass sets it (DeferredRenderer.cpp:1533)
+
+
+def _cas(self, ldr_full, out_band, w, h, row0=0, rows=None, sharpness=0.5):
+    """CAS (Cas.hlsl) of rows [row0,row0+rows) of the full R8G8B8A8 image into a band-local output."""
+    rows = h - row0 if rows is None else rows
+    k = _cas_constants(w, h, sharpness)
+    _lib.check(self._L.ur_cas(self._ctx, C.byref(k), _ptr(ldr_full), _ptr(out_band), w, h, row0, rows), "ur_cas")
+
+
+def _tonemap_cas(self, hdr_full, out_band, w, h, row0=0, rows=None, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None,
+                 sharpness=0.5):
+    """Tonemap of the full frame then CAS of the band, in one launch (the same bytes as tonemap() followed by cas())."""
+    rows = h - row0 if rows is None else rows
+    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    ck = _cas_constants(w, h, sharpness)
+    _lib.check(self._L.ur_tonemap_cas(self._ctx, C.byref(tk), C.byref(ck), _ptr(hdr_full), _ptr(exposure_ev), _ptr(out_band), w, h, row0, rows),
+               "ur_tonemap_cas")
+
+
+HotPath.auto_exposure = _auto_exposure
+HotPath.cas = _cas
+HotPath.tonemap_cas = _tonemap_cas
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

@@ -97,6 +97,25 @@ class TonemapConstants(C.Structure):
     _fields_ = [("EnableTonemap", C.c_uint32), ("EnableAutoExposure", C.c_uint32), ("Exposure", C.c_float), ("Gamma", C.c_float)]
 
 
+class AutoExposureConstants(C.Structure):
+    """AutoExposureConstants (Shaders/AutoExposure.hlsl:1-12), 36 bytes."""
+    _fields_ = [("InputSize", C.c_float * 2), ("DeltaTime", C.c_float), ("AdaptationSpeedUp", C.c_float), ("AdaptationSpeedDown", C.c_float),
+                ("UseHistory", C.c_uint32), ("AutoExposureKey", C.c_float), ("AutoExposureMin", C.c_float), ("AutoExposureMax", C.c_float)]
+
+
+class CasConstants(C.Structure):
+    """CasParams (Shaders/Cas.hlsl:44-49), 16 bytes."""
+    _fields_ = [("TexelDelta", C.c_float * 2), ("Sharpness", C.c_float), ("Padding", C.c_float)]
+
+
+class FramePost(C.Structure):
+    """ur_frame_post (include/ur_frame.h): post-chain resources and parameters of a frame (ur_frame_set_post)."""
+    _fields_ = [("luminance", C.c_void_p * 2), ("tonemap_scratch", C.c_void_p), ("delta_time", C.c_float),
+                ("tonemap_exposure", C.c_float), ("tonemap_gamma", C.c_float),
+                ("ae_key", C.c_float), ("ae_min", C.c_float), ("ae_max", C.c_float), ("ae_speed_up", C.c_float), ("ae_speed_down", C.c_float),
+                ("cas_sharpness", C.c_float)]
+
+
 class FrameResources(C.Structure):
     """ur_frame_resources (include/ur_frame.h)."""
     _fields_ = [
@@ -119,9 +138,13 @@ UR_FRAME_HZB_WITH_LIGHTING = 0x4000
 UR_FRAME_TIME_LIGHTING_RECORD_COST = 0x8000
 UR_FRAME_TIME_LIGHTING_KERNEL = 0x10000
 UR_FRAME_HZB_SHARD = 0x20000
+UR_FRAME_AUTO_EXPOSURE = 0x40000
+UR_FRAME_CAS = 0x80000
+UR_FRAME_FUSE_TONEMAP_CAS = 0x100000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
+assert C.sizeof(AutoExposureConstants) == 36 and C.sizeof(CasConstants) == 16
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
 _VP, _U32, _F = C.c_void_p, C.c_uint32, C.c_float
@@ -160,6 +183,9 @@ SIGNATURES = {
                                            C.POINTER(LightingTables), _VP, _U32, _U32, _U32, _U32]),
     "ur_tonemap": (C.c_int, [_VP, C.POINTER(TonemapConstants), _VP, _VP, _VP, _U32, _U32]),
     "ur_temporal_aa": (C.c_int, [_VP, _VP, _VP, _VP, _F, _U32, _U32, _U32, _U32, _U32]),
+    "ur_auto_exposure": (C.c_int, [_VP, C.POINTER(AutoExposureConstants), _VP, _U32, _U32, _VP, _VP]),
+    "ur_cas": (C.c_int, [_VP, C.POINTER(CasConstants), _VP, _VP, _U32, _U32, _U32, _U32]),
+    "ur_tonemap_cas": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes_ex": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.c_int]),
@@ -183,6 +209,8 @@ SIGNATURES = {
     "ur_frame_lighting_times_ex": (_U32, [_VP, _FP, _FP, _U32]),
     "ur_frame_hzb_ready": (C.c_int, [_VP]),
     "ur_frame_reset_hzb": (None, [_VP]),
+    "ur_frame_set_post": (C.c_int, [_VP, C.POINTER(FramePost)]),
+    "ur_frame_reset_post": (None, [_VP]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
