@@ -878,6 +878,10 @@ void uro_temporal_aa(const ur_half4* current, const ur_half4* history, ur_half4*
                      uint32_t H, uint32_t row0, uint32_t rows)
 {
     const float w = saturate(HistoryWeight);
+    // HLSL min / max ignore a NaN operand. std::fmin / fmax do so for a quiet NaN only: glibc returns NaN when one operand is
+    // a signalling NaN, which h2f passes through from an fp16 pattern such as 0x7d00.
+    auto hmin = [](float a, float b) { return a != a ? b : (b != b ? a : std::fmin(a, b)); };
+    auto hmax = [](float a, float b) { return a != a ? b : (b != b ? a : std::fmax(a, b)); };
     for (uint32_t r = 0; r < rows; ++r)
         for (uint32_t x = 0; x < W; ++x) {
             const int px = (int)x, py = (int)(row0 + r);
@@ -890,13 +894,13 @@ void uro_temporal_aa(const ur_half4* current, const ur_half4* history, ur_half4*
                     const int sx = std::min(std::max(px + ox, 0), (int)W - 1), sy = std::min(std::max(py + oy, 0), (int)H - 1);
                     const ur_half4 s = current[(size_t)sy * W + sx];
                     const float3 c = {h2f(s.x), h2f(s.y), h2f(s.z)};
-                    MinColor = {std::fmin(MinColor.x, c.x), std::fmin(MinColor.y, c.y), std::fmin(MinColor.z, c.z)};
-                    MaxColor = {std::fmax(MaxColor.x, c.x), std::fmax(MaxColor.y, c.y), std::fmax(MaxColor.z, c.z)};
+                    MinColor = {hmin(MinColor.x, c.x), hmin(MinColor.y, c.y), hmin(MinColor.z, c.z)};
+                    MaxColor = {hmax(MaxColor.x, c.x), hmax(MaxColor.y, c.y), hmax(MaxColor.z, c.z)};
                 }
             const ur_half4 hh = history[bi];
             float3 Hist = {h2f(hh.x), h2f(hh.y), h2f(hh.z)};
-            Hist = {std::fmin(std::fmax(Hist.x, MinColor.x), MaxColor.x), std::fmin(std::fmax(Hist.y, MinColor.y), MaxColor.y),
-                    std::fmin(std::fmax(Hist.z, MinColor.z), MaxColor.z)};
+            Hist = {hmin(hmax(Hist.x, MinColor.x), MaxColor.x), hmin(hmax(Hist.y, MinColor.y), MaxColor.y),
+                    hmin(hmax(Hist.z, MinColor.z), MaxColor.z)};
             const float3 Cur = {h2f(Current.x), h2f(Current.y), h2f(Current.z)};
             const float3 Blended = lerp(Cur, Hist, w);
             output[bi] = {f2h(Blended.x), f2h(Blended.y), f2h(Blended.z), Current.w};

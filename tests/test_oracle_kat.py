@@ -380,3 +380,16 @@ def test_temporal_aa_known_answers(oracle):
     assert np.array_equal(oracle.temporal_aa(h16(cur), h16(hist), 0.9, False), h16(cur))
     assert np.array_equal(oracle.temporal_aa(h16(cur), h16(hist), 7.0, True), oracle.temporal_aa(h16(cur), h16(hist), 1.0, True))
     assert np.array_equal(oracle.temporal_aa(h16(cur), h16(hist), -1.0, True)[..., :3], h16(cur)[..., :3])
+    # min / max ignore a NaN operand, a signalling-NaN fp16 pattern too (glibc's fmin / fmax return NaN for one): in any of the
+    # nine positions and in the history, the centre pixel's result is the one without it
+    base = oracle.temporal_aa(h16(cur), h16(hist), 0.9, True)[1, 1]
+    for bits in (0x7D00, 0xFD00, 0x7E00):
+        for y, x in ((0, 0), (2, 2), (1, 2), (2, 0)):
+            c2 = h16(cur).copy()
+            c2[y, x, :3] = bits
+            assert np.array_equal(oracle.temporal_aa(c2, h16(hist), 0.9, True)[1, 1], base), (hex(bits), y, x)
+        h2 = h16(hist).copy()
+        h2[1, 1, :3] = bits
+        # a NaN history clamps to the box minimum: (0.5, 0.25, 0.5) blended with the centre (1, 0.25, 0.5)
+        want = np.array([1.0 + np.float32(0.9) * (0.5 - 1.0), 0.25, 0.5, 2.0], np.float32).astype(np.float16).view(np.uint16)
+        assert np.array_equal(oracle.temporal_aa(h16(cur), h2, 0.9, True)[1, 1], want), hex(bits)

@@ -44,6 +44,11 @@ struct RowMinMax { half2_t mn0, mn1, mx0, mx1; }; // (R,G) and (B,A) pairs
 
 __device__ __forceinline__ half2_t as_h2(uint32_t u) { union { uint32_t u; half2_t h; } c; c.u = u; return c.h; }
 __device__ __forceinline__ uint32_t as_u(half2_t h) { union { uint32_t u; half2_t h; } c; c.h = h; return c.u; }
+// HLSL's min / max ignore a NaN operand. v_pk_min/max_f16 do so for a quiet NaN, but return NaN when an operand is a
+// signalling NaN (IEEE mode), so min(-Inf, sNaN) would drop the -Inf. The texels of a row are quieted (v_pk_max_f16 x, x)
+// before the row's min / max; the compiler did so on its own for most of them, but not for the halo texel a lane at the
+// strip's edge takes from v_readlane through the DPP shift. The centre texel itself stays as loaded: its alpha is copied.
+__device__ __forceinline__ half2_t quiet(uint32_t u) { return __builtin_elementwise_canonicalize(as_h2(u)); }
 __device__ __forceinline__ half2_t pk_min(half2_t a, half2_t b) { return __builtin_elementwise_min(a, b); }
 __device__ __forceinline__ half2_t pk_max(half2_t a, half2_t b) { return __builtin_elementwise_max(a, b); }
 
@@ -54,8 +59,9 @@ __device__ __forceinline__ RowMinMax row_minmax(u32x2_t c, uint32_t hl0, uint32_
     const uint32_t l0 = __builtin_amdgcn_update_dpp(hl0, c.x, 0x138, 0xF, 0xF, false), l1 = __builtin_amdgcn_update_dpp(hl1, c.y, 0x138, 0xF, 0xF, false);
     const uint32_t r0 = __builtin_amdgcn_update_dpp(hr0, c.x, 0x130, 0xF, 0xF, false), r1 = __builtin_amdgcn_update_dpp(hr1, c.y, 0x130, 0xF, 0xF, false);
     RowMinMax m;
-    m.mn0 = pk_min(pk_min(as_h2(l0), as_h2(r0)), as_h2(c.x)); m.mn1 = pk_min(pk_min(as_h2(l1), as_h2(r1)), as_h2(c.y));
-    m.mx0 = pk_max(pk_max(as_h2(l0), as_h2(r0)), as_h2(c.x)); m.mx1 = pk_max(pk_max(as_h2(l1), as_h2(r1)), as_h2(c.y));
+    const half2_t ql0 = quiet(l0), ql1 = quiet(l1), qr0 = quiet(r0), qr1 = quiet(r1), qc0 = quiet(c.x), qc1 = quiet(c.y);
+    m.mn0 = pk_min(pk_min(ql0, qr0), qc0); m.mn1 = pk_min(pk_min(ql1, qr1), qc1);
+    m.mx0 = pk_max(pk_max(ql0, qr0), qc0); m.mx1 = pk_max(pk_max(ql1, qr1), qc1);
     return m;
 }
 
