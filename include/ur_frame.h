@@ -56,11 +56,17 @@ typedef struct ur_frame_resources {
 #define UR_FRAME_TIME_LIGHTING_KERNEL 0x10000u /* time the Lighting pass by a HIP event pair carried on its kernel dispatch (ur_time_next_lighting): from the end of what precedes the kernel to the kernel's end, what rocprofv3's kernel trace reports for the dispatch; no event record behind the kernel; read with ur_frame_lighting_times() */
 #define UR_FRAME_HZB_SHARD 0x20000u /* several ranks (ur_frame_create's world_size > 1): Build HZB builds only this rank's 128x32 pieces of mips 0..4 (ur_build_hzb_band; riding the Lighting launch with HZB_WITH_LIGHTING) and leaves the exchange of the slices and the tail (ur_build_hzb_tail) to the caller, who holds the communicator. One rank: the whole chain as usual */
 /* The rest of the reference's post chain after Tonemap's input (DeferredRenderer.cpp:1363-1573). Each needs UR_FRAME_TONEMAP and a
- * tonemap_band (else UR_EINVAL), and the WHOLE frame in one call: rows == height, else UR_EUNSUPPORTED (a sharded caller gathers
- * the HDR frame first and calls ur_auto_exposure / ur_tonemap_cas itself). Resources and parameters: ur_frame_set_post. */
+ * tonemap_band (else UR_EINVAL), and the WHOLE frame in one call: rows == height, else UR_EUNSUPPORTED - unless UR_FRAME_POST_EXCHANGE
+ * is set (a row band of several ranks). Resources and parameters: ur_frame_set_post. */
 #define UR_FRAME_AUTO_EXPOSURE 0x40000u /* "AutoExposure" pass before Tonemap: Lighting -> luminance[W] (history luminance[1-W]); Tonemap then applies 2^EV */
 #define UR_FRAME_CAS 0x80000u /* "CAS" pass after Tonemap: Tonemap writes tonemap_scratch, CAS sharpens it into tonemap_band */
 #define UR_FRAME_FUSE_TONEMAP_CAS 0x100000u /* with CAS: Tonemap runs ur_tonemap_cas straight into tonemap_band (same bytes, no scratch); the CAS pass is then culled */
+/* With AUTO_EXPOSURE and/or CAS (else ignored), on rank's equal band of world_size (ur_frame_create; world_size | height, one rank
+ * included): ur_frame_render runs through Sky, then a "Post Record" pass packs the band's post record (ur_pack_post_record) into
+ * ur_frame_set_post_records' own_record, and returns with the post passes pending. The caller all-gathers the records in rank order
+ * into all_records and calls ur_frame_finish_post, which runs AutoExposure (from the records), Tonemap and CAS on the band with the
+ * rows around it read from the neighbours' records. The band's bytes and luminance[W] are those of the unsplit frame, on every rank. */
+#define UR_FRAME_POST_EXCHANGE 0x200000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -95,6 +101,14 @@ int ur_frame_set_post(ur_frame* f, const ur_frame_post* post);
 /* The luminance history becomes invalid (like ur_frame_reset_hzb): the next AutoExposure pass runs with UseHistory = 0. The write
  * index is kept: a frame whose AutoExposure ran writes luminance[W], then W flips; any other frame invalidates the history. */
 void ur_frame_reset_post(ur_frame* f);
+/* Device pointers of the post exchange (UR_FRAME_POST_EXCHANGE), each ur_post_record_bytes(width) per rank: own_record receives this
+ * rank's record, all_records holds world_size gathered records in rank order (own_record may alias all_records + rank * bytes, for
+ * an in-place all-gather). They must stay valid while frames use them. */
+int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_records);
+/* The post passes of a frame rendered with UR_FRAME_POST_EXCHANGE, after the records are gathered: AutoExposure, Tonemap and (unless
+ * fused) CAS, with the luminance ping-pong and history of the unsplit frame. UR_EINVAL if nothing is pending or the band is not
+ * rank's equal band. ur_frame_report then lists both halves in order. */
+int ur_frame_finish_post(ur_frame* f);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

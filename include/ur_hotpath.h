@@ -388,6 +388,39 @@ int ur_cas(ur_ctx* ctx, const ur_cas_constants* constants, const uint32_t* ldr_f
 int ur_tonemap_cas(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const ur_half4* hdr_full,
                    const float* exposure_ev, uint32_t* out_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
 
+/* ---- AutoExposure and CAS on row bands: the post exchange ----------------------------------------------------------------
+ * A rank that shaded rows [row0,row0+rows) of a w x h frame publishes one fixed-size post record; after an all-gather of the
+ * records (rank order, N | h, equal bands) every rank computes the single-GPU EV and tonemaps and sharpens its own band, and the
+ * bytes are those of the unsplit frame. Record layout, ur_post_record_bytes(w) = (2*w + 1024) * 8 bytes:
+ *
+ *   offset   contents
+ *   0        first_row[w]: half4, HDR row row0 (after Lighting/Sky)
+ *   8*w      last_row[w]:  half4, HDR row row0 + rows - 1
+ *   16*w     taps[256][4]: half4 texels t00, t10, t01, t11 of AutoExposure tap i = gy*16 + gx (the clamped bilinear footprint
+ *            ur_auto_exposure reads). A texel slot holds the texel when its row lies in the band, else zero; with equal bands
+ *            the texel of row y belongs to rank y / (h / N).
+ *
+ * A record is 16-byte aligned in a gathered buffer when its base is and w is even. */
+uint64_t ur_post_record_bytes(uint32_t w);
+/* Writes this band's record (one launch). hdr_band: device, rows [row0,row0+rows) RGBA16F; record: device, ur_post_record_bytes(w). */
+int ur_pack_post_record(ur_ctx* ctx, const ur_half4* hdr_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, void* record);
+/* ur_auto_exposure of the whole frame from n_ranks gathered records (rank order; n_ranks | h): every texel is read from its
+ * owner's record and summed in ur_auto_exposure's order, so out_ev[0] has the same bits. Arguments otherwise as ur_auto_exposure. */
+int ur_auto_exposure_records(ur_ctx* ctx, const ur_auto_exposure_constants* constants, const void* records, uint32_t n_ranks, uint32_t w,
+                             uint32_t h, const float* prev_ev, float* out_ev);
+/* ur_tonemap_cas of rows [row0,row0+rows) with only the band in memory: hdr_band holds those rows, hdr_above the HDR row row0 - 1
+ * and hdr_below the row row0 + rows (each w half4; e.g. the last_row / first_row of the neighbours' gathered records, used in
+ * place). hdr_above may be null only when row0 == 0, hdr_below only when row0 + rows == h. Same bytes as ur_tonemap_cas of the
+ * full frame. */
+int ur_tonemap_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const ur_half4* hdr_band,
+                        const ur_half4* hdr_above, const ur_half4* hdr_below, const float* exposure_ev, uint32_t* out_band,
+                        uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+/* The unfused form: ldr_band is ur_tonemap's output for rows [row0,row0+rows); the two HDR halo rows are tonemapped here with the
+ * same tonemap constants and exposure_ev. Same bytes as ur_tonemap then ur_cas of the full frame. */
+int ur_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const uint32_t* ldr_band,
+                const ur_half4* hdr_above, const ur_half4* hdr_below, const float* exposure_ev, uint32_t* out_band,
+                uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+
 /* ---- multi-GPU: gather the row bands of the HDR frame ------------------------------------------ */
 
 /* comm: an ncclComm_t (RCCL). hdr_full: device, w*h half4 on every rank; rank r has already written

@@ -18,6 +18,10 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     // (valid and flipped after an AutoExposure pass that ran, invalid after any other frame, :1612-1620). Errors of passes are
     // collected in PassError rather than returned early; an early return added above Execute must do that bookkeeping too.
     PassError = UR_OK;
+    if (bPostPending) { // the last frame's post passes never ran: its AutoExposure did not either
+        bPostPending = false;
+        bLuminanceHistoryValid = false;
+    }
     FRenderGraph Graph;
     Graph.SetDevice(Device);
     Graph.SetGpuTimingEnabled(Options.bGpuTiming);
@@ -168,12 +172,95 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
 
-    // ---- AutoExposure -> Tonemap -> CAS (DeferredRenderer.cpp:1363-1573; TemporalAA left out, see HotPathRenderer.h) ------------
+    const bool bPostPasses = Options.bTonemap && Res.TonemapBand && (Options.bAutoExposure || Options.bCas);
+    if (Options.bPostExchange && bPostPasses) {
+        // ---- Post Record: the band's part of the post exchange; the post passes wait for FinishPost --------------------------
+        struct FPostRecordPassData
+        {
+        };
+        const FRGResourceHandle RecordHandle = Graph.ImportTexture("PostRecord", Res.PostRecord, &Res.PostRecordState,
+                                                                   {static_cast<uint32>(ur_post_record_bytes(Res.Width) / 8u), 1, RG_FORMAT_R16G16B16A16_FLOAT});
+        Graph.AddPass<FPostRecordPassData>("Post Record", [&](FPostRecordPassData&, FRGPassBuilder& Builder)
+        {
+            Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Builder.WriteTexture(RecordHandle, RG_STATE_UNORDERED_ACCESS);
+        }, [this, &Res](const FPostRecordPassData&, FHIPCommandContext& Cmd)
+        {
+            const int rc = ur_pack_post_record(Cmd.GetContext(), Res.LightingBand, Res.Width, Res.Height, Res.Row0, Res.Rows, Res.PostRecord);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
+        Graph.Execute(Cmd);
+        LastReport = Graph.GetLastExecutionReport();
+        bPostPending = PassError == UR_OK;
+        if (bPostPending) {
+            PendingConstants = Constants;
+            PendingOptions = Options;
+        } else {
+            bLuminanceHistoryValid = false;
+        }
+        return PassError;
+    }
+
+    AddPostPasses(Graph, LightingHandle, Res, Constants, Options, 0);
+    Graph.Execute(Cmd);
+    LastReport = Graph.GetLastExecutionReport();
+    EndPostHistory(Options.bTonemap && Res.TonemapBand && Options.bAutoExposure);
+    return PassError;
+}
+
+int FHotPathRenderer::FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res)
+{
+    if (!bPostPending) { ur::set_error("ur_frame_finish_post: no post passes are pending (render with UR_FRAME_POST_EXCHANGE and AUTO_EXPOSURE / CAS first)"); return UR_EINVAL; }
+    bPostPending = false;
+    PassError = UR_OK;
+    FRenderGraph Graph;
+    Graph.SetDevice(Device);
+    Graph.SetGpuTimingEnabled(PendingOptions.bGpuTiming);
+    Graph.SetGraphDumpEnabled(PendingOptions.bGraphDump);
+    Graph.SetResourceLifetimeLogging(PendingOptions.bGraphDump);
+    Graph.SetBarrierLoggingEnabled(PendingOptions.bBarrierLogs);
+    const FRGResourceHandle LightingHandle = Graph.ImportTexture("Lighting", Res.LightingBand, &Res.LightingState, {Res.Width, Res.Rows, RG_FORMAT_R16G16B16A16_FLOAT});
+    AddPostPasses(Graph, LightingHandle, Res, PendingConstants, PendingOptions, static_cast<uint32>(Cmd.GetWorldSize()));
+    Graph.Execute(Cmd);
+    const std::vector<FRenderGraph::FPassReport>& Tail = Graph.GetLastExecutionReport();
+    LastReport.insert(LastReport.end(), Tail.begin(), Tail.end());
+    EndPostHistory(PendingOptions.bAutoExposure);
+    return PassError;
+}
+
+void FHotPathRenderer::EndPostHistory(bool bAutoExposure)
+{
+    // :1612-1620: the luminance written this frame is next frame's history
+    if (bAutoExposure && PassError == UR_OK) {
+        bLuminanceHistoryValid = true;
+        LuminanceWriteIndex = 1u - LuminanceWriteIndex;
+    } else {
+        bLuminanceHistoryValid = false;
+    }
+}
+
+// AutoExposure -> Tonemap -> CAS. RecordRanks != 0: on the band alone, from the RecordRanks gathered post records (FinishPost; the
+// band is this rank's equal band): AutoExposure reads every rank's tap texels, Tonemap / CAS read the rows around the band from the
+// neighbours' records in place.
+void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
+                                     const FHotPathOptions& Options, uint32 RecordRanks)
+{
+    // (DeferredRenderer.cpp:1363-1573; TemporalAA left out, see HotPathRenderer.h)
     // Without AutoExposure and CAS this is the Tonemap pass alone, Lighting -> LDR band, as before they existed.
     const bool bAutoExposure = Options.bTonemap && Res.TonemapBand && Options.bAutoExposure;
     const bool bCas = Options.bTonemap && Res.TonemapBand && Options.bCas;
     const bool bFuseCas = bCas && Options.bFuseTonemapCas;
     const uint32 WriteIndex = LuminanceWriteIndex;
+    const bool bFromRecords = RecordRanks != 0;
+    const uint64 RecordBytes = ur_post_record_bytes(Res.Width);
+    const uint8_t* Records = static_cast<const uint8_t*>(Res.PostRecords);
+    const uint32 Rank = bFromRecords ? Res.Row0 / Res.Rows : 0;
+    // the neighbours' last / first HDR rows: the halo rows of CAS (none at the frame's top / bottom edge)
+    const ur_half4* HaloAbove = bFromRecords && Rank > 0 ? reinterpret_cast<const ur_half4*>(Records + (Rank - 1) * RecordBytes + 8ull * Res.Width) : nullptr;
+    const ur_half4* HaloBelow = bFromRecords && Rank + 1 < RecordRanks ? reinterpret_cast<const ur_half4*>(Records + (Rank + 1) * RecordBytes) : nullptr;
+    const FRGResourceHandle RecordsHandle = bFromRecords
+        ? Graph.ImportTexture("PostRecords", const_cast<void*>(Res.PostRecords), &Res.PostRecordsState, {static_cast<uint32>(RecordBytes / 8u), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
+        : FRGResourceHandle{};
     FRGResourceHandle LuminanceHandles[2];
     if (bAutoExposure) {
         LuminanceHandles[0] = Graph.ImportTexture("LuminanceA", Res.Luminance[0], &Res.LuminanceStates[0], {1, 1, RG_FORMAT_R32_FLOAT});
@@ -185,6 +272,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         bool bEnabled = false;
         ur_auto_exposure_constants K = {};
         uint32 ReadIndex = 0, WriteIndex = 0;
+        uint32 RecordRanks = 0;
     };
     if (bAutoExposure) {
         Graph.AddPass<FAutoExposurePassData>("AutoExposure", [&](FAutoExposurePassData& Data, FRGPassBuilder& Builder)
@@ -201,13 +289,16 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
             Data.K.AutoExposureKey = Constants.AutoExposureKey;
             Data.K.AutoExposureMin = Constants.AutoExposureMin;
             Data.K.AutoExposureMax = Constants.AutoExposureMax;
-            Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Data.RecordRanks = RecordRanks;
+            Builder.ReadTexture(bFromRecords ? RecordsHandle : LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             Builder.ReadTexture(LuminanceHandles[Data.ReadIndex], RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             Builder.WriteTexture(LuminanceHandles[Data.WriteIndex], RG_STATE_UNORDERED_ACCESS);
         }, [this, &Res](const FAutoExposurePassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = ur_auto_exposure(Cmd.GetContext(), &Data.K, Res.LightingBand, Res.Width, Res.Height,
-                                            Data.K.UseHistory ? Res.Luminance[Data.ReadIndex] : nullptr, Res.Luminance[Data.WriteIndex]);
+            const float* Prev = Data.K.UseHistory ? Res.Luminance[Data.ReadIndex] : nullptr;
+            const int rc = Data.RecordRanks
+                ? ur_auto_exposure_records(Cmd.GetContext(), &Data.K, Res.PostRecords, Data.RecordRanks, Res.Width, Res.Height, Prev, Res.Luminance[Data.WriteIndex])
+                : ur_auto_exposure(Cmd.GetContext(), &Data.K, Res.LightingBand, Res.Width, Res.Height, Prev, Res.Luminance[Data.WriteIndex]);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -220,11 +311,19 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         ur_cas_constants Cas;
         const float* ExposureEv = nullptr;
         uint32* Output = nullptr;
+        bool bHalo = false;
+        const ur_half4* HaloAbove = nullptr;
+        const ur_half4* HaloBelow = nullptr;
     };
     struct FCasPassData
     {
         bool bEnabled = false;
         ur_cas_constants K;
+        bool bHalo = false; // the band alone: the rows around it are Tonemap's input rows from the records, tonemapped by the CAS launch
+        ur_tonemap_constants Tonemap;
+        const float* ExposureEv = nullptr;
+        const ur_half4* HaloAbove = nullptr;
+        const ur_half4* HaloBelow = nullptr;
     };
     if (Options.bTonemap && Res.TonemapBand) {
         // the back buffer: "TonemapOutput" itself when nothing follows Tonemap
@@ -243,12 +342,19 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
             Data.Cas = CasK;
             Data.ExposureEv = bAutoExposure ? Res.Luminance[WriteIndex] : nullptr;
             Data.Output = bCas && !bFuseCas ? Res.TonemapScratch : Res.TonemapBand;
+            Data.bHalo = bFromRecords && bFuseCas;
+            Data.HaloAbove = HaloAbove;
+            Data.HaloBelow = HaloBelow;
             Builder.ReadTexture(LightingHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+            if (Data.bHalo) Builder.ReadTexture(RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
             if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
             Builder.WriteTexture(bCas && !bFuseCas ? ScratchHandle : TonemapHandle, RG_STATE_RENDER_TARGET);
         }, [this, &Res](const FTonemapPassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = Data.bFuseCas
+            const int rc = Data.bHalo
+                ? ur_tonemap_cas_halo(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.HaloAbove, Data.HaloBelow, Data.ExposureEv, Data.Output, Res.Width,
+                                      Res.Height, Res.Row0, Res.Rows)
+                : Data.bFuseCas
                 ? ur_tonemap_cas(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Height, Res.Row0, Res.Rows)
                 : ur_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Rows);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
@@ -261,27 +367,29 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
                 Data.bEnabled = !bFuseCas;
                 Data.K = CasK;
                 if (!Data.bEnabled) return;
+                Data.bHalo = bFromRecords;
+                Data.Tonemap = Constants.Tonemap;
+                Data.Tonemap.EnableAutoExposure = bAutoExposure ? 1u : 0u;
+                Data.ExposureEv = bAutoExposure ? Res.Luminance[WriteIndex] : nullptr;
+                Data.HaloAbove = HaloAbove;
+                Data.HaloBelow = HaloBelow;
                 Builder.ReadTexture(ScratchHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+                if (Data.bHalo) {
+                    Builder.ReadTexture(RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+                    if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
+                }
                 Builder.WriteTexture(TonemapHandle, RG_STATE_RENDER_TARGET);
             }, [this, &Res](const FCasPassData& Data, FHIPCommandContext& Cmd)
             {
                 if (!Data.bEnabled) return;
-                const int rc = ur_cas(Cmd.GetContext(), &Data.K, Res.TonemapScratch, Res.TonemapBand, Res.Width, Res.Height, Res.Row0, Res.Rows);
+                const int rc = Data.bHalo
+                    ? ur_cas_halo(Cmd.GetContext(), &Data.Tonemap, &Data.K, Res.TonemapScratch, Data.HaloAbove, Data.HaloBelow, Data.ExposureEv, Res.TonemapBand,
+                                  Res.Width, Res.Height, Res.Row0, Res.Rows)
+                    : ur_cas(Cmd.GetContext(), &Data.K, Res.TonemapScratch, Res.TonemapBand, Res.Width, Res.Height, Res.Row0, Res.Rows);
                 if (rc != UR_OK && PassError == UR_OK) PassError = rc;
             });
         }
     }
-
-    Graph.Execute(Cmd);
-    LastReport = Graph.GetLastExecutionReport();
-    // :1612-1620: the luminance written this frame is next frame's history
-    if (bAutoExposure && PassError == UR_OK) {
-        bLuminanceHistoryValid = true;
-        LuminanceWriteIndex = 1u - LuminanceWriteIndex;
-    } else {
-        bLuminanceHistoryValid = false;
-    }
-    return PassError;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -303,10 +411,21 @@ struct ur_frame
     bool bKernelEvents = false; // UR_FRAME_TIME_LIGHTING_KERNEL: the pair rides on the Lighting dispatch itself, nothing is recorded around it
     bool bStartOnCull = false;  // ... and this frame's START event was handed to the cull launch directly in front of the Lighting launch
     ur_frame_post Post = {{nullptr, nullptr}, nullptr, 0.0f, 0.9f, 2.2f, 0.3f, 0.1f, 5.0f, 3.0f, 1.0f, 0.5f}; // ur_frame_set_post
+    void* PostRecord = nullptr;        // ur_frame_set_post_records
+    const void* PostRecords = nullptr;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
 };
 
 extern "C" {
+
+// rows [row0, row0 + rows) are rank's band of `world_size` equal bands of a frame of `height` rows (dist.plan_bands)
+static bool equal_band(const ur_frame* f, uint32_t height, uint32_t row0, uint32_t rows)
+{
+    const int world = f->Cmd.GetWorldSize(), rank = f->Cmd.GetRank();
+    if (world < 1 || rank < 0 || rank >= world || height % static_cast<uint32_t>(world) != 0) return false;
+    const uint32_t band = height / static_cast<uint32_t>(world);
+    return rows == band && row0 == static_cast<uint32_t>(rank) * band;
+}
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size)
 {
@@ -393,9 +512,17 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
         if (!(flags & UR_FRAME_TONEMAP) || !r->tonemap_band) { ur::set_error("ur_frame_render: AUTO_EXPOSURE / CAS need UR_FRAME_TONEMAP and a tonemap_band"); return UR_EINVAL; }
         if ((flags & UR_FRAME_AUTO_EXPOSURE) && (!f->Post.luminance[0] || !f->Post.luminance[1])) { ur::set_error("ur_frame_render: AUTO_EXPOSURE needs ur_frame_set_post's luminance[2]"); return UR_EINVAL; }
         if (cas_pass && !f->Post.tonemap_scratch) { ur::set_error("ur_frame_render: a CAS pass of its own needs ur_frame_set_post's tonemap_scratch"); return UR_EINVAL; }
-        if ((flags & (UR_FRAME_AUTO_EXPOSURE | UR_FRAME_CAS)) && (r->row0 != 0 || r->rows != r->height)) {
-            ur::set_error("ur_frame_render: AutoExposure and CAS need the whole frame (rows == height); a sharded caller gathers first");
+        const bool exchange = (flags & UR_FRAME_POST_EXCHANGE) && (flags & (UR_FRAME_AUTO_EXPOSURE | UR_FRAME_CAS));
+        if ((flags & (UR_FRAME_AUTO_EXPOSURE | UR_FRAME_CAS)) && !exchange && (r->row0 != 0 || r->rows != r->height)) {
+            ur::set_error("ur_frame_render: AutoExposure and CAS need the whole frame (rows == height), or UR_FRAME_POST_EXCHANGE on a band");
             return UR_EUNSUPPORTED;
+        }
+        if (exchange) {
+            if (!f->PostRecord || !f->PostRecords) { ur::set_error("ur_frame_render: POST_EXCHANGE needs ur_frame_set_post_records"); return UR_EINVAL; }
+            if (!equal_band(f, r->height, r->row0, r->rows)) {
+                ur::set_error("ur_frame_render: POST_EXCHANGE needs rank's equal band (world_size | height)");
+                return UR_EINVAL;
+            }
         }
     }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
@@ -409,6 +536,8 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.TonemapScratch = f->Post.tonemap_scratch;
     R.Luminance[0] = f->Post.luminance[0];
     R.Luminance[1] = f->Post.luminance[1];
+    R.PostRecord = f->PostRecord;
+    R.PostRecords = f->PostRecords;
     R.DepthFull = const_cast<float*>(r->depth_full);
     R.HZB = r->hzb;
     std::memcpy(R.HZBMips, r->hzb_mips, sizeof(R.HZBMips));
@@ -446,6 +575,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bAutoExposure = (flags & UR_FRAME_AUTO_EXPOSURE) != 0;
     O.bCas = (flags & UR_FRAME_CAS) != 0;
     O.bFuseTonemapCas = (flags & UR_FRAME_FUSE_TONEMAP_CAS) != 0;
+    O.bPostExchange = (flags & UR_FRAME_POST_EXCHANGE) != 0;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -503,6 +633,24 @@ int ur_frame_set_post(ur_frame* f, const ur_frame_post* post)
 }
 
 void ur_frame_reset_post(ur_frame* f) { if (f) f->Renderer.ResetLuminanceHistory(); }
+
+int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_records)
+{
+    if (!f || !own_record || !all_records) { ur::set_error("ur_frame_set_post_records: null argument"); return UR_EINVAL; }
+    f->PostRecord = own_record;
+    f->PostRecords = all_records;
+    return UR_OK;
+}
+
+int ur_frame_finish_post(ur_frame* f)
+{
+    if (!f) { ur::set_error("ur_frame_finish_post: null argument"); return UR_EINVAL; }
+    if (!f->Renderer.IsPostPending()) { ur::set_error("ur_frame_finish_post: no post passes are pending"); return UR_EINVAL; }
+    FHotPathResources& R = f->Res;
+    if (!equal_band(f, R.Height, R.Row0, R.Rows)) { ur::set_error("ur_frame_finish_post: the band is not rank's equal band (world_size | height)"); return UR_EINVAL; }
+    R.PostRecords = f->PostRecords;
+    return f->Renderer.FinishPost(f->Cmd, R);
+}
 
 static uint32_t copy_out(const std::string& s, char* buf, uint32_t cap)
 {

@@ -31,6 +31,8 @@ struct FHotPathResources
     uint32* TonemapBand = nullptr;    // optional: R8G8B8A8_UNORM output of the Tonemap pass for this band (the back buffer)
     uint32* TonemapScratch = nullptr; // "TonemapOutput": Tonemap's output when CAS runs as its own pass
     float* Luminance[2] = {};         // LuminanceA / B: 1x1 R32_FLOAT (CreateLuminanceResources, DeferredRenderer.cpp:2692-2712)
+    void* PostRecord = nullptr;        // post exchange (new): this band's record (ur_pack_post_record) ...
+    const void* PostRecords = nullptr; // ... and every rank's, gathered in rank order (may contain PostRecord)
     // full-frame depth for the replicated HZB build, and the HZB itself
     float* DepthFull = nullptr;
     float* HZB = nullptr;
@@ -55,6 +57,8 @@ struct FHotPathResources
     uint32 TonemapState = RG_STATE_RENDER_TARGET;
     uint32 TonemapScratchState = RG_STATE_RENDER_TARGET;
     uint32 LuminanceStates[2] = {RG_STATE_UNORDERED_ACCESS, RG_STATE_UNORDERED_ACCESS};
+    uint32 PostRecordState = RG_STATE_UNORDERED_ACCESS;
+    uint32 PostRecordsState = RG_STATE_UNORDERED_ACCESS;
 };
 
 struct FHotPathFrameConstants
@@ -82,6 +86,7 @@ struct FHotPathOptions
     bool bAutoExposure = false;       // with bTonemap: AutoExposure pass before Tonemap (bAutoExposureEnabled)
     bool bCas = false;                // with bTonemap: CAS pass after Tonemap (bEnableCas)
     bool bFuseTonemapCas = false;     // MI355X fast path: Tonemap + CAS in one launch (ur_tonemap_cas), CAS pass culled
+    bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;
@@ -97,6 +102,10 @@ public:
     // Builds a fresh graph, adds the passes in the reference's order and executes it. Returns UR_OK or the first
     // error a pass reported. bHZBReady carries over between frames exactly like FDeferredRenderer::bHZBReady.
     int RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants, const FHotPathOptions& Options);
+    // The second half of a frame rendered with bPostExchange (and AutoExposure or CAS): AutoExposure, Tonemap and CAS on the band,
+    // from the gathered records (Res.PostRecords), with the frame's constants and options. UR_EINVAL if nothing is pending.
+    int FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res);
+    bool IsPostPending() const { return bPostPending; }
 
     // Optional hook: called right before / after the Lighting pass launches, on the pass's stream (used by the frame
     // object to bracket the dominant kernel with a HIP event pair without timing every pass).
@@ -108,10 +117,17 @@ public:
     const std::vector<FRenderGraph::FPassReport>& GetLastReport() const { return LastReport; }
 
 private:
+    void AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
+                       const FHotPathOptions& Options, uint32 RecordRanks);
+    void EndPostHistory(bool bAutoExposure);
+
     FHIPDevice* Device = nullptr;
     bool bHZBReady = false;
     bool bLuminanceHistoryValid = false;
     uint32 LuminanceWriteIndex = 0;
+    bool bPostPending = false;        // RenderFrame stopped at "Post Record"; FinishPost runs the rest with these
+    FHotPathFrameConstants PendingConstants;
+    FHotPathOptions PendingOptions;
     int PassError = 0;
     std::vector<FRenderGraph::FPassReport> LastReport;
     std::function<void(hipStream_t, bool)> LightingTimer;

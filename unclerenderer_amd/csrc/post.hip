@@ -50,20 +50,35 @@ struct AeParams {
     float key, ev_min, ev_max;
 };
 
-__global__ __launch_bounds__(256) void auto_exposure_kernel(AeParams p)
+// Tap (gx, gy) of AutoExposure.hlsl:27-29 and the 2x2 footprint SampleLevel(linear, clamp) of mip 0 reads around it (the
+// Lighting SRV has one mip, DeferredRenderer.cpp:3006-3007): t = uv * size - 0.5, indices clamped, weights the fractions of t.
+// The one definition of which texels a tap reads: auto_exposure_kernel samples them, post_record_kernel packs them.
+struct AeTap {
+    uint32_t x0, x1, y0, y1; // clamped texel indices of t00 = (x0, y0), t10 = (x1, y0), t01 = (x0, y1), t11 = (x1, y1)
+    float ax, ay;
+};
+
+__device__ __forceinline__ AeTap ae_tap(uint32_t gx, uint32_t gy, uint32_t W, uint32_t H, float size_x, float size_y)
+{
+    const float samplePosX = ((float)gx + 0.5f) * (size_x / 16.0f), samplePosY = ((float)gy + 0.5f) * (size_y / 16.0f);
+    const float u = samplePosX / fmaxf(size_x, 1.0f), v = samplePosY / fmaxf(size_y, 1.0f);
+    const float tx = u * (float)W - 0.5f, ty = v * (float)H - 0.5f;
+    const float fx = floorf(tx), fy = floorf(ty);
+    const int ix = (int)fx, iy = (int)fy, mx = (int)W - 1, my = (int)H - 1;
+    return AeTap{(uint32_t)min(max(ix, 0), mx), (uint32_t)min(max(ix + 1, 0), mx), (uint32_t)min(max(iy, 0), my), (uint32_t)min(max(iy + 1, 0), my),
+                 tx - fx, ty - fy};
+}
+
+// The whole AutoExposure pass for one 256-lane workgroup; fetch(corner, x, y) returns texel (x, y) of the lane's tap, corner 0..3 =
+// t00, t10, t01, t11. Both kernels below share every operation after the fetch, so the same texels give the same bits.
+template <class Fetch>
+__device__ __forceinline__ void ae_body(const AeParams& p, Fetch fetch)
 {
     const uint32_t index = threadIdx.x, gx = index & 15u, gy = index >> 4; // GroupThreadId.xy of [numthreads(16,16,1)]
-    // AutoExposure.hlsl:27-29
-    const float samplePosX = ((float)gx + 0.5f) * (p.size_x / 16.0f), samplePosY = ((float)gy + 0.5f) * (p.size_y / 16.0f);
-    const float u = samplePosX / fmaxf(p.size_x, 1.0f), v = samplePosY / fmaxf(p.size_y, 1.0f);
-    // SampleLevel(linear, clamp) of mip 0 (the Lighting SRV has one mip, DeferredRenderer.cpp:3006-3007): the 2x2 footprint
-    // around t = uv * size - 0.5, indices clamped, weights the fractions of t, blended as two lerps along x then one along y
-    const float tx = u * (float)p.W - 0.5f, ty = v * (float)p.H - 0.5f;
-    const float fx = floorf(tx), fy = floorf(ty), ax = tx - fx, ay = ty - fy;
-    const int ix = (int)fx, iy = (int)fy, mx = (int)p.W - 1, my = (int)p.H - 1;
-    const size_t x0 = (size_t)min(max(ix, 0), mx), x1 = (size_t)min(max(ix + 1, 0), mx);
-    const size_t y0 = (size_t)min(max(iy, 0), my) * p.W, y1 = (size_t)min(max(iy + 1, 0), my) * p.W;
-    const half4_t t00 = p.hdr[y0 + x0], t10 = p.hdr[y0 + x1], t01 = p.hdr[y1 + x0], t11 = p.hdr[y1 + x1];
+    const AeTap t = ae_tap(gx, gy, p.W, p.H, p.size_x, p.size_y);
+    const float ax = t.ax, ay = t.ay;
+    const half4_t t00 = fetch(0u, t.x0, t.y0), t10 = fetch(1u, t.x1, t.y0), t01 = fetch(2u, t.x0, t.y1), t11 = fetch(3u, t.x1, t.y1);
+    // the blend: two lerps along x then one along y
     float c[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -94,6 +109,52 @@ __global__ __launch_bounds__(256) void auto_exposure_kernel(AeParams p)
         adapted = previousLog + fminf(fmaxf(alpha, 0.0f), 1.0f) * (targetExposureEv - previousLog); // lerp(prev, target, saturate(alpha))
     }
     p.out[0] = adapted;
+}
+
+__global__ __launch_bounds__(256) void auto_exposure_kernel(AeParams p)
+{
+    ae_body(p, [&](uint32_t, uint32_t x, uint32_t y) { return p.hdr[(size_t)y * p.W + x]; });
+}
+
+// ---- the post record of a row band (include/ur_hotpath.h, ur_post_record_bytes) -------------------------------------------
+// half4 slots: [0, W) the band's first row, [W, 2W) its last row, [2W, 2W + 1024) the 4 texels of each of the 256 taps (ae_tap) in
+// tap order. A tap texel is written by the band that holds its row, zero by every other band: equal bands, owner = y / (H / N).
+constexpr uint32_t kTapTexels = 1024u;
+
+struct PackParams {
+    const half4_t* band; // rows [row0, row0 + rows) of the W x H frame
+    half4_t* record;
+    uint32_t W, H, row0, rows;
+};
+
+__global__ __launch_bounds__(256) void post_record_kernel(PackParams p)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x, W = p.W;
+    if (j < 2u * W) {
+        p.record[j] = j < W ? p.band[j] : p.band[(size_t)(p.rows - 1u) * W + (j - W)];
+        return;
+    }
+    const uint32_t s = j - 2u * W;
+    if (s >= kTapTexels) return;
+    const uint32_t i = s >> 2, corner = s & 3u;
+    const AeTap t = ae_tap(i & 15u, i >> 4, W, p.H, (float)W, (float)p.H); // InputSize == (W, H), as ur_auto_exposure requires
+    const uint32_t x = (corner & 1u) ? t.x1 : t.x0, y = (corner & 2u) ? t.y1 : t.y0;
+    half4_t v = {0, 0, 0, 0};
+    if (y >= p.row0 && y - p.row0 < p.rows) v = p.band[(size_t)(y - p.row0) * W + x];
+    p.record[j] = v;
+}
+
+struct AeRecordsParams {
+    AeParams ae;             // hdr unused
+    const half4_t* records;  // n_ranks records of record_texels half4 each, in rank order
+    uint32_t record_texels, band_rows;
+};
+
+// auto_exposure_kernel with every texel read from its owner's record
+__global__ __launch_bounds__(256) void ae_records_kernel(AeRecordsParams q)
+{
+    const uint32_t slot = 2u * q.ae.W + threadIdx.x * 4u;
+    ae_body(q.ae, [&](uint32_t corner, uint32_t, uint32_t y) { return q.records[(size_t)(y / q.band_rows) * q.record_texels + slot + corner]; });
 }
 
 // ---- CAS ------------------------------------------------------------------------------------------------------------
@@ -160,10 +221,43 @@ __device__ __forceinline__ Px readlane(const Px& v, int lane)
     return Px{rl(v.r), rl(v.g), rl(v.b), rl(v.l)};
 }
 
-// FUSED: tonemap HDR rows on the way in. PX: pixels per lane - 2 (even width; 16-B aligned HDR / 8-B aligned RGBA8 rows: one
-// 16- or 8-byte load and one 8-byte store per lane and row) or 1 (any width and alignment).
-template <bool FUSED, int PX>
-__global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
+// What the input rows of a strip are: Ldr - R8G8B8A8; Hdr - RGBA16F, tonemapped on the way in (the fused form); LdrHdrHalo - the
+// band's rows R8G8B8A8 (ur_tonemap's output), the two rows around the band RGBA16F, tonemapped here (ur_cas_halo).
+enum class In { Ldr, Hdr, LdrHdrHalo };
+
+// Where input row y (a frame row, already clamped to the frame) is. FrameRows: the full image (cas_strip_kernel). BandRows: a
+// band-local image and one row above and one below it (cas_halo_kernel), each its own pointer; a strip's rows are uniform per wave,
+// so the choice is scalar. Rows further out than the halo rows only feed output rows that are not stored: they read the halo row.
+struct FrameRows {
+    const void* src;
+    uint32_t W;
+    __device__ __forceinline__ bool halo(uint32_t) const { return false; }
+    template <class T> __device__ __forceinline__ const T* row(uint32_t y) const { return static_cast<const T*>(src) + (size_t)y * W; }
+    template <class P> __device__ __forceinline__ const P* pairs(uint32_t y) const { return static_cast<const P*>(src) + (((size_t)y * W) >> 1); }
+    template <class T> __device__ __forceinline__ T texel(uint32_t y, uint32_t x) const { return static_cast<const T*>(src)[(size_t)y * W + x]; }
+};
+
+struct BandRows {
+    const void* band;
+    const void* above; // row row0 - 1 (null iff row0 == 0: never selected then)
+    const void* below; // row row0 + rows (null iff row0 + rows == H)
+    uint32_t W, row0, rows;
+    __device__ __forceinline__ bool halo(uint32_t y) const { return y < row0 || y - row0 >= rows; }
+    template <class T> __device__ __forceinline__ const T* row(uint32_t y) const
+    {
+        return y < row0 ? static_cast<const T*>(above) : y - row0 >= rows ? static_cast<const T*>(below) : static_cast<const T*>(band) + (size_t)(y - row0) * W;
+    }
+    template <class P> __device__ __forceinline__ const P* pairs(uint32_t y) const
+    {
+        return y < row0 ? static_cast<const P*>(above) : y - row0 >= rows ? static_cast<const P*>(below) : static_cast<const P*>(band) + (((size_t)(y - row0) * W) >> 1);
+    }
+    template <class T> __device__ __forceinline__ T texel(uint32_t y, uint32_t x) const { return row<T>(y)[x]; }
+};
+
+// One strip of CAS output (see the file comment). PX: pixels per lane - 2 (even width; 16-B aligned HDR / 8-B aligned RGBA8 rows:
+// one 16- or 8-byte load and one 8-byte store per lane and row) or 1 (any width and alignment).
+template <In MODE, int PX, class Rows>
+__device__ __forceinline__ void cas_strip(const CasParams& p, const Rows& src)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t x0 = (blockIdx.x * 4u + wave) * (64u * PX); // the wave's first column; the four waves side by side
@@ -173,27 +267,25 @@ __global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
     const int maxy = (int)p.H - 1;
     const uint32_t maxx = p.W - 1u, px0 = x0 + lane * PX;       // the lane's first column
     const bool beyond = px0 > maxx;                             // lanes right of the frame repeat the last column
-    const float finalExposure = FUSED ? final_exposure(p.tm) : 0.0f;
+    const float finalExposure = MODE != In::Ldr ? final_exposure(p.tm) : 0.0f;
     // input row k (0 .. kRows + 1) = frame row row0 + rb0 - 1 + k, clamped (the taps' clamp at the top and bottom edges)
-    auto row_offset = [&](int k) -> size_t { return (size_t)(uint32_t)min(max((int)(p.row0 + rb0) - 1 + k, 0), maxy) * p.W; };
+    auto frame_row = [&](int k) -> uint32_t { return (uint32_t)min(max((int)(p.row0 + rb0) - 1 + k, 0), maxy); };
     auto interior = [&](int k) { return k >= 1 && k <= kRows; }; // the strip's own rows (nontemporal; its halo rows are other strips' own)
 
     // ---- the load phase: kRows + 2 rows, and the texels left / right of the strip (lane j < kRows + 2: row j's left one,
     // lane 32 + j: its right one), all in flight before the first is used
     const uint32_t hx = lane < 32u ? (x0 == 0u ? 0u : x0 - 1u) : min(x0 + 64u * PX, maxx);
-    const size_t hoff = row_offset((int)min(lane & 31u, (uint32_t)kRows + 1u)) + hx;
+    const uint32_t hy = frame_row((int)min(lane & 31u, (uint32_t)kRows + 1u));
     uint32_t halo;
     Px rowA[kRows + 2], rowB[kRows + 2]; // the lane's pixel(s) of each input row (rowB: PX == 2 only)
-    if constexpr (FUSED) {
-        const half4_t* hdr = static_cast<const half4_t*>(p.src);
-        const half4_t hh = hdr[hoff];
+    if constexpr (MODE == In::Hdr) {
+        const half4_t hh = src.template texel<half4_t>(hy, hx);
         if constexpr (PX == 2) {
-            const u32x4_t* src = static_cast<const u32x4_t*>(p.src);
             const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
             u32x4_t v[kRows + 2];
 #pragma unroll
             for (int k = 0; k < kRows + 2; ++k) {
-                const u32x4_t* a = src + (row_offset(k) >> 1) + pair;
+                const u32x4_t* a = src.template pairs<u32x4_t>(frame_row(k)) + pair;
                 v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
             }
             halo = tonemap_pixel(p.tm, finalExposure, hh);
@@ -209,21 +301,22 @@ __global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
             const size_t x = min(px0, maxx);
             half4_t v[kRows + 2];
 #pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) v[k] = interior(k) ? __builtin_nontemporal_load(hdr + row_offset(k) + x) : hdr[row_offset(k) + x];
+            for (int k = 0; k < kRows + 2; ++k) {
+                const half4_t* a = src.template row<half4_t>(frame_row(k)) + x;
+                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
+            }
             halo = tonemap_pixel(p.tm, finalExposure, hh);
 #pragma unroll
             for (int k = 0; k < kRows + 2; ++k) rowA[k] = unpack(tonemap_pixel(p.tm, finalExposure, v[k]));
         }
-    } else {
-        const uint32_t* ldr = static_cast<const uint32_t*>(p.src);
-        halo = ldr[hoff];
+    } else if constexpr (MODE == In::Ldr) {
+        halo = src.template texel<uint32_t>(hy, hx);
         if constexpr (PX == 2) {
-            const u32x2_t* src = static_cast<const u32x2_t*>(p.src);
             const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
             u32x2_t v[kRows + 2];
 #pragma unroll
             for (int k = 0; k < kRows + 2; ++k) {
-                const u32x2_t* a = src + (row_offset(k) >> 1) + pair;
+                const u32x2_t* a = src.template pairs<u32x2_t>(frame_row(k)) + pair;
                 v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
             }
 #pragma unroll
@@ -232,9 +325,63 @@ __global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
             const size_t x = min(px0, maxx);
             uint32_t v[kRows + 2];
 #pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) v[k] = interior(k) ? __builtin_nontemporal_load(ldr + row_offset(k) + x) : ldr[row_offset(k) + x];
+            for (int k = 0; k < kRows + 2; ++k) {
+                const uint32_t* a = src.template row<uint32_t>(frame_row(k)) + x;
+                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
+            }
 #pragma unroll
             for (int k = 0; k < kRows + 2; ++k) rowA[k] = unpack(v[k]);
+        }
+    } else { // LdrHdrHalo: per row (uniform) an RGBA8 band row or an RGBA16F halo row; the strip's side texel per lane
+        const bool hh = src.halo(hy);
+        halo = hh ? tonemap_pixel(p.tm, finalExposure, src.template texel<half4_t>(hy, hx)) : src.template texel<uint32_t>(hy, hx);
+        if constexpr (PX == 2) {
+            const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
+            u32x4_t v[kRows + 2]; // RGBA8 rows in .xy
+#pragma unroll
+            for (int k = 0; k < kRows + 2; ++k) {
+                const uint32_t y = frame_row(k);
+                if (src.halo(y)) {
+                    v[k] = src.template pairs<u32x4_t>(y)[pair];
+                } else {
+                    const u32x2_t* a = src.template pairs<u32x2_t>(y) + pair;
+                    const u32x2_t l = interior(k) ? __builtin_nontemporal_load(a) : *a;
+                    v[k] = u32x4_t{l.x, l.y, 0u, 0u};
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kRows + 2; ++k) {
+                uint32_t ta, tb;
+                if (src.halo(frame_row(k))) {
+                    union { u32x2_t u; half4_t h; } a, b;
+                    a.u = u32x2_t{v[k].x, v[k].y}; b.u = u32x2_t{v[k].z, v[k].w};
+                    tb = tonemap_pixel(p.tm, finalExposure, b.h);
+                    ta = beyond ? tb : tonemap_pixel(p.tm, finalExposure, a.h);
+                } else {
+                    tb = v[k].y;
+                    ta = beyond ? v[k].y : v[k].x;
+                }
+                rowA[k] = unpack(ta); rowB[k] = unpack(tb);
+            }
+        } else {
+            const size_t x = min(px0, maxx);
+            u32x2_t v[kRows + 2]; // an RGBA8 row in .x
+#pragma unroll
+            for (int k = 0; k < kRows + 2; ++k) {
+                const uint32_t y = frame_row(k);
+                if (src.halo(y)) {
+                    v[k] = src.template row<u32x2_t>(y)[x];
+                } else {
+                    const uint32_t* a = src.template row<uint32_t>(y) + x;
+                    v[k] = u32x2_t{interior(k) ? __builtin_nontemporal_load(a) : *a, 0u};
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kRows + 2; ++k) {
+                union { u32x2_t u; half4_t h; } a;
+                a.u = v[k];
+                rowA[k] = unpack(src.halo(frame_row(k)) ? tonemap_pixel(p.tm, finalExposure, a.h) : v[k].x);
+            }
         }
     }
     const Px haloPx = unpack(halo);
@@ -258,19 +405,57 @@ __global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
     }
 }
 
+// FUSED: tonemap HDR rows on the way in; the input is the full image
+template <bool FUSED, int PX>
+__global__ __launch_bounds__(256) void cas_strip_kernel(CasParams p)
+{
+    cas_strip<FUSED ? In::Hdr : In::Ldr, PX>(p, FrameRows{p.src, p.W});
+}
+
+struct CasHaloParams {
+    CasParams c;         // src: the band-local input rows
+    const void* above;   // RGBA16F row row0 - 1, nullable iff row0 == 0
+    const void* below;   // RGBA16F row row0 + rows, nullable iff row0 + rows == H
+};
+
+// MODE Hdr: ur_tonemap_cas_halo; LdrHdrHalo: ur_cas_halo
+template <In MODE, int PX>
+__global__ __launch_bounds__(256) void cas_halo_kernel(CasHaloParams p)
+{
+    cas_strip<MODE, PX>(p.c, BandRows{p.c.src, p.above, p.below, p.c.W, p.c.row0, p.c.rows});
+}
+
 bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + b_bytes && y < x + a_bytes;
 }
 
-// shared checks and launch of both CAS forms
-int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, bool fused, const void* src, const TonemapParams* tm, uint32_t* out,
-               uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+TonemapParams tonemap_params(const ur_tonemap_constants* tonemap, const float* exposure_ev)
+{
+    TonemapParams tm{}; // exactly ur_tonemap's (csrc/tonemap.hip)
+    tm.exposure_ev = exposure_ev;
+    tm.enable_tonemap = tonemap->EnableTonemap;
+    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
+    tm.exposure = tonemap->Exposure;
+    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
+    return tm;
+}
+
+// shared checks and launch of every CAS form. halo: src holds the band's rows only, above / below the RGBA16F rows around it.
+int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, In mode, bool halo, const void* src, const void* above, const void* below,
+               const TonemapParams* tm, uint32_t* out, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("%s: empty or out-of-frame band", who); return UR_EINVAL; }
-    const size_t src_bytes = (size_t)w * h * (fused ? 8u : 4u), out_bytes = (size_t)w * rows * 4u;
-    if (overlaps(src, src_bytes, out, out_bytes)) { ur::set_error("%s: the output band overlaps the input frame", who); return UR_EINVAL; }
+    if (halo && ((row0 > 0 && !above) || (row0 + rows < h && !below))) {
+        ur::set_error("%s: hdr_above may be null only when row0 == 0, hdr_below only when row0 + rows == h", who);
+        return UR_EINVAL;
+    }
+    const size_t src_bytes = (size_t)w * (halo ? rows : h) * (mode == In::Hdr ? 8u : 4u), out_bytes = (size_t)w * rows * 4u, halo_bytes = (size_t)w * 8u;
+    if (overlaps(src, src_bytes, out, out_bytes) || (above && overlaps(above, halo_bytes, out, out_bytes)) || (below && overlaps(below, halo_bytes, out, out_bytes))) {
+        ur::set_error("%s: the output band overlaps the input frame", who);
+        return UR_EINVAL;
+    }
     // the taps are the 4-neighbour texels: TexelDelta must be one texel (relative tolerance for a delta computed in double)
     const float dx = 1.0f / (float)w, dy = 1.0f / (float)h;
     if (!(fabsf(cas->TexelDelta[0] - dx) <= 1e-6f * dx) || !(fabsf(cas->TexelDelta[1] - dy) <= 1e-6f * dy)) {
@@ -284,10 +469,20 @@ int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, bool f
     p.W = w; p.H = h; p.row0 = row0; p.rows = rows;
     p.sharpness = cas->Sharpness;
     if (tm) p.tm = *tm;
-    const bool pairs = (w % 2u) == 0u && (reinterpret_cast<uintptr_t>(src) & (fused ? 15u : 7u)) == 0u && (reinterpret_cast<uintptr_t>(out) & 7u) == 0u;
+    auto aligned = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) == 0u; };
+    const bool pairs = (w % 2u) == 0u && aligned(src, mode == In::Hdr ? 15u : 7u) && aligned(out, 7u) && aligned(above, 15u) && aligned(below, 15u);
     const uint32_t px = pairs ? 2u : 1u;
     const dim3 grid((w + 256u * px - 1u) / (256u * px), grid_y);
-    if (fused) {
+    if (halo) {
+        const CasHaloParams q{p, above, below};
+        if (mode == In::Hdr) {
+            if (pairs) hipLaunchKernelGGL((cas_halo_kernel<In::Hdr, 2>), grid, dim3(256), 0, ctx->stream, q);
+            else hipLaunchKernelGGL((cas_halo_kernel<In::Hdr, 1>), grid, dim3(256), 0, ctx->stream, q);
+        } else {
+            if (pairs) hipLaunchKernelGGL((cas_halo_kernel<In::LdrHdrHalo, 2>), grid, dim3(256), 0, ctx->stream, q);
+            else hipLaunchKernelGGL((cas_halo_kernel<In::LdrHdrHalo, 1>), grid, dim3(256), 0, ctx->stream, q);
+        }
+    } else if (mode == In::Hdr) {
         if (pairs) hipLaunchKernelGGL((cas_strip_kernel<true, 2>), grid, dim3(256), 0, ctx->stream, p);
         else hipLaunchKernelGGL((cas_strip_kernel<true, 1>), grid, dim3(256), 0, ctx->stream, p);
     } else {
@@ -296,6 +491,18 @@ int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, bool f
     }
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
+}
+
+AeParams ae_params(const ur_auto_exposure_constants* constants, uint32_t w, uint32_t h, const float* prev_ev, float* out_ev)
+{
+    AeParams p{};
+    p.prev = prev_ev; p.out = out_ev;
+    p.W = w; p.H = h;
+    p.size_x = constants->InputSize[0]; p.size_y = constants->InputSize[1];
+    p.delta_time = constants->DeltaTime; p.speed_up = constants->AdaptationSpeedUp; p.speed_down = constants->AdaptationSpeedDown;
+    p.use_history = constants->UseHistory;
+    p.key = constants->AutoExposureKey; p.ev_min = constants->AutoExposureMin; p.ev_max = constants->AutoExposureMax;
+    return p;
 }
 
 } // namespace
@@ -311,14 +518,8 @@ extern "C" int ur_auto_exposure(ur_ctx* ctx, const ur_auto_exposure_constants* c
         ur::set_error("ur_auto_exposure: InputSize must be (w, h) of a non-empty frame");
         return UR_EINVAL;
     }
-    AeParams p{};
+    AeParams p = ae_params(constants, w, h, prev_ev, out_ev);
     p.hdr = reinterpret_cast<const half4_t*>(hdr_full);
-    p.prev = prev_ev; p.out = out_ev;
-    p.W = w; p.H = h;
-    p.size_x = constants->InputSize[0]; p.size_y = constants->InputSize[1];
-    p.delta_time = constants->DeltaTime; p.speed_up = constants->AdaptationSpeedUp; p.speed_down = constants->AdaptationSpeedDown;
-    p.use_history = constants->UseHistory;
-    p.key = constants->AutoExposureKey; p.ev_min = constants->AutoExposureMin; p.ev_max = constants->AutoExposureMax;
     hipLaunchKernelGGL(auto_exposure_kernel, dim3(1), dim3(256), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
@@ -328,18 +529,69 @@ extern "C" int ur_cas(ur_ctx* ctx, const ur_cas_constants* constants, const uint
                       uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !constants || !ldr_full || !out_band) { ur::set_error("ur_cas: null argument"); return UR_EINVAL; }
-    return launch_cas(ctx, "ur_cas", constants, false, ldr_full, nullptr, out_band, w, h, row0, rows);
+    return launch_cas(ctx, "ur_cas", constants, In::Ldr, false, ldr_full, nullptr, nullptr, nullptr, out_band, w, h, row0, rows);
 }
 
 extern "C" int ur_tonemap_cas(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const ur_half4* hdr_full,
                               const float* exposure_ev, uint32_t* out_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !tonemap || !cas || !hdr_full || !out_band) { ur::set_error("ur_tonemap_cas: null argument"); return UR_EINVAL; }
-    TonemapParams tm{}; // exactly ur_tonemap's (csrc/tonemap.hip)
-    tm.exposure_ev = exposure_ev;
-    tm.enable_tonemap = tonemap->EnableTonemap;
-    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
-    tm.exposure = tonemap->Exposure;
-    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
-    return launch_cas(ctx, "ur_tonemap_cas", cas, true, hdr_full, &tm, out_band, w, h, row0, rows);
+    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    return launch_cas(ctx, "ur_tonemap_cas", cas, In::Hdr, false, hdr_full, nullptr, nullptr, &tm, out_band, w, h, row0, rows);
+}
+
+// ---- the post exchange of row bands ---------------------------------------------------------------------------------------
+
+extern "C" uint64_t ur_post_record_bytes(uint32_t w) { return ((uint64_t)2u * w + kTapTexels) * 8u; }
+
+extern "C" int ur_pack_post_record(ur_ctx* ctx, const ur_half4* hdr_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, void* record)
+{
+    if (!ctx || !hdr_band || !record) { ur::set_error("ur_pack_post_record: null argument"); return UR_EINVAL; }
+    if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("ur_pack_post_record: empty or out-of-frame band"); return UR_EINVAL; }
+    if (overlaps(hdr_band, (size_t)w * rows * 8u, record, ur_post_record_bytes(w))) { ur::set_error("ur_pack_post_record: the record overlaps the band"); return UR_EINVAL; }
+    PackParams p{reinterpret_cast<const half4_t*>(hdr_band), static_cast<half4_t*>(record), w, h, row0, rows};
+    const uint32_t n = 2u * w + kTapTexels;
+    hipLaunchKernelGGL(post_record_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, p);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+extern "C" int ur_auto_exposure_records(ur_ctx* ctx, const ur_auto_exposure_constants* constants, const void* records, uint32_t n_ranks, uint32_t w,
+                                        uint32_t h, const float* prev_ev, float* out_ev)
+{
+    if (!ctx || !constants || !records || !out_ev || (constants->UseHistory != 0u && !prev_ev)) {
+        ur::set_error("ur_auto_exposure_records: null argument");
+        return UR_EINVAL;
+    }
+    if (w == 0 || h == 0 || constants->InputSize[0] != (float)w || constants->InputSize[1] != (float)h) {
+        ur::set_error("ur_auto_exposure_records: InputSize must be (w, h) of a non-empty frame");
+        return UR_EINVAL;
+    }
+    if (n_ranks == 0 || h % n_ranks != 0) { ur::set_error("ur_auto_exposure_records: n_ranks must divide h (equal bands)"); return UR_EINVAL; }
+    AeRecordsParams q{};
+    q.ae = ae_params(constants, w, h, prev_ev, out_ev);
+    q.records = static_cast<const half4_t*>(records);
+    q.record_texels = 2u * w + kTapTexels;
+    q.band_rows = h / n_ranks;
+    hipLaunchKernelGGL(ae_records_kernel, dim3(1), dim3(256), 0, ctx->stream, q);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+extern "C" int ur_tonemap_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const ur_half4* hdr_band,
+                                   const ur_half4* hdr_above, const ur_half4* hdr_below, const float* exposure_ev, uint32_t* out_band,
+                                   uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    if (!ctx || !tonemap || !cas || !hdr_band || !out_band) { ur::set_error("ur_tonemap_cas_halo: null argument"); return UR_EINVAL; }
+    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    return launch_cas(ctx, "ur_tonemap_cas_halo", cas, In::Hdr, true, hdr_band, hdr_above, hdr_below, &tm, out_band, w, h, row0, rows);
+}
+
+extern "C" int ur_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_constants* cas, const uint32_t* ldr_band,
+                           const ur_half4* hdr_above, const ur_half4* hdr_below, const float* exposure_ev, uint32_t* out_band,
+                           uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    if (!ctx || !tonemap || !cas || !ldr_band || !out_band) { ur::set_error("ur_cas_halo: null argument"); return UR_EINVAL; }
+    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    return launch_cas(ctx, "ur_cas_halo", cas, In::LdrHdrHalo, true, ldr_band, hdr_above, hdr_below, &tm, out_band, w, h, row0, rows);
 }

@@ -8,6 +8,10 @@ the GPU box, "gloo" in the CPU tests). The reference is single-GPU; this is new 
     all-gathered first, then the lists are all-gathered padded to the largest count.
   * Tonemap ahead of the gather: the band is tonemapped to R8G8B8A8 on the rank that shaded it and the
     4-byte pixels are gathered instead (allgather_rows), halving the xGMI payload.
+  * AutoExposure and CAS on the bands (the post exchange, UR_FRAME_POST_EXCHANGE): each rank packs one fixed-size record - its
+    first and last HDR rows and the AutoExposure tap texels in its rows, hotpath.post_record_bytes(W) bytes - and ONE all-gather
+    of the records (allgather_post_records) lets every rank compute the single-GPU EV and tonemap and sharpen its own band
+    (Frame.finish_post); the RGBA8 bands are then gathered with allgather_rows: render -> records -> finish -> RGBA8.
   * BuildHZB: replicated (every rank builds the full chain from the full depth) — no exchange; or band-sharded
     (allgather_hzb_slices): a rank builds mips 0..4 for the 128x32 source pieces its rows own, the slices (5 contiguous runs of
     floats per rank) are exchanged peer to peer straight into place, and every rank runs the single-workgroup tail behind it.
@@ -119,6 +123,13 @@ def allgather_rows(full: torch.Tensor, band: torch.Tensor, group=None, async_op:
     """The same collective for any row-major image whose leading dimension is rows (the tonemapped R8G8B8A8 band,
     Tonemap.hlsl:57-79: 4 B/pixel instead of the HDR band's 8): `full` (H, ...) on every rank, `band` this rank's H/N rows."""
     return allgather_hdr(full, band, group=group, async_op=async_op, mode=mode)
+
+
+def allgather_post_records(all_records: torch.Tensor, own: torch.Tensor, group=None, async_op: bool = False, mode: str = "ring"):
+    """The post exchange: `all_records` (N, post_record_bytes(W)) uint8 on every rank, `own` this rank's record (may be all_records[rank]:
+    in place). The same collectives as allgather_rows, one record per rank in rank order."""
+    return allgather_rows(all_records.view(torch.uint8).view(all_records.shape[0], -1), own.view(torch.uint8).view(1, -1), group=group,
+                          async_op=async_op, mode=mode)
 
 
 def allgather_visible(visible_idx: torch.Tensor, visible_count: torch.Tensor, group=None) -> tuple[torch.Tensor, int]:

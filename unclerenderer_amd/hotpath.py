@@ -287,6 +287,18 @@ class Frame:
     def reset_post(self):
         self._L.ur_frame_reset_post(self._f)
 
+    def set_post_records(self, own_record, all_records):
+        """ur_frame_set_post_records: where UR_FRAME_POST_EXCHANGE packs this rank's record (own_record) and where finish_post reads
+        every rank's (all_records, rank order; own_record may be a view of its row). Device tensors, kept alive here."""
+        self._records_keep = (own_record, all_records)
+        _lib.check(self._L.ur_frame_set_post_records(self._f, C.c_void_p(own_record.data_ptr()), C.c_void_p(all_records.data_ptr())),
+                   "ur_frame_set_post_records")
+
+    def finish_post(self):
+        """ur_frame_finish_post: the AutoExposure / Tonemap / CAS passes of a frame rendered with UR_FRAME_POST_EXCHANGE, once the records
+        are gathered."""
+        _lib.check(self._L.ur_frame_finish_post(self._f), "ur_frame_finish_post")
+
     def report(self):
         """[(pass name, culled, transitions)] of the last executed graph."""
         n = self._L.ur_frame_report(self._f, None, 0)
@@ -363,6 +375,51 @@ def _tonemap_cas(self, hdr_full, out_band, w, h, row0=0, rows=None, exposure=1.0
 HotPath.auto_exposure = _auto_exposure
 HotPath.cas = _cas
 HotPath.tonemap_cas = _tonemap_cas
+
+
+# ---- the post exchange of row bands (include/ur_hotpath.h, ur_post_record_bytes) ----
+
+def post_record_bytes(w: int) -> int:
+    """Bytes of one rank's post record at width w: its first and last HDR rows and the 1024 AutoExposure tap texels, 8 B each."""
+    return int(_lib.load().ur_post_record_bytes(w))
+
+
+def _pack_post_record(self, hdr_band, record, w, h, row0, rows):
+    """This band's post record (rows [row0,row0+rows) of the w x h frame) into `record` (post_record_bytes(w) bytes)."""
+    _lib.check(self._L.ur_pack_post_record(self._ctx, _ptr(hdr_band), w, h, row0, rows, _ptr(record)), "ur_pack_post_record")
+
+
+def _auto_exposure_records(self, records, n_ranks, out_ev, w, h, prev_ev=None, use_history=False, delta_time=0.0, speed_up=3.0, speed_down=1.0,
+                           key=0.3, ev_min=0.1, ev_max=5.0):
+    """auto_exposure of the whole frame from n_ranks gathered records (rank order): the same bits."""
+    k = _lib.AutoExposureConstants((C.c_float * 2)(w, h), delta_time, speed_up, speed_down, int(use_history), key, ev_min, ev_max)
+    _lib.check(self._L.ur_auto_exposure_records(self._ctx, C.byref(k), _ptr(records), n_ranks, w, h, _ptr(prev_ev), _ptr(out_ev)),
+               "ur_auto_exposure_records")
+
+
+def _tonemap_cas_halo(self, hdr_band, above, below, out_band, w, h, row0, rows, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None,
+                      sharpness=0.5):
+    """tonemap_cas of rows [row0,row0+rows) from the band and the HDR rows above / below it (None at the frame's edges)."""
+    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    ck = _cas_constants(w, h, sharpness)
+    _lib.check(self._L.ur_tonemap_cas_halo(self._ctx, C.byref(tk), C.byref(ck), _ptr(hdr_band), _ptr(above), _ptr(below), _ptr(exposure_ev),
+                                           _ptr(out_band), w, h, row0, rows), "ur_tonemap_cas_halo")
+
+
+def _cas_halo(self, ldr_band, above, below, out_band, w, h, row0, rows, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None,
+              sharpness=0.5):
+    """cas of rows [row0,row0+rows) from tonemap()'s band output and the HDR rows above / below it, tonemapped with the same constants."""
+    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    ck = _cas_constants(w, h, sharpness)
+    _lib.check(self._L.ur_cas_halo(self._ctx, C.byref(tk), C.byref(ck), _ptr(ldr_band), _ptr(above), _ptr(below), _ptr(exposure_ev),
+                                   _ptr(out_band), w, h, row0, rows), "ur_cas_halo")
+
+
+HotPath.post_record_bytes = staticmethod(post_record_bytes)
+HotPath.pack_post_record = _pack_post_record
+HotPath.auto_exposure_records = _auto_exposure_records
+HotPath.tonemap_cas_halo = _tonemap_cas_halo
+HotPath.cas_halo = _cas_halo
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

@@ -141,6 +141,7 @@ UR_FRAME_HZB_SHARD = 0x20000
 UR_FRAME_AUTO_EXPOSURE = 0x40000
 UR_FRAME_CAS = 0x80000
 UR_FRAME_FUSE_TONEMAP_CAS = 0x100000
+UR_FRAME_POST_EXCHANGE = 0x200000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -186,6 +187,11 @@ SIGNATURES = {
     "ur_auto_exposure": (C.c_int, [_VP, C.POINTER(AutoExposureConstants), _VP, _U32, _U32, _VP, _VP]),
     "ur_cas": (C.c_int, [_VP, C.POINTER(CasConstants), _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_tonemap_cas": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
+    "ur_post_record_bytes": (C.c_uint64, [_U32]),
+    "ur_pack_post_record": (C.c_int, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
+    "ur_auto_exposure_records": (C.c_int, [_VP, C.POINTER(AutoExposureConstants), _VP, _U32, _U32, _U32, _VP, _VP]),
+    "ur_tonemap_cas_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
+    "ur_cas_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes_ex": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.c_int]),
@@ -211,6 +217,8 @@ SIGNATURES = {
     "ur_frame_reset_hzb": (None, [_VP]),
     "ur_frame_set_post": (C.c_int, [_VP, C.POINTER(FramePost)]),
     "ur_frame_reset_post": (None, [_VP]),
+    "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
+    "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
