@@ -109,6 +109,12 @@ int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_rec
  * fused) CAS, with the luminance ping-pong and history of the unsplit frame. UR_EINVAL if nothing is pending or the band is not
  * rank's equal band. ur_frame_report then lists both halves in order. */
 int ur_frame_finish_post(ur_frame* f);
+/* Draw ranges of the "GPU Culling" pass (include/ur_hotpath.h, ur_draw_ranges) for the frames that follow: the pass then calls
+ * ur_cull_indirect_args_draws, on the async-compute lane too, and fills commands / counts beside the InstanceCount words. The pass list,
+ * its culling and ur_frame_report are the same with and without ranges; a frame whose cull pass does not run leaves commands and counts
+ * alone. Offsets are local to the frame's indirect_args (a rank's command slice). NULL clears them. The pointers must stay valid while
+ * frames use them. UR_EINVAL for a null frame, a null member or range_count == 0. */
+int ur_frame_set_draw_ranges(ur_frame* f, const ur_draw_ranges* draws);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

@@ -277,6 +277,29 @@ int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_fl
                              uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count,
                              uint32_t index_base);
 
+/* Draw ranges: compacted indirect draw commands and a draw count per range, for a count-buffer draw
+ * (D3D12 ExecuteIndirect(sig, Range.Count, commands, Range.Start * 64, counts, r * 4); Vulkan vkCmdDrawIndexedIndirectCount).
+ * Range r is commands [offsets[r], offsets[r+1]) of indirect_args (the reference's FIndirectDrawRanges, DeferredRenderer.cpp:3327-3360).
+ * A command is visible when the call sets its InstanceCount word to 1. For each range the call writes counts[r] = its visible
+ * commands, and those commands, in ascending order, to command slots offsets[r], offsets[r]+1, ... of `commands`: bytes 0-43 and
+ * 48-63 as in indirect_args, dword 11 (InstanceCount) = 1. Slots [offsets[r] + counts[r], offsets[r+1]) are not written.
+ * Offsets are local to indirect_args (index_base changes nothing here). The same bytes under every UR_OPT_CULL_STORE flavour. */
+typedef struct ur_draw_ranges {
+    const uint32_t* offsets;  /* device u32[range_count + 1]: offsets[0] = 0, non-decreasing, offsets[range_count] = ModelCount
+                                 (a precondition the call does not check) */
+    uint32_t range_count;     /* >= 1; empty ranges allowed */
+    void* commands;           /* device, ModelCount * 64 B, 16-byte aligned; must not overlap indirect_args */
+    uint32_t* counts;         /* device u32[range_count] */
+} ur_draw_ranges;
+/* ur_cull_indirect_args_ex plus the draw ranges (draws == NULL: exactly ur_cull_indirect_args_ex). The InstanceCount words, stats2 and
+ * the optional list are written as there. Launches: one for <= 256 instances (also when ModelCount == 0: it zeroes every counts[r]),
+ * two above; the last carries ur_time_next_cull's event. indirect_args must be 16-byte aligned when ranges are given.
+ * UR_EINVAL, nothing launched: a null member of draws, range_count == 0, commands overlapping indirect_args, a misaligned buffer. */
+int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds,
+                                const float* hzb_base, const ur_mip_desc* mips, void* indirect_args,
+                                uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count,
+                                uint32_t index_base, const ur_draw_ranges* draws);
+
 /* ---- DeferredLighting / SkyAtmosphere ---------------------------------------------------------- */
 
 /* Number of half4 units (8 bytes) ur_stage_env_cube() writes for (base_size, mip_count): the bordered faces, 6 (N+2)^2 texels per mip,

@@ -13,6 +13,10 @@
 // atomic append): pass 1 stores per-wave masks and per-workgroup counts, pass 2 (one thread per mask) takes the exclusive
 // prefix of the counts and writes out the set bits of its mask. Up to 256 instances (Sponza 25, pica_pica 170) both passes
 // run inside one launch.
+//
+// Draw ranges (ur_cull_indirect_args_draws): the same two passes also place every visible command of range r, whole, at command
+// slots offsets[r], offsets[r] + 1, ... of a second buffer and write counts[r], for ExecuteIndirect / vkCmdDrawIndexedIndirectCount
+// with a count buffer. The work is the RANGES template parameter: the instantiations without it are the kernels as they were.
 
 #include "ur_internal.h"
 #include "ur_device.h"
@@ -43,6 +47,18 @@ struct CullParams {
     uint32_t mip_width[UR_MAX_HZB_MIPS];
     unsigned long long* timeline; // debug: {first entry, last exit} of this launch (ur_debug_timeline), else null
 };
+
+// ur_draw_ranges on the device
+struct DrawParams {
+    const uint32_t* offsets; // [range_count + 1], offsets[0] = 0, non-decreasing, offsets[range_count] = ModelCount
+    uint8_t* commands;
+    uint32_t* counts;
+    uint32_t range_count;
+};
+
+// The kernel arguments: CullParams alone without ranges (the layout the kernels always had), CullParams + DrawParams with them
+template <bool RANGES> struct CullArgs : CullParams { DrawParams D; };
+template <> struct CullArgs<false> : CullParams {};
 
 __device__ __forceinline__ float saturate_f(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
@@ -123,8 +139,77 @@ __device__ __forceinline__ void ScatterBlock(const CullParams& C, uint32_t block
     }
 }
 
-template <bool SINGLE_BLOCK>
-__global__ __launch_bounds__(256) void cull_kernel(CullParams C)
+// The range r in [lo, hi) holding command i: offsets[r] <= i < offsets[r + 1] (needs offsets[lo] <= i < offsets[hi]).
+__device__ __forceinline__ uint32_t RangeOf(const uint32_t* offsets, uint32_t lo, uint32_t hi, uint32_t i)
+{
+    while (lo + 1u < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The command whose mask writes counts[r]: a non-empty range's last, an empty range's first (the last command if it starts at n).
+// Non-decreasing in r, so the ranges one compaction workgroup writes are a run found by binary search.
+__device__ __forceinline__ uint32_t CountOwner(const uint32_t* offsets, uint32_t r, uint32_t n)
+{
+    const uint32_t o0 = offsets[r], o1 = offsets[r + 1u];
+    return min(o1 > o0 ? o1 - 1u : o0, n - 1u);
+}
+
+// The first range in [0, R) whose count owner is >= t (R if none).
+__device__ __forceinline__ uint32_t FirstRangeOwnedFrom(const uint32_t* offsets, uint32_t R, uint32_t n, uint32_t t)
+{
+    uint32_t lo = 0, hi = R;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (CountOwner(offsets, mid, n) < t) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One 64-byte command, InstanceCount (dword 11) set to 1 instead of read: four 16-byte loads, four 16-byte stores.
+__device__ __forceinline__ void CopyCommand(const uint8_t* args, uint8_t* commands, uint32_t src, uint32_t dst)
+{
+    const uint4* s = reinterpret_cast<const uint4*>(args + (size_t)src * UR_INDIRECT_COMMAND_STRIDE);
+    uint4* d = reinterpret_cast<uint4*>(commands + (size_t)dst * UR_INDIRECT_COMMAND_STRIDE);
+    const uint4 a = s[0], b = s[1], e = s[3];
+    uint4 c = s[2];
+    c.w = 1u;
+    d[0] = a; d[1] = b; d[2] = c; d[3] = e;
+}
+
+// Visible commands below x (<= 256) of the single block, from its four wave masks.
+__device__ __forceinline__ uint32_t BlockRankAt(const uint64_t* masks, uint32_t x)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4u; ++w) {
+        const uint32_t lo = w * 64u;
+        if (x >= lo + 64u) r += (uint32_t)__popcll(masks[w]);
+        else if (x > lo) r += (uint32_t)__popcll(masks[w] & ((1ull << (x - lo)) - 1ull));
+    }
+    return r;
+}
+
+// The single block's ranges: each visible command goes to offsets[r] + (visible in r before it); counts[r] from the masks.
+// (A destination past the commands can only come from offsets that break the documented precondition: it is skipped.)
+__device__ __forceinline__ void PlaceBlock(const DrawParams& D, const uint8_t* args, const uint64_t* masks, uint32_t n)
+{
+    const uint32_t tid = threadIdx.x;
+    if (tid < n && ((masks[tid >> 6] >> (tid & 63u)) & 1ull)) {
+        const uint32_t r = RangeOf(D.offsets, 0, D.range_count, tid);
+        const uint32_t start = D.offsets[r];
+        const uint32_t dst = start + BlockRankAt(masks, tid) - BlockRankAt(masks, start);
+        if (dst < n) CopyCommand(args, D.commands, tid, dst);
+    }
+    for (uint32_t r = tid; r < D.range_count; r += 256u) D.counts[r] = BlockRankAt(masks, D.offsets[r + 1u]) - BlockRankAt(masks, D.offsets[r]);
+}
+
+template <bool SINGLE_BLOCK, bool RANGES>
+__global__ __launch_bounds__(256) void cull_kernel(CullArgs<RANGES> C)
 {
     __shared__ float4 sb[512];
     __shared__ uint64_t smask[4];
@@ -219,7 +304,7 @@ __global__ __launch_bounds__(256) void cull_kernel(CullParams C)
         }
     }
 
-    if (C.visible_idx == nullptr) { // uniform
+    if (!RANGES && C.visible_idx == nullptr) { // uniform (with ranges the masks are needed below, list or not)
         if (!SINGLE_BLOCK && C.store_flavour == 4u) { // the record of what the command buffer holds now (a launch with a list writes it below)
             const uint64_t m = __ballot(visible);
             if (lane == 0) C.wave_masks[(size_t)blockIdx.x * 4u + wave] = m;
@@ -231,8 +316,11 @@ __global__ __launch_bounds__(256) void cull_kernel(CullParams C)
     if (lane == 0) smask[wave] = mask;
     __syncthreads();
     if (SINGLE_BLOCK) {
-        ScatterBlock(C, 0, smask, 0);
-        if (tid == 0) *C.visible_count = __popcll(smask[0]) + __popcll(smask[1]) + __popcll(smask[2]) + __popcll(smask[3]);
+        if (!RANGES || C.visible_idx != nullptr) {
+            ScatterBlock(C, 0, smask, 0);
+            if (tid == 0) *C.visible_count = __popcll(smask[0]) + __popcll(smask[1]) + __popcll(smask[2]) + __popcll(smask[3]);
+        }
+        if constexpr (RANGES) PlaceBlock(C.D, C.args, smask, C.ModelCount); // (each visible lane copies the command whose word it stored)
     } else {
         if (lane == 0) C.wave_masks[(size_t)blockIdx.x * 4u + wave] = mask;
         if (tid == 0) C.block_counts[blockIdx.x] = __popcll(smask[0]) + __popcll(smask[1]) + __popcll(smask[2]) + __popcll(smask[3]);
@@ -243,9 +331,16 @@ __global__ __launch_bounds__(256) void cull_kernel(CullParams C)
 // Pass 2: one thread per wave mask (64 instances), one workgroup per 256 masks = 64 cull blocks. The workgroup's base is
 // the sum of the block counts in front of it (a few loads per thread), a thread's offset the exclusive scan of the mask
 // popcounts inside the workgroup; the few set bits of a mask are written out in ascending order.
-__global__ __launch_bounds__(256) void compact_kernel(CullParams C, uint32_t num_blocks)
+// RANGES: a visible command i of range r goes to slot offsets[r] + rank(i) - rank(offsets[r]) (rank = visible commands in front).
+// The ranks inside the workgroup's span of 16384 commands are its threads' prefixes + popcounts (in LDS); the one range start in
+// front of the span that matters - that of the range holding the span's first command - is summed in the same sweep over the
+// block counts (a second accumulator up to that start's block) plus the masks of its block below it. counts[r] is written by
+// the workgroup that holds CountOwner(r).
+template <bool RANGES>
+__global__ __launch_bounds__(256) void compact_kernel(CullArgs<RANGES> C, uint32_t num_blocks)
 {
     __shared__ uint32_t spart[4], swave[4];
+    [[maybe_unused]] __shared__ uint32_t spart2[4]; // RANGES
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t num_masks = num_blocks * 4u, mi = blockIdx.x * 256u + tid;
     const uint64_t m = mi < num_masks ? C.wave_masks[mi] : 0ull;
@@ -253,13 +348,29 @@ __global__ __launch_bounds__(256) void compact_kernel(CullParams C, uint32_t num
     // workgroups of a 1 M-instance cull wait for fifteen memory round trips in a row), then the rare rest
     uint32_t s = 0;
     const uint32_t limit = blockIdx.x * 64u;
+    // RANGES: span_start = the span's first command, r0 = the range holding it, s0 = that range's start (<= span_start), s0_block its block
+    const uint32_t span_start = blockIdx.x * 16384u;
+    uint32_t r0 = 0, s0 = 0, s0_block = 0, s2 = 0;
     if (limit != 0u) { // uniform
         uint32_t part[16];
 #pragma unroll
         for (uint32_t k = 0; k < 16u; ++k) part[k] = C.block_counts[min(tid + k * 256u, limit - 1u)];
+        if constexpr (RANGES) { // (uniform: scalar loads, under the vector loads above)
+            r0 = RangeOf(C.D.offsets, 0, C.D.range_count, span_start);
+            s0 = C.D.offsets[r0];
+            s0_block = s0 >> 8;
+        }
 #pragma unroll
         for (uint32_t k = 0; k < 16u; ++k) s += tid + k * 256u < limit ? part[k] : 0u;
-        for (uint32_t b = tid + 4096u; b < limit; b += 256u) s += C.block_counts[b];
+        if constexpr (RANGES) {
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; ++k) s2 += tid + k * 256u < s0_block ? part[k] : 0u;
+        }
+        for (uint32_t b = tid + 4096u; b < limit; b += 256u) {
+            const uint32_t v = C.block_counts[b];
+            s += v;
+            if constexpr (RANGES) s2 += b < s0_block ? v : 0u;
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -273,9 +384,55 @@ __global__ __launch_bounds__(256) void compact_kernel(CullParams C, uint32_t num
     }
     if (lane == 0) spart[wave] = s;
     if (lane == 63) swave[wave] = incl;
+    if constexpr (RANGES) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
+        if (lane == 0) spart2[wave] = s2;
+    }
     __syncthreads();
     uint32_t at = spart[0] + spart[1] + spart[2] + spart[3] + incl - c;
     for (uint32_t w = 0; w < wave; ++w) at += swave[w];
+    if constexpr (RANGES) {
+        __shared__ uint32_t sat[257];
+        __shared__ uint64_t sbits[256];
+        const DrawParams& D = C.D;
+        const uint32_t n = C.ModelCount;
+        // rank(s0): the blocks in front of its block, then its block's masks below it (s0 == span_start: nothing more)
+        uint32_t rank_s0 = spart2[0] + spart2[1] + spart2[2] + spart2[3];
+        for (uint32_t j = s0_block * 4u; j < (s0 >> 6); ++j) rank_s0 += (uint32_t)__popcll(C.wave_masks[j]);
+        if (s0 & 63u) rank_s0 += (uint32_t)__popcll(C.wave_masks[s0 >> 6] & ((1ull << (s0 & 63u)) - 1ull));
+        sat[tid] = at;
+        sbits[tid] = m;
+        if (tid == 255u) sat[256] = at + c;
+        // the ranges whose counts this workgroup writes, and the last range a command of the span can lie in
+        const uint32_t r_first = FirstRangeOwnedFrom(D.offsets, D.range_count, n, span_start);
+        const uint32_t r_end = FirstRangeOwnedFrom(D.offsets, D.range_count, n, span_start + 16384u);
+        const uint32_t r_hi = min(r_end + 1u, D.range_count);
+        __syncthreads();
+        // rank(x) for x = s0 or x in (span_start, span_start + 16384]
+        auto rank_at = [&](uint32_t x) -> uint32_t {
+            if (x < span_start) return rank_s0;
+            const uint32_t d = x - span_start;
+            if (d >= 16384u) return sat[256];
+            return sat[d >> 6] + (uint32_t)__popcll(sbits[d >> 6] & ((1ull << (d & 63u)) - 1ull));
+        };
+        uint64_t bits = m;
+        uint32_t rank = at, r = r0;
+        while (bits) {
+            const uint32_t i = mi * 64u + (uint32_t)__builtin_ctzll(bits);
+            r = RangeOf(D.offsets, r, r_hi, i);
+            const uint32_t start = D.offsets[r];
+            const uint32_t dst = start + rank - rank_at(start);
+            if (dst < n) CopyCommand(C.args, D.commands, i, dst); // (only offsets that break the precondition could send it further)
+            ++rank;
+            bits &= bits - 1ull;
+        }
+        for (uint32_t q = r_first + tid; q < r_end; q += 256u) {
+            const uint32_t o0 = D.offsets[q], o1 = D.offsets[q + 1u];
+            D.counts[q] = o1 > o0 ? rank_at(o1) - rank_at(o0) : 0u;
+        }
+        if (C.visible_idx == nullptr) return; // (the list is optional with ranges)
+    }
     uint64_t bits = m;
     const uint32_t first = mi * 64u + C.index_base;
     while (bits) {
@@ -286,22 +443,52 @@ __global__ __launch_bounds__(256) void compact_kernel(CullParams C, uint32_t num
     if (mi == num_masks - 1u) *C.visible_count = at;
 }
 
+__global__ void zero_counts_kernel(uint32_t* visible_count, uint32_t* counts, uint32_t range_count)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0 && visible_count) *visible_count = 0;
+    if (i < range_count) counts[i] = 0;
+}
+
 __global__ void zero_count_kernel(uint32_t* p) { *p = 0; }
 
 } // namespace
 
 namespace ur {
 
+namespace {
+
+// The launches of a call with n > 256 (blocks >= 2): the cull, then the compaction when there is a list or there are ranges
+template <bool RANGES>
+int launch_blocks(ur_ctx* ctx, const CullArgs<RANGES>& P, uint32_t blocks, hipEvent_t stop)
+{
+    const bool compact = RANGES || P.visible_idx != nullptr;
+    const auto cull = cull_kernel<false, RANGES>;
+    const auto compaction = compact_kernel<RANGES>;
+    if (stop != nullptr && !compact) hipExtLaunchKernelGGL(cull, dim3(blocks), dim3(256), 0, ctx->stream, nullptr, stop, 0, P);
+    else hipLaunchKernelGGL(cull, dim3(blocks), dim3(256), 0, ctx->stream, P);
+    UR_HIP_TRY(hipGetLastError());
+    if (compact) {
+        if (stop != nullptr) hipExtLaunchKernelGGL(compaction, dim3((blocks * 4u + 255u) / 256u), dim3(256), 0, ctx->stream, nullptr, stop, 0, P, blocks);
+        else hipLaunchKernelGGL(compaction, dim3((blocks * 4u + 255u) / 256u), dim3(256), 0, ctx->stream, P, blocks);
+        UR_HIP_TRY(hipGetLastError());
+    }
+    return UR_OK;
+}
+
+} // namespace
+
 int launch_cull(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb, const ur_mip_desc* mips,
-                void* indirect_args, uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count, uint32_t index_base)
+                void* indirect_args, uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count, uint32_t index_base,
+                const ur_draw_ranges* draws)
 {
     {
         const int rc = flush_hzb_tail(ctx); // the cull reads the whole chain
         if (rc != UR_OK) return rc;
     }
-    CullParams P{};
+    CullArgs<true> P{};
     static_assert(sizeof(float4) * 6 + sizeof(float) * 16 + 6 * 4 == UR_CULL_CONSTANT_DWORDS * 4, "46 dwords");
-    std::memcpy(&P, constants, UR_CULL_CONSTANT_DWORDS * 4);
+    std::memcpy(static_cast<CullParams*>(&P), constants, UR_CULL_CONSTANT_DWORDS * 4);
     P.bounds = reinterpret_cast<const float4*>(bounds);
     P.hzb = hzb;
     P.args = static_cast<uint8_t*>(indirect_args);
@@ -317,6 +504,9 @@ int launch_cull(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds,
             P.mip_width[m] = mips[m].width;
         }
     }
+    if (draws) P.D = {draws->offsets, static_cast<uint8_t*>(draws->commands), draws->counts, draws->range_count};
+    CullArgs<false> Q{};
+    static_cast<CullParams&>(Q) = P; // (the same parameters without the ranges)
     // ur_time_next_cull: the call's LAST launch carries the event on its dispatch (its completion stamp is somebody's start time).
     // (ur_cull_indirect_args_ex clears the context's copy behind this function on every path: a raw hipEvent_t must not stay in
     // the context for a later call.)
@@ -324,7 +514,13 @@ int launch_cull(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds,
     const uint32_t n = P.ModelCount;
     if (n == 0) {
         ctx->cull_record_args = nullptr;
-        if (visible_count) {
+        if (draws) { // one launch zeroes the counts (and the list's count)
+            const uint32_t grid = (uint32_t)(((uint64_t)draws->range_count + 255u) / 256u);
+            if (stop != nullptr) hipExtLaunchKernelGGL(zero_counts_kernel, dim3(grid), dim3(256), 0, ctx->stream, nullptr, stop, 0, visible_count, draws->counts, draws->range_count);
+            else hipLaunchKernelGGL(zero_counts_kernel, dim3(grid), dim3(256), 0, ctx->stream, visible_count, draws->counts, draws->range_count);
+            UR_HIP_TRY(hipGetLastError());
+            ctx->time_cull_carried = stop != nullptr;
+        } else if (visible_count) {
             if (stop != nullptr) hipExtLaunchKernelGGL(zero_count_kernel, dim3(1), dim3(1), 0, ctx->stream, nullptr, stop, 0, visible_count);
             else hipLaunchKernelGGL(zero_count_kernel, dim3(1), dim3(1), 0, ctx->stream, visible_count);
             UR_HIP_TRY(hipGetLastError());
@@ -335,33 +531,34 @@ int launch_cull(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds,
     const uint32_t blocks = (n + 255u) / 256u;
     if (blocks == 1) {
         ctx->cull_record_args = nullptr; // (one block keeps no masks)
-        if (stop != nullptr) hipExtLaunchKernelGGL(cull_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, nullptr, stop, 0, P);
-        else hipLaunchKernelGGL(cull_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, P);
+        const auto single = cull_kernel<true, false>;
+        const auto single_draws = cull_kernel<true, true>;
+        if (draws) {
+            if (stop != nullptr) hipExtLaunchKernelGGL(single_draws, dim3(1), dim3(256), 0, ctx->stream, nullptr, stop, 0, P);
+            else hipLaunchKernelGGL(single_draws, dim3(1), dim3(256), 0, ctx->stream, P);
+        } else {
+            if (stop != nullptr) hipExtLaunchKernelGGL(single, dim3(1), dim3(256), 0, ctx->stream, nullptr, stop, 0, Q);
+            else hipLaunchKernelGGL(single, dim3(1), dim3(256), 0, ctx->stream, Q);
+        }
         UR_HIP_TRY(hipGetLastError());
         ctx->time_cull_carried = stop != nullptr;
         return UR_OK;
     }
-    if (visible_idx || P.store_flavour == 4u) {
+    if (visible_idx || draws || P.store_flavour == 4u) { // the masks and block counts: the compaction's input, flavour 4's record
         if (n > ctx->ws_instances) {
             const int rc = ur_reserve(ctx, n); // (a new workspace forgets the record)
             if (rc != UR_OK) return rc;
         }
-        P.block_counts = ctx->block_counts;
-        P.wave_masks = ctx->wave_masks;
+        P.block_counts = Q.block_counts = ctx->block_counts;
+        P.wave_masks = Q.wave_masks = ctx->wave_masks;
     }
     // UR_OPT_CULL_STORE = 4: the wave masks ARE the record of what this launch leaves in the command buffer; they describe the buffer the
     // next launch meets if that launch is on the same buffer with the same count (and the caller keeps the promise of the option)
-    P.record_valid = (P.store_flavour == 4u && ctx->cull_record_args == indirect_args && ctx->cull_record_n == n) ? 1u : 0u;
+    P.record_valid = Q.record_valid = (P.store_flavour == 4u && ctx->cull_record_args == indirect_args && ctx->cull_record_n == n) ? 1u : 0u;
     ctx->cull_record_args = P.store_flavour == 4u ? indirect_args : nullptr;
     ctx->cull_record_n = n;
-    if (stop != nullptr && !visible_idx) hipExtLaunchKernelGGL(cull_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, nullptr, stop, 0, P);
-    else hipLaunchKernelGGL(cull_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, P);
-    UR_HIP_TRY(hipGetLastError());
-    if (visible_idx) {
-        if (stop != nullptr) hipExtLaunchKernelGGL(compact_kernel, dim3((blocks * 4u + 255u) / 256u), dim3(256), 0, ctx->stream, nullptr, stop, 0, P, blocks);
-        else hipLaunchKernelGGL(compact_kernel, dim3((blocks * 4u + 255u) / 256u), dim3(256), 0, ctx->stream, P, blocks);
-        UR_HIP_TRY(hipGetLastError());
-    }
+    const int rc = draws ? launch_blocks<true>(ctx, P, blocks, stop) : launch_blocks<false>(ctx, Q, blocks, stop);
+    if (rc != UR_OK) return rc;
     ctx->time_cull_carried = stop != nullptr;
     return UR_OK;
 }

@@ -72,8 +72,9 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     {
         if (!Data.bEnabled) return;
         // DispatchGpuCulling (Renderer.cpp:394-472): the UAV / INDIRECT_ARGUMENT transitions are stream order here.
-        const int rc = ur_cull_indirect_args_ex(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
-                                                Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase);
+        // With draw ranges the same call also places the visible commands of each range and writes its count (ur_cull_indirect_args_draws).
+        const int rc = ur_cull_indirect_args_draws(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
+                                                   Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges);
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
 
@@ -411,6 +412,8 @@ struct ur_frame
     bool bKernelEvents = false; // UR_FRAME_TIME_LIGHTING_KERNEL: the pair rides on the Lighting dispatch itself, nothing is recorded around it
     bool bStartOnCull = false;  // ... and this frame's START event was handed to the cull launch directly in front of the Lighting launch
     ur_frame_post Post = {{nullptr, nullptr}, nullptr, 0.0f, 0.9f, 2.2f, 0.3f, 0.1f, 5.0f, 3.0f, 1.0f, 0.5f}; // ur_frame_set_post
+    ur_draw_ranges DrawRanges = {};    // ur_frame_set_draw_ranges
+    bool bDrawRanges = false;
     void* PostRecord = nullptr;        // ur_frame_set_post_records
     const void* PostRecords = nullptr;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -550,6 +553,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.VisibleIndices = r->visible_indices;
     R.VisibleCount = r->visible_count;
     R.CullStats = r->cull_stats;
+    R.DrawRanges = f->bDrawRanges ? &f->DrawRanges : nullptr;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -629,6 +633,18 @@ int ur_frame_set_post(ur_frame* f, const ur_frame_post* post)
 {
     if (!f || !post) { ur::set_error("ur_frame_set_post: null argument"); return UR_EINVAL; }
     f->Post = *post;
+    return UR_OK;
+}
+
+int ur_frame_set_draw_ranges(ur_frame* f, const ur_draw_ranges* draws)
+{
+    if (!f) { ur::set_error("ur_frame_set_draw_ranges: null frame"); return UR_EINVAL; }
+    if (draws && (!draws->offsets || !draws->commands || !draws->counts || draws->range_count == 0)) {
+        ur::set_error("ur_frame_set_draw_ranges: null member / no range");
+        return UR_EINVAL;
+    }
+    f->bDrawRanges = draws != nullptr;
+    f->DrawRanges = draws ? *draws : ur_draw_ranges{};
     return UR_OK;
 }
 

@@ -48,6 +48,7 @@ struct FHotPathResources
     uint32* VisibleIndices = nullptr; // optional (new): compacted ascending list
     uint32* VisibleCount = nullptr;
     uint32* CullStats = nullptr;      // optional: [frustum-culled, occluded]
+    const ur_draw_ranges* DrawRanges = nullptr; // optional (ur_frame_set_draw_ranges): compacted commands + a count per range
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};

@@ -357,7 +357,7 @@ int ur_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h
 
 static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
                         const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                        uint32_t* visible_count, uint32_t index_base)
+                        uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws)
 {
     if (!ctx || !constants) { set_error("ur_cull_indirect_args: null ctx/constants"); return UR_EINVAL; }
     const uint32_t n = constants[40], hzb_on = constants[41], mipc = constants[42];
@@ -369,9 +369,16 @@ static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4*
         // the kernel indexes hzb + mips[level].offset with pitch mips[level].width for every level up to HZBMipCount - 1
         if (!valid_hzb_chain_below_mip0(mips, mipc)) { set_error("ur_cull_indirect_args: mips[1..%u] do not halve from mips[0] / overlap", mipc - 1); return UR_EINVAL; }
     }
+    if (draws) {
+        if (!draws->offsets || !draws->commands || !draws->counts || draws->range_count == 0) { set_error("ur_cull_indirect_args_draws: null member / no range"); return UR_EINVAL; }
+        const uintptr_t c = reinterpret_cast<uintptr_t>(draws->commands), a = reinterpret_cast<uintptr_t>(indirect_args);
+        const uintptr_t bytes = (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE;
+        if (n != 0 && c < a + bytes && a < c + bytes) { set_error("ur_cull_indirect_args_draws: commands overlap indirect_args"); return UR_EINVAL; }
+        if (n != 0 && ((c | a) & 15u) != 0) { set_error("ur_cull_indirect_args_draws: commands / indirect_args not 16-byte aligned"); return UR_EINVAL; }
+    }
     const int trc = ur::check_hzb_timeout(ctx, "ur_cull_indirect_args");
     if (trc != UR_OK) return trc;
-    return ur::launch_cull(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base);
+    return ur::launch_cull(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws);
 }
 
 int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
@@ -379,7 +386,17 @@ int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_fl
                              uint32_t* visible_count, uint32_t index_base)
 {
     if (ctx) ctx->time_cull_carried = false;
-    const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base);
+    const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, nullptr);
+    if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
+    return rc;
+}
+
+int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws)
+{
+    if (ctx) ctx->time_cull_carried = false;
+    const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws);
     if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
     return rc;
 }

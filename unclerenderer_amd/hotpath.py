@@ -157,13 +157,32 @@ class HotPath:
 
     # ---- CullIndirectArgs ----
     def cull_indirect_args(self, constants: np.ndarray, bounds: torch.Tensor, hzb, layout, indirect_args: torch.Tensor,
-                           stats=None, visible_idx=None, visible_count=None, index_base: int = 0):
+                           stats=None, visible_idx=None, visible_count=None, index_base: int = 0,
+                           draw_offsets=None, draw_commands=None, draw_counts=None):
+        """CullIndirectArgs (+ the optional visible list). With draw_offsets / draw_commands / draw_counts (all three or none) the same
+        call also writes each range's visible commands to draw_commands slots draw_offsets[r], ... and its count to draw_counts[r]
+        (ur_cull_indirect_args_draws). draw_offsets: a host array (checked here, then uploaded) or a device tensor from
+        draw_offsets_to_device."""
         constants = np.ascontiguousarray(constants, np.uint32)
         assert constants.size == _lib.UR_CULL_CONSTANT_DWORDS
         cptr = constants.ctypes.data_as(C.POINTER(C.c_uint32))
         mips = layout.mips if layout is not None else None
-        _lib.check(self._L.ur_cull_indirect_args_ex(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
-                                                    _ptr(visible_idx), _ptr(visible_count), index_base), "ur_cull_indirect_args")
+        if draw_offsets is None and draw_commands is None and draw_counts is None:
+            _lib.check(self._L.ur_cull_indirect_args_ex(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
+                                                        _ptr(visible_idx), _ptr(visible_count), index_base), "ur_cull_indirect_args")
+            return
+        if draw_offsets is None or draw_commands is None or draw_counts is None:
+            raise ValueError("draw_offsets, draw_commands and draw_counts go together")
+        if not isinstance(draw_offsets, torch.Tensor):
+            draw_offsets = self.draw_offsets_to_device(draw_offsets, int(constants[40]))
+        dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
+        _lib.check(self._L.ur_cull_indirect_args_draws(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
+                                                       _ptr(visible_idx), _ptr(visible_count), index_base, C.byref(dr)), "ur_cull_indirect_args_draws")
+
+    def draw_offsets_to_device(self, offsets, command_count: int) -> torch.Tensor:
+        """Check the precondition of ur_draw_ranges.offsets on the host array (offsets[0] == 0, non-decreasing, last == command_count,
+        at least one range), then upload it (uint32)."""
+        return to_device(check_draw_offsets(offsets, command_count))
 
     # ---- lighting tables ----
     def stage_env_cube(self, cube_dds_order: np.ndarray, base: int, mips: int) -> torch.Tensor:
@@ -203,6 +222,30 @@ class HotPath:
         rows = h - row0 if rows is None else rows
         _lib.check(self._L.ur_deferred_lighting_sky(self._ctx, C.byref(scene), C.byref(sky), _ptr(A), _ptr(B), _ptr(Cc), _ptr(depth), C.byref(tables),
                                                     _ptr(hdr), w, h, row0, rows), "ur_deferred_lighting_sky")
+
+
+def check_draw_offsets(offsets, command_count: int) -> np.ndarray:
+    """The precondition ur_cull_indirect_args_draws does not check, checked on the host: uint32[R + 1], R >= 1, offsets[0] == 0,
+    non-decreasing, offsets[R] == command_count. Returns the array as contiguous uint32."""
+    o = np.asarray(offsets)
+    if o.ndim != 1 or o.size < 2:
+        raise ValueError("draw offsets: need range_count + 1 >= 2 entries")
+    if o.dtype.kind not in "iu" or (o.dtype.kind == "i" and (o < 0).any()) or (o > 0xFFFFFFFF).any():
+        raise ValueError("draw offsets: must be unsigned 32-bit integers")
+    o = np.ascontiguousarray(o, np.uint32)
+    if o[0] != 0 or o[-1] != command_count or (np.diff(o.astype(np.int64)) < 0).any():
+        raise ValueError(f"draw offsets: need offsets[0] == 0, non-decreasing, offsets[-1] == {command_count}")
+    return o
+
+
+def draw_ranges(offsets: torch.Tensor, commands: torch.Tensor, counts: torch.Tensor) -> _lib.DrawRanges:
+    """ur_draw_ranges over device tensors: offsets uint32[R + 1] (checked with check_draw_offsets), commands n * 64 bytes, counts uint32[R]."""
+    assert offsets.numel() >= 2 and counts.numel() >= offsets.numel() - 1 and offsets.element_size() == 4 and counts.element_size() == 4
+    dr = _lib.DrawRanges(offsets.data_ptr(), offsets.numel() - 1, commands.data_ptr(), counts.data_ptr())
+    for t in (offsets, commands, counts):
+        assert t.is_cuda and t.is_contiguous(), "device tensors must be contiguous CUDA/HIP tensors"
+    dr._keep = (offsets, commands, counts)
+    return dr
 
 
 class Frame:
@@ -286,6 +329,24 @@ class Frame:
 
     def reset_post(self):
         self._L.ur_frame_reset_post(self._f)
+
+    def set_draw_ranges(self, offsets=None, commands=None, counts=None, command_count: "int | None" = None):
+        """ur_frame_set_draw_ranges: the "GPU Culling" pass of the frames that follow also writes each range's visible commands to
+        `commands` slots offsets[r], ... and the range's count to counts[r] (device tensors, kept alive here). offsets: a host array
+        (checked with check_draw_offsets against command_count, by default its own last entry, then uploaded) or a device uint32
+        tensor. No arguments: clear."""
+        if offsets is None and commands is None and counts is None:
+            self._draws_keep = None
+            _lib.check(self._L.ur_frame_set_draw_ranges(self._f, None), "ur_frame_set_draw_ranges")
+            return
+        if offsets is None or commands is None or counts is None:
+            raise ValueError("offsets, commands and counts go together")
+        if not isinstance(offsets, torch.Tensor):
+            o = np.asarray(offsets)
+            offsets = to_device(check_draw_offsets(o, command_count if command_count is not None else (int(o[-1]) if o.size else -1)))
+        dr = draw_ranges(offsets, commands, counts)
+        self._draws_keep = dr
+        _lib.check(self._L.ur_frame_set_draw_ranges(self._f, C.byref(dr)), "ur_frame_set_draw_ranges")
 
     def set_post_records(self, own_record, all_records):
         """ur_frame_set_post_records: where UR_FRAME_POST_EXCHANGE packs this rank's record (own_record) and where finish_post reads

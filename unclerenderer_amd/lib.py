@@ -32,6 +32,11 @@ class MipDesc(C.Structure):
     _fields_ = [("offset", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class DrawRanges(C.Structure):
+    """ur_draw_ranges (include/ur_hotpath.h): per-range compacted draw commands and counts of ur_cull_indirect_args_draws."""
+    _fields_ = [("offsets", C.c_void_p), ("range_count", C.c_uint32), ("commands", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class HzbSlice(C.Structure):
     """ur_hzb_slice: one contiguous run of floats of the HZB allocation."""
     _fields_ = [("offset", C.c_uint32), ("count", C.c_uint32)]
@@ -176,6 +181,8 @@ SIGNATURES = {
     "ur_build_hzb_tail": (C.c_int, [_VP, _VP, C.POINTER(MipDesc), _U32]),
     "ur_cull_indirect_args": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP]),
     "ur_cull_indirect_args_ex": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP, _U32]),
+    "ur_cull_indirect_args_draws": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP, _U32,
+                                              C.POINTER(DrawRanges)]),
     "ur_env_cube_texels": (C.c_size_t, [_U32, _U32]),
     "ur_stage_env_cube": (C.c_int, [_VP, _VP, _U32, _U32, _VP]),
     "ur_deferred_lighting": (C.c_int, [_VP, C.POINTER(SceneConstants), _VP, _VP, _VP, C.POINTER(LightingTables), _VP, _U32, _U32, _U32, _U32]),
@@ -217,6 +224,7 @@ SIGNATURES = {
     "ur_frame_reset_hzb": (None, [_VP]),
     "ur_frame_set_post": (C.c_int, [_VP, C.POINTER(FramePost)]),
     "ur_frame_reset_post": (None, [_VP]),
+    "ur_frame_set_draw_ranges": (C.c_int, [_VP, C.POINTER(DrawRanges)]),
     "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),

@@ -57,3 +57,17 @@ def load_scene_bounds(scene_json_path, assets_root=None) -> SceneBounds:
     return SceneBounds(bounds, np.array([x.pipeline_key for x in models], np.uint32), np.array([x.material_index for x in models], np.uint32),
                        np.array([list(x.center) for x in models], np.float32), np.array([x.radius for x in models], np.float32),
                        np.array(list(summary.scene_center), np.float32), float(summary.scene_radius))
+
+
+def draw_offsets(keys) -> np.ndarray:
+    """Draw-range offsets (ur_draw_ranges.offsets) over commands in command order: a new range starts wherever the key changes.
+    uint32[R + 1] with offsets[0] = 0 and offsets[R] = len(keys). The reference's FIndirectDrawRanges break on every texture-handle
+    change (DeferredRenderer.cpp:3327-3360), and the handle is per model: keys = arange(n), one range per command. Ranges per pipeline
+    bucket: keys = SceneBounds.pipeline_keys. No commands: [0, 0], one empty range."""
+    k = np.asarray(keys)
+    if k.ndim != 1:
+        raise ValueError("draw_offsets: keys must be one-dimensional")
+    if k.size == 0:
+        return np.zeros(2, np.uint32)
+    starts = np.flatnonzero(k[1:] != k[:-1]) + 1
+    return np.concatenate([[0], starts, [k.size]]).astype(np.uint32)
