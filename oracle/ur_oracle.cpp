@@ -117,6 +117,9 @@ struct float3 { float x, y, z; };
 struct float4 { float x, y, z, w; };
 
 inline float saturate(float x) { return std::fmin(std::fmax(x, 0.0f), 1.0f); }
+// HLSL min: a NaN operand, quiet or signalling, is ignored (std::fmin in glibc returns NaN for a signalling one)
+inline float hmin(float a, float b) { return a != a ? b : (b != b ? a : std::fmin(a, b)); }
+inline float hmin4(float a, float b, float c, float d) { return hmin(hmin(a, b), hmin(c, d)); }
 inline float lerp(float a, float b, float t) { return a + t * (b - a); }
 inline float dot(float3 a, float3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 inline float3 operator+(float3 a, float3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -181,7 +184,7 @@ void BuildHZB_dispatch(const HZBConstants& C, const float* Source, float* Dest0,
                         const uint32_t bx = dx * 2, by = dy * 2;
                         const float d0 = SampleDepth(bx, by), d1 = SampleDepth(bx + 1, by);
                         const float d2 = SampleDepth(bx, by + 1), d3 = SampleDepth(bx + 1, by + 1);
-                        minDepth = std::fmin(std::fmin(d0, d1), std::fmin(d2, d3));
+                        minDepth = hmin4(d0, d1, d2, d3);
                         Dest0[(size_t)dy * C.DestWidth + dx] = minDepth;
                     }
                     SharedDepth[ty][tx] = minDepth;
@@ -192,8 +195,7 @@ void BuildHZB_dispatch(const HZBConstants& C, const float* Source, float* Dest0,
                     const uint32_t x1 = gx * 4 + tx, y1 = gy * 4 + ty;
                     if (x1 < C.DestWidth1 && y1 < C.DestHeight1) {
                         const uint32_t bx = tx * 2, by = ty * 2;
-                        const float m = std::fmin(std::fmin(SharedDepth[by][bx], SharedDepth[by][bx + 1]),
-                                                  std::fmin(SharedDepth[by + 1][bx], SharedDepth[by + 1][bx + 1]));
+                        const float m = hmin4(SharedDepth[by][bx], SharedDepth[by][bx + 1], SharedDepth[by + 1][bx], SharedDepth[by + 1][bx + 1]);
                         Dest1[(size_t)y1 * C.DestWidth1 + x1] = m;
                         SharedDepth1[ty][tx] = m;
                     } else {
@@ -206,8 +208,7 @@ void BuildHZB_dispatch(const HZBConstants& C, const float* Source, float* Dest0,
                     const uint32_t x2 = gx * 2 + tx, y2 = gy * 2 + ty;
                     if (x2 < C.DestWidth2 && y2 < C.DestHeight2) {
                         const uint32_t bx = tx * 2, by = ty * 2;
-                        const float m = std::fmin(std::fmin(SharedDepth1[by][bx], SharedDepth1[by][bx + 1]),
-                                                  std::fmin(SharedDepth1[by + 1][bx], SharedDepth1[by + 1][bx + 1]));
+                        const float m = hmin4(SharedDepth1[by][bx], SharedDepth1[by][bx + 1], SharedDepth1[by + 1][bx], SharedDepth1[by + 1][bx + 1]);
                         Dest2[(size_t)y2 * C.DestWidth2 + x2] = m;
                         SharedDepth2[ty][tx] = m;
                     } else {
@@ -216,8 +217,7 @@ void BuildHZB_dispatch(const HZBConstants& C, const float* Source, float* Dest0,
                 }
             if (MipsPerDispatch < 4) continue;
             if (gx < C.DestWidth3 && gy < C.DestHeight3) { // BuildHZB.hlsl:108-122
-                Dest3[(size_t)gy * C.DestWidth3 + gx] =
-                    std::fmin(std::fmin(SharedDepth2[0][0], SharedDepth2[0][1]), std::fmin(SharedDepth2[1][0], SharedDepth2[1][1]));
+                Dest3[(size_t)gy * C.DestWidth3 + gx] = hmin4(SharedDepth2[0][0], SharedDepth2[0][1], SharedDepth2[1][0], SharedDepth2[1][1]);
             }
         }
 }
@@ -309,10 +309,10 @@ bool IsOccluded(const CullingConstants& C, const float* hzb, const ur_mip_desc* 
     const ur_mip_desc& M = mips[mipLevel];
     auto Load = [&](uint32_t x, uint32_t y) { return hzb[M.offset + (size_t)y * M.width + x]; };
     float hzbDepth = 1.0f;
-    hzbDepth = std::fmin(hzbDepth, Load(minX, minY));
-    hzbDepth = std::fmin(hzbDepth, Load(maxX, minY));
-    hzbDepth = std::fmin(hzbDepth, Load(minX, maxY));
-    hzbDepth = std::fmin(hzbDepth, Load(maxX, maxY));
+    hzbDepth = hmin(hzbDepth, Load(minX, minY));
+    hzbDepth = hmin(hzbDepth, Load(maxX, minY));
+    hzbDepth = hmin(hzbDepth, Load(minX, maxY));
+    hzbDepth = hmin(hzbDepth, Load(maxX, maxY));
     return maxDepth < hzbDepth;
 }
 

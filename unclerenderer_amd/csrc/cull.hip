@@ -118,11 +118,12 @@ __device__ __forceinline__ bool IsOccluded(const CullParams& C, float3 mn, float
     maxX = min(maxX, mipWidth - 1u); maxY = min(maxY, mipHeight - 1u);
     const float* mip = C.hzb + C.mip_offset[mipLevel];
     const uint32_t pitch = C.mip_width[mipLevel];
+    // HLSL min ignores a NaN texel, signalling or quiet: the loads are quieted first (a raw sNaN operand of v_min_f32 gives NaN)
     float hzbDepth = 1.0f;
-    hzbDepth = fminf(hzbDepth, mip[(size_t)minY * pitch + minX]);
-    hzbDepth = fminf(hzbDepth, mip[(size_t)minY * pitch + maxX]);
-    hzbDepth = fminf(hzbDepth, mip[(size_t)maxY * pitch + minX]);
-    hzbDepth = fminf(hzbDepth, mip[(size_t)maxY * pitch + maxX]);
+    hzbDepth = fminf(hzbDepth, __builtin_canonicalizef(mip[(size_t)minY * pitch + minX]));
+    hzbDepth = fminf(hzbDepth, __builtin_canonicalizef(mip[(size_t)minY * pitch + maxX]));
+    hzbDepth = fminf(hzbDepth, __builtin_canonicalizef(mip[(size_t)maxY * pitch + minX]));
+    hzbDepth = fminf(hzbDepth, __builtin_canonicalizef(mip[(size_t)maxY * pitch + maxX]));
     return maxDepth < hzbDepth;
 }
 

@@ -9,7 +9,8 @@
 // wave (lane^1, lane^32) and only mip k+3 crosses waves through a 64-float LDS tile. One barrier per workgroup instead
 // of three; HBM traffic == algorithmic bytes (every source texel read once, every mip texel written once).
 //
-// Built with -ffp-contract=off; the only arithmetic is fminf.
+// Built with -ffp-contract=off; the only arithmetic is fminf, on quieted operands (hzb_min4, hzb_tail.h: HLSL min ignores a
+// NaN operand, a signalling one included).
 
 #include "ur_internal.h"
 #include "ur_device.h"
@@ -20,7 +21,7 @@ namespace {
 
 using ur::HzbDispatch;
 
-__device__ __forceinline__ float min4(float a, float b, float c, float d) { return fminf(fminf(a, b), fminf(c, d)); }
+using ur::hzb_min4;
 
 __global__ __launch_bounds__(256) void hzb_reduce4_kernel(HzbDispatch p)
 {
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(256) void hzb_reduce4_kernel(HzbDispatch p)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const uint32_t x0 = x1 * 2u + i, y0 = y1 * 2u + j;
-                if (x0 < p.W[0] && y0 < p.H[0]) v0[j][i] = min4(s[2 * j][2 * i], s[2 * j][2 * i + 1], s[2 * j + 1][2 * i], s[2 * j + 1][2 * i + 1]);
+                if (x0 < p.W[0] && y0 < p.H[0]) v0[j][i] = hzb_min4(s[2 * j][2 * i], s[2 * j][2 * i + 1], s[2 * j + 1][2 * i], s[2 * j + 1][2 * i + 1]);
             }
         float* d0 = p.dst[0];
         const uint32_t x0 = x1 * 2u, y0 = y1 * 2u;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void hzb_reduce4_kernel(HzbDispatch p)
     // ---- mip k+1: this lane's texel; out-of-range lanes hold 0.0 (:81)
     float v1 = 0.0f;
     if (x1 < p.W[1] && y1 < p.H[1]) {
-        v1 = min4(v0[0][0], v0[0][1], v0[1][0], v0[1][1]);
+        v1 = hzb_min4(v0[0][0], v0[0][1], v0[1][0], v0[1][1]);
         p.dst[1][(size_t)y1 * p.W[1] + x1] = v1;
     }
     if (p.mips < 3u) return; // uniform
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(256) void hzb_reduce4_kernel(HzbDispatch p)
         const uint32_t x3 = x1 >> 2, y3 = y1 >> 2;
         if (x3 < p.W[3] && y3 < p.H[3]) {
             const uint32_t cx = tx >> 1, cy = ty >> 1;
-            const float v3 = min4(sh2[cy][cx], sh2[cy][cx + 1], sh2[cy + 1][cx], sh2[cy + 1][cx + 1]);
+            const float v3 = hzb_min4(sh2[cy][cx], sh2[cy][cx + 1], sh2[cy + 1][cx], sh2[cy + 1][cx + 1]);
             p.dst[3][(size_t)y3 * p.W[3] + x3] = v3;
             sh3[ty >> 2][tx >> 2] = v3;
         }
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void hzb_reduce4_kernel(HzbDispatch p)
         if (x4 < p.W[4] && y4 < p.H[4]) {
             const uint32_t c0 = min(2u * x4, p.W[3] - 1u) & 7u, c1 = min(2u * x4 + 1u, p.W[3] - 1u) & 7u;
             const uint32_t r0 = min(2u * y4, p.H[3] - 1u) & 1u, r1 = min(2u * y4 + 1u, p.H[3] - 1u) & 1u;
-            p.dst[4][(size_t)y4 * p.W[4] + x4] = min4(sh3[r0][c0], sh3[r0][c1], sh3[r1][c0], sh3[r1][c1]);
+            p.dst[4][(size_t)y4 * p.W[4] + x4] = hzb_min4(sh3[r0][c0], sh3[r0][c1], sh3[r1][c0], sh3[r1][c1]);
         }
     }
 }

@@ -9,7 +9,16 @@
 
 namespace ur {
 
-__device__ __forceinline__ float hzb_min4(float a, float b, float c, float d) { return fminf(fminf(a, b), fminf(c, d)); }
+// HLSL min(min(a, b), min(c, d)): a NaN operand is ignored, signalling or quiet, and the result is NaN only if all four are.
+// fminf does not promise that for a signalling NaN: gfx950's v_min_f32 / v_min3_f32 return NaN for one in IEEE mode, and the
+// compiler quiets only the operands it does not know to be canonical (a raw load is fed as it is). So every operand is quieted
+// first (v_max_f32 x, x; free where the compiler knows the value is canonical already, e.g. the result of another min).
+__device__ __forceinline__ float hzb_min4(float a, float b, float c, float d)
+{
+    a = __builtin_canonicalizef(a); b = __builtin_canonicalizef(b);
+    c = __builtin_canonicalizef(c); d = __builtin_canonicalizef(d);
+    return fminf(fminf(a, b), fminf(c, d));
+}
 
 // ---- the tail of the chain in ONE single-workgroup launch ----------------------------------------------------------------
 // Once a mip has <= 16384 texels every remaining level fits in LDS, and the reference's further dispatches (<= 4 mips

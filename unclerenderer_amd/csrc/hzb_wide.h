@@ -13,6 +13,8 @@
 
 #include <cstdint>
 
+#include "hzb_tail.h"
+
 namespace ur {
 
 struct HzbDispatch {
@@ -27,7 +29,8 @@ struct HzbDispatch {
                       // band-sharded: ur_build_hzb_band)
 };
 
-__device__ __forceinline__ float hzbw_min4(float a, float b, float c, float d) { return fminf(fminf(a, b), fminf(c, d)); }
+// HLSL min of four, a NaN operand ignored whether signalling or quiet: hzb_min4 of hzb_tail.h (the operands are quieted first)
+__device__ __forceinline__ float hzbw_min4(float a, float b, float c, float d) { return hzb_min4(a, b, c, d); }
 
 // One 128x32 source piece (bx, by) of a five-level dispatch (p.mips == 5), walked by ONE wave: pass q covers the rows the
 // workgroup form gives to its wave q. sh2: 64 floats, sh3: 16 floats of LDS private to the wave. P: HzbDispatch in any
