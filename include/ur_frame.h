@@ -67,6 +67,7 @@ typedef struct ur_frame_resources {
  * into all_records and calls ur_frame_finish_post, which runs AutoExposure (from the records), Tonemap and CAS on the band with the
  * rows around it read from the neighbours' records. The band's bytes and luminance[W] are those of the unsplit frame, on every rank. */
 #define UR_FRAME_POST_EXCHANGE 0x200000u
+#define UR_FRAME_CULL_VIEWS 0x400000u /* the "GPU Culling" pass also culls the views of ur_frame_set_cull_views (ur_cull_indirect_args_views), on the async-compute lane too */
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -115,6 +116,12 @@ int ur_frame_finish_post(ur_frame* f);
  * alone. Offsets are local to the frame's indirect_args (a rank's command slice). NULL clears them. The pointers must stay valid while
  * frames use them. UR_EINVAL for a null frame, a null member or range_count == 0. */
 int ur_frame_set_draw_ranges(ur_frame* f, const ur_draw_ranges* draws);
+/* Extra views of the "GPU Culling" pass (include/ur_hotpath.h, ur_cull_view) for the frames rendered with UR_FRAME_CULL_VIEWS: the pass
+ * then calls ur_cull_indirect_args_views, with the draw ranges of ur_frame_set_draw_ranges when those are set. The frame keeps a copy of
+ * the views and of the ur_draw_ranges they point to; the buffers must stay valid while frames use them. count == 0 clears them.
+ * Without the flag, or when the cull pass does not run, the views' buffers are left alone. UR_EINVAL for a null frame, count >
+ * UR_MAX_CULL_VIEWS, views == NULL with count != 0, and the view errors of ur_cull_indirect_args_views that need no command count. */
+int ur_frame_set_cull_views(ur_frame* f, const ur_cull_view* views, uint32_t count);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

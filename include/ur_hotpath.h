@@ -300,6 +300,40 @@ int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur
                                 uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count,
                                 uint32_t index_base, const ur_draw_ranges* draws);
 
+/* Extra views: frustum-only visibility for more cameras in the same cull launch, for the reference's per-model CPU loops that draw
+ * without occlusion. FDeferredRenderer::UpdateCullingVisibility (DeferredRenderer.cpp:392, :3803-3812, RendererUtils.cpp:830-843)
+ * tests every model against the camera frustum every frame, and the DepthPrepass (DeferredRenderer.cpp:676-700) and ObjectId (:913)
+ * loops draw from that SceneModelVisibility; the ShadowMap pass builds planes from the light's view-projection (:583-591) and runs the
+ * same test per model. Each view is six planes (ur_host_frustum_planes of its view-projection) tested with that CPU test,
+ * IsAabbInCameraFrustum (RendererUtils.cpp:1192-1218), not with the shader's IsAabbVisible, on the AABBs the cull launch already
+ * reads: a plane component >= 0 (-0 too, NaN not) picks the max corner, d = ((x*X + y*Y) + z*Z) + w without contraction, only
+ * d < 0 rejects. No HZB. A view asks for any of:
+ *  - mask: bit (i & 31) of u32 word (i >> 5) = local instance i visible; ceil(ModelCount / 32) words, bits past ModelCount 0;
+ *  - visible_idx + visible_count (both or neither): ascending i + index_base, as the camera's list;
+ *  - draws: ranges over indirect_args with the semantics of ur_cull_indirect_args_draws, this view's visibility in place of the
+ *    InstanceCount word (the copied commands carry InstanceCount = 1; the word of indirect_args is never read). */
+#define UR_MAX_CULL_VIEWS 4
+typedef struct ur_cull_view {
+    float planes[24];            /* host: six (x, y, z, w) planes, ur_host_frustum_planes of the view's view-projection */
+    uint32_t* mask;              /* device or NULL: ceil(ModelCount / 32) u32, 4-byte aligned */
+    uint32_t* visible_idx;       /* device or NULL: ModelCount u32     \ both or neither */
+    uint32_t* visible_count;     /* device or NULL: one u32            / */
+    const ur_draw_ranges* draws; /* NULL or this view's ranges over indirect_args; commands 16-byte aligned and overlapping neither
+                                    indirect_args, the camera's commands nor another view's */
+} ur_cull_view;
+/* ur_cull_indirect_args_draws plus up to UR_MAX_CULL_VIEWS views (views == NULL or view_count == 0: exactly
+ * ur_cull_indirect_args_draws). The camera's words, stats2, list and ranges are the same bytes as without views. Launches: one for
+ * <= 256 instances; above, the cull, plus one compaction launch for every list and every set of ranges (camera's and views') when
+ * there is any - a call whose views ask for masks only launches what the call without them does. ModelCount == 0: every count and
+ * every counts[r] zeroed in one launch, no mask word written. The last launch carries ur_time_next_cull's event.
+ * UR_EINVAL, nothing launched: view_count > UR_MAX_CULL_VIEWS, a view that asks for nothing, a list without its count or a count
+ * without its list, a null member of a view's draws or range_count == 0, overlapping command buffers, a misaligned buffer. */
+int ur_cull_indirect_args_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds,
+                                const float* hzb_base, const ur_mip_desc* mips, void* indirect_args,
+                                uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count,
+                                uint32_t index_base, const ur_draw_ranges* draws,
+                                const ur_cull_view* views, uint32_t view_count);
+
 /* ---- DeferredLighting / SkyAtmosphere ---------------------------------------------------------- */
 
 /* Number of half4 units (8 bytes) ur_stage_env_cube() writes for (base_size, mip_count): the bordered faces, 6 (N+2)^2 texels per mip,

@@ -30,6 +30,7 @@ SOURCES = [
     ("ur_api.hip", []),
     ("hzb.hip", EXACT),
     ("cull.hip", EXACT),
+    ("cull_views.hip", EXACT),
     # packed fp32 VALU ops are not faster on gfx950 and cost v_mov traffic; the atomic optimizer would turn the one-lane LDS
     # work-counter claim into a scan + broadcast with an immediate wait
     ("lighting.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]),

@@ -73,8 +73,13 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         if (!Data.bEnabled) return;
         // DispatchGpuCulling (Renderer.cpp:394-472): the UAV / INDIRECT_ARGUMENT transitions are stream order here.
         // With draw ranges the same call also places the visible commands of each range and writes its count (ur_cull_indirect_args_draws).
-        const int rc = ur_cull_indirect_args_draws(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
-                                                   Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges);
+        // With extra views (UR_FRAME_CULL_VIEWS) the same launch also tests them (ur_cull_indirect_args_views): the DepthPrepass / ShadowMap
+        // visibility of UpdateCullingVisibility (DeferredRenderer.cpp:3803-3812) and the shadow pass (:583-591).
+        const int rc = Res.CullViewCount != 0
+            ? ur_cull_indirect_args_views(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
+                                          Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges, Res.CullViews, Res.CullViewCount)
+            : ur_cull_indirect_args_draws(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
+                                          Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges);
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
 
@@ -414,6 +419,9 @@ struct ur_frame
     ur_frame_post Post = {{nullptr, nullptr}, nullptr, 0.0f, 0.9f, 2.2f, 0.3f, 0.1f, 5.0f, 3.0f, 1.0f, 0.5f}; // ur_frame_set_post
     ur_draw_ranges DrawRanges = {};    // ur_frame_set_draw_ranges
     bool bDrawRanges = false;
+    ur_cull_view CullViews[UR_MAX_CULL_VIEWS] = {};  // ur_frame_set_cull_views (draws point into ViewDraws)
+    ur_draw_ranges ViewDraws[UR_MAX_CULL_VIEWS] = {};
+    uint32_t CullViewCount = 0;
     void* PostRecord = nullptr;        // ur_frame_set_post_records
     const void* PostRecords = nullptr;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -554,6 +562,8 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.VisibleCount = r->visible_count;
     R.CullStats = r->cull_stats;
     R.DrawRanges = f->bDrawRanges ? &f->DrawRanges : nullptr;
+    R.CullViews = f->CullViews;
+    R.CullViewCount = (flags & UR_FRAME_CULL_VIEWS) ? f->CullViewCount : 0u;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -645,6 +655,22 @@ int ur_frame_set_draw_ranges(ur_frame* f, const ur_draw_ranges* draws)
     }
     f->bDrawRanges = draws != nullptr;
     f->DrawRanges = draws ? *draws : ur_draw_ranges{};
+    return UR_OK;
+}
+
+int ur_frame_set_cull_views(ur_frame* f, const ur_cull_view* views, uint32_t count)
+{
+    if (!f) { ur::set_error("ur_frame_set_cull_views: null frame"); return UR_EINVAL; }
+    if (count > UR_MAX_CULL_VIEWS) { ur::set_error("ur_frame_set_cull_views: %u views (at most %u)", count, (uint32_t)UR_MAX_CULL_VIEWS); return UR_EINVAL; }
+    if (count != 0 && !views) { ur::set_error("ur_frame_set_cull_views: null views"); return UR_EINVAL; }
+    const int rc = ur::check_cull_views(views, count);
+    if (rc != UR_OK) return rc;
+    for (uint32_t v = 0; v < count; ++v) {
+        f->CullViews[v] = views[v];
+        f->ViewDraws[v] = views[v].draws ? *views[v].draws : ur_draw_ranges{};
+        f->CullViews[v].draws = views[v].draws ? &f->ViewDraws[v] : nullptr;
+    }
+    f->CullViewCount = count;
     return UR_OK;
 }
 

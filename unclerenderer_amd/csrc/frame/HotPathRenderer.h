@@ -49,6 +49,8 @@ struct FHotPathResources
     uint32* VisibleCount = nullptr;
     uint32* CullStats = nullptr;      // optional: [frustum-culled, occluded]
     const ur_draw_ranges* DrawRanges = nullptr; // optional (ur_frame_set_draw_ranges): compacted commands + a count per range
+    const ur_cull_view* CullViews = nullptr;     // optional (ur_frame_set_cull_views + UR_FRAME_CULL_VIEWS): extra frustum-only views
+    uint32 CullViewCount = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};

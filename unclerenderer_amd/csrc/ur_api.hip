@@ -318,8 +318,9 @@ int ur_reserve(ur_ctx* ctx, uint32_t max_instances)
     ctx->block_counts = nullptr; ctx->wave_masks = nullptr; ctx->ws_instances = 0;
     ctx->cull_record_args = nullptr;
     const size_t blocks = ((size_t)max_instances + 255u) / 256u;
-    if (hipMalloc(&ctx->block_counts, blocks * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&ctx->wave_masks, blocks * 4u * sizeof(uint64_t)) != hipSuccess) {
+    const size_t slices = 1u + UR_MAX_CULL_VIEWS; // the camera's, then one per extra view (ur_cull_indirect_args_views)
+    if (hipMalloc(&ctx->block_counts, slices * blocks * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&ctx->wave_masks, slices * blocks * 4u * sizeof(uint64_t)) != hipSuccess) {
         set_error("ur_reserve: workspace allocation for %u instances failed", max_instances);
         return UR_ENOMEM;
     }
@@ -357,7 +358,8 @@ int ur_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h
 
 static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
                         const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                        uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws)
+                        uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws,
+                        const ur_cull_view* views = nullptr, uint32_t view_count = 0)
 {
     if (!ctx || !constants) { set_error("ur_cull_indirect_args: null ctx/constants"); return UR_EINVAL; }
     const uint32_t n = constants[40], hzb_on = constants[41], mipc = constants[42];
@@ -378,7 +380,8 @@ static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4*
     }
     const int trc = ur::check_hzb_timeout(ctx, "ur_cull_indirect_args");
     if (trc != UR_OK) return trc;
-    return ur::launch_cull(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws);
+    return ur::launch_cull(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws,
+                           views, view_count);
 }
 
 int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
@@ -397,6 +400,58 @@ int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur
 {
     if (ctx) ctx->time_cull_carried = false;
     const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws);
+    if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
+    return rc;
+}
+
+// The arguments of the views that need no device (ur_cull_indirect_args_views, ur_frame_set_cull_views). n = ModelCount, or ~0 when
+// the commands are not known yet (the frame's copy): the overlap and alignment checks of the command buffers then wait for the call.
+static int check_views(const char* who, const ur_cull_view* views, uint32_t view_count, uint32_t n, const void* indirect_args,
+                       const ur_draw_ranges* draws)
+{
+    if (!views || view_count == 0) return UR_OK;
+    if (view_count > UR_MAX_CULL_VIEWS) { set_error("%s: %u views (at most %u)", who, view_count, (uint32_t)UR_MAX_CULL_VIEWS); return UR_EINVAL; }
+    const bool known = n != ~0u;
+    const uintptr_t bytes = known ? (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE : 0u;
+    auto overlap = [&](const void* x, const void* y) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+        return known && n != 0 && a < b + bytes && b < a + bytes;
+    };
+    for (uint32_t v = 0; v < view_count; ++v) {
+        const ur_cull_view& V = views[v];
+        if (!V.mask && !V.visible_idx && !V.visible_count && !V.draws) { set_error("%s: view %u asks for nothing (no mask, list or ranges)", who, v); return UR_EINVAL; }
+        if ((V.visible_idx == nullptr) != (V.visible_count == nullptr)) { set_error("%s: view %u: visible_idx and visible_count go together", who, v); return UR_EINVAL; }
+        if (((reinterpret_cast<uintptr_t>(V.mask) | reinterpret_cast<uintptr_t>(V.visible_idx) | reinterpret_cast<uintptr_t>(V.visible_count)) & 3u) != 0) {
+            set_error("%s: view %u: mask / visible_idx / visible_count not 4-byte aligned", who, v);
+            return UR_EINVAL;
+        }
+        const ur_draw_ranges* d = V.draws;
+        if (!d) continue;
+        if (!d->offsets || !d->commands || !d->counts || d->range_count == 0) { set_error("%s: view %u: null member of draws / no range", who, v); return UR_EINVAL; }
+        if (known && n != 0 && ((reinterpret_cast<uintptr_t>(d->commands) | reinterpret_cast<uintptr_t>(indirect_args)) & 15u) != 0) {
+            set_error("%s: view %u: commands / indirect_args not 16-byte aligned", who, v);
+            return UR_EINVAL;
+        }
+        if (overlap(d->commands, indirect_args)) { set_error("%s: view %u: commands overlap indirect_args", who, v); return UR_EINVAL; }
+        if (draws && draws->commands && overlap(d->commands, draws->commands)) { set_error("%s: view %u: commands overlap the camera's commands", who, v); return UR_EINVAL; }
+        for (uint32_t u = 0; u < v; ++u)
+            if (views[u].draws && views[u].draws->commands && overlap(d->commands, views[u].draws->commands)) {
+                set_error("%s: view %u: commands overlap view %u's", who, v, u);
+                return UR_EINVAL;
+            }
+    }
+    return UR_OK;
+}
+
+int ur_cull_indirect_args_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws,
+                                const ur_cull_view* views, uint32_t view_count)
+{
+    if (ctx) ctx->time_cull_carried = false;
+    int rc = check_views("ur_cull_indirect_args_views", views, view_count, constants ? constants[40] : 0u, indirect_args, draws);
+    if (rc == UR_OK) rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws,
+                                       views, views ? view_count : 0u);
     if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
     return rc;
 }
@@ -621,3 +676,5 @@ int ur_allgather_rows(ur_ctx* ctx, void* comm, ur_half4* hdr_full, uint32_t w, u
 }
 
 } // extern "C"
+
+int ur::check_cull_views(const ur_cull_view* views, uint32_t view_count) { return check_views("ur_frame_set_cull_views", views, view_count, ~0u, nullptr, nullptr); }

@@ -26,6 +26,7 @@ struct ur_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // compaction workspace (grown by ur_reserve / lazily outside graph capture)
+    // 1 + UR_MAX_CULL_VIEWS slices of ws_instances / 256 block counts (and 4x as many masks): the camera's, then one per view
     uint32_t* block_counts = nullptr; // one per 256-instance block
     uint64_t* wave_masks = nullptr;   // one per 64 instances
     uint32_t ws_instances = 0;
@@ -96,7 +97,15 @@ int launch_build_hzb_band(ur_ctx* ctx, const float* depth, uint32_t src_w, uint3
 int launch_build_hzb_tail(ur_ctx* ctx, float* hzb_base, const ur_mip_desc* mips, uint32_t mip_count);
 int launch_cull(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
                 const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws);
+                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws, const ur_cull_view* views,
+                uint32_t view_count);
+// launch_cull with views (cull_views.hip), after launch_cull has flushed the HZB tail
+int launch_cull_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                      const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                      uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws, const ur_cull_view* views,
+                      uint32_t view_count);
+// ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
+int check_cull_views(const ur_cull_view* views, uint32_t view_count);
 int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_constants* sky, const ur_half4* gbuf_a,
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);

@@ -44,6 +44,8 @@ def mat_inverse(m) -> np.ndarray:
 
 
 def frustum_planes(view_proj) -> np.ndarray:
+    """BuildFrustumPlanesFromMatrix: 24 floats, also the planes of an extra cull view (ur_cull_view.planes). A light's view:
+    frustum_planes(light_view_projection(fc.scene_center, fc.scene_radius, fc.light_direction))."""
     out = np.zeros(24, np.float32)
     _lib.load().ur_host_frustum_planes(_lib.fptr(_f(*view_proj)), _lib.fptr(out))
     return out

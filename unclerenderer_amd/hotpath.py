@@ -158,15 +158,30 @@ class HotPath:
     # ---- CullIndirectArgs ----
     def cull_indirect_args(self, constants: np.ndarray, bounds: torch.Tensor, hzb, layout, indirect_args: torch.Tensor,
                            stats=None, visible_idx=None, visible_count=None, index_base: int = 0,
-                           draw_offsets=None, draw_commands=None, draw_counts=None):
+                           draw_offsets=None, draw_commands=None, draw_counts=None, views=None):
         """CullIndirectArgs (+ the optional visible list). With draw_offsets / draw_commands / draw_counts (all three or none) the same
         call also writes each range's visible commands to draw_commands slots draw_offsets[r], ... and its count to draw_counts[r]
         (ur_cull_indirect_args_draws). draw_offsets: a host array (checked here, then uploaded) or a device tensor from
-        draw_offsets_to_device."""
+        draw_offsets_to_device. views: up to UR_MAX_CULL_VIEWS extra frustum-only views (ur_cull_indirect_args_views), each a
+        cull_view(...) or a dict of its arguments."""
         constants = np.ascontiguousarray(constants, np.uint32)
         assert constants.size == _lib.UR_CULL_CONSTANT_DWORDS
         cptr = constants.ctypes.data_as(C.POINTER(C.c_uint32))
         mips = layout.mips if layout is not None else None
+        if views:
+            n = int(constants[40])
+            arr = cull_views_array([v if isinstance(v, _lib.CullView) else cull_view(command_count=n, **v) for v in views])
+            dr = None
+            if draw_offsets is not None or draw_commands is not None or draw_counts is not None:
+                if draw_offsets is None or draw_commands is None or draw_counts is None:
+                    raise ValueError("draw_offsets, draw_commands and draw_counts go together")
+                if not isinstance(draw_offsets, torch.Tensor):
+                    draw_offsets = self.draw_offsets_to_device(draw_offsets, n)
+                dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
+            _lib.check(self._L.ur_cull_indirect_args_views(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
+                                                           _ptr(visible_idx), _ptr(visible_count), index_base,
+                                                           C.byref(dr) if dr is not None else None, arr, len(arr)), "ur_cull_indirect_args_views")
+            return
         if draw_offsets is None and draw_commands is None and draw_counts is None:
             _lib.check(self._L.ur_cull_indirect_args_ex(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
                                                         _ptr(visible_idx), _ptr(visible_count), index_base), "ur_cull_indirect_args")
@@ -246,6 +261,44 @@ def draw_ranges(offsets: torch.Tensor, commands: torch.Tensor, counts: torch.Ten
         assert t.is_cuda and t.is_contiguous(), "device tensors must be contiguous CUDA/HIP tensors"
     dr._keep = (offsets, commands, counts)
     return dr
+
+
+def cull_view(planes, mask=None, visible_idx=None, visible_count=None, draw_offsets=None, draw_commands=None, draw_counts=None,
+              command_count: "int | None" = None) -> _lib.CullView:
+    """ur_cull_view: 24 plane floats (hostmath.frustum_planes of the view's view-projection) and the device tensors the view writes:
+    mask (uint32[ceil(n / 32)]), visible_idx + visible_count (both or neither), draw_offsets / draw_commands / draw_counts (all three or
+    none; draw_offsets a host array checked with check_draw_offsets against command_count, or a device uint32 tensor). Keeps them alive."""
+    p = np.ascontiguousarray(planes, np.float32).reshape(-1)
+    if p.size != 24:
+        raise ValueError("cull_view: planes must be 24 floats")
+    if (visible_idx is None) != (visible_count is None):
+        raise ValueError("cull_view: visible_idx and visible_count go together")
+    v = _lib.CullView()
+    v.planes[:] = p.tolist()
+    keep = [t for t in (mask, visible_idx, visible_count) if t is not None]
+    for t in keep:
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 4, "view buffers must be contiguous 32-bit CUDA/HIP tensors"
+    v.mask, v.visible_idx, v.visible_count = (t.data_ptr() if t is not None else None for t in (mask, visible_idx, visible_count))
+    if draw_offsets is not None or draw_commands is not None or draw_counts is not None:
+        if draw_offsets is None or draw_commands is None or draw_counts is None:
+            raise ValueError("cull_view: draw_offsets, draw_commands and draw_counts go together")
+        if not isinstance(draw_offsets, torch.Tensor):
+            o = np.asarray(draw_offsets)
+            draw_offsets = to_device(check_draw_offsets(o, command_count if command_count is not None else (int(o[-1]) if o.size else -1)))
+        dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
+        v.draws = C.pointer(dr)
+        keep.append(dr)
+    v._keep = keep
+    return v
+
+
+def cull_views_array(views) -> "C.Array":
+    """A ctypes ur_cull_view[] of cull_view(...) results, keeping them alive."""
+    if len(views) > _lib.UR_MAX_CULL_VIEWS:
+        raise ValueError(f"at most {_lib.UR_MAX_CULL_VIEWS} cull views")
+    arr = (_lib.CullView * len(views))(*views)
+    arr._keep = [getattr(v, "_keep", None) for v in views]
+    return arr
 
 
 class Frame:
@@ -347,6 +400,14 @@ class Frame:
         dr = draw_ranges(offsets, commands, counts)
         self._draws_keep = dr
         _lib.check(self._L.ur_frame_set_draw_ranges(self._f, C.byref(dr)), "ur_frame_set_draw_ranges")
+
+    def set_cull_views(self, views=()):
+        """ur_frame_set_cull_views: the "GPU Culling" pass of the frames rendered with UR_FRAME_CULL_VIEWS also culls these views
+        (cull_view(...) results or dicts of its arguments; kept alive here). No views: clear."""
+        views = [v if isinstance(v, _lib.CullView) else cull_view(**v) for v in views]
+        arr = cull_views_array(views) if views else None
+        self._views_keep = arr
+        _lib.check(self._L.ur_frame_set_cull_views(self._f, arr, len(views)), "ur_frame_set_cull_views")
 
     def set_post_records(self, own_record, all_records):
         """ur_frame_set_post_records: where UR_FRAME_POST_EXCHANGE packs this rank's record (own_record) and where finish_post reads

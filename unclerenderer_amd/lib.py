@@ -37,6 +37,15 @@ class DrawRanges(C.Structure):
     _fields_ = [("offsets", C.c_void_p), ("range_count", C.c_uint32), ("commands", C.c_void_p), ("counts", C.c_void_p)]
 
 
+UR_MAX_CULL_VIEWS = 4
+
+
+class CullView(C.Structure):
+    """ur_cull_view (include/ur_hotpath.h): one extra frustum-only view of ur_cull_indirect_args_views."""
+    _fields_ = [("planes", C.c_float * 24), ("mask", C.c_void_p), ("visible_idx", C.c_void_p), ("visible_count", C.c_void_p),
+                ("draws", C.POINTER(DrawRanges))]
+
+
 class HzbSlice(C.Structure):
     """ur_hzb_slice: one contiguous run of floats of the HZB allocation."""
     _fields_ = [("offset", C.c_uint32), ("count", C.c_uint32)]
@@ -147,6 +156,7 @@ UR_FRAME_AUTO_EXPOSURE = 0x40000
 UR_FRAME_CAS = 0x80000
 UR_FRAME_FUSE_TONEMAP_CAS = 0x100000
 UR_FRAME_POST_EXCHANGE = 0x200000
+UR_FRAME_CULL_VIEWS = 0x400000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -183,6 +193,8 @@ SIGNATURES = {
     "ur_cull_indirect_args_ex": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP, _U32]),
     "ur_cull_indirect_args_draws": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP, _U32,
                                               C.POINTER(DrawRanges)]),
+    "ur_cull_indirect_args_views": (C.c_int, [_VP, C.POINTER(_U32), _VP, _VP, C.POINTER(MipDesc), _VP, _VP, _VP, _VP, _U32,
+                                              C.POINTER(DrawRanges), C.POINTER(CullView), _U32]),
     "ur_env_cube_texels": (C.c_size_t, [_U32, _U32]),
     "ur_stage_env_cube": (C.c_int, [_VP, _VP, _U32, _U32, _VP]),
     "ur_deferred_lighting": (C.c_int, [_VP, C.POINTER(SceneConstants), _VP, _VP, _VP, C.POINTER(LightingTables), _VP, _U32, _U32, _U32, _U32]),
@@ -225,6 +237,7 @@ SIGNATURES = {
     "ur_frame_set_post": (C.c_int, [_VP, C.POINTER(FramePost)]),
     "ur_frame_reset_post": (None, [_VP]),
     "ur_frame_set_draw_ranges": (C.c_int, [_VP, C.POINTER(DrawRanges)]),
+    "ur_frame_set_cull_views": (C.c_int, [_VP, C.POINTER(CullView), _U32]),
     "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
