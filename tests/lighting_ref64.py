@@ -262,6 +262,32 @@ def sample_cmp(shadow: np.ndarray, u, v, cmp):
     return _lerp(_lerp(r[0], r[1], fx), _lerp(r[2], r[3], fx), fy), tie
 
 
+def shadow_decisions(scene, A, w, h, row0=0, rows=None, pixels=None) -> dict:
+    """The float64 arguments of PSMain's shadow decisions per pixel (flat (n,) or (n, k) arrays over `pixels`, or the whole band):
+    uv (n, 2) shadowUV; inside (n,) the [0, 1] window test; cmp64 (n,) the compare value shadowDepth - ShadowBias; and the four
+    SampleCmpLevelZero taps' 3x3 union: ia, ja (n,) the block's first texel (texel (ia + c, ja + r) for r, c in 0..2) and
+    wx, wy (n, 3) its separable weights (1 - f, 1, f) per axis, whose products sum to 4."""
+    rows = A.shape[0] if rows is None else rows
+    ys, xs = _pixels(rows, w, pixels)
+    ViewInverse, Projection, LVP = _mat(scene.ViewInverse), _mat(scene.Projection), _mat(scene.LightViewProjection)
+    depth = np.ascontiguousarray(A, np.uint16).view(np.float16)[ys, xs, 3].astype(F64)
+    ndcx, ndcy = (xs + 0.5) / w * 2.0 - 1.0, (ys + row0 + 0.5) / h * 2.0 - 1.0
+    viewZ = -depth
+    viewPos = np.stack([ndcx * viewZ / Projection[0, 0], -ndcy * viewZ / Projection[1, 1], viewZ], -1)
+    worldPos = viewPos @ ViewInverse[:3, :3] + ViewInverse[3, :3]
+    sp = worldPos @ LVP[:3, :] + LVP[3, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sc = sp[:, :3] / sp[:, 3:]
+    uv = np.stack([sc[:, 0] * 0.5 + 0.5, sc[:, 1] * -0.5 + 0.5], -1)
+    x, y = uv[:, 0] * F64(scene.ShadowMapSize[0]) - 0.5, uv[:, 1] * F64(scene.ShadowMapSize[1]) - 0.5
+    ok = np.isfinite(x) & np.isfinite(y)
+    x0, y0 = np.floor(np.where(ok, x, 0.0)), np.floor(np.where(ok, y, 0.0))
+    fx, fy = x - x0, y - y0
+    return dict(uv=uv, inside=np.all((uv >= 0.0) & (uv <= 1.0), -1), cmp64=sc[:, 2] - F64(scene.ShadowBias),
+                ia=x0.astype(np.int64), ja=y0.astype(np.int64), wx=np.stack([1.0 - fx, np.ones_like(fx), fx], -1),
+                wy=np.stack([1.0 - fy, np.ones_like(fy), fy], -1))
+
+
 def srgb_to_linear(byte) -> np.ndarray:
     c = np.asarray(byte, F64) / 255.0
     return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)

@@ -47,7 +47,7 @@ struct StreamHot {
     float skyInvP11, nSkyInvP22, skyNearOverR2, maxMip;
     float envMaxLevel, irrNf, irrEf, irrEEf, irrOfff; // irradiance mip: N, N+2, (N+2)^2, texel offset — as floats (exact)
     float shadowWm3, shadowHm3, shadowWf;     // W-3, H-3, W as floats
-    float shadowXmax, shadowYmax, shadowStrength, shadowNegQuarterStrength; // W - 0.5, H - 0.5, s, -s/4
+    float shadowXmax, shadowYmax, shadowStrength, shadowQuarterStrength, shadowOneMinusStrength; // W - 0.5, H - 0.5, s, s/4, 1 - s
     uint32_t shadowRowBytes;
     int32_t shadowWi, shadowHi;
     const void* env;
@@ -301,13 +301,11 @@ __device__ __forceinline__ void lut_taps_filter(const LutTaps& t, float& a, floa
     b = fmaf(w11, (float)(t.t11 >> 16), fmaf(w01, (float)(t.t01 >> 16), fmaf(w10, (float)(t.t10 >> 16), w00 * (float)(t.t00 >> 16))));
 }
 
-// step(t) = (cmp <= t) as saturate((t - cmp) * 2^126 + 1): a full-rate subtract + clamped FMA instead of the half-rate
-// v_cmp + v_cndmask pair; exact for every normal pair (equality gives 1, NaN gives 0 like the comparison).
+// step(t) = (cmp <= t), LESS_EQUAL as the shader states it (a NaN on either side fails). A compare, not
+// saturate((t - cmp) * 2^126 + 1): that form returns a fraction when 0 < |t - cmp| < 2^-126 (cmp = 0, t = -2^-149).
 __device__ __forceinline__ float step_le(float cmp, float t)
 {
-    float r;
-    asm("v_fma_f32 %0, %1, %2, 1.0 clamp" : "=v"(r) : "v"(t - cmp), "v"(0x1p126f));
-    return r;
+    return cmp <= t ? 1.0f : 0.0f;
 }
 
 // The four PCF samples of DeferredLighting.hlsl:62-70: SampleCmpLevelZero (bilinear blend of four LESS_EQUAL results,
@@ -372,8 +370,9 @@ __device__ __forceinline__ float shadow_pcf_border_inline(const float* __restric
         for (int c = 0; c < 3; ++c) {
             const int xi = ia + c;
             const bool in = (uint32_t)xi < (uint32_t)W && (uint32_t)yj < (uint32_t)H;
-            const float t = ld<float>(map, (rowo + (uint32_t)min(max(xi, 0), W - 1)) * 4u);
-            s += (in ? cmp <= t : true) ? (c == 0 ? 1.0f - fx : (c == 1 ? 1.0f : fx)) : 0.0f;
+            // (the clamped address is always valid; an out-of-map tap compares against the border depth 1.0)
+            const float t = in ? ld<float>(map, (rowo + (uint32_t)min(max(xi, 0), W - 1)) * 4u) : 1.0f;
+            s += cmp <= t ? (c == 0 ? 1.0f - fx : (c == 1 ? 1.0f : fx)) : 0.0f;
         }
         acc = fmaf(r == 0 ? 1.0f - fy : (r == 1 ? 1.0f : fy), s, acc);
     }
@@ -732,12 +731,20 @@ __device__ __forceinline__ float h2f_lo(uint32_t w)
 }
 __device__ __forceinline__ float h2f_hi(uint32_t w) { return h2f_lo(w >> 16); }
 
-// g = (cmp > t) as clamp(cmp * 2^126 - t * 2^126): one clamped FMA per tap (cmpBig = cmp * 2^126 is exact), exact for every
-// finite pair; equality gives 0 (LESS_EQUAL passes).
-__device__ __forceinline__ float gt_step(float cmpBig, float t, float negBig /* -2^126 in a VGPR */)
+// LESS_EQUAL with one clamped FMA per tap. For finite cmp, (cmp <= t) = (t > pred(cmp)), pred the next float below cmp, so
+// the tap is clamp(t * 2^126 - pred(cmp) * 2^126): a texel at or above cmp sits at least one spacing of cmp above pred(cmp),
+// >= 2^-123 while |cmp| >= 2^-100, i.e. >= 8 after the scale; one at or below pred(cmp) gives <= 0; a NaN texel gives NaN,
+// which the clamp sends to 0 (the compare fails, as LESS_EQUAL does); +-Inf and huge texels overflow with their sign.
+// The form holds while 2^-100 <= |cmp| < 2 (cmp_step_exact): the scaled pred stays finite and the spacing large. Pixels outside
+// take the compare form (shadow_pcf_border_inline).
+__device__ __forceinline__ bool cmp_step_exact(float cmp) { return fabsf(cmp) >= 0x1p-100f && fabsf(cmp) < 2.0f; }
+// -pred(cmp) * 2^126: |cmp| * (2^-24 + 2^-47) lies strictly between half a spacing and 1.5 spacings of cmp on the side away from
+// zero (a power of two included), so one rounding of cmp - |cmp| (2^-24 + 2^-47) lands on pred(cmp)
+__device__ __forceinline__ float neg_pred_big(float cmp) { return fmaf(fabsf(cmp), 0x1.000002p-24f, -cmp) * 0x1p126f; }
+__device__ __forceinline__ float le_step(float negPredBig, float t, float negBig /* -2^126 in a VGPR */)
 {
     float r;
-    asm("v_fma_f32 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(t), "v"(negBig), "v"(cmpBig));
+    asm("v_fma_f32 %0, -%1, %2, %3 clamp" : "=v"(r) : "v"(t), "v"(negBig), "v"(negPredBig));
     return r;
 }
 
@@ -1154,8 +1161,9 @@ __global__ __launch_bounds__(64 * WPB, 1) void lighting_stream_kernel(LightingPa
             // no pixel of the frame has a sphere depth above skyDepthMax: a wave of nearer geometry skips the per-pixel test
             if (__any(!(depth > p.hot.skyDepthMax))) {
                 const float vx = ndcx * p.hot.skyInvP11, vy = ndcy * p.hot.nSkyInvP22;
-                // sphere depth (Near/R) * |(vx, vy, 1)| >= depth, compared squared (depth is in [0,1]): no square root
-                sky = p.hot.skyNearOverR2 * fmaf(vx, vx, fmaf(vy, vy, 1.0f)) >= depth * depth;
+                // sphere depth (Near/R) * |(vx, vy, 1)| >= depth, compared squared (no square root) where depth > 0; the sphere's depth
+                // is positive, so a stored depth <= 0 (-0 included) is sky and a NaN is not
+                sky = depth <= 0.0f || p.hot.skyNearOverR2 * fmaf(vx, vx, fmaf(vy, vy, 1.0f)) >= depth * depth;
                 all_sky = flag_all(sky);
                 if (sky) out = sky_pixel(kp, vx, vy);
             }
@@ -1269,7 +1277,7 @@ __global__ __launch_bounds__(64 * WPB, 1) void lighting_stream_kernel(LightingPa
                     sf = f2(xya.x - xa0, xya.y - ya0);
                     // 3x3 block origin clamped into the map (always a valid address); unclamped <=> no tap touches the border
                     const float ic = __builtin_amdgcn_fmed3f(xa0, 0.0f, p.hot.shadowWm3), jc = __builtin_amdgcn_fmed3f(ya0, 0.0f, p.hot.shadowHm3);
-                    any_slow = flag_any(ic != xa0) | flag_any(jc != ya0); // (each ballot straight off its comparison)
+                    any_slow = flag_any(ic != xa0) | flag_any(jc != ya0) | flag_any(!cmp_step_exact(cmp)); // (each ballot straight off its comparison)
                     // Only lanes that face the light need their block: the shadow term multiplies N.L, so a lane with N.L = 0 gets
                     // direct = 0 whatever its taps say. Such lanes all fetch the map's first block instead of their own - one cache line
                     // per row for the lot of them instead of up to three lines EACH (independent-per-pixel G-buffers: half the lanes of
@@ -1408,19 +1416,19 @@ __global__ __launch_bounds__(64 * WPB, 1) void lighting_stream_kernel(LightingPa
                 // ---- shadow filter first (the same uniform region: the explicit vmcnt(0) at the prefetch point has retired its taps) ----
                 float shadow = 1.0f;
                 if (SHADOWS) {
-                    // PCF = 1 - 0.25 sum w (cmp > t) with separable weights (1-f, 1, f); then lerp(1, pcf, strength)
+                    // PCF = 0.25 sum w (cmp <= t) with separable weights (1-f, 1, f); then lerp(1, pcf, strength)
                     const float sfx = sf.x, sfy = sf.y;
-                    const float cb = cmp * 0x1p126f;
+                    const float npb = neg_pred_big(cmp);
                     const float wx0 = 1.0f - sfx, wy0 = 1.0f - sfy;
-                    const float r0 = fmaf(gt_step(cb, sa.z, negBig), sfx, fmaf(gt_step(cb, sa.x, negBig), wx0, gt_step(cb, sa.y, negBig)));
-                    const float r1 = fmaf(gt_step(cb, sb.z, negBig), sfx, fmaf(gt_step(cb, sb.x, negBig), wx0, gt_step(cb, sb.y, negBig)));
-                    const float r2 = fmaf(gt_step(cb, sc3.z, negBig), sfx, fmaf(gt_step(cb, sc3.x, negBig), wx0, gt_step(cb, sc3.y, negBig)));
-                    shadow = fmaf(fmaf(sfy, r2, fmaf(wy0, r0, r1)), p.hot.shadowNegQuarterStrength, 1.0f);
-                    if (__builtin_expect(any_slow != 0u, 0)) { // some pixel's footprint touches the border (or lies outside the map)
+                    const float r0 = fmaf(le_step(npb, sa.z, negBig), sfx, fmaf(le_step(npb, sa.x, negBig), wx0, le_step(npb, sa.y, negBig)));
+                    const float r1 = fmaf(le_step(npb, sb.z, negBig), sfx, fmaf(le_step(npb, sb.x, negBig), wx0, le_step(npb, sb.y, negBig)));
+                    const float r2 = fmaf(le_step(npb, sc3.z, negBig), sfx, fmaf(le_step(npb, sc3.x, negBig), wx0, le_step(npb, sc3.y, negBig)));
+                    shadow = fmaf(fmaf(sfy, r2, fmaf(wy0, r0, r1)), p.hot.shadowQuarterStrength, p.hot.shadowOneMinusStrength);
+                    if (__builtin_expect(any_slow != 0u, 0)) { // some pixel's footprint touches the border (or lies outside the map), or its cmp is outside le_step's range
                         const float xa = xya.x, ya = xya.y;
                         const bool lit = xa >= -0.5f && ya >= -0.5f && xa <= kp->hot.shadowXmax && ya <= kp->hot.shadowYmax;
                         const float xa0 = floorf(xa), ya0 = floorf(ya);
-                        if (!(__builtin_amdgcn_fmed3f(xa0, 0.0f, kp->hot.shadowWm3) == xa0 && __builtin_amdgcn_fmed3f(ya0, 0.0f, kp->hot.shadowHm3) == ya0)) {
+                        if (!(__builtin_amdgcn_fmed3f(xa0, 0.0f, kp->hot.shadowWm3) == xa0 && __builtin_amdgcn_fmed3f(ya0, 0.0f, kp->hot.shadowHm3) == ya0 && cmp_step_exact(cmp))) {
                             const float s = shadow_pcf_border_inline(p.hot.shadow, kp->hot.shadowWi, kp->hot.shadowHi, (int)xa0, (int)ya0, sfx, sfy, cmp);
                             shadow = mix(1.0f, s, kp->hot.shadowStrength);
                         }
@@ -1794,7 +1802,8 @@ int launch_lighting(ur_ctx* ctx, const ur_scene_constants* S, const ur_sky_const
             h.shadowWm3 = (float)(p.shadowWi - 3); h.shadowHm3 = (float)(p.shadowHi - 3); h.shadowWf = (float)p.shadowWi;
             h.shadowRowBytes = (uint32_t)p.shadowWi * 4u;
             h.shadowStrength = p.shadowStrength;
-            h.shadowNegQuarterStrength = -0.25f * p.shadowStrength;
+            h.shadowQuarterStrength = 0.25f * p.shadowStrength;
+            h.shadowOneMinusStrength = 1.0f - p.shadowStrength;
             h.shadow = p.shadow;
             ok = ok && (uint64_t)p.shadowWi * (uint64_t)p.shadowHi < (1ull << 24); // texel indices are computed in fp32 (exact below 2^24)
         }
