@@ -2,14 +2,18 @@
 """bench.py — the reference's headline metric on MI355X: shaded Mpixels/s of the 4K deferred frame (BuildHZB +
 CullIndirectArgs + DeferredLighting/Sky) on the Sponza constants, with % of HBM roofline for the dominant kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline figure needs: set-up, the untimed frames, the K timed ones, --dump-outputs, the line.
+--full adds every leg of its own behind the timed region: the CPU baseline, the side measurements, the streaming ceiling, the
+Lighting kernel alone and between ordinary event pairs, and the timed frames again with Python's collector on.
 
 A step = one frame of BASELINE.json configs[2] on synthetic inputs already resident in HBM:
   cull (Sponza's 25 commands, last frame's HZB) -> BuildHZB (full chain) -> DeferredLighting+Sky (fused kernel).
 N > 1: the frame is sharded by screen row bands (rank r shades rows [r*H/N,(r+1)*H/N)), the cull by instance ranges, the
 HZB build is replicated, and the HDR bands are all-gathered with RCCL (torch.distributed backend "nccl") every frame.
-Rank 0 prints ONE JSON line. The CPU oracle is used only for the cpu_baseline leg (rank 0, N == 1).
+Rank 0 prints ONE JSON line. The CPU oracle is used only for the cpu_baseline leg (--full, rank 0, N == 1).
 """
 from __future__ import annotations
 
@@ -82,8 +86,14 @@ def parse():
     ap.add_argument("--timeline", action="store_true",
                     help="GPU-side timeline of the timed region (ur_debug_timeline: each cull / Lighting launch stamps its first entry and "
                          "last exit with the constant 100 MHz clock): per-kernel spans and the gaps between consecutive launches, without a profiler")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the 1M-instance cull and iid side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the side measurements (1M-instance cull, "
+                         "8K Build HZB, Lighting on other G-buffers and sizes, Tonemap, TemporalAA), the streaming ceiling, the Lighting "
+                         "kernel alone on the stream and between ordinary event pairs, the timed frames once more with Python's collector "
+                         "on, and the recorded HBM traffic. Off by default: a plain run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the streaming ceiling and the side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed frame computed (HDR frame, HZB chain, the cull's command words and "
                          "visible list) to DIR/<name>.npy as float32 / float64, at most 64 MB in all (see dump_outputs)")
@@ -430,10 +440,13 @@ def main():
         dt = float(t.item())
 
     light_ms, _ = (a.astype(np.float64) for a in frame.lighting_times_and_record_cost_ms())  # inside the timed region
+    # Every leg from here on that runs frames or kernels of its own is --full only, except the standalone Lighting loop when the
+    # timed region sampled nothing (--no-light-events): the line's roofline figure needs it then.
+
     # The same frames once more with Python's collector left on (a host that drives frames from Python without freezing it):
     # reported beside `value`, never instead of it
     gc_on = None
-    if not args.python_gc and N == 1:
+    if args.full and not args.python_gc and N == 1:
         gc.unfreeze()  # (the timed region above ran with the set-up heap frozen and the collector off)
         t1 = time.perf_counter()
         for k in range(args.steps):
@@ -443,33 +456,40 @@ def main():
         gc_on = {"value": W * H * args.steps / dt_gc / 1e6, "ms_per_step": dt_gc / args.steps * 1e3}
     # secondary (untimed frames): the Lighting pass between an ordinary event pair (hipEventRecord in front and behind), with a
     # third event recorded right behind each pair: what round 2 reported (bracket, and bracket minus one record's cost)
-    for k in range(32):
-        s_ = sets[k % ring]
-        if s_.get("gather") is not None:
-            s_["gather"].wait()
-            s_["gather"] = None
-        frame.render(s_["res"], cull_consts, fc.scene, fc.sky, flags | urlib.UR_FRAME_TIME_LIGHTING_RECORD_COST)
-    fence()
-    bracket_ms, record_ms = (a.astype(np.float64) for a in frame.lighting_times_and_record_cost_ms())
-    record_ms = record_ms[record_ms >= 0]
-    if record_ms.size == 0:
-        record_ms = np.zeros(1)
-    if bracket_ms.size == 0:
-        bracket_ms = np.zeros(1)
+    bracket_avg_s = record_avg_s = None
+    if args.full:
+        for k in range(32):
+            s_ = sets[k % ring]
+            if s_.get("gather") is not None:
+                s_["gather"].wait()
+                s_["gather"] = None
+            frame.render(s_["res"], cull_consts, fc.scene, fc.sky, flags | urlib.UR_FRAME_TIME_LIGHTING_RECORD_COST)
+        fence()
+        bracket_ms, record_ms = (a.astype(np.float64) for a in frame.lighting_times_and_record_cost_ms())
+        record_ms = record_ms[record_ms >= 0]
+        if record_ms.size == 0:
+            record_ms = np.zeros(1)
+        if bracket_ms.size == 0:
+            bracket_ms = np.zeros(1)
+        bracket_avg_s = float(bracket_ms.mean()) * 1e-3  # secondary: [record, launch, record] of the untimed frames behind it
+        record_avg_s = float(record_ms.mean()) * 1e-3
     # the same kernel in a loop of its own (no visibility passes around it): ONE event pair around the whole batch, so that
     # no event record sits between two launches (the figure includes the ~2 us boundary between back-to-back launches)
-    n_alone = min(max(args.steps, 50), 300)
-    for k in range(20):
-        s = sets[k % ring]
-        hp.deferred_lighting_sky(fc.scene, fc.sky, s["A"], s["B"], s["C"], s["depth_band"], tables, s["hdr_band"], W, H, row0, band)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for k in range(n_alone):
-        s = sets[k % ring]
-        hp.deferred_lighting_sky(fc.scene, fc.sky, s["A"], s["B"], s["C"], s["depth_band"], tables, s["hdr_band"], W, H, row0, band)
-    e1.record()
-    torch.cuda.synchronize()
-    alone_ms = np.array([e0.elapsed_time(e1) / n_alone], dtype=np.float64)
+    alone_ms = schedule = None
+    if args.full or light_ms.size == 0:
+        n_alone = min(max(args.steps, 50), 300)
+        for k in range(20):
+            s = sets[k % ring]
+            hp.deferred_lighting_sky(fc.scene, fc.sky, s["A"], s["B"], s["C"], s["depth_band"], tables, s["hdr_band"], W, H, row0, band)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for k in range(n_alone):
+            s = sets[k % ring]
+            hp.deferred_lighting_sky(fc.scene, fc.sky, s["A"], s["B"], s["C"], s["depth_band"], tables, s["hdr_band"], W, H, row0, band)
+        e1.record()
+        torch.cuda.synchronize()
+        alone_ms = np.array([e0.elapsed_time(e1) / n_alone], dtype=np.float64)
+        schedule = hp.lighting_schedule()  # the tile schedule of this loop's last launch (it carries no HZB chain): null where the loop did not run
     if light_ms.size == 0:
         light_ms = alone_ms
     n_sky = int((g.depth == 0).sum())
@@ -486,8 +506,6 @@ def main():
     # same rows for the sky test), so the launch's compulsory bytes are smaller by one depth buffer
     light_bytes_dedup = light_bytes - (4 * W * band if rides else 0)  # (at N > 1: the rows of this rank's band)
     light_avg_s = float(light_ms.mean()) * 1e-3        # dispatch begin -> end, averaged over the samples of the timed region
-    bracket_avg_s = float(bracket_ms.mean()) * 1e-3    # secondary: [record, launch, record] of the untimed frames behind it
-    record_avg_s = float(record_ms.mean()) * 1e-3
     achieved = light_bytes / light_avg_s / 1e9
 
     result = {
@@ -532,15 +550,15 @@ def main():
             "lighting_bytes": light_only_bytes, "hzb_bytes_in_launch": hzb_bytes if rides else 0,
             "frac_lighting_bytes_only": light_only_bytes / light_avg_s / 1e9 / HBM_PEAK_GBS,
             "shade_only_mpixels_per_s": g.depth.size * N / light_avg_s / 1e6,
-            "launches_sampled": int(light_ms.size), "alone_on_stream_us": float(alone_ms.mean()) * 1e3,
-            "alone_on_stream_frac": light_only_bytes / (float(alone_ms.mean()) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "event_bracket_us": bracket_avg_s * 1e6, "event_record_us": record_avg_s * 1e6,
-            "frac_event_bracket": light_bytes / bracket_avg_s / 1e9 / HBM_PEAK_GBS if bracket_avg_s > 0 else None,
-            "frac_event_bracket_minus_record": light_bytes / (bracket_avg_s - record_avg_s) / 1e9 / HBM_PEAK_GBS if bracket_avg_s > record_avg_s else None,
-            "schedule": hp.lighting_schedule(),
+            "launches_sampled": int(light_ms.size), "alone_on_stream_us": float(alone_ms.mean()) * 1e3 if alone_ms is not None else None,
+            "alone_on_stream_frac": light_only_bytes / (float(alone_ms.mean()) * 1e-3) / 1e9 / HBM_PEAK_GBS if alone_ms is not None else None,
+            "event_bracket_us": bracket_avg_s * 1e6 if args.full else None, "event_record_us": record_avg_s * 1e6 if args.full else None,
+            "frac_event_bracket": light_bytes / bracket_avg_s / 1e9 / HBM_PEAK_GBS if args.full and bracket_avg_s > 0 else None,
+            "frac_event_bracket_minus_record": light_bytes / (bracket_avg_s - record_avg_s) / 1e9 / HBM_PEAK_GBS if args.full and bracket_avg_s > record_avg_s else None,
+            "schedule": schedule,
         },
     }
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         # the practical ceiling, on this box, in this run, at this launch's byte count (untimed leg)
         sc = stream_ceiling_leg(hp, torch, light_bytes, dev)
         r_ = result["roofline"]
@@ -548,19 +566,19 @@ def main():
         r_["frac_of_stream_ceiling"] = achieved / sc["GBps"]
         r_["stream_ceiling"] = sc
     traffic_file = ROOT / "profiles" / "traffic_latest.json"
-    if traffic_file.exists():
+    if args.full and traffic_file.exists():
         try:
             result["roofline"]["traffic"] = json.loads(traffic_file.read_text()).get("lighting_kernel_fused_bytes_per_launch")
         except Exception:
             pass
 
-    if rank == 0 and N == 1 and not args.no_extras:
+    if args.full and rank == 0 and N == 1 and not args.no_extras:
         result["extras"] = ex = side_measurements(args, hp, fc, torch, to_device, HzbLayout, synth, hostmath, dev, (d_env_cube, d_lut))
         # the same kernel on SURVEY.md §8d's own generator travels in the roofline block too (the headline input is the
         # coherent "scene" G-buffer; on independent-per-pixel normals every lane gathers its own cube/shadow line)
         result["roofline"]["other_inputs"] = {k: {"us": ex[k]["us"], "achieved": ex[k]["GBps"], "frac": ex[k]["frac_hbm"]}
                                               for k in ("lighting_iid", "lighting_1080p_scene", "lighting_8k_scene")}
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(fc, g, shadow, env, lut, bounds, lay, W, H)
     if timeline is not None:
         result["timeline"] = timeline
