@@ -284,3 +284,24 @@ def test_the_product_kernel_source_carries_no_variant_switches():
     src = (ROOT / "unclerenderer_amd" / "csrc" / "lighting.hip").read_text()
     for switch in ("UR_LOADER_WAVE", "UR_ABLATE", "UR_STAMP", "UR_HDR_STORE", "UR_DMA_NT", "UR_RIDE_RELEASE_FENCE"):
         assert switch not in src, f"{switch} is back in the product source"
+
+
+def test_camera_and_view_cull_kernels_live_in_modules_of_their_own(tmp_path, urlib):
+    """cull.hip and cull_views.hip share the kernels and their host launch path (cull_kernels.h) but instantiate them apart: the camera-only
+    cull_kernel / compact_kernel (last template argument VIEWS = false, Lb0) in one code object, those with views (Lb1) in another. The
+    views kernels change cull_kernel<true, true>'s code when they share its module. Each module holds one zeroing kernel."""
+    if not (LLVM / "llvm-readelf").exists():
+        pytest.skip("llvm tools not found")
+    modules = []
+    for co in _code_objects(tmp_path):
+        syms = subprocess.run([str(LLVM / "llvm-readelf"), "-s", "--wide", str(co)], capture_output=True, text=True, check=True).stdout
+        kernels = set(re.findall(r"\s(\S+)\.kd\s*$", syms, re.M))
+        cull = {k: re.search(r"(?:cull|compact)_kernelI((?:Lb[01]E)+)E", k).group(1) for k in kernels if re.search(r"(?:cull|compact)_kernelI", k)}
+        if any("cull_kernelI" in k for k in cull):
+            modules.append((co.name, cull, sorted(k for k in kernels if re.search(r"zero\w*_kernel", k))))
+    assert len(modules) == 2, [m[0] for m in modules]
+    views = {name: {args.endswith("Lb1E") for args in cull.values()} for name, cull, _ in modules}
+    assert sorted(map(sorted, views.values())) == [[False], [True]], {name: sorted(cull) for name, cull, _ in modules}
+    for name, cull, zero in modules:
+        assert sum("cull_kernelI" in k for k in cull) == 4 and sum("compact_kernelI" in k for k in cull) == 2, (name, sorted(cull))
+        assert len(zero) == 1, (name, zero)

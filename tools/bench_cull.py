@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Timing of the cull with extra views (ur_cull_indirect_args_views) on one GPU (development aid; bench.py is the contract benchmark
-and never sets views).
+"""Timing of the cull with draw ranges (ur_cull_indirect_args_draws) and with extra views (ur_cull_indirect_args_views) on one GPU
+(development aid; bench.py is the contract benchmark and never sets ranges or views).
 
-    python tools/bench_cull_views.py [--batches 9] [--iters 30] [--json out.jsonl]
-    python tools/bench_cull_views.py --quick      # each shape a few times: for a rocprofv3 --kernel-trace --stats run
+    python tools/bench_cull.py [--shapes ranges|views|both] [--batches 9] [--iters 30] [--json out.jsonl]
+    python tools/bench_cull.py --quick      # each shape a few times: for a rocprofv3 --kernel-trace --stats run
 
 C5 (BASELINE config 5): 1 M instance AABBs against the 12-mip HZB of a 7680x4320 depth, with the camera's visible list, over six
-rotating buffer sets (cold, as bench.py's extras): the plain call, plus one view (mask; mask + list; R = 64 ranges), plus two and four
-views (masks), and the two-call alternative - the plain call, then ur_cull_indirect_args with the light's constants and HZBEnabled = 0
-into a second command buffer. The shapes alternate batch by batch in one process. Then the single-block calls of Sponza's 25 and
-pica_pica's 170 commands with and without one view. Each time is one device-event pair around a batch of back-to-back calls, divided
-by the calls (launch gaps included). Kernel times and launch counts come from a separate rocprofv3 --kernel-trace --stats run of --quick.
+rotating buffer sets (bounds, commands, lists, masks and compacted commands: cold, as bench.py's extras). The plain call, then
+  ranges: R = 1, 64, 4096 (a random partition) and one range per command;
+  views:  one view (mask; mask + list; R = 64 ranges), two and four views (masks), and the two-call alternative - the plain call,
+          then ur_cull_indirect_args with the light's constants and HZBEnabled = 0 into a second command buffer.
+The shapes alternate batch by batch in one process. Then the single-block calls of Sponza's 25 and pica_pica's 170 commands: plain,
+with one range per command (ranges) and with one view (views). Each time is one device-event pair around a batch of back-to-back
+calls, divided by the calls (launch gaps included). Kernel times and launch counts come from a separate rocprofv3 --kernel-trace
+--stats run of --quick.
 """
 import argparse
 import json
@@ -35,6 +38,7 @@ def time_batch(torch, fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", choices=("ranges", "views", "both"), default="both", help="the shapes beside the plain call")
     ap.add_argument("--instances", type=int, default=1_000_000)
     ap.add_argument("--batches", type=int, default=9)
     ap.add_argument("--iters", type=int, default=30, help="calls per timed batch")
@@ -44,10 +48,11 @@ def main():
     a = ap.parse_args()
     if a.quick:
         a.batches, a.iters, a.ring = 1, 3, 2
+    ranges, views = a.shapes in ("ranges", "both"), a.shapes in ("views", "both")
     import torch
     from unclerenderer_amd import hostmath, scene, synth
     from unclerenderer_amd.hotpath import HotPath, HzbLayout, cull_view, to_device
-    assert torch.cuda.is_available(), "bench_cull_views needs a GPU"
+    assert torch.cuda.is_available(), "bench_cull needs a GPU"
     hp = HotPath(0)
     n = a.instances
     W8, H8 = 7680, 4320
@@ -69,35 +74,44 @@ def main():
     bounds = to_device(synth.instances_random(n, synth.SEED_BASE + 5, center=fc8.camera_position, box=400.0))
     args0 = to_device(synth.indirect_args_initial(n))
     words = (n + 31) // 32
-    o64 = np.linspace(0, n, 65).astype(np.uint32)
-    d_o64 = hp.draw_offsets_to_device(o64, n)
     cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(4096)
+    layouts = {"R=1": np.array([0, n], np.uint32), "R=64": np.linspace(0, n, 65).astype(np.uint32),
+               "R=4096": np.sort(np.concatenate([[0], rng.integers(0, n + 1, 4095), [n]])).astype(np.uint32),
+               "R=n": np.arange(n + 1, dtype=np.uint32)}
+    dev_layouts = {k: (hp.draw_offsets_to_device(o, n), torch.zeros(o.size - 1, dtype=torch.int32, device="cuda")) for k, o in layouts.items()}
+    zeros = lambda k: torch.zeros(k, dtype=torch.int32, device="cuda")
     sets = []
     for k in range(a.ring):
-        s = dict(bounds=bounds if k == 0 else bounds.clone(), args=args0.clone(), vis=torch.zeros(n, dtype=torch.int32, device="cuda"),
-                 args2=args0.clone(), masks=[torch.zeros(words, dtype=torch.int32, device="cuda") for _ in range(4)],
-                 vvis=torch.zeros(n, dtype=torch.int32, device="cuda"), vcnt=torch.zeros(1, dtype=torch.int32, device="cuda"),
-                 cmds=torch.zeros(n * 16, dtype=torch.int32, device="cuda"), counts=torch.zeros(64, dtype=torch.int32, device="cuda"))
-        s["views"] = {
-            "none": None,
-            "1 view, mask": [cull_view(light, mask=s["masks"][0])],
-            "1 view, mask + list": [cull_view(light, mask=s["masks"][0], visible_idx=s["vvis"], visible_count=s["vcnt"])],
-            "1 view, R=64 ranges": [cull_view(light, draw_offsets=d_o64, draw_commands=s["cmds"], draw_counts=s["counts"])],
-            "2 views, masks": [cull_view(planes[i], mask=s["masks"][i]) for i in range(2)],
-            "4 views, masks": [cull_view(planes[i], mask=s["masks"][i]) for i in range(4)],
-        }
+        s = dict(bounds=bounds if k == 0 else bounds.clone(), args=args0.clone(), vis=zeros(n), cmds=zeros(n * 16))
+        if views:
+            s.update(args2=args0.clone(), masks=[zeros(words) for _ in range(4)], vvis=zeros(n), vcnt=zeros(1), vcounts=zeros(64))
         sets.append(s)
-    shapes = list(sets[0]["views"]) + ["two calls (plain + light, HZB off)"]
+    # shape -> the keyword arguments of the call on buffer set s (None: the two-call alternative)
+    shapes = {"plain": lambda s: {}}
+    if ranges:
+        for key, (d_o, d_n) in dev_layouts.items():
+            shapes[f"ranges {key}"] = lambda s, d_o=d_o, d_n=d_n: dict(draw_offsets=d_o, draw_commands=s["cmds"], draw_counts=d_n)
+    if views:
+        d_o64 = dev_layouts["R=64"][0]
+        shapes.update({
+            "1 view, mask": lambda s: dict(views=[cull_view(light, mask=s["masks"][0])]),
+            "1 view, mask + list": lambda s: dict(views=[cull_view(light, mask=s["masks"][0], visible_idx=s["vvis"], visible_count=s["vcnt"])]),
+            "1 view, R=64 ranges": lambda s: dict(views=[cull_view(light, draw_offsets=d_o64, draw_commands=s["cmds"], draw_counts=s["vcounts"])]),
+            "2 views, masks": lambda s: dict(views=[cull_view(planes[i], mask=s["masks"][i]) for i in range(2)]),
+            "4 views, masks": lambda s: dict(views=[cull_view(planes[i], mask=s["masks"][i]) for i in range(4)]),
+            "two calls (plain + light, HZB off)": None,
+        })
+    calls = {key: [f(s) if f is not None else None for s in sets] for key, f in shapes.items()}  # (built once per buffer set)
     turn = [0]
 
     def call(key):
-        s = sets[turn[0] % a.ring]
+        i = turn[0] % a.ring
+        s, kw = sets[i], calls[key][i]
         turn[0] += 1
-        if key.startswith("two calls"):
-            hp.cull_indirect_args(consts, s["bounds"], hzb8, lay8, s["args"], None, s["vis"], cnt)
+        hp.cull_indirect_args(consts, s["bounds"], hzb8, lay8, s["args"], None, s["vis"], cnt, **(kw or {}))
+        if kw is None:
             hp.cull_indirect_args(light_consts, s["bounds"], None, None, s["args2"], None)
-        else:
-            hp.cull_indirect_args(consts, s["bounds"], hzb8, lay8, s["args"], None, s["vis"], cnt, views=s["views"][key])
 
     for key in shapes:  # warm-up, and the steady state of the words (UR_OPT_CULL_STORE = 3) in every set
         for _ in range(a.ring):
@@ -112,7 +126,7 @@ def main():
     for key, t in times.items():
         rows.append({"shape": f"C5 {n} instances, {visible} visible, list on, {key}", "median_us": float(np.median(t)),
                      "min_us": float(np.min(t)), "batches": len(t), "calls_per_batch": a.iters, "inputs": f"{a.ring} buffer sets cycled (cold)"})
-    del sets
+    del sets, calls, dev_layouts
     torch.cuda.empty_cache()
 
     # the single-block calls: the scenes' own command AABBs and cameras
@@ -126,20 +140,24 @@ def main():
         hp.build_hzb(to_device(g.depth), hzb, lay)
         c = hostmath.pack_culling_constants(fc.view, fc.proj, m, True, lay.count, lay.width, lay.height, False)
         d_b, d_a = to_device(sb.bounds), to_device(synth.indirect_args_initial(m))
-        d_v, d_c = torch.zeros(m, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
-        d_m = torch.zeros((m + 31) // 32, dtype=torch.int32, device="cuda")
-        lv = [cull_view(hostmath.frustum_planes(hostmath.light_view_projection(fc.scene_center, fc.scene_radius, fc.light_direction)), mask=d_m)]
-        plain = lambda k: hp.cull_indirect_args(c, d_b, hzb, lay, d_a, None, d_v, d_c)
-        viewed = lambda k: hp.cull_indirect_args(c, d_b, hzb, lay, d_a, None, d_v, d_c, views=lv)
-        for f in (plain, viewed):
+        d_v, d_c = zeros(m), zeros(1)
+        small = {"plain": {}}
+        if ranges:
+            small["ranges one per command"] = dict(draw_offsets=hp.draw_offsets_to_device(scene.draw_offsets(np.arange(m)), m),
+                                                  draw_commands=zeros(m * 16), draw_counts=zeros(m))
+        if views:
+            lv = hostmath.frustum_planes(hostmath.light_view_projection(fc.scene_center, fc.scene_radius, fc.light_direction))
+            small["1 view, mask"] = dict(views=[cull_view(lv, mask=zeros((m + 31) // 32))])
+        fns = {key: lambda k, kw=kw: hp.cull_indirect_args(c, d_b, hzb, lay, d_a, None, d_v, d_c, **kw) for key, kw in small.items()}
+        for f in fns.values():
             for k in range(5):
                 f(k)
         torch.cuda.synchronize()
-        tp, tv = [], []
+        ts = {key: [] for key in fns}
         for _ in range(a.batches):
-            tp.append(time_batch(torch, plain, a.iters * 4))
-            tv.append(time_batch(torch, viewed, a.iters * 4))
-        for key, t in (("no view", tp), ("1 view, mask", tv)):
+            for key, f in fns.items():
+                ts[key].append(time_batch(torch, f, a.iters * 4))
+        for key, t in ts.items():
             rows.append({"shape": f"{name} {m} commands, list on, {key}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
                          "batches": len(t), "calls_per_batch": a.iters * 4, "inputs": "one buffer set"})
     hp.close()
@@ -149,7 +167,7 @@ def main():
         with open(a.json, "a") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
-    print(json.dumps({"tool": "bench_cull_views", "quick": a.quick, "results": rows}))
+    print(json.dumps({"tool": "bench_cull", "shapes": a.shapes, "quick": a.quick, "results": rows}))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
-// The CullIndirectArgs kernels (see cull.hip), shared by the two translation units that launch them: cull.hip the camera-only
-// instantiations, cull_views.hip those with extra views. Each kernel is instantiated in one of them only, so the camera-only kernels
-// are compiled in a module of their own, as they were before the views existed.
+// The CullIndirectArgs kernels (see cull.hip) and their one host launch path (cull_launches), shared by the two translation units that
+// launch them: cull.hip the camera-only instantiations, cull_views.hip those with extra views. Each kernel is instantiated in one of
+// them only, so the camera-only kernels are compiled in a module of their own, as they were before the views existed.
 #pragma once
 
 #include "ur_internal.h"
@@ -546,16 +546,7 @@ __global__ __launch_bounds__(256) void compact_kernel(CullArgs<RANGES, VIEWS> C,
     if (mi == num_masks - 1u) *A.visible_count = at;
 }
 
-__global__ void zero_counts_kernel(uint32_t* visible_count, uint32_t* counts, uint32_t range_count)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i == 0 && visible_count) *visible_count = 0;
-    if (i < range_count) counts[i] = 0;
-}
-
-__global__ void zero_count_kernel(uint32_t* p) { *p = 0; }
-
-// ModelCount == 0 with views: every count (camera's and views') and every counts[r], one launch
+// ModelCount == 0: every count (camera's and views') and every counts[r], one launch
 struct ZeroArgs {
     uint32_t* count[1 + UR_MAX_CULL_VIEWS];
     uint32_t* counts[1 + UR_MAX_CULL_VIEWS];
@@ -569,6 +560,140 @@ __global__ void zero_views_kernel(ZeroArgs Z)
         if (i == 0 && Z.count[k]) *Z.count[k] = 0;
         if (i < Z.range_count[k]) Z.counts[k][i] = 0;
     }
+}
+
+// One 256-thread launch on the context's stream; with `stop` (ur_time_next_cull) its dispatch carries the event
+template <class K, class... Args>
+int launch_stop(ur_ctx* ctx, hipEvent_t stop, K kernel, dim3 grid, const Args&... args)
+{
+    if (stop != nullptr) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, nullptr, stop, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, args...);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+DrawParams draw_params(const ur_draw_ranges& d) { return {d.offsets, static_cast<uint8_t*>(d.commands), d.counts, d.range_count}; }
+
+// The launches of one cull call after the HZB tail is flushed: the camera alone (VIEWS = false, cull.hip) or with view_count >= 1
+// extra views (cull_views.hip). Each translation unit instantiates it once, so each module holds its own set of kernels only.
+template <bool VIEWS>
+int cull_launches(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb, const ur_mip_desc* mips,
+                  void* indirect_args, uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count, uint32_t index_base,
+                  const ur_draw_ranges* draws, const ur_cull_view* views, uint32_t view_count)
+{
+    if constexpr (!VIEWS) view_count = 0;
+    CullArgs<true, VIEWS> P{};
+    static_assert(sizeof(float4) * 6 + sizeof(float) * 16 + 6 * 4 == UR_CULL_CONSTANT_DWORDS * 4, "46 dwords");
+    std::memcpy(static_cast<CullParams*>(&P), constants, UR_CULL_CONSTANT_DWORDS * 4);
+    P.bounds = reinterpret_cast<const float4*>(bounds);
+    P.hzb = hzb;
+    P.args = static_cast<uint8_t*>(indirect_args);
+    P.stats = stats2;
+    P.visible_idx = visible_idx;
+    P.visible_count = visible_count;
+    P.index_base = index_base;
+    P.store_flavour = (uint32_t)ctx->opt.cull_store; // UR_OPT_CULL_STORE
+    P.timeline = P.ModelCount != 0 ? ur::next_timeline_pair(ctx) : nullptr; // (the compaction launch of a large cull is not stamped)
+    if (P.HZBEnabled != 0) {
+        for (uint32_t m = 0; m < P.HZBMipCount && m < UR_MAX_HZB_MIPS; ++m) {
+            P.mip_offset[m] = mips[m].offset;
+            P.mip_width[m] = mips[m].width;
+        }
+    }
+    if (draws) P.D = draw_params(*draws);
+    if constexpr (VIEWS) {
+        P.V.count = view_count;
+        for (uint32_t v = 0; v < view_count; ++v) {
+            std::memcpy(P.V.planes[v], views[v].planes, sizeof(P.V.planes[v]));
+            P.V.mask[v] = views[v].mask;
+            P.V.visible_idx[v] = views[v].visible_idx;
+            P.V.visible_count[v] = views[v].visible_count;
+            if (views[v].draws) P.V.D[v] = draw_params(*views[v].draws);
+        }
+    }
+    // UR_OPT_CULL_STORE = 4: the wave masks ARE the record of what a multi-block launch leaves in the command buffer; they describe the
+    // buffer the next launch meets if that launch is on the same buffer with the same count (and the caller keeps the promise of the
+    // option). The record is forgotten here and kept again only once every launch of this call has gone out.
+    const uint32_t n = P.ModelCount;
+    bool record_valid = P.store_flavour == 4u && ctx->cull_record_args == indirect_args && ctx->cull_record_n == n;
+    ctx->cull_record_args = nullptr;
+    // ur_time_next_cull: the call's LAST launch carries the event on its dispatch (its completion stamp is somebody's start time).
+    // (The entry point clears the context's copy behind this function on every path: a raw hipEvent_t must not stay in the context.)
+    hipEvent_t stop = ctx->time_cull_stop;
+    // a view with a list or ranges (compacted, with a scratch slice of its own, above one block)
+    auto compacted = [&](uint32_t v) { return views[v].visible_idx != nullptr || views[v].draws != nullptr; };
+
+    if (n == 0) { // one launch zeroes every count and every counts[r], if there are any (no mask word is written)
+        ZeroArgs Z{};
+        Z.count[0] = visible_count;
+        if (draws) { Z.counts[0] = draws->counts; Z.range_count[0] = draws->range_count; }
+        bool zero = visible_count != nullptr || draws != nullptr;
+        uint32_t most = Z.range_count[0];
+        for (uint32_t v = 0; v < view_count; ++v) {
+            zero = zero || views[v].visible_count || views[v].draws;
+            Z.count[1 + v] = views[v].visible_count;
+            if (views[v].draws) {
+                Z.counts[1 + v] = views[v].draws->counts;
+                Z.range_count[1 + v] = views[v].draws->range_count;
+                most = std::max(most, views[v].draws->range_count);
+            }
+        }
+        if (!zero) return UR_OK;
+        const int rc = launch_stop(ctx, stop, zero_views_kernel, dim3(std::max(1u, (uint32_t)(((uint64_t)most + 255u) / 256u))), Z);
+        if (rc != UR_OK) return rc;
+        ctx->time_cull_carried = stop != nullptr;
+        return UR_OK;
+    }
+    CullArgs<false, VIEWS> Q{}; // (the same parameters without the camera's ranges; filled in front of the launches)
+    const uint32_t blocks = (n + 255u) / 256u;
+    int rc = UR_OK;
+    if (blocks == 1) { // (one block keeps no masks: no record)
+        static_cast<CullParams&>(Q) = P;
+        if constexpr (VIEWS) Q.V = P.V;
+        rc = draws ? launch_stop(ctx, stop, cull_kernel<true, true, VIEWS>, dim3(1), P) : launch_stop(ctx, stop, cull_kernel<true, false, VIEWS>, dim3(1), Q);
+        if (rc != UR_OK) return rc;
+        ctx->time_cull_carried = stop != nullptr;
+        return UR_OK;
+    }
+    // the masks and block counts: the compaction's input, flavour 4's record (with views the camera's are always written)
+    bool compact = draws != nullptr || visible_idx != nullptr;
+    if (VIEWS || compact || P.store_flavour == 4u) {
+        if (n > ctx->ws_instances) {
+            rc = ur_reserve(ctx, n);
+            if (rc != UR_OK) return rc;
+            record_valid = false; // (a new workspace holds no record)
+        }
+        P.block_counts = ctx->block_counts;
+        P.wave_masks = ctx->wave_masks;
+        if constexpr (VIEWS) { // slice 0 is the camera's (and flavour 4's record); view v's is slice 1 + v
+            const uint32_t stride = ctx->ws_instances / 256u;
+            for (uint32_t v = 0; v < view_count; ++v) {
+                if (!compacted(v)) continue;
+                compact = true;
+                P.V.block_counts[v] = ctx->block_counts + (size_t)(1u + v) * stride;
+                P.V.wave_masks[v] = ctx->wave_masks + (size_t)(1u + v) * stride * 4u;
+            }
+        }
+    }
+    P.record_valid = record_valid ? 1u : 0u;
+    static_cast<CullParams&>(Q) = P;
+    if constexpr (VIEWS) Q.V = P.V;
+    // the cull, then the compaction when there is a list or there are ranges: one row of workgroups for the camera, one per view
+    const dim3 compaction_grid((blocks * 4u + 255u) / 256u, 1u + view_count);
+    if (draws) {
+        rc = launch_stop(ctx, compact ? nullptr : stop, cull_kernel<false, true, VIEWS>, dim3(blocks), P);
+        if (rc == UR_OK && compact) rc = launch_stop(ctx, stop, compact_kernel<true, VIEWS>, compaction_grid, P, blocks);
+    } else {
+        rc = launch_stop(ctx, compact ? nullptr : stop, cull_kernel<false, false, VIEWS>, dim3(blocks), Q);
+        if (rc == UR_OK && compact) rc = launch_stop(ctx, stop, compact_kernel<false, VIEWS>, compaction_grid, Q, blocks);
+    }
+    if (rc != UR_OK) return rc;
+    if (P.store_flavour == 4u) {
+        ctx->cull_record_args = indirect_args;
+        ctx->cull_record_n = n;
+    }
+    ctx->time_cull_carried = stop != nullptr;
+    return UR_OK;
 }
 
 } // namespace

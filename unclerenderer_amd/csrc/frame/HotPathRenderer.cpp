@@ -75,11 +75,10 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         // With draw ranges the same call also places the visible commands of each range and writes its count (ur_cull_indirect_args_draws).
         // With extra views (UR_FRAME_CULL_VIEWS) the same launch also tests them (ur_cull_indirect_args_views): the DepthPrepass / ShadowMap
         // visibility of UpdateCullingVisibility (DeferredRenderer.cpp:3803-3812) and the shadow pass (:583-591).
-        const int rc = Res.CullViewCount != 0
-            ? ur_cull_indirect_args_views(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
-                                          Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges, Res.CullViews, Res.CullViewCount)
-            : ur_cull_indirect_args_draws(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
-                                          Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges);
+        // (No views: views = NULL, exactly ur_cull_indirect_args_draws.)
+        const int rc = ur_cull_indirect_args_views(Cmd.GetContext(), Data.Constants, Res.ModelBounds, Res.HZB, Res.HZBMips, Res.IndirectArgs, Res.CullStats,
+                                                   Res.VisibleIndices, Res.VisibleCount, Res.InstanceIndexBase, Res.DrawRanges,
+                                                   Res.CullViewCount != 0 ? Res.CullViews : nullptr, Res.CullViewCount);
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
 

@@ -356,10 +356,24 @@ int ur_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h
     return ur::launch_build_hzb(ctx, depth, src_w, src_h, hzb_base, mips, mip_count);
 }
 
+// What is wrong with one set of draw ranges, the camera's or a view's, against indirect_args. n = ModelCount, or ~0 when the commands
+// are not known yet (the frame's copy of the views): the overlap and alignment checks then wait for the call.
+enum class DrawsFault { none, member, overlap, alignment };
+static DrawsFault check_draws(const ur_draw_ranges& d, uint32_t n, const void* indirect_args)
+{
+    if (!d.offsets || !d.commands || !d.counts || d.range_count == 0) return DrawsFault::member;
+    if (n == ~0u || n == 0) return DrawsFault::none;
+    const uintptr_t c = reinterpret_cast<uintptr_t>(d.commands), a = reinterpret_cast<uintptr_t>(indirect_args);
+    const uintptr_t bytes = (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE;
+    if (c < a + bytes && a < c + bytes) return DrawsFault::overlap;
+    if (((c | a) & 15u) != 0) return DrawsFault::alignment;
+    return DrawsFault::none;
+}
+
 static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
                         const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
                         uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws,
-                        const ur_cull_view* views = nullptr, uint32_t view_count = 0)
+                        const ur_cull_view* views, uint32_t view_count)
 {
     if (!ctx || !constants) { set_error("ur_cull_indirect_args: null ctx/constants"); return UR_EINVAL; }
     const uint32_t n = constants[40], hzb_on = constants[41], mipc = constants[42];
@@ -371,37 +385,16 @@ static int cull_checked(ur_ctx* ctx, const uint32_t* constants, const ur_float4*
         // the kernel indexes hzb + mips[level].offset with pitch mips[level].width for every level up to HZBMipCount - 1
         if (!valid_hzb_chain_below_mip0(mips, mipc)) { set_error("ur_cull_indirect_args: mips[1..%u] do not halve from mips[0] / overlap", mipc - 1); return UR_EINVAL; }
     }
-    if (draws) {
-        if (!draws->offsets || !draws->commands || !draws->counts || draws->range_count == 0) { set_error("ur_cull_indirect_args_draws: null member / no range"); return UR_EINVAL; }
-        const uintptr_t c = reinterpret_cast<uintptr_t>(draws->commands), a = reinterpret_cast<uintptr_t>(indirect_args);
-        const uintptr_t bytes = (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE;
-        if (n != 0 && c < a + bytes && a < c + bytes) { set_error("ur_cull_indirect_args_draws: commands overlap indirect_args"); return UR_EINVAL; }
-        if (n != 0 && ((c | a) & 15u) != 0) { set_error("ur_cull_indirect_args_draws: commands / indirect_args not 16-byte aligned"); return UR_EINVAL; }
+    switch (draws ? check_draws(*draws, n, indirect_args) : DrawsFault::none) {
+    case DrawsFault::none: break;
+    case DrawsFault::member: set_error("ur_cull_indirect_args_draws: null member / no range"); return UR_EINVAL;
+    case DrawsFault::overlap: set_error("ur_cull_indirect_args_draws: commands overlap indirect_args"); return UR_EINVAL;
+    case DrawsFault::alignment: set_error("ur_cull_indirect_args_draws: commands / indirect_args not 16-byte aligned"); return UR_EINVAL;
     }
     const int trc = ur::check_hzb_timeout(ctx, "ur_cull_indirect_args");
     if (trc != UR_OK) return trc;
     return ur::launch_cull(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws,
                            views, view_count);
-}
-
-int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
-                             const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                             uint32_t* visible_count, uint32_t index_base)
-{
-    if (ctx) ctx->time_cull_carried = false;
-    const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, nullptr);
-    if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
-    return rc;
-}
-
-int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
-                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws)
-{
-    if (ctx) ctx->time_cull_carried = false;
-    const int rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws);
-    if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
-    return rc;
 }
 
 // The arguments of the views that need no device (ur_cull_indirect_args_views, ur_frame_set_cull_views). n = ModelCount, or ~0 when
@@ -427,12 +420,12 @@ static int check_views(const char* who, const ur_cull_view* views, uint32_t view
         }
         const ur_draw_ranges* d = V.draws;
         if (!d) continue;
-        if (!d->offsets || !d->commands || !d->counts || d->range_count == 0) { set_error("%s: view %u: null member of draws / no range", who, v); return UR_EINVAL; }
-        if (known && n != 0 && ((reinterpret_cast<uintptr_t>(d->commands) | reinterpret_cast<uintptr_t>(indirect_args)) & 15u) != 0) {
-            set_error("%s: view %u: commands / indirect_args not 16-byte aligned", who, v);
-            return UR_EINVAL;
+        switch (check_draws(*d, n, indirect_args)) {
+        case DrawsFault::none: break;
+        case DrawsFault::member: set_error("%s: view %u: null member of draws / no range", who, v); return UR_EINVAL;
+        case DrawsFault::overlap: set_error("%s: view %u: commands overlap indirect_args", who, v); return UR_EINVAL;
+        case DrawsFault::alignment: set_error("%s: view %u: commands / indirect_args not 16-byte aligned", who, v); return UR_EINVAL;
         }
-        if (overlap(d->commands, indirect_args)) { set_error("%s: view %u: commands overlap indirect_args", who, v); return UR_EINVAL; }
         if (draws && draws->commands && overlap(d->commands, draws->commands)) { set_error("%s: view %u: commands overlap the camera's commands", who, v); return UR_EINVAL; }
         for (uint32_t u = 0; u < v; ++u)
             if (views[u].draws && views[u].draws->commands && overlap(d->commands, views[u].draws->commands)) {
@@ -443,17 +436,47 @@ static int check_views(const char* who, const ur_cull_view* views, uint32_t view
     return UR_OK;
 }
 
-int ur_cull_indirect_args_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
-                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws,
-                                const ur_cull_view* views, uint32_t view_count)
+// Every ur_cull_indirect_args* entry point (views == NULL or view_count == 0: the camera alone). ur_time_next_cull's event is one-shot:
+// cleared here whatever the call did, and ur_time_cull_carried reports whether a dispatch of THIS call took it.
+static int cull_call(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base, const ur_mip_desc* mips,
+                     void* indirect_args, uint32_t* stats2, uint32_t* visible_idx, uint32_t* visible_count, uint32_t index_base,
+                     const ur_draw_ranges* draws, const ur_cull_view* views, uint32_t view_count)
 {
     if (ctx) ctx->time_cull_carried = false;
     int rc = check_views("ur_cull_indirect_args_views", views, view_count, constants ? constants[40] : 0u, indirect_args, draws);
     if (rc == UR_OK) rc = cull_checked(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws,
                                        views, views ? view_count : 0u);
-    if (ctx) ctx->time_cull_stop = nullptr; // one-shot whatever the call did (ur_time_next_cull)
+    if (ctx) ctx->time_cull_stop = nullptr;
     return rc;
+}
+
+int ur_cull_indirect_args(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                          const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                          uint32_t* visible_count)
+{
+    return cull_call(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, 0, nullptr, nullptr, 0);
+}
+
+int ur_cull_indirect_args_ex(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                             const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                             uint32_t* visible_count, uint32_t index_base)
+{
+    return cull_call(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, nullptr, nullptr, 0);
+}
+
+int ur_cull_indirect_args_draws(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws)
+{
+    return cull_call(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws, nullptr, 0);
+}
+
+int ur_cull_indirect_args_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
+                                const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
+                                uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws,
+                                const ur_cull_view* views, uint32_t view_count)
+{
+    return cull_call(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, index_base, draws, views, view_count);
 }
 
 int ur_hzb_band_pieces(uint32_t src_h, uint32_t n_ranks, uint32_t rank, uint32_t* piece_row0, uint32_t* piece_rows)
@@ -495,13 +518,6 @@ int ur_build_hzb_tail(ur_ctx* ctx, float* hzb_base, const ur_mip_desc* mips, uin
     const int trc = ur::check_hzb_timeout(ctx, "ur_build_hzb_tail");
     if (trc != UR_OK) return trc;
     return ur::launch_build_hzb_tail(ctx, hzb_base, mips, mip_count);
-}
-
-int ur_cull_indirect_args(ur_ctx* ctx, const uint32_t* constants, const ur_float4* bounds, const float* hzb_base,
-                          const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
-                          uint32_t* visible_count)
-{
-    return ur_cull_indirect_args_ex(ctx, constants, bounds, hzb_base, mips, indirect_args, stats2, visible_idx, visible_count, 0);
 }
 
 size_t ur_env_cube_texels(uint32_t base_size, uint32_t mip_count)

@@ -168,31 +168,20 @@ class HotPath:
         assert constants.size == _lib.UR_CULL_CONSTANT_DWORDS
         cptr = constants.ctypes.data_as(C.POINTER(C.c_uint32))
         mips = layout.mips if layout is not None else None
-        if views:
-            n = int(constants[40])
-            arr = cull_views_array([v if isinstance(v, _lib.CullView) else cull_view(command_count=n, **v) for v in views])
-            dr = None
-            if draw_offsets is not None or draw_commands is not None or draw_counts is not None:
-                if draw_offsets is None or draw_commands is None or draw_counts is None:
-                    raise ValueError("draw_offsets, draw_commands and draw_counts go together")
-                if not isinstance(draw_offsets, torch.Tensor):
-                    draw_offsets = self.draw_offsets_to_device(draw_offsets, n)
-                dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
-            _lib.check(self._L.ur_cull_indirect_args_views(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
-                                                           _ptr(visible_idx), _ptr(visible_count), index_base,
-                                                           C.byref(dr) if dr is not None else None, arr, len(arr)), "ur_cull_indirect_args_views")
-            return
-        if draw_offsets is None and draw_commands is None and draw_counts is None:
-            _lib.check(self._L.ur_cull_indirect_args_ex(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
-                                                        _ptr(visible_idx), _ptr(visible_count), index_base), "ur_cull_indirect_args")
-            return
-        if draw_offsets is None or draw_commands is None or draw_counts is None:
-            raise ValueError("draw_offsets, draw_commands and draw_counts go together")
-        if not isinstance(draw_offsets, torch.Tensor):
-            draw_offsets = self.draw_offsets_to_device(draw_offsets, int(constants[40]))
-        dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
-        _lib.check(self._L.ur_cull_indirect_args_draws(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
-                                                       _ptr(visible_idx), _ptr(visible_count), index_base, C.byref(dr)), "ur_cull_indirect_args_draws")
+        n = int(constants[40])
+        arr = cull_views_array([v if isinstance(v, _lib.CullView) else cull_view(command_count=n, **v) for v in views]) if views else None
+        dr = None
+        if draw_offsets is not None or draw_commands is not None or draw_counts is not None:
+            if draw_offsets is None or draw_commands is None or draw_counts is None:
+                raise ValueError("draw_offsets, draw_commands and draw_counts go together")
+            if not isinstance(draw_offsets, torch.Tensor):
+                draw_offsets = self.draw_offsets_to_device(draw_offsets, n)
+            dr = draw_ranges(draw_offsets, draw_commands, draw_counts)
+        where = "ur_cull_indirect_args_views" if views else "ur_cull_indirect_args_draws" if dr is not None else "ur_cull_indirect_args"
+        # one entry point for every shape: views == NULL is exactly ur_cull_indirect_args_draws, draws == NULL exactly _ex
+        _lib.check(self._L.ur_cull_indirect_args_views(self._ctx, cptr, _ptr(bounds), _ptr(hzb), mips, _ptr(indirect_args), _ptr(stats),
+                                                       _ptr(visible_idx), _ptr(visible_count), index_base,
+                                                       C.byref(dr) if dr is not None else None, arr, len(arr) if arr is not None else 0), where)
 
     def draw_offsets_to_device(self, offsets, command_count: int) -> torch.Tensor:
         """Check the precondition of ur_draw_ranges.offsets on the host array (offsets[0] == 0, non-decreasing, last == command_count,
