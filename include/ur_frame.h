@@ -68,6 +68,15 @@ typedef struct ur_frame_resources {
  * rows around it read from the neighbours' records. The band's bytes and luminance[W] are those of the unsplit frame, on every rank. */
 #define UR_FRAME_POST_EXCHANGE 0x200000u
 #define UR_FRAME_CULL_VIEWS 0x400000u /* the "GPU Culling" pass also culls the views of ur_frame_set_cull_views (ur_cull_indirect_args_views), on the async-compute lane too */
+/* "TemporalAA" pass between Sky and AutoExposure (DeferredRenderer.cpp:1308-1361): Lighting + history[read] -> history[write] with
+ * ur_temporal_aa; Tonemap (ur_tonemap_cas under FUSE_TONEMAP_CAS) then reads history[write] instead of Lighting, AutoExposure keeps
+ * reading Lighting. Needs UR_FRAME_TONEMAP, a tonemap_band and ur_frame_set_taa's ring (else UR_EINVAL), and the whole frame: rows !=
+ * height or UR_FRAME_POST_EXCHANGE is UR_EUNSUPPORTED. Without the flag the frame is what it is without a ring. */
+#define UR_FRAME_TAA 0x800000u
+/* With TAA: the Tonemap pass runs ur_temporal_aa_tonemap (history[write] and the LDR image in one launch, the same bytes); the
+ * TemporalAA pass is then culled. Not together with UR_FRAME_FUSE_TONEMAP_CAS (UR_EINVAL); with a CAS pass of its own the launch
+ * writes tonemap_scratch. */
+#define UR_FRAME_FUSE_TAA_TONEMAP 0x1000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -102,6 +111,29 @@ int ur_frame_set_post(ur_frame* f, const ur_frame_post* post);
 /* The luminance history becomes invalid (like ur_frame_reset_hzb): the next AutoExposure pass runs with UseHistory = 0. The write
  * index is kept: a frame whose AutoExposure ran writes luminance[W], then W flips; any other frame invalidates the history. */
 void ur_frame_reset_post(ur_frame* f);
+/* The TemporalAA history ring of the frames that follow (CreateTaaResources, DeferredRenderer.cpp:2740-2785): history_count device
+ * images of width x height ur_half4 each, owned by the caller like the luminance pair; all invalid after this call. history_count
+ * must be the frame's frames_in_flight (ur_frame_create; 0 counts as 1) and no image may be null, else UR_EINVAL. NULL clears the ring.
+ * The array is copied; the images must stay valid while frames use them. history_weight: TaaHistoryWeight [0.9]. */
+typedef struct ur_frame_taa {
+    ur_half4* const* history;
+    uint32_t history_count;
+    float history_weight;
+} ur_frame_taa;
+int ur_frame_set_taa(ur_frame* f, const ur_frame_taa* taa);
+/* The reference's bookkeeping (:394-410, :1602-1610, OnFrameFenceSignaled :2787-2799): a frame with UR_FRAME_TAA at frame slot i of N
+ * (the slot advances with every ur_frame_render) writes history[i % N] and reads history[(i + N - 1) % N], with UseHistory = whether
+ * that image is valid. After such a frame returned UR_OK the image it wrote is valid and the sample index advances (mod 8); after any
+ * other frame all images are invalid and the sample index is 0. ur_frame_reset_taa does the latter on request (a resize). */
+void ur_frame_reset_taa(ur_frame* f);
+/* What the next ur_frame_render with UR_FRAME_TAA will do: the slots, use_history, and the jitter of its sample index
+ * (ur_host_taa_jitter; zero when use_history is 0). The caller jitters its projection with it (ur_host_apply_taa_jitter) before it
+ * rasterises the G-buffer and fills the constant blocks. UR_EINVAL without a ring. */
+typedef struct ur_frame_taa_info {
+    uint32_t read_slot, write_slot, use_history;
+    float jitter[2];
+} ur_frame_taa_info;
+int ur_frame_taa_next(const ur_frame* f, ur_frame_taa_info* info);
 /* Device pointers of the post exchange (UR_FRAME_POST_EXCHANGE), each ur_post_record_bytes(width) per rank: own_record receives this
  * rank's record, all_records holds world_size gathered records in rank order (own_record may alias all_records + rank * bytes, for
  * an in-place all-gather). They must stay valid while frames use them. */

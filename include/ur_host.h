@@ -51,6 +51,13 @@ void ur_host_fill_scene_constants(const float view[16], const float proj[16], co
 void ur_host_fill_sky_constants(const float view[16], const float proj[16], const float camera_pos[3], float sky_radius,
                                 const float light_dir[3], const float light_color[3], ur_sky_constants* out);
 
+/* BuildTaaJitter (DeferredRenderer.cpp:47-67): (Halton(sample_index + 1, 2) - 0.5, Halton(sample_index + 1, 3) - 0.5) in fp32,
+ * in pixels. The renderer's sample index runs 0..7 (ur_frame_taa_next). */
+void ur_host_taa_jitter(uint32_t sample_index, float out[2]);
+/* The jittered projection of a frame with history (DeferredRenderer.cpp:415-421): _31 += 2 jx / width, _32 += 2 jy / height
+ * (elements 8 and 9); nothing when width or height is not positive. */
+void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width, float height);
+
 /* Scene JSON conventions: BuildDirectionFromEulerDegrees (Scene/SceneJsonLoader.cpp:257-269); camera forward from
  * (pitch, yaw) degrees via RotationRollPitchYaw (Core/Application.cpp:896-902); and the light vector the renderer
  * ends up with after the app's asin/atan2 round trip (Core/Application.cpp:236-242,1225-1230), i.e. (d.x,-d.y,d.z). */

@@ -218,6 +218,7 @@ int ur_time_cull_carried(const ur_ctx* ctx);
 #define UR_OPT_DEBUG_HZB_RIDE_STALL 11  /* [0] debug, the one option that DOES change results: 1 = the tail workgroup of a riding Build HZB chain expects
                                            one arrival more than there are producers and gives up after ~1 ms, i.e. every riding launch takes the
                                            real time-out path (UR_ETIMEOUT at the next entry point, stale small HZB levels) - for tests of that path */
+#define UR_OPT_TAA_TONEMAP_HISTORY_STORE 12 /* [0] history store of ur_temporal_aa_tonemap: 0 = write-through + nontemporal (as ur_temporal_aa), 1 = plain */
 int ur_set_option(ur_ctx* ctx, int option, int value);
 int ur_get_option(const ur_ctx* ctx, int option, int* value);
 const char* ur_last_error(void);
@@ -399,9 +400,18 @@ int ur_tonemap(ur_ctx* ctx, const ur_tonemap_constants* constants, const ur_half
 
 /* current_frame: device, the FULL w x h RGBA16F frame (the 3x3 neighbourhood of a band's edge rows lies outside the
  * band; with multi-GPU sharding this is the all-gathered frame). history_band / output_band: band-local rows
- * [row0,row0+rows). use_history == 0 copies current (first frame). Bit-exact against the oracle. 24 B/pixel. */
+ * [row0,row0+rows). use_history == 0 copies current (first frame). Bit-exact against the oracle. 24 B/pixel.
+ * history_band may be output_band itself (a history ring of one image): a history texel is read only by the lane that writes
+ * it, before it writes; current_frame must be a different buffer. */
 int ur_temporal_aa(ur_ctx* ctx, const ur_half4* current_frame, const ur_half4* history_band, ur_half4* output_band, float history_weight,
                    uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+/* ur_temporal_aa followed by ur_tonemap of its output band, in ONE launch: history_out_band receives the bytes ur_temporal_aa
+ * writes, ldr_out_band (w x rows R8G8B8A8_UNORM) the bytes ur_tonemap writes from that image with the same constants and
+ * exposure_ev (nullable), for use_history 0 and 1, at any width and band. The resolved image is not read back: 8 + 8 read,
+ * 8 + 4 written = 28 B/pixel instead of 24 + 12. Arguments and aliasing otherwise as ur_temporal_aa. */
+int ur_temporal_aa_tonemap(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_half4* current_frame, const ur_half4* history_band,
+                           ur_half4* history_out_band, const float* exposure_ev, uint32_t* ldr_out_band, float history_weight,
+                           uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
 
 /* ---- AutoExposure and CAS: the rest of the reference's post chain (DeferredRenderer.cpp:1363-1573) ------------ */
 

@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "../../../include/ur_frame.h"
+#include "../../../include/ur_host.h"
 #include "../ur_internal.h"
 
 int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
@@ -41,6 +42,18 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
                                                                {static_cast<uint32>(Constants.Scene.ShadowMapSize[0]), static_cast<uint32>(Constants.Scene.ShadowMapSize[1]), RG_FORMAT_R32_FLOAT});
     const FRGResourceHandle LightingHandle = Graph.ImportTexture("Lighting", Res.LightingBand, &Res.LightingState, {Res.Width, Res.Rows, RG_FORMAT_R16G16B16A16_FLOAT});
     const FRGResourceHandle HZBHandle = Graph.ImportTexture("HZB", Res.HZB, &Res.HZBState, {HZBWidth, HZBHeight, RG_FORMAT_R32_FLOAT});
+
+    // TemporalAA (:394-403): the slots of this frame slot and whether the image read was written by a frame that completed
+    const uint32 TaaSlotCount = static_cast<uint32>(Res.TaaHistory.size());
+    if (Res.TaaHistoryStates.size() != Res.TaaHistory.size()) Res.TaaHistoryStates.assign(Res.TaaHistory.size(), RG_STATE_UNORDERED_ACCESS);
+    const bool bPostExchangeFrame = Options.bPostExchange && Options.bTonemap && Res.TonemapBand && (Options.bAutoExposure || Options.bCas);
+    const bool bTaaActive = Options.bTaa && Options.bTonemap && Res.TonemapBand && TaaSlotCount != 0 && !bPostExchangeFrame;
+    TaaFrame = FTaaFrame{};
+    if (bTaaActive) {
+        TaaFrame.bActive = true;
+        TaaFrame.bFuseTonemap = Options.bFuseTaaTonemap;
+        TaaFrame.Slots = GetTaaSlots(Cmd.GetCurrentFrameIndex(), TaaSlotCount);
+    }
 
     const bool bHZBEnabled = Options.bHZBEnabled && Res.HZB != nullptr && Res.HZBMipCount != 0;
     if (!bHZBEnabled) bHZBReady = false; // :514-517
@@ -203,6 +216,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         } else {
             bLuminanceHistoryValid = false;
         }
+        EndTaaHistory(false, 0, TaaSlotCount);
         return PassError;
     }
 
@@ -210,6 +224,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     Graph.Execute(Cmd);
     LastReport = Graph.GetLastExecutionReport();
     EndPostHistory(Options.bTonemap && Res.TonemapBand && Options.bAutoExposure);
+    EndTaaHistory(bTaaActive, TaaFrame.Slots.Write, TaaSlotCount);
     return PassError;
 }
 
@@ -218,6 +233,7 @@ int FHotPathRenderer::FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res
     if (!bPostPending) { ur::set_error("ur_frame_finish_post: no post passes are pending (render with UR_FRAME_POST_EXCHANGE and AUTO_EXPOSURE / CAS first)"); return UR_EINVAL; }
     bPostPending = false;
     PassError = UR_OK;
+    TaaFrame = FTaaFrame{}; // (a frame of the post exchange runs without TemporalAA)
     FRenderGraph Graph;
     Graph.SetDevice(Device);
     Graph.SetGpuTimingEnabled(PendingOptions.bGpuTiming);
@@ -244,14 +260,39 @@ void FHotPathRenderer::EndPostHistory(bool bAutoExposure)
     }
 }
 
-// AutoExposure -> Tonemap -> CAS. RecordRanks != 0: on the band alone, from the RecordRanks gathered post records (FinishPost; the
+FHotPathRenderer::FTaaSlots FHotPathRenderer::GetTaaSlots(uint32 FrameIndex, uint32 SlotCount) const
+{
+    FTaaSlots S;
+    if (SlotCount == 0) return S;
+    S.Read = (FrameIndex + SlotCount - 1u) % SlotCount; // :396-397
+    S.Write = FrameIndex % SlotCount;
+    S.bUseHistory = S.Read < TaaHistoryValid.size() && TaaHistoryValid[S.Read];
+    S.SampleIndex = TaaSampleIndex;
+    return S;
+}
+
+void FHotPathRenderer::EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 SlotCount)
+{
+    // :1602-1610, and OnFrameFenceSignaled (:2787-2799): the slot a TemporalAA frame wrote is next frame's history. The reference marks
+    // it when the frame's fence is signalled and does not wait for the GPU either; here stream order makes the image complete before
+    // the next frame's pass reads it. A frame whose pass failed hands on nothing.
+    if (TaaHistoryValid.size() != SlotCount) TaaHistoryValid.assign(SlotCount, false);
+    if (bTaaActive && PassError == UR_OK) {
+        TaaHistoryValid[WriteIndex] = true;
+        TaaSampleIndex = (TaaSampleIndex + 1u) % 8u;
+    } else {
+        ResetTaa();
+    }
+}
+
+// [TemporalAA ->] AutoExposure -> Tonemap -> CAS. RecordRanks != 0: on the band alone, from the RecordRanks gathered post records (FinishPost; the
 // band is this rank's equal band): AutoExposure reads every rank's tap texels, Tonemap / CAS read the rows around the band from the
 // neighbours' records in place.
 void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
                                      const FHotPathOptions& Options, uint32 RecordRanks)
 {
-    // (DeferredRenderer.cpp:1363-1573; TemporalAA left out, see HotPathRenderer.h)
-    // Without AutoExposure and CAS this is the Tonemap pass alone, Lighting -> LDR band, as before they existed.
+    // (DeferredRenderer.cpp:1308-1573)
+    // Without TemporalAA, AutoExposure and CAS this is the Tonemap pass alone, Lighting -> LDR band, as before they existed.
     const bool bAutoExposure = Options.bTonemap && Res.TonemapBand && Options.bAutoExposure;
     const bool bCas = Options.bTonemap && Res.TonemapBand && Options.bCas;
     const bool bFuseCas = bCas && Options.bFuseTonemapCas;
@@ -270,6 +311,45 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
     if (bAutoExposure) {
         LuminanceHandles[0] = Graph.ImportTexture("LuminanceA", Res.Luminance[0], &Res.LuminanceStates[0], {1, 1, RG_FORMAT_R32_FLOAT});
         LuminanceHandles[1] = Graph.ImportTexture("LuminanceB", Res.Luminance[1], &Res.LuminanceStates[1], {1, 1, RG_FORMAT_R32_FLOAT});
+    }
+
+    // ---- TemporalAA (:1308-1361): Lighting + TaaHistory_<Read> -> TaaHistory_<Write>; AutoExposure keeps reading Lighting (:1387),
+    // Tonemap reads TaaHistory_<Write> (:1454-1459). With bFuseTaaTonemap the pass stays in the graph, disabled and culled, and the
+    // Tonemap pass makes the one launch (ur_temporal_aa_tonemap).
+    struct FTemporalAAPassData
+    {
+        bool bEnabled = false;
+        float HistoryWeight = 0.9f;
+        uint32 UseHistory = 0, ReadIndex = 0, WriteIndex = 0;
+    };
+    const bool bTaa = TaaFrame.bActive && !bFromRecords;
+    const bool bFuseTaa = bTaa && TaaFrame.bFuseTonemap;
+    const FHotPathRenderer::FTaaSlots Taa = TaaFrame.Slots;
+    FRGResourceHandle TaaReadHandle, TaaWriteHandle;
+    if (bTaa) {
+        auto Import = [&](uint32 I) {
+            return Graph.ImportTexture("TaaHistory_" + std::to_string(I), Res.TaaHistory[I], &Res.TaaHistoryStates[I], {Res.Width, Res.Height, RG_FORMAT_R16G16B16A16_FLOAT});
+        };
+        TaaWriteHandle = Import(Taa.Write);
+        TaaReadHandle = Taa.Read == Taa.Write ? TaaWriteHandle : Import(Taa.Read); // a ring of one image: read and written in place
+        Graph.AddPass<FTemporalAAPassData>("TemporalAA", [&](FTemporalAAPassData& Data, FRGPassBuilder& Builder)
+        {
+            Data.bEnabled = !bFuseTaa;
+            if (!Data.bEnabled) return;
+            Data.ReadIndex = Taa.Read;
+            Data.WriteIndex = Taa.Write;
+            Data.HistoryWeight = Constants.TaaHistoryWeight;
+            Data.UseHistory = Taa.bUseHistory ? 1u : 0u;
+            Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            if (Taa.Read != Taa.Write) Builder.ReadTexture(TaaReadHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Builder.WriteTexture(TaaWriteHandle, RG_STATE_UNORDERED_ACCESS);
+        }, [this, &Res](const FTemporalAAPassData& Data, FHIPCommandContext& Cmd)
+        {
+            if (!Data.bEnabled) return;
+            const int rc = ur_temporal_aa(Cmd.GetContext(), Res.LightingBand, Res.TaaHistory[Data.ReadIndex], Res.TaaHistory[Data.WriteIndex], Data.HistoryWeight,
+                                          Data.UseHistory, Res.Width, Res.Height, 0, Res.Height);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
     }
 
     struct FAutoExposurePassData
@@ -319,6 +399,10 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
         bool bHalo = false;
         const ur_half4* HaloAbove = nullptr;
         const ur_half4* HaloBelow = nullptr;
+        const ur_half4* Input = nullptr; // Lighting, or TaaHistory_<Write> behind a TemporalAA pass
+        bool bFuseTaa = false;           // TemporalAA + Tonemap in this pass's launch
+        float TaaHistoryWeight = 0.9f;
+        uint32 TaaUseHistory = 0, TaaReadIndex = 0, TaaWriteIndex = 0;
     };
     struct FCasPassData
     {
@@ -350,18 +434,33 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
             Data.bHalo = bFromRecords && bFuseCas;
             Data.HaloAbove = HaloAbove;
             Data.HaloBelow = HaloBelow;
-            Builder.ReadTexture(LightingHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+            Data.Input = bTaa ? Res.TaaHistory[Taa.Write] : Res.LightingBand;
+            Data.bFuseTaa = bFuseTaa;
+            Data.TaaHistoryWeight = Constants.TaaHistoryWeight;
+            Data.TaaUseHistory = Taa.bUseHistory ? 1u : 0u;
+            Data.TaaReadIndex = Taa.Read;
+            Data.TaaWriteIndex = Taa.Write;
+            if (bFuseTaa) { // the TemporalAA pass's usages move here
+                Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+                if (Taa.Read != Taa.Write) Builder.ReadTexture(TaaReadHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+                Builder.WriteTexture(TaaWriteHandle, RG_STATE_UNORDERED_ACCESS);
+            } else {
+                Builder.ReadTexture(bTaa ? TaaWriteHandle : LightingHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+            }
             if (Data.bHalo) Builder.ReadTexture(RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
             if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
             Builder.WriteTexture(bCas && !bFuseCas ? ScratchHandle : TonemapHandle, RG_STATE_RENDER_TARGET);
         }, [this, &Res](const FTonemapPassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = Data.bHalo
+            const int rc = Data.bFuseTaa
+                ? ur_temporal_aa_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, Res.TaaHistory[Data.TaaReadIndex], Res.TaaHistory[Data.TaaWriteIndex],
+                                         Data.ExposureEv, Data.Output, Data.TaaHistoryWeight, Data.TaaUseHistory, Res.Width, Res.Height, 0, Res.Height)
+                : Data.bHalo
                 ? ur_tonemap_cas_halo(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.HaloAbove, Data.HaloBelow, Data.ExposureEv, Data.Output, Res.Width,
                                       Res.Height, Res.Row0, Res.Rows)
                 : Data.bFuseCas
-                ? ur_tonemap_cas(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Height, Res.Row0, Res.Rows)
-                : ur_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, Data.ExposureEv, Data.Output, Res.Width, Res.Rows);
+                ? ur_tonemap_cas(Cmd.GetContext(), &Data.K, &Data.Cas, Data.Input, Data.ExposureEv, Data.Output, Res.Width, Res.Height, Res.Row0, Res.Rows)
+                : ur_tonemap(Cmd.GetContext(), &Data.K, Data.Input, Data.ExposureEv, Data.Output, Res.Width, Res.Rows);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
             Res.LightingState = RG_STATE_RENDER_TARGET; // the reference transitions the lighting buffer back (:1511-1512)
         });
@@ -421,6 +520,8 @@ struct ur_frame
     ur_cull_view CullViews[UR_MAX_CULL_VIEWS] = {};  // ur_frame_set_cull_views (draws point into ViewDraws)
     ur_draw_ranges ViewDraws[UR_MAX_CULL_VIEWS] = {};
     uint32_t CullViewCount = 0;
+    std::vector<ur_half4*> TaaHistory; // ur_frame_set_taa
+    float TaaHistoryWeight = 0.9f;
     void* PostRecord = nullptr;        // ur_frame_set_post_records
     const void* PostRecords = nullptr;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -535,6 +636,19 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
             }
         }
     }
+    if (flags & (UR_FRAME_TAA | UR_FRAME_FUSE_TAA_TONEMAP)) {
+        if (!(flags & UR_FRAME_TAA)) { ur::set_error("ur_frame_render: FUSE_TAA_TONEMAP needs UR_FRAME_TAA"); return UR_EINVAL; }
+        if (!(flags & UR_FRAME_TONEMAP) || !r->tonemap_band) { ur::set_error("ur_frame_render: TAA needs UR_FRAME_TONEMAP and a tonemap_band"); return UR_EINVAL; }
+        if (f->TaaHistory.empty()) { ur::set_error("ur_frame_render: TAA needs ur_frame_set_taa's history ring"); return UR_EINVAL; }
+        if ((flags & UR_FRAME_FUSE_TAA_TONEMAP) && (flags & UR_FRAME_FUSE_TONEMAP_CAS)) {
+            ur::set_error("ur_frame_render: FUSE_TAA_TONEMAP and FUSE_TONEMAP_CAS exclude each other (TAA + Tonemap + CAS in one launch is not built)");
+            return UR_EINVAL;
+        }
+        if ((flags & UR_FRAME_POST_EXCHANGE) || r->row0 != 0 || r->rows != r->height) {
+            ur::set_error("ur_frame_render: TAA needs the whole frame (rows == height, no UR_FRAME_POST_EXCHANGE)");
+            return UR_EUNSUPPORTED;
+        }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -548,6 +662,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.Luminance[1] = f->Post.luminance[1];
     R.PostRecord = f->PostRecord;
     R.PostRecords = f->PostRecords;
+    R.TaaHistory = f->TaaHistory; // (RenderFrame sizes TaaHistoryStates)
     R.DepthFull = const_cast<float*>(r->depth_full);
     R.HZB = r->hzb;
     std::memcpy(R.HZBMips, r->hzb_mips, sizeof(R.HZBMips));
@@ -577,6 +692,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     K.AutoExposureSpeedUp = f->Post.ae_speed_up;
     K.AutoExposureSpeedDown = f->Post.ae_speed_down;
     K.CasSharpness = f->Post.cas_sharpness;
+    K.TaaHistoryWeight = f->TaaHistoryWeight;
     FHotPathOptions O;
     O.bEnableIndirectDraw = (flags & UR_FRAME_INDIRECT_DRAW) != 0;
     O.bHZBEnabled = (flags & UR_FRAME_HZB) != 0;
@@ -589,6 +705,8 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bCas = (flags & UR_FRAME_CAS) != 0;
     O.bFuseTonemapCas = (flags & UR_FRAME_FUSE_TONEMAP_CAS) != 0;
     O.bPostExchange = (flags & UR_FRAME_POST_EXCHANGE) != 0;
+    O.bTaa = (flags & UR_FRAME_TAA) != 0;
+    O.bFuseTaaTonemap = (flags & UR_FRAME_FUSE_TAA_TONEMAP) != 0;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -674,6 +792,43 @@ int ur_frame_set_cull_views(ur_frame* f, const ur_cull_view* views, uint32_t cou
 }
 
 void ur_frame_reset_post(ur_frame* f) { if (f) f->Renderer.ResetLuminanceHistory(); }
+
+int ur_frame_set_taa(ur_frame* f, const ur_frame_taa* taa)
+{
+    if (!f) { ur::set_error("ur_frame_set_taa: null frame"); return UR_EINVAL; }
+    if (taa) {
+        if (!taa->history || taa->history_count != f->Cmd.GetFrameCount()) {
+            ur::set_error("ur_frame_set_taa: %u history images, the frame has %u frames in flight", taa->history ? taa->history_count : 0u, f->Cmd.GetFrameCount());
+            return UR_EINVAL;
+        }
+        for (uint32_t i = 0; i < taa->history_count; ++i)
+            if (!taa->history[i]) { ur::set_error("ur_frame_set_taa: history[%u] is null", i); return UR_EINVAL; }
+        f->TaaHistory.assign(taa->history, taa->history + taa->history_count);
+        f->TaaHistoryWeight = taa->history_weight;
+    } else {
+        f->TaaHistory.clear();
+        f->TaaHistoryWeight = 0.9f;
+    }
+    f->Renderer.ResetTaa(); // new images: all invalid at creation (CreateTaaResources)
+    return UR_OK;
+}
+
+void ur_frame_reset_taa(ur_frame* f) { if (f) f->Renderer.ResetTaa(); }
+
+int ur_frame_taa_next(const ur_frame* f, ur_frame_taa_info* info)
+{
+    if (!f || !info) { ur::set_error("ur_frame_taa_next: null argument"); return UR_EINVAL; }
+    if (f->TaaHistory.empty()) { ur::set_error("ur_frame_taa_next: no history ring (ur_frame_set_taa)"); return UR_EINVAL; }
+    // ur_frame_render begins the frame (BeginFrame: the next frame slot) before it reads the slot index
+    const uint32_t next = (f->Cmd.GetCurrentFrameIndex() + 1u) % f->Cmd.GetFrameCount();
+    const FHotPathRenderer::FTaaSlots s = f->Renderer.GetTaaSlots(next, static_cast<uint32_t>(f->TaaHistory.size()));
+    info->read_slot = s.Read;
+    info->write_slot = s.Write;
+    info->use_history = s.bUseHistory ? 1u : 0u;
+    info->jitter[0] = info->jitter[1] = 0.0f; // bUseTaaJitter = bTaaActive && bTaaHistoryReady (:403-411)
+    if (s.bUseHistory) ur_host_taa_jitter(s.SampleIndex, info->jitter);
+    return UR_OK;
+}
 
 int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_records)
 {

@@ -1,14 +1,17 @@
-// HotPathRenderer — the four hot passes of FDeferredRenderer::RenderFrame wired onto the render graph.
+// HotPathRenderer — the four hot passes of FDeferredRenderer::RenderFrame, and its post chain, wired onto the render graph.
 //
 // Reference wiring (Source/Render/DeferredRenderer.cpp): "GPU Culling" :508-542 (+ FRenderer::ConfigureHZBOcclusion /
 // DispatchGpuCulling, Renderer.cpp:384-472), "Build HZB" :982-1212, "Lighting" :1214-1255, "Sky" :1257-1296, and optionally the
-// post chain "AutoExposure" :1363-1438, "Tonemap" :1440-1513, "CAS" :1515-1573 (TemporalAA is left out: the reference never
-// validates its history, so its pass is a copy of Lighting).
+// post chain "TemporalAA" :1308-1361, "AutoExposure" :1363-1438, "Tonemap" :1440-1513, "CAS" :1515-1573. TemporalAA keeps the
+// reference's history ring: FDeferredRenderer::OnFrameFenceSignaled (:2787-2799, called by FApplication::RenderFrame after every
+// submission) marks the slot a frame wrote as valid, so from the second frame on the pass runs with UseHistory = 1 and Tonemap reads
+// its output instead of Lighting (:1454-1459).
 // Pass names, PassData structs, declared usages/states and pass order are the reference's; the execute lambdas call
 // the C-ABI (include/ur_hotpath.h) instead of recording D3D12 commands. The passes between them (shadow map, depth
 // prepass, G-buffer raster, post FX) are out of scope: their outputs arrive as imported textures.
 #pragma once
 
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -31,6 +34,7 @@ struct FHotPathResources
     uint32* TonemapBand = nullptr;    // optional: R8G8B8A8_UNORM output of the Tonemap pass for this band (the back buffer)
     uint32* TonemapScratch = nullptr; // "TonemapOutput": Tonemap's output when CAS runs as its own pass
     float* Luminance[2] = {};         // LuminanceA / B: 1x1 R32_FLOAT (CreateLuminanceResources, DeferredRenderer.cpp:2692-2712)
+    std::vector<ur_half4*> TaaHistory; // TaaHistory_<i>: max(1, FrameCount) Width x Height images in Lighting's format (CreateTaaResources, :2740-2785)
     void* PostRecord = nullptr;        // post exchange (new): this band's record (ur_pack_post_record) ...
     const void* PostRecords = nullptr; // ... and every rank's, gathered in rank order (may contain PostRecord)
     // full-frame depth for the replicated HZB build, and the HZB itself
@@ -60,6 +64,7 @@ struct FHotPathResources
     uint32 TonemapState = RG_STATE_RENDER_TARGET;
     uint32 TonemapScratchState = RG_STATE_RENDER_TARGET;
     uint32 LuminanceStates[2] = {RG_STATE_UNORDERED_ACCESS, RG_STATE_UNORDERED_ACCESS};
+    std::vector<uint32> TaaHistoryStates; // one per image, RG_STATE_UNORDERED_ACCESS at creation
     uint32 PostRecordState = RG_STATE_UNORDERED_ACCESS;
     uint32 PostRecordsState = RG_STATE_UNORDERED_ACCESS;
 };
@@ -74,6 +79,7 @@ struct FHotPathFrameConstants
     float AutoExposureKey = 0.3f, AutoExposureMin = 0.1f, AutoExposureMax = 5.0f; // RendererConfig.h:28-30
     float AutoExposureSpeedUp = 3.0f, AutoExposureSpeedDown = 1.0f;              // RendererConfig.h:31-32
     float CasSharpness = 0.5f;                                                   // RendererConfig.h:26
+    float TaaHistoryWeight = 0.9f;                                               // RendererConfig.h:34
 };
 
 struct FHotPathOptions
@@ -89,6 +95,8 @@ struct FHotPathOptions
     bool bAutoExposure = false;       // with bTonemap: AutoExposure pass before Tonemap (bAutoExposureEnabled)
     bool bCas = false;                // with bTonemap: CAS pass after Tonemap (bEnableCas)
     bool bFuseTonemapCas = false;     // MI355X fast path: Tonemap + CAS in one launch (ur_tonemap_cas), CAS pass culled
+    bool bTaa = false;                // with bTonemap and a history ring: TemporalAA pass after Sky (bEnableTAA); Tonemap reads its output
+    bool bFuseTaaTonemap = false;     // with bTaa: TemporalAA + Tonemap in one launch (ur_temporal_aa_tonemap), TemporalAA pass culled
     bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
@@ -117,17 +125,26 @@ public:
     void ResetHZB() { bHZBReady = false; }
     // luminance ping-pong of the AutoExposure pass (LuminanceWriteIndex / bLuminanceHistoryValid, DeferredRenderer.cpp:1612-1620)
     void ResetLuminanceHistory() { bLuminanceHistoryValid = false; }
+    // TemporalAA history (TaaHistoryValid / TaaSampleIndex, DeferredRenderer.cpp:1602-1610): all slots invalid, sample index 0
+    void ResetTaa() { std::fill(TaaHistoryValid.begin(), TaaHistoryValid.end(), false); TaaSampleIndex = 0; }
+    // What a frame with TemporalAA and a ring of SlotCount images does at frame slot FrameIndex (:394-403)
+    struct FTaaSlots { uint32 Read = 0, Write = 0; bool bUseHistory = false; uint32 SampleIndex = 0; };
+    FTaaSlots GetTaaSlots(uint32 FrameIndex, uint32 SlotCount) const;
     const std::vector<FRenderGraph::FPassReport>& GetLastReport() const { return LastReport; }
 
 private:
     void AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
                        const FHotPathOptions& Options, uint32 RecordRanks);
     void EndPostHistory(bool bAutoExposure);
+    void EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 SlotCount);
 
     FHIPDevice* Device = nullptr;
     bool bHZBReady = false;
     bool bLuminanceHistoryValid = false;
     uint32 LuminanceWriteIndex = 0;
+    std::vector<bool> TaaHistoryValid; // one per ring image
+    uint32 TaaSampleIndex = 0;
+    struct FTaaFrame { bool bActive = false, bFuseTonemap = false; FTaaSlots Slots; } TaaFrame; // this frame's TemporalAA, for AddPostPasses
     bool bPostPending = false;        // RenderFrame stopped at "Post Record"; FinishPost runs the rest with these
     FHotPathFrameConstants PendingConstants;
     FHotPathOptions PendingOptions;

@@ -26,9 +26,35 @@ void plane_normalize(float a, float b, float c, float d, float* out)
     out[0] = a / l; out[1] = b / l; out[2] = c / l; out[3] = d / l;
 }
 
+// HaltonSequence (DeferredRenderer.cpp:47-59)
+float halton(uint32_t index, uint32_t base)
+{
+    float result = 0.0f;
+    float fraction = 1.0f / static_cast<float>(base);
+    for (uint32_t current = index; current > 0; current /= base) {
+        result += static_cast<float>(current % base) * fraction;
+        fraction /= static_cast<float>(base);
+    }
+    return result;
+}
+
 } // namespace
 
 extern "C" {
+
+void ur_host_taa_jitter(uint32_t sample_index, float out[2])
+{
+    const uint32_t index = sample_index + 1u;
+    out[0] = halton(index, 2) - 0.5f;
+    out[1] = halton(index, 3) - 0.5f;
+}
+
+void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width, float height)
+{
+    if (!(width > 0.0f) || !(height > 0.0f)) return;
+    proj[8] += (2.0f * jitter[0]) / width;
+    proj[9] += (2.0f * jitter[1]) / height;
+}
 
 void ur_host_look_to_lh(const float eye[3], const float dir[3], const float up[3], float out[16])
 {

@@ -13,9 +13,15 @@
 // (a chain of five dependent memory round trips per wave: 8 us of fixed cost); 8-row strips loaded in one phase 42.5 us
 // (68 VGPRs: 7 waves/SIMD, the grid took 2.3 rounds = 3); the halo texels of a strip in ONE load, 56 VGPRs, 8 waves/SIMD,
 // two rounds: 37.0 us = 5.4 TB/s.
+//
+// ur_temporal_aa_tonemap is the same strip body with a Tonemap epilogue (the Post policy of taa_strip_kernel): each blended
+// texel, after its rounding to fp16, also goes through tonemap_pixel (csrc/post_common.h, the one ur_tonemap runs) while it is
+// in registers, so the history image is not read back by a Tonemap launch: 8 + 8 read, 8 + 4 written = 28 B/pixel in one
+// launch instead of 24 + 12 in two. The history bytes are ur_temporal_aa's and the LDR bytes ur_tonemap's of that image.
 
 #include "ur_internal.h"
 #include "ur_device.h"
+#include "post_common.h"
 
 namespace {
 
@@ -65,7 +71,29 @@ __device__ __forceinline__ RowMinMax row_minmax(u32x2_t c, uint32_t hl0, uint32_
     return m;
 }
 
-__global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p)
+// What happens to a resolved texel besides the history store. NoPost: nothing (ur_temporal_aa). TonemapPost: the Tonemap pixel
+// of the stored fp16 value into the LDR band (ur_temporal_aa_tonemap); ONCE = the history store keeps its write-through +
+// nontemporal hint (nothing reads the image again in this frame), else it is a plain store (UR_OPT_TAA_TONEMAP_HISTORY_STORE).
+struct NoPost {
+    static constexpr bool kHistoryOnce = true;
+    __device__ __forceinline__ float prepare() const { return 0.0f; }
+    __device__ __forceinline__ void texel(float, size_t, uint32_t, uint32_t) const {}
+};
+template <bool ONCE>
+struct TonemapPost {
+    static constexpr bool kHistoryOnce = ONCE;
+    ur_post::TonemapParams tm; // hdr / count unused: the texel comes from the strip; out = the LDR band
+    __device__ __forceinline__ float prepare() const { return ur_post::final_exposure(tm); } // uniform: one scalar load of the EV per wave
+    __device__ __forceinline__ void texel(float finalExposure, size_t i, uint32_t lo, uint32_t hi) const
+    {
+        union { u32x2_t u; ur_post::half4_t h; } t;
+        t.u = u32x2_t{lo, hi};
+        ur::store_once_b32(tm.out + i, ur_post::tonemap_pixel(tm, finalExposure, t.h));
+    }
+};
+
+template <class Post>
+__global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // the four waves of a workgroup sit side by side: a workgroup touches 2 KB of contiguous bytes per row and buffer
@@ -87,9 +115,15 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p)
         const int fr = (int)p.row0 + band_row;
         return (size_t)(uint32_t)min(max(fr, 0), (int)maxy) * p.W;
     };
+    const float finalExposure = post.prepare();
     if (p.use_history == 0) { // UseHistory == 0: the resolve is a copy of the current frame (TemporalAA.hlsl:23-27)
         for (uint32_t k = 0; k < min((uint32_t)kStripRows, p.rows - r0); ++k)
-            if (px <= maxx) out[(size_t)(r0 + k) * p.W + px] = cur[frame_row((int)(r0 + k)) + px];
+            if (px <= maxx) {
+                const size_t i = (size_t)(r0 + k) * p.W + px;
+                const u32x2_t v = cur[frame_row((int)(r0 + k)) + px];
+                out[i] = v;
+                post.texel(finalExposure, i, v.x, v.y);
+            }
         return;
     }
     // One load phase per wave: the strip's kStripRows + 2 current rows (with their halo texels) and kStripRows history
@@ -127,7 +161,10 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p)
             }
             half2_t o0, o1;
             o0.x = (_Float16)b[0]; o0.y = (_Float16)b[1]; o1.x = (_Float16)b[2]; o1.y = c1.y; // alpha of the current texel
-            ur::store_once_b64(out + (size_t)r * p.W + px, ur::once_u32x2_t{as_u(o0), as_u(o1)});
+            const size_t i = (size_t)r * p.W + px;
+            if constexpr (Post::kHistoryOnce) ur::store_once_b64(out + i, ur::once_u32x2_t{as_u(o0), as_u(o1)});
+            else out[i] = u32x2_t{as_u(o0), as_u(o1)};
+            post.texel(finalExposure, i, as_u(o0), as_u(o1)); // the row is tonemapped right before its store: no row stays live for it
         }
         mPrev = mCur; mCur = mNext;
     }
@@ -135,13 +172,11 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p)
 
 } // namespace
 
-extern "C" int ur_temporal_aa(ur_ctx* ctx, const ur_half4* current_frame, const ur_half4* history_band, ur_half4* output_band, float history_weight,
-                              uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+static int fill_params(const char* who, TaaParams& p, ur_ctx* ctx, const ur_half4* current_frame, const ur_half4* history_band, ur_half4* output_band,
+                       float history_weight, uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
-    if (!ctx || !current_frame || !output_band || (use_history && !history_band)) { ur::set_error("ur_temporal_aa: null argument"); return UR_EINVAL; }
-    if (w == 0 || h == 0 || (uint64_t)row0 + rows > h) { ur::set_error("ur_temporal_aa: bad frame/band"); return UR_EINVAL; }
-    if (rows == 0) return UR_OK;
-    TaaParams p{};
+    if (!ctx || !current_frame || !output_band || (use_history && !history_band)) { ur::set_error("%s: null argument", who); return UR_EINVAL; }
+    if (w == 0 || h == 0 || (uint64_t)row0 + rows > h) { ur::set_error("%s: bad frame/band", who); return UR_EINVAL; }
     p.current = reinterpret_cast<const half4_t*>(current_frame);
     p.history = reinterpret_cast<const half4_t*>(history_band);
     p.output = reinterpret_cast<half4_t*>(output_band);
@@ -149,7 +184,42 @@ extern "C" int ur_temporal_aa(ur_ctx* ctx, const ur_half4* current_frame, const 
     p.weight = history_weight < 0.0f ? 0.0f : (history_weight > 1.0f ? 1.0f : history_weight);
     if (!(history_weight == history_weight)) p.weight = 0.0f; // saturate(NaN) = 0
     p.use_history = use_history ? 1u : 0u;
-    hipLaunchKernelGGL(taa_strip_kernel, dim3((w + 255u) / 256u, (rows + kStripRows - 1u) / kStripRows), dim3(256), 0, ctx->stream, p);
+    return UR_OK;
+}
+
+// history_band may BE output_band (a ring of one image): a history texel is read only by the lane that writes it, and every load
+// of a wave is issued before its first store; current_frame is a different buffer.
+extern "C" int ur_temporal_aa(ur_ctx* ctx, const ur_half4* current_frame, const ur_half4* history_band, ur_half4* output_band, float history_weight,
+                              uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    TaaParams p{};
+    const int rc = fill_params("ur_temporal_aa", p, ctx, current_frame, history_band, output_band, history_weight, use_history, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    if (rows == 0) return UR_OK;
+    hipLaunchKernelGGL(taa_strip_kernel<NoPost>, dim3((w + 255u) / 256u, (rows + kStripRows - 1u) / kStripRows), dim3(256), 0, ctx->stream, p, NoPost{});
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+extern "C" int ur_temporal_aa_tonemap(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_half4* current_frame, const ur_half4* history_band,
+                                      ur_half4* history_out_band, const float* exposure_ev, uint32_t* ldr_out_band, float history_weight,
+                                      uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    if (!tonemap || !ldr_out_band) { ur::set_error("ur_temporal_aa_tonemap: null argument"); return UR_EINVAL; }
+    TaaParams p{};
+    const int rc = fill_params("ur_temporal_aa_tonemap", p, ctx, current_frame, history_band, history_out_band, history_weight, use_history, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    if (rows == 0) return UR_OK;
+    ur_post::TonemapParams tm{}; // as ur_tonemap fills it
+    tm.exposure_ev = exposure_ev;
+    tm.out = ldr_out_band;
+    tm.enable_tonemap = tonemap->EnableTonemap;
+    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
+    tm.exposure = tonemap->Exposure;
+    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
+    const dim3 grid((w + 255u) / 256u, (rows + kStripRows - 1u) / kStripRows);
+    if (ctx->opt.taa_tonemap_history_store == 0) hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<true>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<true>{tm});
+    else hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<false>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<false>{tm});
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }

@@ -14,6 +14,11 @@ __device__ __forceinline__ void store_once_b64(void* p, once_u32x2_t v)
 {
     asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
 }
+// the same for four bytes
+__device__ __forceinline__ void store_once_b32(void* p, uint32_t v)
+{
+    asm volatile("global_store_dword %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+}
 
 // Touch every 64-byte line of the kernarg segment (explicit arguments of BYTES bytes plus the hidden ones behind them)
 // with one batch of scalar loads and ONE wait. hipcc reads kernel parameters lazily, a few dwords at a time with a wait

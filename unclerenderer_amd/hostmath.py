@@ -61,6 +61,20 @@ def light_view_projection(center, radius: float, light_dir) -> np.ndarray:
     return out
 
 
+def taa_jitter(sample_index: int) -> np.ndarray:
+    """BuildTaaJitter: the sub-pixel offset (x, y) of TemporalAA sample `sample_index` (the renderer's runs 0..7), fp32."""
+    out = np.zeros(2, np.float32)
+    _lib.load().ur_host_taa_jitter(sample_index, _lib.fptr(out))
+    return out
+
+
+def apply_taa_jitter(proj, jitter, width: float, height: float) -> np.ndarray:
+    """A copy of the projection with _31 += 2 jx / width, _32 += 2 jy / height (elements 8 and 9), as the reference jitters it."""
+    out = _f(*proj)
+    _lib.load().ur_host_apply_taa_jitter(_lib.fptr(out), _lib.fptr(_f(*jitter)), float(width), float(height))
+    return out
+
+
 def pack_culling_constants(view, proj, model_count: int, hzb_enabled: bool, hzb_mip_count: int, hzb_width: int,
                            hzb_height: int, debug_print: bool = False) -> np.ndarray:
     out = np.zeros(_lib.UR_CULL_CONSTANT_DWORDS, np.uint32)

@@ -372,6 +372,30 @@ class Frame:
     def reset_post(self):
         self._L.ur_frame_reset_post(self._f)
 
+    def set_taa(self, history=None, history_weight=0.9):
+        """ur_frame_set_taa: the TemporalAA history ring of the frames rendered with UR_FRAME_TAA - as many (height, width, 4) fp16
+        device tensors as the frame has frames in flight (kept alive here), all invalid after the call. No history: clear."""
+        if not history:
+            self._taa_keep = None
+            _lib.check(self._L.ur_frame_set_taa(self._f, None), "ur_frame_set_taa")
+            return
+        ptrs = (C.c_void_p * len(history))(*[t.data_ptr() if t is not None else None for t in history])
+        t = _lib.FrameTaa(C.cast(ptrs, C.POINTER(C.c_void_p)), len(history), history_weight)
+        _lib.check(self._L.ur_frame_set_taa(self._f, C.byref(t)), "ur_frame_set_taa")
+        self._taa_keep = tuple(history)
+
+    def taa_next(self) -> dict:
+        """ur_frame_taa_next: {"read_slot", "write_slot", "use_history", "jitter"} of the next render with UR_FRAME_TAA; the caller
+        jitters its projection with hostmath.apply_taa_jitter(proj, jitter, width, height) before it fills the frame's inputs."""
+        i = _lib.FrameTaaInfo()
+        _lib.check(self._L.ur_frame_taa_next(self._f, C.byref(i)), "ur_frame_taa_next")
+        return {"read_slot": int(i.read_slot), "write_slot": int(i.write_slot), "use_history": bool(i.use_history),
+                "jitter": np.array([i.jitter[0], i.jitter[1]], np.float32)}
+
+    def reset_taa(self):
+        """ur_frame_reset_taa: every history image invalid, sample index 0 (a resize)."""
+        self._L.ur_frame_reset_taa(self._f)
+
     def set_draw_ranges(self, offsets=None, commands=None, counts=None, command_count: "int | None" = None):
         """ur_frame_set_draw_ranges: the "GPU Culling" pass of the frames that follow also writes each range's visible commands to
         `commands` slots offsets[r], ... and the range's count to counts[r] (device tensors, kept alive here). offsets: a host array
@@ -452,6 +476,18 @@ def _temporal_aa(self, current_frame, history_band, output_band, history_weight,
 
 
 HotPath.temporal_aa = _temporal_aa
+
+
+def _temporal_aa_tonemap(self, current_frame, history_band, history_out_band, ldr_out_band, history_weight, use_history, w, h, row0=0, rows=None,
+                         exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None):
+    """temporal_aa() followed by tonemap() of its output band, in one launch (the same bytes in history_out_band and ldr_out_band)."""
+    rows = h - row0 if rows is None else rows
+    k = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    _lib.check(self._L.ur_temporal_aa_tonemap(self._ctx, C.byref(k), _ptr(current_frame), _ptr(history_band), _ptr(history_out_band), _ptr(exposure_ev),
+                                              _ptr(ldr_out_band), history_weight, int(use_history), w, h, row0, rows), "ur_temporal_aa_tonemap")
+
+
+HotPath.temporal_aa_tonemap = _temporal_aa_tonemap
 
 
 def _auto_exposure(self, hdr_full, out_ev, w, h, prev_ev=None, use_history=False, delta_time=0.0, speed_up=3.0, speed_down=1.0,

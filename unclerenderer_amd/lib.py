@@ -26,6 +26,7 @@ UR_INDIRECT_INSTANCE_COUNT_OFFSET = 44
 # ur_set_option keys (include/ur_hotpath.h)
 UR_OPT_LIGHTING_STREAM, UR_OPT_LIGHTING_WAVES_PER_WG, UR_OPT_LIGHTING_TILED_WAVES, UR_OPT_LIGHTING_LEAVE_CUS, UR_OPT_RIDE_WALKERS = 1, 2, 3, 4, 5
 UR_OPT_CULL_STORE, UR_OPT_LIGHTING_BALANCE, UR_OPT_BALANCE_POOL_16THS, UR_OPT_BALANCE_CHUNK_SHIFT, UR_OPT_DEBUG_HZB_RIDE_STALL = 7, 8, 9, 10, 11
+UR_OPT_TAA_TONEMAP_HISTORY_STORE = 12
 
 
 class MipDesc(C.Structure):
@@ -130,6 +131,16 @@ class FramePost(C.Structure):
                 ("cas_sharpness", C.c_float)]
 
 
+class FrameTaa(C.Structure):
+    """ur_frame_taa (include/ur_frame.h): the TemporalAA history ring of a frame (ur_frame_set_taa)."""
+    _fields_ = [("history", C.POINTER(C.c_void_p)), ("history_count", C.c_uint32), ("history_weight", C.c_float)]
+
+
+class FrameTaaInfo(C.Structure):
+    """ur_frame_taa_info (include/ur_frame.h): what the next frame with UR_FRAME_TAA does (ur_frame_taa_next)."""
+    _fields_ = [("read_slot", C.c_uint32), ("write_slot", C.c_uint32), ("use_history", C.c_uint32), ("jitter", C.c_float * 2)]
+
+
 class FrameResources(C.Structure):
     """ur_frame_resources (include/ur_frame.h)."""
     _fields_ = [
@@ -157,6 +168,8 @@ UR_FRAME_CAS = 0x80000
 UR_FRAME_FUSE_TONEMAP_CAS = 0x100000
 UR_FRAME_POST_EXCHANGE = 0x200000
 UR_FRAME_CULL_VIEWS = 0x400000
+UR_FRAME_TAA = 0x800000
+UR_FRAME_FUSE_TAA_TONEMAP = 0x1000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -203,6 +216,7 @@ SIGNATURES = {
                                            C.POINTER(LightingTables), _VP, _U32, _U32, _U32, _U32]),
     "ur_tonemap": (C.c_int, [_VP, C.POINTER(TonemapConstants), _VP, _VP, _VP, _U32, _U32]),
     "ur_temporal_aa": (C.c_int, [_VP, _VP, _VP, _VP, _F, _U32, _U32, _U32, _U32, _U32]),
+    "ur_temporal_aa_tonemap": (C.c_int, [_VP, C.POINTER(TonemapConstants), _VP, _VP, _VP, _VP, _VP, _F, _U32, _U32, _U32, _U32, _U32]),
     "ur_auto_exposure": (C.c_int, [_VP, C.POINTER(AutoExposureConstants), _VP, _U32, _U32, _VP, _VP]),
     "ur_cas": (C.c_int, [_VP, C.POINTER(CasConstants), _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_tonemap_cas": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
@@ -236,6 +250,9 @@ SIGNATURES = {
     "ur_frame_reset_hzb": (None, [_VP]),
     "ur_frame_set_post": (C.c_int, [_VP, C.POINTER(FramePost)]),
     "ur_frame_reset_post": (None, [_VP]),
+    "ur_frame_set_taa": (C.c_int, [_VP, C.POINTER(FrameTaa)]),
+    "ur_frame_reset_taa": (None, [_VP]),
+    "ur_frame_taa_next": (C.c_int, [_VP, C.POINTER(FrameTaaInfo)]),
     "ur_frame_set_draw_ranges": (C.c_int, [_VP, C.POINTER(DrawRanges)]),
     "ur_frame_set_cull_views": (C.c_int, [_VP, C.POINTER(CullView), _U32]),
     "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
@@ -255,6 +272,8 @@ SIGNATURES = {
     "ur_host_pack_culling_constants": (None, [_FP, _FP, _U32, _U32, _U32, _U32, _U32, _U32, C.POINTER(_U32)]),
     "ur_host_fill_scene_constants": (None, [_FP, _FP, _FP, _F, _FP, _FP, _FP, _F, _F, _F, _F, _F, C.POINTER(SceneConstants)]),
     "ur_host_fill_sky_constants": (None, [_FP, _FP, _FP, _F, _FP, _FP, C.POINTER(SkyConstants)]),
+    "ur_host_taa_jitter": (None, [_U32, _FP]),
+    "ur_host_apply_taa_jitter": (None, [_FP, _FP, _F, _F]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_light_direction_roundtrip": (None, [_FP, _FP]),
