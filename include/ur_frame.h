@@ -71,12 +71,27 @@ typedef struct ur_frame_resources {
 /* "TemporalAA" pass between Sky and AutoExposure (DeferredRenderer.cpp:1308-1361): Lighting + history[read] -> history[write] with
  * ur_temporal_aa; Tonemap (ur_tonemap_cas under FUSE_TONEMAP_CAS) then reads history[write] instead of Lighting, AutoExposure keeps
  * reading Lighting. Needs UR_FRAME_TONEMAP, a tonemap_band and ur_frame_set_taa's ring (else UR_EINVAL), and the whole frame: rows !=
- * height or UR_FRAME_POST_EXCHANGE is UR_EUNSUPPORTED. Without the flag the frame is what it is without a ring. */
+ * height or UR_FRAME_POST_EXCHANGE is UR_EUNSUPPORTED (unless UR_FRAME_TAA_BAND asks for the band form). Without the flag the frame is
+ * what it is without a ring. */
 #define UR_FRAME_TAA 0x800000u
 /* With TAA: the Tonemap pass runs ur_temporal_aa_tonemap (history[write] and the LDR image in one launch, the same bytes); the
  * TemporalAA pass is then culled. Not together with UR_FRAME_FUSE_TONEMAP_CAS (UR_EINVAL); with a CAS pass of its own the launch
  * writes tonemap_scratch. */
 #define UR_FRAME_FUSE_TAA_TONEMAP 0x1000000u
+/* TemporalAA on rank's equal row band through the post exchange (opt-in; without it TAA on a band or with POST_EXCHANGE stays
+ * UR_EUNSUPPORTED). Needs UR_FRAME_TAA and UR_FRAME_POST_EXCHANGE, UR_FRAME_TONEMAP and a tonemap_band, ur_frame_set_taa's ring - its
+ * images now band-local, width x rows -, ur_frame_set_post_records, ur_frame_set_taa_records and rank's equal band (else UR_EINVAL); a
+ * one-row band of several ranks is UR_EUNSUPPORTED. The exchange is then active with or without AUTO_EXPOSURE / CAS: ur_frame_render
+ * runs through Sky, the "Post Record" pass packs the post record and the TAA record (ur_pack_taa_record, from the history image the
+ * frame reads), and the frame returns with the post passes pending. The caller all-gathers BOTH record buffers (they may be in flight
+ * together) and calls ur_frame_finish_post: TemporalAA (ur_temporal_aa_halo) -> AutoExposure from the records (it keeps reading
+ * Lighting) -> Tonemap of the resolved band -> CAS with the resolved rows around the band. FUSE_TAA_TONEMAP runs
+ * ur_temporal_aa_tonemap_halo (the TemporalAA pass stays in the graph, disabled and culled), FUSE_TONEMAP_CAS ur_tonemap_cas_halo on the
+ * resolved band; the two together stay UR_EINVAL. The history images, the LDR band and luminance[W] hold the bytes of the unsplit frame.
+ * The written image becomes valid and the sample index advances when ur_frame_finish_post returns UR_OK; a frame that is never
+ * finished, like any other frame, invalidates the ring. The ranks' histories stay in step only if ALL RANKS RENDER THE SAME FLAGS every
+ * frame: a rank packs history rows exactly when its own ring is valid, and its neighbours read them exactly when theirs is. */
+#define UR_FRAME_TAA_BAND 0x2000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -128,7 +143,8 @@ int ur_frame_set_taa(ur_frame* f, const ur_frame_taa* taa);
 void ur_frame_reset_taa(ur_frame* f);
 /* What the next ur_frame_render with UR_FRAME_TAA will do: the slots, use_history, and the jitter of its sample index
  * (ur_host_taa_jitter; zero when use_history is 0). The caller jitters its projection with it (ur_host_apply_taa_jitter) before it
- * rasterises the G-buffer and fills the constant blocks. UR_EINVAL without a ring. */
+ * rasterises the G-buffer and fills the constant blocks. UR_EINVAL without a ring. While the post passes of a UR_FRAME_TAA_BAND frame are
+ * pending the answer does not count that frame yet: ask after ur_frame_finish_post. */
 typedef struct ur_frame_taa_info {
     uint32_t read_slot, write_slot, use_history;
     float jitter[2];
@@ -138,7 +154,13 @@ int ur_frame_taa_next(const ur_frame* f, ur_frame_taa_info* info);
  * rank's record, all_records holds world_size gathered records in rank order (own_record may alias all_records + rank * bytes, for
  * an in-place all-gather). They must stay valid while frames use them. */
 int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_records);
-/* The post passes of a frame rendered with UR_FRAME_POST_EXCHANGE, after the records are gathered: AutoExposure, Tonemap and (unless
+/* The TAA records of UR_FRAME_TAA_BAND, each ur_taa_record_bytes(width) per rank, with the aliasing rule of the post records:
+ * own_record receives this rank's record, all_records holds world_size gathered records in rank order (own_record may alias
+ * all_records + rank * bytes). They must stay valid while frames use them. The two resolved HDR rows that CAS reads around the band
+ * (2 * width ur_half4) are the frame's own: allocated at the first such frame with CAS, freed by ur_frame_destroy. */
+int ur_frame_set_taa_records(ur_frame* f, void* own_record, const void* all_records);
+/* The post passes of a frame rendered with UR_FRAME_POST_EXCHANGE, after the records are gathered: (with UR_FRAME_TAA_BAND,
+ * TemporalAA,) AutoExposure, Tonemap and (unless
  * fused) CAS, with the luminance ping-pong and history of the unsplit frame. UR_EINVAL if nothing is pending or the band is not
  * rank's equal band. ur_frame_report then lists both halves in order. */
 int ur_frame_finish_post(ur_frame* f);

@@ -488,6 +488,49 @@ int ur_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_cas_c
                 const ur_half4* hdr_above, const ur_half4* hdr_below, const float* exposure_ev, uint32_t* out_band,
                 uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
 
+/* ---- TemporalAA on row bands: the TAA record and the halo forms -----------------------------------------------------------
+ * The resolve of a band needs one current row from each neighbour: the post record's last_row / first_row. CAS behind TemporalAA
+ * needs the RESOLVED row just outside the band, which is recomputed locally from two current rows and one history row of the
+ * neighbour. Those travel in a second fixed-size record per rank beside the post record (whose layout is unchanged), gathered the
+ * same way; ur_taa_record_bytes(w) = 4 * w * 8 bytes:
+ *
+ *   offset   contents
+ *   0        second_row[w]:        half4, current HDR row row0 + 1 (after Lighting/Sky)
+ *   8*w      second_last_row[w]:   current HDR row row0 + rows - 2
+ *   16*w     history_first_row[w]: row row0 of the history image this frame READS (zeros when use_history == 0)
+ *   24*w     history_last_row[w]:  row row0 + rows - 1 of that image (zeros when use_history == 0)
+ *
+ * With a two-row band second_row is the last row and second_last_row the first. Per frame a rank sends (2*w + 1024) * 8 + 32 * w
+ * bytes, about 184 KB at 4K, against the 8.3 MB of an RGBA16F band of an 8-rank 4K frame. */
+uint64_t ur_taa_record_bytes(uint32_t w);
+/* Writes this band's TAA record, every byte of it (one launch). hdr_band / history_read_band: device, rows [row0,row0+rows) of the
+ * current frame and of the history image the frame reads; history_read_band may be null iff use_history == 0. A band that is not the
+ * whole frame needs rows >= 2, else UR_EUNSUPPORTED. Pack it BEFORE the resolve when the history is read and written in place. */
+int ur_pack_taa_record(ur_ctx* ctx, const ur_half4* hdr_band, const ur_half4* history_read_band, uint32_t use_history, uint32_t w, uint32_t h,
+                       uint32_t row0, uint32_t rows, void* record);
+/* ur_temporal_aa of rows [row0,row0+rows) with only the band in memory: current_band holds those rows of the current frame,
+ * cur_above / cur_below the current rows row0 - 1 / row0 + rows (w half4 each; the neighbours' last_row / first_row, used in place in
+ * the gathered post records). cur_above must be null when row0 == 0 and non-null otherwise, cur_below likewise for row0 + rows == h
+ * (UR_EINVAL). output_band receives the bytes ur_temporal_aa writes for those rows from the full frame; history_band may be
+ * output_band (a ring of one image).
+ * The same launch can resolve the rows row0 - 1 and row0 + rows: resolved_above / resolved_below (w half4 each; each side on its own,
+ * null = not wanted, and null at the frame's edge) receive exactly the texels the neighbour rank writes into its own history image for
+ * that row: the hdr_above / hdr_below of ur_cas_halo / ur_tonemap_cas_halo behind TemporalAA. A side that is resolved needs above2 /
+ * below2 - the current row max(row0 - 2, 0) / min(row0 + rows + 1, h - 1), the neighbour's second_last_row / second_row - and, when
+ * use_history != 0, hist_above / hist_below, the neighbour's history_last_row / history_first_row; a side that is not resolved passes
+ * null for all three (UR_EINVAL otherwise). The clamp at the frame's first and last row applies to the resolved rows too. */
+int ur_temporal_aa_halo(ur_ctx* ctx, const ur_half4* current_band, const ur_half4* cur_above, const ur_half4* cur_below, const ur_half4* history_band,
+                        ur_half4* output_band, const ur_half4* above2, const ur_half4* hist_above, const ur_half4* below2, const ur_half4* hist_below,
+                        ur_half4* resolved_above, ur_half4* resolved_below, float history_weight, uint32_t use_history, uint32_t w, uint32_t h,
+                        uint32_t row0, uint32_t rows);
+/* The same with the Tonemap epilogue of ur_temporal_aa_tonemap: history_out_band and ldr_out_band (w x rows R8G8B8A8_UNORM) in one
+ * launch, plus the resolved HDR rows. The history store keeps its write-once hint under either UR_OPT_TAA_TONEMAP_HISTORY_STORE. */
+int ur_temporal_aa_tonemap_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_half4* current_band, const ur_half4* cur_above,
+                                const ur_half4* cur_below, const ur_half4* history_band, ur_half4* history_out_band, const float* exposure_ev,
+                                uint32_t* ldr_out_band, const ur_half4* above2, const ur_half4* hist_above, const ur_half4* below2,
+                                const ur_half4* hist_below, ur_half4* resolved_above, ur_half4* resolved_below, float history_weight,
+                                uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
+
 /* ---- multi-GPU: gather the row bands of the HDR frame ------------------------------------------ */
 
 /* comm: an ncclComm_t (RCCL). hdr_full: device, w*h half4 on every rank; rank r has already written

@@ -10,6 +10,12 @@ ur_tonemap_cas of the same rows of the full frame, the two timed in alternating 
 batch of back-to-back launches (per-launch time = batch time / launches) after a warm-up, over rotating buffer sets whose bytes
 exceed the 256 MiB memory-side cache, as in tools/bench_post.py. Before the times of a case are printed, the halo form's bytes are
 checked equal to ur_tonemap_cas's. Per rank it prints the bytes of a record, of the RGBA8 band and of the HDR band.
+
+The TemporalAA legs (--no-taa leaves them out) run behind them with buffer sets of their own: ur_pack_taa_record of the band, and the band
+forms ur_temporal_aa_halo / ur_temporal_aa_tonemap_halo - each with the two resolved rows around the band, as a frame with CAS runs them -
+against the same rows resolved by ur_temporal_aa / ur_temporal_aa_tonemap out of the full frame, in the same alternating batches, with
+history (use_history = 1) and separate output images. The band forms' bytes are checked equal first. After each pair it prints halo / full
+and the batch-to-batch spread (max - min of the batch times) of the full-frame form, the yardstick of "not slower".
 """
 import argparse
 import json
@@ -24,6 +30,68 @@ from tools.bench_post import CACHE_BYTES, time_batches  # noqa: E402
 SIZES = {"1080p": (1920, 1080), "4k": (3840, 2160), "8k": (7680, 4320)}
 
 
+def taa_legs(torch, hp, a, name, w, h, hdr, nsets, PB, TB, ev, rows_out):
+    """The TemporalAA legs of one frame size (see the file comment). hdr: the current frames of the buffer sets."""
+    g = torch.Generator(device="cuda").manual_seed(2)
+    hist = [(torch.rand((h, w, 4), device="cuda", generator=g) * 3.0).half() for _ in range(nsets)]
+    tkw = dict(exposure=0.9, gamma=2.2, exposure_ev=ev)
+    for rows in (int(r) for r in a.rows.split(",")):
+        if h % rows or h // rows < 3:
+            continue
+        n, r0 = h // rows, rows  # rank 1: a neighbour on both sides
+        post = [torch.zeros((n, PB), dtype=torch.uint8, device="cuda") for _ in range(nsets)]
+        taa = [torch.zeros((n, TB), dtype=torch.uint8, device="cuda") for _ in range(nsets)]
+        for i in range(nsets):
+            for r in (0, 1, 2):
+                hp.pack_post_record(hdr[i][r * rows:(r + 1) * rows], post[i][r], w, h, r * rows, rows)
+                hp.pack_taa_record(hdr[i][r * rows:(r + 1) * rows], hist[i][r * rows:(r + 1) * rows], 1, taa[i][r], w, h, r * rows, rows)
+        row = lambda t, off: t[off:off + 8 * w]
+        band = [x[r0:r0 + rows] for x in hdr]
+        hband = [x[r0:r0 + rows] for x in hist]
+        side = [dict(above2=row(t[0], 8 * w), hist_above=row(t[0], 24 * w), below2=row(t[2], 0), hist_below=row(t[2], 16 * w)) for t in taa]
+        above = [row(p[0], 8 * w) for p in post]
+        below = [row(p[2], 0) for p in post]
+        mk = lambda shape, dt: [torch.zeros(shape, dtype=dt, device="cuda") for _ in range(nsets)]
+        out_full, out_halo = mk((rows, w, 4), torch.int16), mk((rows, w, 4), torch.int16)
+        ldr_full, ldr_halo = mk((rows, w), torch.int32), mk((rows, w), torch.int32)
+        res = [dict(resolved_above=torch.zeros((w, 4), dtype=torch.int16, device="cuda"), resolved_below=torch.zeros((w, 4), dtype=torch.int16, device="cuda"))
+               for _ in range(nsets)]
+        cases = {
+            "ur_pack_taa_record": lambda i: hp.pack_taa_record(band[i], hband[i], 1, taa[i][1], w, h, r0, rows),
+            "ur_temporal_aa": lambda i: hp.temporal_aa(hdr[i], hband[i], out_full[i], 0.9, 1, w, h, r0, rows),
+            "ur_temporal_aa_halo": lambda i: hp.temporal_aa_halo(band[i], above[i], below[i], hband[i], out_halo[i], 0.9, 1, w, h, r0, rows, **side[i], **res[i]),
+            "ur_temporal_aa_tonemap": lambda i: hp.temporal_aa_tonemap(hdr[i], hband[i], out_full[i], ldr_full[i], 0.9, 1, w, h, r0, rows, **tkw),
+            "ur_temporal_aa_tonemap_halo": lambda i: hp.temporal_aa_tonemap_halo(band[i], above[i], below[i], hband[i], out_halo[i], ldr_halo[i], 0.9, 1, w, h,
+                                                                                 r0, rows, **side[i], **res[i], **tkw),
+        }
+        for k in ("ur_temporal_aa", "ur_temporal_aa_halo"):
+            cases[k](0)
+        torch.cuda.synchronize()
+        assert torch.equal(out_full[0], out_halo[0]), f"{name}/{rows}: ur_temporal_aa_halo differs from ur_temporal_aa"
+        out_halo[0].zero_()
+        for k in ("ur_temporal_aa_tonemap", "ur_temporal_aa_tonemap_halo"):
+            cases[k](0)
+        torch.cuda.synchronize()
+        assert torch.equal(out_full[0], out_halo[0]) and torch.equal(ldr_full[0], ldr_halo[0]), f"{name}/{rows}: ur_temporal_aa_tonemap_halo differs"
+        times = {k: [] for k in cases}
+        for _ in range(a.batches):
+            for k, fn in cases.items():
+                times[k] += time_batches(torch, fn, nsets, a.iters, 1, warm=3)
+        per_rank = {"post_record": PB, "taa_record": TB, "exchanged": PB + TB, "hdr_band": w * rows * 8}
+        print(f"{name:>5} rows {rows:5d} (N = {n:2d})  TemporalAA; bytes per rank: post record {PB / 1e3:.1f} KB + TAA record {TB / 1e3:.1f} KB = "
+              f"{(PB + TB) / 1e3:.1f} KB exchanged, HDR band {w * rows * 8 / 1e6:.2f} MB", flush=True)
+        for k, t in times.items():
+            med = float(np.median(t))
+            print(f"      {k:<28} {med:8.2f} us  [{min(t):.2f}, {max(t):.2f}]", flush=True)
+            rows_out.append({"size": name, "w": w, "h": h, "rows": rows, "ranks": n, "op": k, "us_median": round(med, 2), "us_min": round(min(t), 2),
+                             "us_max": round(max(t), 2), "sets": nsets, **per_rank})
+        for full, halo in (("ur_temporal_aa", "ur_temporal_aa_halo"), ("ur_temporal_aa_tonemap", "ur_temporal_aa_tonemap_halo")):
+            tf, th = float(np.median(times[full])), float(np.median(times[halo]))
+            print(f"      {halo} / {full} {th / tf:.4f}  ({th - tf:+.2f} us; spread of the full-frame form {max(times[full]) - min(times[full]):.2f} us)", flush=True)
+        del post, taa, band, hband, side, above, below, out_full, out_halo, ldr_full, ldr_halo, res
+    del hist
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="4k,8k")
@@ -31,9 +99,11 @@ def main():
     ap.add_argument("--iters", type=int, default=200, help="launches per timed batch")
     ap.add_argument("--batches", type=int, default=7)
     ap.add_argument("--json", default="", help="also append one JSON line per measurement to this file")
+    ap.add_argument("--no-taa", action="store_true", help="leave out the TemporalAA legs")
+    ap.add_argument("--only-taa", action="store_true", help="only the TemporalAA legs")
     a = ap.parse_args()
     import torch
-    from unclerenderer_amd.hotpath import HotPath, post_record_bytes
+    from unclerenderer_amd.hotpath import HotPath, post_record_bytes, taa_record_bytes
     assert torch.cuda.is_available(), "bench_post_band needs a GPU"
     hp = HotPath(0)
     rows_out = []
@@ -47,7 +117,7 @@ def main():
         kw = dict(exposure=0.9, gamma=2.2, exposure_ev=ev, sharpness=0.5)
         B = post_record_bytes(w)
         for rows in (int(r) for r in a.rows.split(",")):
-            if h % rows:
+            if h % rows or a.only_taa:
                 continue
             n, r0 = h // rows, rows  # rank 1
             recs = [torch.zeros((n, B), dtype=torch.uint8, device="cuda") for _ in range(nsets)]
@@ -87,6 +157,8 @@ def main():
             tf, th = float(np.median(times["ur_tonemap_cas"])), float(np.median(times["ur_tonemap_cas_halo"]))
             print(f"      halo / full {th / tf:.4f}  ({th - tf:+.2f} us)", flush=True)
             del recs, out_full, out_halo, band, above, below
+        if not a.no_taa:
+            taa_legs(torch, hp, a, name, w, h, hdr, nsets, B, taa_record_bytes(w), ev, rows_out)
         del hdr
         torch.cuda.empty_cache()
     if a.json:

@@ -19,9 +19,10 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     // (valid and flipped after an AutoExposure pass that ran, invalid after any other frame, :1612-1620). Errors of passes are
     // collected in PassError rather than returned early; an early return added above Execute must do that bookkeeping too.
     PassError = UR_OK;
-    if (bPostPending) { // the last frame's post passes never ran: its AutoExposure did not either
+    if (bPostPending) { // the last frame's post passes never ran: neither its AutoExposure nor its TemporalAA did
         bPostPending = false;
         bLuminanceHistoryValid = false;
+        ResetTaa();
     }
     FRenderGraph Graph;
     Graph.SetDevice(Device);
@@ -46,8 +47,9 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     // TemporalAA (:394-403): the slots of this frame slot and whether the image read was written by a frame that completed
     const uint32 TaaSlotCount = static_cast<uint32>(Res.TaaHistory.size());
     if (Res.TaaHistoryStates.size() != Res.TaaHistory.size()) Res.TaaHistoryStates.assign(Res.TaaHistory.size(), RG_STATE_UNORDERED_ACCESS);
-    const bool bPostExchangeFrame = Options.bPostExchange && Options.bTonemap && Res.TonemapBand && (Options.bAutoExposure || Options.bCas);
-    const bool bTaaActive = Options.bTaa && Options.bTonemap && Res.TonemapBand && TaaSlotCount != 0 && !bPostExchangeFrame;
+    const bool bTaaBand = Options.bTaaBand && Options.bTaa && Options.bPostExchange; // TemporalAA on the band, through the exchange
+    const bool bPostExchangeFrame = Options.bPostExchange && Options.bTonemap && Res.TonemapBand && (Options.bAutoExposure || Options.bCas || bTaaBand);
+    const bool bTaaActive = Options.bTaa && Options.bTonemap && Res.TonemapBand && TaaSlotCount != 0 && (!bPostExchangeFrame || bTaaBand);
     TaaFrame = FTaaFrame{};
     if (bTaaActive) {
         TaaFrame.bActive = true;
@@ -191,20 +193,44 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     });
 
     const bool bPostPasses = Options.bTonemap && Res.TonemapBand && (Options.bAutoExposure || Options.bCas);
-    if (Options.bPostExchange && bPostPasses) {
+    const bool bTaaBandFrame = bTaaBand && bTaaActive;
+    if (Options.bPostExchange && (bPostPasses || bTaaBandFrame)) {
         // ---- Post Record: the band's part of the post exchange; the post passes wait for FinishPost --------------------------
+        // With TemporalAA on the band the pass packs the TAA record too, from the history image the frame reads: before the resolve,
+        // which with a ring of one image overwrites it.
         struct FPostRecordPassData
         {
+            bool bTaa = false;
+            uint32 TaaUseHistory = 0, TaaReadIndex = 0;
         };
+        const FHotPathRenderer::FTaaSlots Taa = TaaFrame.Slots;
+        FRGResourceHandle TaaRecordHandle, TaaReadHandle;
+        if (bTaaBandFrame) {
+            TaaRecordHandle = Graph.ImportTexture("TaaRecord", Res.TaaRecord, &Res.TaaRecordState,
+                                                  {static_cast<uint32>(ur_taa_record_bytes(Res.Width) / 8u), 1, RG_FORMAT_R16G16B16A16_FLOAT});
+            if (Taa.bUseHistory)
+                TaaReadHandle = Graph.ImportTexture("TaaHistory_" + std::to_string(Taa.Read), Res.TaaHistory[Taa.Read], &Res.TaaHistoryStates[Taa.Read],
+                                                    {Res.Width, Res.Rows, RG_FORMAT_R16G16B16A16_FLOAT});
+        }
         const FRGResourceHandle RecordHandle = Graph.ImportTexture("PostRecord", Res.PostRecord, &Res.PostRecordState,
                                                                    {static_cast<uint32>(ur_post_record_bytes(Res.Width) / 8u), 1, RG_FORMAT_R16G16B16A16_FLOAT});
-        Graph.AddPass<FPostRecordPassData>("Post Record", [&](FPostRecordPassData&, FRGPassBuilder& Builder)
+        Graph.AddPass<FPostRecordPassData>("Post Record", [&](FPostRecordPassData& Data, FRGPassBuilder& Builder)
         {
+            Data.bTaa = bTaaBandFrame;
+            Data.TaaUseHistory = Taa.bUseHistory ? 1u : 0u;
+            Data.TaaReadIndex = Taa.Read;
             Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             Builder.WriteTexture(RecordHandle, RG_STATE_UNORDERED_ACCESS);
-        }, [this, &Res](const FPostRecordPassData&, FHIPCommandContext& Cmd)
+            if (Data.bTaa) {
+                if (Taa.bUseHistory) Builder.ReadTexture(TaaReadHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+                Builder.WriteTexture(TaaRecordHandle, RG_STATE_UNORDERED_ACCESS);
+            }
+        }, [this, &Res](const FPostRecordPassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = ur_pack_post_record(Cmd.GetContext(), Res.LightingBand, Res.Width, Res.Height, Res.Row0, Res.Rows, Res.PostRecord);
+            int rc = ur_pack_post_record(Cmd.GetContext(), Res.LightingBand, Res.Width, Res.Height, Res.Row0, Res.Rows, Res.PostRecord);
+            if (rc == UR_OK && Data.bTaa)
+                rc = ur_pack_taa_record(Cmd.GetContext(), Res.LightingBand, Data.TaaUseHistory ? Res.TaaHistory[Data.TaaReadIndex] : nullptr, Data.TaaUseHistory,
+                                        Res.Width, Res.Height, Res.Row0, Res.Rows, Res.TaaRecord);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
         Graph.Execute(Cmd);
@@ -216,7 +242,8 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         } else {
             bLuminanceHistoryValid = false;
         }
-        EndTaaHistory(false, 0, TaaSlotCount);
+        // a TemporalAA frame on the band has not written its image yet: FinishPost does the ring's bookkeeping
+        if (!(bPostPending && bTaaBandFrame)) EndTaaHistory(false, 0, TaaSlotCount);
         return PassError;
     }
 
@@ -230,10 +257,11 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
 
 int FHotPathRenderer::FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res)
 {
-    if (!bPostPending) { ur::set_error("ur_frame_finish_post: no post passes are pending (render with UR_FRAME_POST_EXCHANGE and AUTO_EXPOSURE / CAS first)"); return UR_EINVAL; }
+    if (!bPostPending) { ur::set_error("ur_frame_finish_post: no post passes are pending (render with UR_FRAME_POST_EXCHANGE and AUTO_EXPOSURE / CAS / TAA_BAND first)"); return UR_EINVAL; }
     bPostPending = false;
     PassError = UR_OK;
-    TaaFrame = FTaaFrame{}; // (a frame of the post exchange runs without TemporalAA)
+    const bool bTaaBandFrame = TaaFrame.bActive && PendingOptions.bTaaBand; // RenderFrame's slots, kept while the passes were pending
+    if (!bTaaBandFrame) TaaFrame = FTaaFrame{}; // (without bTaaBand a frame of the post exchange runs without TemporalAA)
     FRenderGraph Graph;
     Graph.SetDevice(Device);
     Graph.SetGpuTimingEnabled(PendingOptions.bGpuTiming);
@@ -246,6 +274,7 @@ int FHotPathRenderer::FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res
     const std::vector<FRenderGraph::FPassReport>& Tail = Graph.GetLastExecutionReport();
     LastReport.insert(LastReport.end(), Tail.begin(), Tail.end());
     EndPostHistory(PendingOptions.bAutoExposure);
+    if (bTaaBandFrame) EndTaaHistory(true, TaaFrame.Slots.Write, static_cast<uint32>(Res.TaaHistory.size())); // (else RenderFrame dropped the ring)
     return PassError;
 }
 
@@ -287,7 +316,8 @@ void FHotPathRenderer::EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 
 
 // [TemporalAA ->] AutoExposure -> Tonemap -> CAS. RecordRanks != 0: on the band alone, from the RecordRanks gathered post records (FinishPost; the
 // band is this rank's equal band): AutoExposure reads every rank's tap texels, Tonemap / CAS read the rows around the band from the
-// neighbours' records in place.
+// neighbours' records in place. TemporalAA on the band (TaaFrame active in FinishPost) resolves from the neighbours' current rows in the
+// post records and, for CAS, also resolves the row on either side of the band from their TAA records into Res.TaaHaloRows: CAS's halo rows.
 void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
                                      const FHotPathOptions& Options, uint32 RecordRanks)
 {
@@ -301,9 +331,44 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
     const uint64 RecordBytes = ur_post_record_bytes(Res.Width);
     const uint8_t* Records = static_cast<const uint8_t*>(Res.PostRecords);
     const uint32 Rank = bFromRecords ? Res.Row0 / Res.Rows : 0;
-    // the neighbours' last / first HDR rows: the halo rows of CAS (none at the frame's top / bottom edge)
-    const ur_half4* HaloAbove = bFromRecords && Rank > 0 ? reinterpret_cast<const ur_half4*>(Records + (Rank - 1) * RecordBytes + 8ull * Res.Width) : nullptr;
-    const ur_half4* HaloBelow = bFromRecords && Rank + 1 < RecordRanks ? reinterpret_cast<const ur_half4*>(Records + (Rank + 1) * RecordBytes) : nullptr;
+    // the neighbours' last / first HDR rows: the halo rows of CAS (none at the frame's top / bottom edge), and of TemporalAA on the band
+    const ur_half4* CurAbove = bFromRecords && Rank > 0 ? reinterpret_cast<const ur_half4*>(Records + (Rank - 1) * RecordBytes + 8ull * Res.Width) : nullptr;
+    const ur_half4* CurBelow = bFromRecords && Rank + 1 < RecordRanks ? reinterpret_cast<const ur_half4*>(Records + (Rank + 1) * RecordBytes) : nullptr;
+    // TemporalAA on the band: behind it CAS's halo rows are the RESOLVED rows around the band, which the TemporalAA launch writes
+    // from the neighbours' TAA records: above second_last_row / history_last_row, below second_row / history_first_row
+    const bool bTaaRecords = TaaFrame.bActive && bFromRecords;
+    const bool bTaaHalo = bTaaRecords && bCas;
+    const uint64 TaaRecordBytes = ur_taa_record_bytes(Res.Width);
+    const uint8_t* TaaRecs = static_cast<const uint8_t*>(Res.TaaRecords);
+    struct FTaaBandRows
+    {
+        const ur_half4 *CurAbove = nullptr, *CurBelow = nullptr, *Above2 = nullptr, *HistAbove = nullptr, *Below2 = nullptr, *HistBelow = nullptr;
+        ur_half4 *ResolvedAbove = nullptr, *ResolvedBelow = nullptr;
+    } TaaRows;
+    if (bTaaRecords) {
+        TaaRows.CurAbove = CurAbove;
+        TaaRows.CurBelow = CurBelow;
+        if (bTaaHalo && CurAbove) {
+            const uint8_t* N = TaaRecs + (Rank - 1) * TaaRecordBytes;
+            TaaRows.Above2 = reinterpret_cast<const ur_half4*>(N + 8ull * Res.Width);
+            if (TaaFrame.Slots.bUseHistory) TaaRows.HistAbove = reinterpret_cast<const ur_half4*>(N + 24ull * Res.Width);
+            TaaRows.ResolvedAbove = Res.TaaHaloRows;
+        }
+        if (bTaaHalo && CurBelow) {
+            const uint8_t* N = TaaRecs + (Rank + 1) * TaaRecordBytes;
+            TaaRows.Below2 = reinterpret_cast<const ur_half4*>(N);
+            if (TaaFrame.Slots.bUseHistory) TaaRows.HistBelow = reinterpret_cast<const ur_half4*>(N + 16ull * Res.Width);
+            TaaRows.ResolvedBelow = Res.TaaHaloRows + Res.Width;
+        }
+    }
+    const ur_half4* HaloAbove = bTaaRecords ? TaaRows.ResolvedAbove : CurAbove;
+    const ur_half4* HaloBelow = bTaaRecords ? TaaRows.ResolvedBelow : CurBelow;
+    const FRGResourceHandle TaaRecordsHandle = bTaaHalo
+        ? Graph.ImportTexture("TaaRecords", const_cast<void*>(Res.TaaRecords), &Res.TaaRecordsState, {static_cast<uint32>(TaaRecordBytes / 8u), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
+        : FRGResourceHandle{};
+    const FRGResourceHandle TaaHaloHandle = bTaaHalo
+        ? Graph.ImportTexture("TaaHaloRows", Res.TaaHaloRows, &Res.TaaHaloRowsState, {Res.Width, 2, RG_FORMAT_R16G16B16A16_FLOAT})
+        : FRGResourceHandle{};
     const FRGResourceHandle RecordsHandle = bFromRecords
         ? Graph.ImportTexture("PostRecords", const_cast<void*>(Res.PostRecords), &Res.PostRecordsState, {static_cast<uint32>(RecordBytes / 8u), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
         : FRGResourceHandle{};
@@ -321,14 +386,24 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
         bool bEnabled = false;
         float HistoryWeight = 0.9f;
         uint32 UseHistory = 0, ReadIndex = 0, WriteIndex = 0;
+        bool bHalo = false; // the band alone (FinishPost): ur_temporal_aa_halo
     };
-    const bool bTaa = TaaFrame.bActive && !bFromRecords;
+    // the rows around the band that a TemporalAA launch on the band reads, declared by the pass that makes the launch
+    auto DeclareTaaBandRows = [&](FRGPassBuilder& Builder) {
+        if (!bTaaRecords) return;
+        Builder.ReadTexture(RecordsHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+        if (bTaaHalo) {
+            Builder.ReadTexture(TaaRecordsHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            Builder.WriteTexture(TaaHaloHandle, RG_STATE_UNORDERED_ACCESS);
+        }
+    };
+    const bool bTaa = TaaFrame.bActive;
     const bool bFuseTaa = bTaa && TaaFrame.bFuseTonemap;
     const FHotPathRenderer::FTaaSlots Taa = TaaFrame.Slots;
     FRGResourceHandle TaaReadHandle, TaaWriteHandle;
     if (bTaa) {
         auto Import = [&](uint32 I) {
-            return Graph.ImportTexture("TaaHistory_" + std::to_string(I), Res.TaaHistory[I], &Res.TaaHistoryStates[I], {Res.Width, Res.Height, RG_FORMAT_R16G16B16A16_FLOAT});
+            return Graph.ImportTexture("TaaHistory_" + std::to_string(I), Res.TaaHistory[I], &Res.TaaHistoryStates[I], {Res.Width, Res.Rows, RG_FORMAT_R16G16B16A16_FLOAT});
         };
         TaaWriteHandle = Import(Taa.Write);
         TaaReadHandle = Taa.Read == Taa.Write ? TaaWriteHandle : Import(Taa.Read); // a ring of one image: read and written in place
@@ -340,13 +415,19 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
             Data.WriteIndex = Taa.Write;
             Data.HistoryWeight = Constants.TaaHistoryWeight;
             Data.UseHistory = Taa.bUseHistory ? 1u : 0u;
+            Data.bHalo = bTaaRecords;
             Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             if (Taa.Read != Taa.Write) Builder.ReadTexture(TaaReadHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            DeclareTaaBandRows(Builder);
             Builder.WriteTexture(TaaWriteHandle, RG_STATE_UNORDERED_ACCESS);
-        }, [this, &Res](const FTemporalAAPassData& Data, FHIPCommandContext& Cmd)
+        }, [this, &Res, TaaRows](const FTemporalAAPassData& Data, FHIPCommandContext& Cmd)
         {
             if (!Data.bEnabled) return;
-            const int rc = ur_temporal_aa(Cmd.GetContext(), Res.LightingBand, Res.TaaHistory[Data.ReadIndex], Res.TaaHistory[Data.WriteIndex], Data.HistoryWeight,
+            const int rc = Data.bHalo
+                ? ur_temporal_aa_halo(Cmd.GetContext(), Res.LightingBand, TaaRows.CurAbove, TaaRows.CurBelow, Res.TaaHistory[Data.ReadIndex],
+                                      Res.TaaHistory[Data.WriteIndex], TaaRows.Above2, TaaRows.HistAbove, TaaRows.Below2, TaaRows.HistBelow, TaaRows.ResolvedAbove,
+                                      TaaRows.ResolvedBelow, Data.HistoryWeight, Data.UseHistory, Res.Width, Res.Height, Res.Row0, Res.Rows)
+                : ur_temporal_aa(Cmd.GetContext(), Res.LightingBand, Res.TaaHistory[Data.ReadIndex], Res.TaaHistory[Data.WriteIndex], Data.HistoryWeight,
                                           Data.UseHistory, Res.Width, Res.Height, 0, Res.Height);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
@@ -401,6 +482,7 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
         const ur_half4* HaloBelow = nullptr;
         const ur_half4* Input = nullptr; // Lighting, or TaaHistory_<Write> behind a TemporalAA pass
         bool bFuseTaa = false;           // TemporalAA + Tonemap in this pass's launch
+        bool bTaaHalo = false;           // ... on the band alone (ur_temporal_aa_tonemap_halo)
         float TaaHistoryWeight = 0.9f;
         uint32 TaaUseHistory = 0, TaaReadIndex = 0, TaaWriteIndex = 0;
     };
@@ -436,6 +518,7 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
             Data.HaloBelow = HaloBelow;
             Data.Input = bTaa ? Res.TaaHistory[Taa.Write] : Res.LightingBand;
             Data.bFuseTaa = bFuseTaa;
+            Data.bTaaHalo = bFuseTaa && bTaaRecords;
             Data.TaaHistoryWeight = Constants.TaaHistoryWeight;
             Data.TaaUseHistory = Taa.bUseHistory ? 1u : 0u;
             Data.TaaReadIndex = Taa.Read;
@@ -443,20 +526,26 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
             if (bFuseTaa) { // the TemporalAA pass's usages move here
                 Builder.ReadTexture(LightingHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
                 if (Taa.Read != Taa.Write) Builder.ReadTexture(TaaReadHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+                DeclareTaaBandRows(Builder);
                 Builder.WriteTexture(TaaWriteHandle, RG_STATE_UNORDERED_ACCESS);
             } else {
                 Builder.ReadTexture(bTaa ? TaaWriteHandle : LightingHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
             }
-            if (Data.bHalo) Builder.ReadTexture(RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+            if (Data.bHalo) Builder.ReadTexture(bTaaRecords ? TaaHaloHandle : RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
             if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
             Builder.WriteTexture(bCas && !bFuseCas ? ScratchHandle : TonemapHandle, RG_STATE_RENDER_TARGET);
-        }, [this, &Res](const FTonemapPassData& Data, FHIPCommandContext& Cmd)
+        }, [this, &Res, TaaRows](const FTonemapPassData& Data, FHIPCommandContext& Cmd)
         {
-            const int rc = Data.bFuseTaa
+            const int rc = Data.bTaaHalo
+                ? ur_temporal_aa_tonemap_halo(Cmd.GetContext(), &Data.K, Res.LightingBand, TaaRows.CurAbove, TaaRows.CurBelow, Res.TaaHistory[Data.TaaReadIndex],
+                                              Res.TaaHistory[Data.TaaWriteIndex], Data.ExposureEv, Data.Output, TaaRows.Above2, TaaRows.HistAbove, TaaRows.Below2,
+                                              TaaRows.HistBelow, TaaRows.ResolvedAbove, TaaRows.ResolvedBelow, Data.TaaHistoryWeight, Data.TaaUseHistory, Res.Width,
+                                              Res.Height, Res.Row0, Res.Rows)
+                : Data.bFuseTaa
                 ? ur_temporal_aa_tonemap(Cmd.GetContext(), &Data.K, Res.LightingBand, Res.TaaHistory[Data.TaaReadIndex], Res.TaaHistory[Data.TaaWriteIndex],
                                          Data.ExposureEv, Data.Output, Data.TaaHistoryWeight, Data.TaaUseHistory, Res.Width, Res.Height, 0, Res.Height)
                 : Data.bHalo
-                ? ur_tonemap_cas_halo(Cmd.GetContext(), &Data.K, &Data.Cas, Res.LightingBand, Data.HaloAbove, Data.HaloBelow, Data.ExposureEv, Data.Output, Res.Width,
+                ? ur_tonemap_cas_halo(Cmd.GetContext(), &Data.K, &Data.Cas, Data.Input, Data.HaloAbove, Data.HaloBelow, Data.ExposureEv, Data.Output, Res.Width,
                                       Res.Height, Res.Row0, Res.Rows)
                 : Data.bFuseCas
                 ? ur_tonemap_cas(Cmd.GetContext(), &Data.K, &Data.Cas, Data.Input, Data.ExposureEv, Data.Output, Res.Width, Res.Height, Res.Row0, Res.Rows)
@@ -479,7 +568,7 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
                 Data.HaloBelow = HaloBelow;
                 Builder.ReadTexture(ScratchHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
                 if (Data.bHalo) {
-                    Builder.ReadTexture(RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
+                    Builder.ReadTexture(bTaaRecords ? TaaHaloHandle : RecordsHandle, RG_STATE_PIXEL_SHADER_RESOURCE);
                     if (bAutoExposure) Builder.ReadTexture(LuminanceHandles[WriteIndex], RG_STATE_PIXEL_SHADER_RESOURCE);
                 }
                 Builder.WriteTexture(TonemapHandle, RG_STATE_RENDER_TARGET);
@@ -524,6 +613,10 @@ struct ur_frame
     float TaaHistoryWeight = 0.9f;
     void* PostRecord = nullptr;        // ur_frame_set_post_records
     const void* PostRecords = nullptr;
+    void* TaaRecord = nullptr;         // ur_frame_set_taa_records
+    const void* TaaRecords = nullptr;
+    ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
+    uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
 };
 
@@ -610,6 +703,7 @@ void ur_frame_destroy(ur_frame* f)
     if (f->AsyncCtx) ur_destroy(f->AsyncCtx);
     if (f->AsyncStream) (void)hipStreamDestroy(f->AsyncStream);
     for (auto& e : f->LightEvents) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); (void)hipEventDestroy(e.after); }
+    if (f->TaaHaloRows) (void)hipFree(f->TaaHaloRows);
     delete f;
 }
 
@@ -644,9 +738,26 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
             ur::set_error("ur_frame_render: FUSE_TAA_TONEMAP and FUSE_TONEMAP_CAS exclude each other (TAA + Tonemap + CAS in one launch is not built)");
             return UR_EINVAL;
         }
-        if ((flags & UR_FRAME_POST_EXCHANGE) || r->row0 != 0 || r->rows != r->height) {
-            ur::set_error("ur_frame_render: TAA needs the whole frame (rows == height, no UR_FRAME_POST_EXCHANGE)");
+        if (!(flags & UR_FRAME_TAA_BAND) && ((flags & UR_FRAME_POST_EXCHANGE) || r->row0 != 0 || r->rows != r->height)) {
+            ur::set_error("ur_frame_render: TAA needs the whole frame (rows == height, no UR_FRAME_POST_EXCHANGE), or UR_FRAME_TAA_BAND");
             return UR_EUNSUPPORTED;
+        }
+    }
+    if (flags & UR_FRAME_TAA_BAND) {
+        if (!(flags & UR_FRAME_TAA) || !(flags & UR_FRAME_POST_EXCHANGE)) { ur::set_error("ur_frame_render: TAA_BAND needs UR_FRAME_TAA and UR_FRAME_POST_EXCHANGE"); return UR_EINVAL; }
+        if (!f->PostRecord || !f->PostRecords) { ur::set_error("ur_frame_render: TAA_BAND needs ur_frame_set_post_records"); return UR_EINVAL; }
+        if (!f->TaaRecord || !f->TaaRecords) { ur::set_error("ur_frame_render: TAA_BAND needs ur_frame_set_taa_records"); return UR_EINVAL; }
+        if (!equal_band(f, r->height, r->row0, r->rows)) {
+            ur::set_error("ur_frame_render: TAA_BAND needs rank's equal band (world_size | height)");
+            return UR_EINVAL;
+        }
+        if (r->rows < 2u && f->Cmd.GetWorldSize() > 1) { ur::set_error("ur_frame_render: TAA_BAND needs bands of at least 2 rows"); return UR_EUNSUPPORTED; }
+        if ((flags & UR_FRAME_CAS) && (!f->TaaHaloRows || f->TaaHaloWidth < r->width)) { // the resolved rows around the band: the frame's own
+            if (f->TaaHaloRows) { (void)hipStreamSynchronize(f->Cmd.GetStream()); (void)hipFree(f->TaaHaloRows); f->TaaHaloRows = nullptr; f->TaaHaloWidth = 0; }
+            void* rows2 = nullptr;
+            if (hipMalloc(&rows2, static_cast<size_t>(r->width) * 2u * sizeof(ur_half4)) != hipSuccess) { ur::set_error("ur_frame_render: no memory for the resolved rows of TAA_BAND"); return UR_ENOMEM; }
+            f->TaaHaloRows = static_cast<ur_half4*>(rows2);
+            f->TaaHaloWidth = r->width;
         }
     }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
@@ -662,6 +773,9 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.Luminance[1] = f->Post.luminance[1];
     R.PostRecord = f->PostRecord;
     R.PostRecords = f->PostRecords;
+    R.TaaRecord = f->TaaRecord;
+    R.TaaRecords = f->TaaRecords;
+    R.TaaHaloRows = f->TaaHaloRows;
     R.TaaHistory = f->TaaHistory; // (RenderFrame sizes TaaHistoryStates)
     R.DepthFull = const_cast<float*>(r->depth_full);
     R.HZB = r->hzb;
@@ -707,6 +821,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bPostExchange = (flags & UR_FRAME_POST_EXCHANGE) != 0;
     O.bTaa = (flags & UR_FRAME_TAA) != 0;
     O.bFuseTaaTonemap = (flags & UR_FRAME_FUSE_TAA_TONEMAP) != 0;
+    O.bTaaBand = (flags & UR_FRAME_TAA_BAND) != 0;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -838,6 +953,14 @@ int ur_frame_set_post_records(ur_frame* f, void* own_record, const void* all_rec
     return UR_OK;
 }
 
+int ur_frame_set_taa_records(ur_frame* f, void* own_record, const void* all_records)
+{
+    if (!f || !own_record || !all_records) { ur::set_error("ur_frame_set_taa_records: null argument"); return UR_EINVAL; }
+    f->TaaRecord = own_record;
+    f->TaaRecords = all_records;
+    return UR_OK;
+}
+
 int ur_frame_finish_post(ur_frame* f)
 {
     if (!f) { ur::set_error("ur_frame_finish_post: null argument"); return UR_EINVAL; }
@@ -845,6 +968,7 @@ int ur_frame_finish_post(ur_frame* f)
     FHotPathResources& R = f->Res;
     if (!equal_band(f, R.Height, R.Row0, R.Rows)) { ur::set_error("ur_frame_finish_post: the band is not rank's equal band (world_size | height)"); return UR_EINVAL; }
     R.PostRecords = f->PostRecords;
+    R.TaaRecords = f->TaaRecords;
     return f->Renderer.FinishPost(f->Cmd, R);
 }
 

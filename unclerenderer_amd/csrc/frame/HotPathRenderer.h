@@ -37,6 +37,9 @@ struct FHotPathResources
     std::vector<ur_half4*> TaaHistory; // TaaHistory_<i>: max(1, FrameCount) Width x Height images in Lighting's format (CreateTaaResources, :2740-2785)
     void* PostRecord = nullptr;        // post exchange (new): this band's record (ur_pack_post_record) ...
     const void* PostRecords = nullptr; // ... and every rank's, gathered in rank order (may contain PostRecord)
+    void* TaaRecord = nullptr;         // TemporalAA on a band (new): this band's TAA record (ur_pack_taa_record) ...
+    const void* TaaRecords = nullptr;  // ... and every rank's, gathered in rank order (may contain TaaRecord)
+    ur_half4* TaaHaloRows = nullptr;   // ... and the resolved rows above / below the band (2 x Width texels; only with CAS), CAS's HDR halo rows
     // full-frame depth for the replicated HZB build, and the HZB itself
     float* DepthFull = nullptr;
     float* HZB = nullptr;
@@ -67,6 +70,9 @@ struct FHotPathResources
     std::vector<uint32> TaaHistoryStates; // one per image, RG_STATE_UNORDERED_ACCESS at creation
     uint32 PostRecordState = RG_STATE_UNORDERED_ACCESS;
     uint32 PostRecordsState = RG_STATE_UNORDERED_ACCESS;
+    uint32 TaaRecordState = RG_STATE_UNORDERED_ACCESS;
+    uint32 TaaRecordsState = RG_STATE_UNORDERED_ACCESS;
+    uint32 TaaHaloRowsState = RG_STATE_UNORDERED_ACCESS;
 };
 
 struct FHotPathFrameConstants
@@ -98,6 +104,7 @@ struct FHotPathOptions
     bool bTaa = false;                // with bTonemap and a history ring: TemporalAA pass after Sky (bEnableTAA); Tonemap reads its output
     bool bFuseTaaTonemap = false;     // with bTaa: TemporalAA + Tonemap in one launch (ur_temporal_aa_tonemap), TemporalAA pass culled
     bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
+    bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;
@@ -113,8 +120,9 @@ public:
     // Builds a fresh graph, adds the passes in the reference's order and executes it. Returns UR_OK or the first
     // error a pass reported. bHZBReady carries over between frames exactly like FDeferredRenderer::bHZBReady.
     int RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants, const FHotPathOptions& Options);
-    // The second half of a frame rendered with bPostExchange (and AutoExposure or CAS): AutoExposure, Tonemap and CAS on the band,
-    // from the gathered records (Res.PostRecords), with the frame's constants and options. UR_EINVAL if nothing is pending.
+    // The second half of a frame rendered with bPostExchange (and AutoExposure, CAS or bTaaBand): [TemporalAA,] AutoExposure, Tonemap and
+    // CAS on the band, from the gathered records (Res.PostRecords, Res.TaaRecords), with the frame's constants and options. UR_EINVAL if
+    // nothing is pending. A TemporalAA frame's history bookkeeping (EndTaaHistory) happens here, when the image has been written.
     int FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res);
     bool IsPostPending() const { return bPostPending; }
 

@@ -18,6 +18,13 @@
 // texel, after its rounding to fp16, also goes through tonemap_pixel (csrc/post_common.h, the one ur_tonemap runs) while it is
 // in registers, so the history image is not read back by a Tonemap launch: 8 + 8 read, 8 + 4 written = 28 B/pixel in one
 // launch instead of 24 + 12 in two. The history bytes are ur_temporal_aa's and the LDR bytes ur_tonemap's of that image.
+//
+// Row bands (the TAA record and ur_temporal_aa_halo / ur_temporal_aa_tonemap_halo, include/ur_hotpath.h): taa_band_kernel runs the
+// same strip body (taa_strip below) with only the band in memory. Where a row is comes from a rows policy: FrameRows - the full
+// frame, one base pointer (taa_strip_kernel); BandRows - the band, the current row above and below it, the second row out on either
+// side, and the neighbours' history rows, each its own pointer. A strip's rows are uniform per wave, so the choice of the base
+// pointer is scalar. The same launch resolves the rows row0 - 1 and row0 + rows (two more one-row strips at the end of the grid):
+// the HDR halo rows of the CAS launch behind it, the very texels the neighbour rank writes into its own history image.
 
 #include "ur_internal.h"
 #include "ur_device.h"
@@ -92,37 +99,73 @@ struct TonemapPost {
     }
 };
 
-template <class Post>
-__global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
+// Where the rows of a strip are. cur(y): y is a frame row already clamped to the frame (the taps' clamp, TemporalAA.hlsl:38);
+// hist(r) / out(r) / in_band(r): r is a row relative to the band's first (an output row of the strip).
+// FrameRows: current = the full frame, history / output = band-local images of rows [row0, row0 + rows).
+struct FrameRows {
+    const u32x2_t* current;
+    const u32x2_t* history;
+    u32x2_t* output;
+    uint32_t W;
+    __device__ __forceinline__ const u32x2_t* cur(uint32_t y) const { return current + (size_t)y * W; }
+    __device__ __forceinline__ const u32x2_t* hist(int r) const { return history + (size_t)(uint32_t)r * W; }
+    __device__ __forceinline__ u32x2_t* out(int r) const { return output + (size_t)(uint32_t)r * W; }
+    __device__ __forceinline__ bool in_band(int) const { return true; }
+};
+
+// BandRows: only the band's rows of the three images are in memory; the rows around it are the neighbours' record rows.
+// Current rows: above2 | above | band | below | below2 = frame rows max(row0 - 2, 0), row0 - 1, the band, row0 + rows, min(row0 + rows
+// + 1, H - 1). [ylo, yhi] are the outermost rows that have a pointer: a row further out only feeds output rows that are not stored, and
+// reads the outermost row instead (never a null pointer). History / output rows outside the band are the resolved rows' own.
+struct BandRows {
+    const u32x2_t *band, *above, *below, *above2, *below2;
+    const u32x2_t *history, *hist_above, *hist_below;
+    u32x2_t *output, *res_above, *res_below;
+    uint32_t W, row0, rows, ylo, yhi;
+    __device__ __forceinline__ const u32x2_t* cur(uint32_t y) const
+    {
+        y = min(max(y, ylo), yhi);
+        return y < row0 ? (y + 1u == row0 ? above : above2) : y - row0 < rows ? band + (size_t)(y - row0) * W : (y - row0 == rows ? below : below2);
+    }
+    __device__ __forceinline__ const u32x2_t* hist(int r) const
+    {
+        return r < 0 ? hist_above : (uint32_t)r < rows ? history + (size_t)(uint32_t)r * W : hist_below;
+    }
+    __device__ __forceinline__ u32x2_t* out(int r) const
+    {
+        return r < 0 ? res_above : (uint32_t)r < rows ? output + (size_t)(uint32_t)r * W : res_below;
+    }
+    __device__ __forceinline__ bool in_band(int r) const { return r >= 0 && (uint32_t)r < rows; }
+};
+
+// One strip: output rows [r0, r0 + nrows) (relative to the band's first row row0; nrows <= kStripRows) of the wave's 64 columns. The one body of every TemporalAA
+// launch: the same texels give the same bits wherever the rows come from. Post::texel runs for rows of the band only (its index is
+// band-local); a resolved row outside the band is stored and nothing else.
+template <class Post, class Rows>
+__device__ __forceinline__ void taa_strip(const Rows& R, const Post& post, uint32_t W, uint32_t H, float weight, uint32_t use_history, uint32_t row0,
+                                          int r0, uint32_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // the four waves of a workgroup sit side by side: a workgroup touches 2 KB of contiguous bytes per row and buffer
     // (with the waves stacked vertically - 512-byte segments - the kernel ran at 4.5 TB/s, as did the LDS-tiled one with
     // its 64x8 tiles; a plain streaming kernel of the same byte mix reaches 5.6: tools/microbench/stream_ceiling.hip)
     const uint32_t x0 = (blockIdx.x * 4u + wave) * 64u;
-    const uint32_t r0 = blockIdx.y * (uint32_t)kStripRows; // first row of the strip inside the band
-    if (x0 >= p.W) return;                                 // uniform per wave (no barrier in this kernel)
-    const uint32_t maxx = p.W - 1u, maxy = p.H - 1u;
+    if (x0 >= W) return;                                 // uniform per wave (no barrier in this kernel)
+    const uint32_t maxx = W - 1u, maxy = H - 1u;
     const uint32_t px = x0 + lane, cx = min(px, maxx);                    // lanes right of the frame re-read the last column
     // halo texels: ONE load for the whole strip - lane k holds the texel left of the strip in row k, lane 32 + k the one
     // right of it (k < kStripRows + 2); row k's pair is broadcast from there when the row is reduced
     const uint32_t hx = lane < 32u ? (x0 == 0u ? 0u : x0 - 1u) : min(x0 + 64u, maxx); // clamped to the frame (:38)
-    const u32x2_t* cur = reinterpret_cast<const u32x2_t*>(p.current);
-    const u32x2_t* his = reinterpret_cast<const u32x2_t*>(p.history);
-    u32x2_t* out = reinterpret_cast<u32x2_t*>(p.output);
 
-    auto frame_row = [&](int band_row) -> size_t { // band row (may be -1 or rows) -> clamped frame row offset in texels
-        const int fr = (int)p.row0 + band_row;
-        return (size_t)(uint32_t)min(max(fr, 0), (int)maxy) * p.W;
-    };
+    auto frame_row = [&](int band_row) -> uint32_t { return (uint32_t)min(max((int)row0 + band_row, 0), (int)maxy); }; // band row (may be outside the band) -> clamped frame row
     const float finalExposure = post.prepare();
-    if (p.use_history == 0) { // UseHistory == 0: the resolve is a copy of the current frame (TemporalAA.hlsl:23-27)
-        for (uint32_t k = 0; k < min((uint32_t)kStripRows, p.rows - r0); ++k)
+    if (use_history == 0) { // UseHistory == 0: the resolve is a copy of the current frame (TemporalAA.hlsl:23-27)
+        for (uint32_t k = 0; k < nrows; ++k)
             if (px <= maxx) {
-                const size_t i = (size_t)(r0 + k) * p.W + px;
-                const u32x2_t v = cur[frame_row((int)(r0 + k)) + px];
-                out[i] = v;
-                post.texel(finalExposure, i, v.x, v.y);
+                const int r = r0 + (int)k;
+                const u32x2_t v = R.cur(frame_row(r))[px];
+                R.out(r)[px] = v;
+                if (R.in_band(r)) post.texel(finalExposure, (size_t)(uint32_t)r * W + px, v.x, v.y);
             }
         return;
     }
@@ -131,12 +174,12 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
     // stores. (Walking a taller strip group by group made every wave a chain of five dependent round trips: 8 us of
     // fixed cost per launch at any frame size.) Later workgroups of the grid load while earlier ones compute and store.
     u32x2_t c[kStripRows + 2], hist[kStripRows];
-    const u32x2_t halo = cur[frame_row((int)r0 - 1 + (int)min(lane & 31u, (uint32_t)kStripRows + 1u)) + hx];
+    const u32x2_t halo = R.cur(frame_row(r0 - 1 + (int)min(lane & 31u, (uint32_t)kStripRows + 1u)))[hx];
 #pragma unroll
-    for (int k = 0; k < kStripRows + 2; ++k) c[k] = cur[frame_row((int)r0 + k - 1) + cx];
+    for (int k = 0; k < kStripRows + 2; ++k) c[k] = R.cur(frame_row(r0 + k - 1))[cx];
+    const int rlast = r0 + (int)nrows - 1;
 #pragma unroll
-    for (int k = 0; k < kStripRows; ++k) hist[k] = __builtin_nontemporal_load(his + (size_t)min(r0 + (uint32_t)k, p.rows - 1u) * p.W + cx); // read once
-    const uint32_t nrows = min((uint32_t)kStripRows, p.rows - r0);
+    for (int k = 0; k < kStripRows; ++k) hist[k] = __builtin_nontemporal_load(R.hist(min(r0 + k, rlast)) + cx); // read once
     auto reduce_row = [&](int k) {
         return row_minmax(c[k], __builtin_amdgcn_readlane(halo.x, k), __builtin_amdgcn_readlane(halo.y, k),
                           __builtin_amdgcn_readlane(halo.x, 32 + k), __builtin_amdgcn_readlane(halo.y, 32 + k));
@@ -144,7 +187,7 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
     RowMinMax mPrev = reduce_row(0), mCur = reduce_row(1);
 #pragma unroll
     for (int k = 0; k < kStripRows; ++k) {
-        const uint32_t r = r0 + (uint32_t)k;
+        const int r = r0 + k;
         const RowMinMax mNext = reduce_row(k + 2);
         if ((uint32_t)k < nrows && px <= maxx) {
             const half2_t mn0 = pk_min(pk_min(mPrev.mn0, mNext.mn0), mCur.mn0), mn1 = pk_min(pk_min(mPrev.mn1, mNext.mn1), mCur.mn1);
@@ -157,17 +200,75 @@ __global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const float hc = fminf(fmaxf(hv[ch], mn[ch]), mx[ch]); // clamp(History, Min, Max)
-                b[ch] = cf[ch] + p.weight * (hc - cf[ch]);            // lerp(Current, History, w)
+                b[ch] = cf[ch] + weight * (hc - cf[ch]);              // lerp(Current, History, w)
             }
             half2_t o0, o1;
             o0.x = (_Float16)b[0]; o0.y = (_Float16)b[1]; o1.x = (_Float16)b[2]; o1.y = c1.y; // alpha of the current texel
-            const size_t i = (size_t)r * p.W + px;
-            if constexpr (Post::kHistoryOnce) ur::store_once_b64(out + i, ur::once_u32x2_t{as_u(o0), as_u(o1)});
-            else out[i] = u32x2_t{as_u(o0), as_u(o1)};
-            post.texel(finalExposure, i, as_u(o0), as_u(o1)); // the row is tonemapped right before its store: no row stays live for it
+            u32x2_t* o = R.out(r) + px;
+            if constexpr (Post::kHistoryOnce) ur::store_once_b64(o, ur::once_u32x2_t{as_u(o0), as_u(o1)});
+            else *o = u32x2_t{as_u(o0), as_u(o1)};
+            // the row is tonemapped right before its store: no row stays live for it
+            if (R.in_band(r)) post.texel(finalExposure, (size_t)(uint32_t)r * W + px, as_u(o0), as_u(o1));
         }
         mPrev = mCur; mCur = mNext;
     }
+}
+
+template <class Post>
+__global__ __launch_bounds__(256) void taa_strip_kernel(TaaParams p, Post post)
+{
+    const uint32_t r0 = blockIdx.y * (uint32_t)kStripRows; // first row of the strip inside the band
+    const FrameRows R{reinterpret_cast<const u32x2_t*>(p.current), reinterpret_cast<const u32x2_t*>(p.history), reinterpret_cast<u32x2_t*>(p.output), p.W};
+    taa_strip(R, post, p.W, p.H, p.weight, p.use_history, p.row0, (int)r0, min((uint32_t)kStripRows, p.rows - r0));
+}
+
+struct TaaBandParams {
+    BandRows R;
+    uint32_t H;
+    float weight; // saturate(HistoryWeight)
+    uint32_t use_history;
+    uint32_t strips; // strips of the band; behind them in the grid: the resolved row above (if any), then the one below (if any)
+};
+
+// The band alone (ur_temporal_aa_halo / ur_temporal_aa_tonemap_halo): blockIdx.y < strips - a strip of the band, whose outer rows come
+// from the rows around the band; then one one-row strip per resolved row.
+template <class Post>
+__global__ __launch_bounds__(256) void taa_band_kernel(TaaBandParams p, Post post)
+{
+    const uint32_t s = blockIdx.y; // uniform: the choice of a row's base pointer in BandRows is scalar
+    int r0; // relative to the band's first row
+    uint32_t nrows;
+    if (s < p.strips) {
+        r0 = (int)(s * (uint32_t)kStripRows);
+        nrows = min((uint32_t)kStripRows, p.R.rows - s * (uint32_t)kStripRows);
+    } else {
+        const bool above = s == p.strips && p.R.res_above != nullptr;
+        r0 = above ? -1 : (int)p.R.rows;
+        nrows = 1u;
+    }
+    taa_strip(p.R, post, p.R.W, p.H, p.weight, p.use_history, p.R.row0, r0, nrows);
+}
+
+// ---- the TAA record of a row band (include/ur_hotpath.h, ur_taa_record_bytes) -----------------------------------------------
+// half4 slots: [0, W) the band's second current row, [W, 2W) its second-last, [2W, 3W) / [3W, 4W) the first / last row of the history
+// image the frame reads (zeros without history).
+struct TaaRecordParams {
+    const u32x2_t* band;    // current rows [row0, row0 + rows)
+    const u32x2_t* history; // the same rows of the history image read; null without history
+    u32x2_t* record;
+    uint32_t W, rows;
+};
+
+__global__ __launch_bounds__(256) void taa_record_kernel(TaaRecordParams p)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x, W = p.W;
+    if (j >= 4u * W) return;
+    const uint32_t part = j / W, x = j - part * W; // uniform per wave except across a part's edge
+    const uint32_t second = min(1u, p.rows - 1u), second_last = p.rows >= 2u ? p.rows - 2u : 0u;
+    u32x2_t v = {0u, 0u};
+    if (part < 2u) v = p.band[(size_t)(part == 0u ? second : second_last) * W + x];
+    else if (p.history != nullptr) v = p.history[(size_t)(part == 2u ? 0u : p.rows - 1u) * W + x];
+    p.record[j] = v;
 }
 
 } // namespace
@@ -220,6 +321,130 @@ extern "C" int ur_temporal_aa_tonemap(ur_ctx* ctx, const ur_tonemap_constants* t
     const dim3 grid((w + 255u) / 256u, (rows + kStripRows - 1u) / kStripRows);
     if (ctx->opt.taa_tonemap_history_store == 0) hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<true>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<true>{tm});
     else hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<false>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<false>{tm});
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+// ---- row bands: the TAA record and the halo forms ---------------------------------------------------------------------------
+
+static bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+extern "C" uint64_t ur_taa_record_bytes(uint32_t w) { return (uint64_t)4u * w * 8u; }
+
+extern "C" int ur_pack_taa_record(ur_ctx* ctx, const ur_half4* hdr_band, const ur_half4* history_read_band, uint32_t use_history, uint32_t w, uint32_t h,
+                                  uint32_t row0, uint32_t rows, void* record)
+{
+    if (!ctx || !hdr_band || !record || (use_history && !history_read_band)) { ur::set_error("ur_pack_taa_record: null argument"); return UR_EINVAL; }
+    if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("ur_pack_taa_record: empty or out-of-frame band"); return UR_EINVAL; }
+    if (rows < 2u && rows != h) { ur::set_error("ur_pack_taa_record: a band that is not the whole frame needs at least 2 rows"); return UR_EUNSUPPORTED; }
+    const size_t band_bytes = (size_t)w * rows * 8u;
+    if (overlaps(hdr_band, band_bytes, record, ur_taa_record_bytes(w)) || (use_history && overlaps(history_read_band, band_bytes, record, ur_taa_record_bytes(w)))) {
+        ur::set_error("ur_pack_taa_record: the record overlaps a band");
+        return UR_EINVAL;
+    }
+    const TaaRecordParams p{reinterpret_cast<const u32x2_t*>(hdr_band), use_history ? reinterpret_cast<const u32x2_t*>(history_read_band) : nullptr,
+                            static_cast<u32x2_t*>(record), w, rows};
+    hipLaunchKernelGGL(taa_record_kernel, dim3((uint32_t)(((uint64_t)4u * w + 255u) / 256u)), dim3(256), 0, ctx->stream, p);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+// shared checks of the two halo forms; fills the launch parameters and the grid's row count
+static int fill_band_params(const char* who, TaaBandParams& q, uint32_t& grid_y, ur_ctx* ctx, const ur_half4* current_band, const ur_half4* cur_above,
+                            const ur_half4* cur_below, const ur_half4* history_band, ur_half4* output_band, const ur_half4* above2, const ur_half4* hist_above,
+                            const ur_half4* below2, const ur_half4* hist_below, ur_half4* resolved_above, ur_half4* resolved_below, float history_weight,
+                            uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    TaaParams p{};
+    const int rc = fill_params(who, p, ctx, current_band, history_band, output_band, history_weight, use_history, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    if (rows == 0) { ur::set_error("%s: empty band", who); return UR_EINVAL; }
+    const bool top = row0 == 0, bottom = row0 + rows == h;
+    if ((!top && !cur_above) || (!bottom && !cur_below)) {
+        ur::set_error("%s: cur_above may be null only when row0 == 0, cur_below only when row0 + rows == h", who);
+        return UR_EINVAL;
+    }
+    if ((top && (cur_above || above2 || hist_above || resolved_above)) || (bottom && (cur_below || below2 || hist_below || resolved_below))) {
+        ur::set_error("%s: there is no row beyond the frame's edge: the pointers of that side must be null", who);
+        return UR_EINVAL;
+    }
+    // a resolved row needs the second current row out and, with history, the neighbour's history row; they come together or not at all
+    if ((resolved_above != nullptr) != (above2 != nullptr) || (resolved_below != nullptr) != (below2 != nullptr) ||
+        (hist_above && !resolved_above) || (hist_below && !resolved_below) ||
+        (use_history && ((resolved_above && !hist_above) || (resolved_below && !hist_below)))) {
+        ur::set_error("%s: resolved_above goes with above2 (and hist_above when use_history), resolved_below with below2 (and hist_below)", who);
+        return UR_EINVAL;
+    }
+    const size_t band_bytes = (size_t)w * rows * 8u, row_bytes = (size_t)w * 8u;
+    const void* ins[] = {cur_above, cur_below, above2, below2, hist_above, hist_below};
+    void* outs[] = {resolved_above, resolved_below};
+    for (void* o : outs) {
+        if (!o) continue;
+        bool bad = overlaps(o, row_bytes, current_band, band_bytes) || overlaps(o, row_bytes, output_band, band_bytes) ||
+                   (use_history && overlaps(o, row_bytes, history_band, band_bytes));
+        for (const void* i : ins) bad = bad || (i && overlaps(o, row_bytes, i, row_bytes));
+        if (bad) { ur::set_error("%s: a resolved row overlaps another buffer", who); return UR_EINVAL; }
+    }
+    if (resolved_above && resolved_below && overlaps(resolved_above, row_bytes, resolved_below, row_bytes)) { ur::set_error("%s: the resolved rows overlap", who); return UR_EINVAL; }
+    bool bad = overlaps(current_band, band_bytes, output_band, band_bytes);
+    for (const void* i : ins) bad = bad || (i && overlaps(i, row_bytes, output_band, band_bytes));
+    if (bad) { ur::set_error("%s: the output band overlaps a current or neighbour row", who); return UR_EINVAL; }
+    const uint32_t strips = (rows + (uint32_t)kStripRows - 1u) / (uint32_t)kStripRows;
+    grid_y = strips + (resolved_above ? 1u : 0u) + (resolved_below ? 1u : 0u);
+    if (grid_y > 65535u) { ur::set_error("%s: band too tall", who); return UR_EUNSUPPORTED; }
+    auto in = [](const ur_half4* x) { return reinterpret_cast<const u32x2_t*>(x); };
+    BandRows& R = q.R;
+    R.band = in(current_band); R.above = in(cur_above); R.below = in(cur_below); R.above2 = in(above2); R.below2 = in(below2);
+    R.history = in(history_band); R.hist_above = in(hist_above); R.hist_below = in(hist_below);
+    R.output = reinterpret_cast<u32x2_t*>(output_band); R.res_above = reinterpret_cast<u32x2_t*>(resolved_above); R.res_below = reinterpret_cast<u32x2_t*>(resolved_below);
+    R.W = w; R.row0 = row0; R.rows = rows;
+    R.ylo = top ? 0u : (above2 ? (row0 >= 2u ? row0 - 2u : 0u) : row0 - 1u);
+    R.yhi = bottom ? h - 1u : (below2 ? min(row0 + rows + 1u, h - 1u) : row0 + rows);
+    q.H = h; q.weight = p.weight; q.use_history = p.use_history; q.strips = strips;
+    return UR_OK;
+}
+
+// history_band may BE output_band, as for ur_temporal_aa; the rows around the band and the resolved rows are buffers of their own.
+extern "C" int ur_temporal_aa_halo(ur_ctx* ctx, const ur_half4* current_band, const ur_half4* cur_above, const ur_half4* cur_below, const ur_half4* history_band,
+                                   ur_half4* output_band, const ur_half4* above2, const ur_half4* hist_above, const ur_half4* below2, const ur_half4* hist_below,
+                                   ur_half4* resolved_above, ur_half4* resolved_below, float history_weight, uint32_t use_history, uint32_t w, uint32_t h,
+                                   uint32_t row0, uint32_t rows)
+{
+    TaaBandParams q{};
+    uint32_t grid_y = 0;
+    const int rc = fill_band_params("ur_temporal_aa_halo", q, grid_y, ctx, current_band, cur_above, cur_below, history_band, output_band, above2, hist_above, below2,
+                                    hist_below, resolved_above, resolved_below, history_weight, use_history, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    hipLaunchKernelGGL(taa_band_kernel<NoPost>, dim3((w + 255u) / 256u, grid_y), dim3(256), 0, ctx->stream, q, NoPost{});
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+// The history store keeps its write-once hint under either value of UR_OPT_TAA_TONEMAP_HISTORY_STORE: one form of the band launch.
+extern "C" int ur_temporal_aa_tonemap_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, const ur_half4* current_band, const ur_half4* cur_above,
+                                           const ur_half4* cur_below, const ur_half4* history_band, ur_half4* history_out_band, const float* exposure_ev,
+                                           uint32_t* ldr_out_band, const ur_half4* above2, const ur_half4* hist_above, const ur_half4* below2,
+                                           const ur_half4* hist_below, ur_half4* resolved_above, ur_half4* resolved_below, float history_weight,
+                                           uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    if (!tonemap || !ldr_out_band) { ur::set_error("ur_temporal_aa_tonemap_halo: null argument"); return UR_EINVAL; }
+    TaaBandParams q{};
+    uint32_t grid_y = 0;
+    const int rc = fill_band_params("ur_temporal_aa_tonemap_halo", q, grid_y, ctx, current_band, cur_above, cur_below, history_band, history_out_band, above2,
+                                    hist_above, below2, hist_below, resolved_above, resolved_below, history_weight, use_history, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    ur_post::TonemapParams tm{}; // as ur_tonemap fills it
+    tm.exposure_ev = exposure_ev;
+    tm.out = ldr_out_band;
+    tm.enable_tonemap = tonemap->EnableTonemap;
+    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
+    tm.exposure = tonemap->Exposure;
+    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
+    hipLaunchKernelGGL(taa_band_kernel<TonemapPost<true>>, dim3((w + 255u) / 256u, grid_y), dim3(256), 0, ctx->stream, q, TonemapPost<true>{tm});
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }

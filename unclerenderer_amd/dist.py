@@ -12,6 +12,10 @@ the GPU box, "gloo" in the CPU tests). The reference is single-GPU; this is new 
     first and last HDR rows and the AutoExposure tap texels in its rows, hotpath.post_record_bytes(W) bytes - and ONE all-gather
     of the records (allgather_post_records) lets every rank compute the single-GPU EV and tonemap and sharpen its own band
     (Frame.finish_post); the RGBA8 bands are then gathered with allgather_rows: render -> records -> finish -> RGBA8.
+  * TemporalAA on the bands (UR_FRAME_TAA_BAND): a second fixed-size record per rank beside the post record - the band's second and
+    second-last current rows and the first and last row of the history image it reads, hotpath.taa_record_bytes(W) = 32 W bytes -
+    gathered the same way (allgather_taa_records); finish_post then resolves the band and, for CAS, the row on either side of it.
+    Every rank must render the same flags every frame: the histories stay in step on that promise alone.
   * BuildHZB: replicated (every rank builds the full chain from the full depth) — no exchange; or band-sharded
     (allgather_hzb_slices): a rank builds mips 0..4 for the 128x32 source pieces its rows own, the slices (5 contiguous runs of
     floats per rank) are exchanged peer to peer straight into place, and every rank runs the single-workgroup tail behind it.
@@ -130,6 +134,13 @@ def allgather_post_records(all_records: torch.Tensor, own: torch.Tensor, group=N
     in place). The same collectives as allgather_rows, one record per rank in rank order."""
     return allgather_rows(all_records.view(torch.uint8).view(all_records.shape[0], -1), own.view(torch.uint8).view(1, -1), group=group,
                           async_op=async_op, mode=mode)
+
+
+def allgather_taa_records(all_records: torch.Tensor, own: torch.Tensor, group=None, async_op: bool = False, mode: str = "ring"):
+    """The TAA records of UR_FRAME_TAA_BAND: `all_records` (N, taa_record_bytes(W)) uint8 on every rank, `own` this rank's (may be
+    all_records[rank]). The collective of allgather_post_records on the second buffer; with async_op=True both may be in flight together
+    (wait for both before Frame.finish_post)."""
+    return allgather_post_records(all_records, own, group=group, async_op=async_op, mode=mode)
 
 
 def allgather_visible(visible_idx: torch.Tensor, visible_count: torch.Tensor, group=None) -> tuple[torch.Tensor, int]:

@@ -429,9 +429,17 @@ class Frame:
         _lib.check(self._L.ur_frame_set_post_records(self._f, C.c_void_p(own_record.data_ptr()), C.c_void_p(all_records.data_ptr())),
                    "ur_frame_set_post_records")
 
+    def set_taa_records(self, own_record, all_records):
+        """ur_frame_set_taa_records: where UR_FRAME_TAA_BAND packs this rank's TAA record (own_record, taa_record_bytes(w) bytes) and
+        where finish_post reads every rank's (all_records, rank order; own_record may be a view of its row). Device tensors, kept alive
+        here."""
+        self._taa_records_keep = (own_record, all_records)
+        _lib.check(self._L.ur_frame_set_taa_records(self._f, C.c_void_p(own_record.data_ptr()), C.c_void_p(all_records.data_ptr())),
+                   "ur_frame_set_taa_records")
+
     def finish_post(self):
-        """ur_frame_finish_post: the AutoExposure / Tonemap / CAS passes of a frame rendered with UR_FRAME_POST_EXCHANGE, once the records
-        are gathered."""
+        """ur_frame_finish_post: the (TemporalAA /) AutoExposure / Tonemap / CAS passes of a frame rendered with UR_FRAME_POST_EXCHANGE, once
+        the records are gathered."""
         _lib.check(self._L.ur_frame_finish_post(self._f), "ur_frame_finish_post")
 
     def report(self):
@@ -567,6 +575,46 @@ HotPath.pack_post_record = _pack_post_record
 HotPath.auto_exposure_records = _auto_exposure_records
 HotPath.tonemap_cas_halo = _tonemap_cas_halo
 HotPath.cas_halo = _cas_halo
+
+
+# ---- TemporalAA on row bands (include/ur_hotpath.h, ur_taa_record_bytes) ----
+
+def taa_record_bytes(w: int) -> int:
+    """Bytes of one rank's TAA record at width w: its second and second-last current rows and the first and last row of the history
+    image it reads, 8 B a texel."""
+    return int(_lib.load().ur_taa_record_bytes(w))
+
+
+def _pack_taa_record(self, hdr_band, history_read_band, use_history, record, w, h, row0, rows):
+    """This band's TAA record into `record` (taa_record_bytes(w) bytes); history_read_band may be None iff not use_history."""
+    _lib.check(self._L.ur_pack_taa_record(self._ctx, _ptr(hdr_band), _ptr(history_read_band), int(use_history), w, h, row0, rows, _ptr(record)),
+               "ur_pack_taa_record")
+
+
+def _temporal_aa_halo(self, current_band, cur_above, cur_below, history_band, output_band, history_weight, use_history, w, h, row0, rows,
+                      above2=None, hist_above=None, below2=None, hist_below=None, resolved_above=None, resolved_below=None):
+    """temporal_aa of rows [row0,row0+rows) from the band and the current rows above / below it (None at the frame's edges); with
+    resolved_above / resolved_below (and above2 / below2, hist_above / hist_below) the launch also resolves the rows around the band."""
+    _lib.check(self._L.ur_temporal_aa_halo(self._ctx, _ptr(current_band), _ptr(cur_above), _ptr(cur_below), _ptr(history_band), _ptr(output_band),
+                                           _ptr(above2), _ptr(hist_above), _ptr(below2), _ptr(hist_below), _ptr(resolved_above), _ptr(resolved_below),
+                                           history_weight, int(use_history), w, h, row0, rows), "ur_temporal_aa_halo")
+
+
+def _temporal_aa_tonemap_halo(self, current_band, cur_above, cur_below, history_band, history_out_band, ldr_out_band, history_weight, use_history,
+                              w, h, row0, rows, above2=None, hist_above=None, below2=None, hist_below=None, resolved_above=None, resolved_below=None,
+                              exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None):
+    """temporal_aa_halo() followed by tonemap() of its output band, in one launch."""
+    k = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    _lib.check(self._L.ur_temporal_aa_tonemap_halo(self._ctx, C.byref(k), _ptr(current_band), _ptr(cur_above), _ptr(cur_below), _ptr(history_band),
+                                                   _ptr(history_out_band), _ptr(exposure_ev), _ptr(ldr_out_band), _ptr(above2), _ptr(hist_above),
+                                                   _ptr(below2), _ptr(hist_below), _ptr(resolved_above), _ptr(resolved_below), history_weight,
+                                                   int(use_history), w, h, row0, rows), "ur_temporal_aa_tonemap_halo")
+
+
+HotPath.taa_record_bytes = staticmethod(taa_record_bytes)
+HotPath.pack_taa_record = _pack_taa_record
+HotPath.temporal_aa_halo = _temporal_aa_halo
+HotPath.temporal_aa_tonemap_halo = _temporal_aa_tonemap_halo
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

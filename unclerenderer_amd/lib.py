@@ -170,6 +170,7 @@ UR_FRAME_POST_EXCHANGE = 0x200000
 UR_FRAME_CULL_VIEWS = 0x400000
 UR_FRAME_TAA = 0x800000
 UR_FRAME_FUSE_TAA_TONEMAP = 0x1000000
+UR_FRAME_TAA_BAND = 0x2000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -225,6 +226,11 @@ SIGNATURES = {
     "ur_auto_exposure_records": (C.c_int, [_VP, C.POINTER(AutoExposureConstants), _VP, _U32, _U32, _U32, _VP, _VP]),
     "ur_tonemap_cas_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_cas_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), C.POINTER(CasConstants), _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _U32]),
+    "ur_taa_record_bytes": (C.c_uint64, [_U32]),
+    "ur_pack_taa_record": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _U32, _VP]),
+    "ur_temporal_aa_halo": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _U32, _U32, _U32, _U32, _U32]),
+    "ur_temporal_aa_tonemap_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F,
+                                              _U32, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes_ex": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.c_int]),
@@ -256,6 +262,7 @@ SIGNATURES = {
     "ur_frame_set_draw_ranges": (C.c_int, [_VP, C.POINTER(DrawRanges)]),
     "ur_frame_set_cull_views": (C.c_int, [_VP, C.POINTER(CullView), _U32]),
     "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
+    "ur_frame_set_taa_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
