@@ -92,6 +92,16 @@ typedef struct ur_frame_resources {
  * finished, like any other frame, invalidates the ring. The ranks' histories stay in step only if ALL RANKS RENDER THE SAME FLAGS every
  * frame: a rank packs history rows exactly when its own ring is valid, and its neighbours read them exactly when theirs is. */
 #define UR_FRAME_TAA_BAND 0x2000000u
+/* "GpuDebugPrint", the reference's last pass (DeferredRenderer.cpp:1575-1598): the cull's two counters drawn onto the LDR band as
+ * "FRUSTUM n" / "OCCLUDE n". Needs UR_FRAME_TONEMAP, a tonemap_band, cull_stats and ur_frame_set_debug_print's buffer and font (else
+ * UR_EINVAL). The "GPU Culling" pass then first zeroes the buffer's count and cull_stats (PrepareGpuDebugPrint, on its own stream,
+ * also when the cull itself does not run) and culls with DebugPrintEnabled (dword 45) = 1; "GpuDebugPrint" runs behind CAS (behind
+ * Tonemap when there is no CAS pass): ur_debug_print_stats, then ur_debug_print_draw in place on tonemap_band, rows [row0,row0+rows).
+ * With an active post exchange the pass runs in ur_frame_finish_post, behind CAS: cull_stats then hold this rank's counts, and the
+ * caller sums them over the ranks (dist.allreduce_cull_stats) beside the record gathers so that every band prints the frame's totals.
+ * Text the caller prints into the buffer between the cull and the pass (ur_debug_print_text, or its own kernels by the slot rule) comes
+ * ahead of the two stats lines' entries in the buffer: it is blended first and lies beneath them where they overlap. Without the flag nothing of this happens: the frame is what it is today. */
+#define UR_FRAME_DEBUG_PRINT 0x4000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -176,6 +186,18 @@ int ur_frame_set_draw_ranges(ur_frame* f, const ur_draw_ranges* draws);
  * Without the flag, or when the cull pass does not run, the views' buffers are left alone. UR_EINVAL for a null frame, count >
  * UR_MAX_CULL_VIEWS, views == NULL with count != 0, and the view errors of ur_cull_indirect_args_views that need no command count. */
 int ur_frame_set_cull_views(ur_frame* f, const ur_cull_view* views, uint32_t count);
+/* The text buffer (ur_debug_print_buffer_bytes(), device) and the font (device glyph table indexed by code, device R8 atlas; e.g.
+ * ur_host_debug_font's, uploaded) of the frames rendered with UR_FRAME_DEBUG_PRINT. The pointers must stay valid while frames use them.
+ * NULL clears. UR_EINVAL for a null frame, a null member, glyph_count == 0 or a zero-sized atlas. */
+typedef struct ur_frame_debug_print {
+    void* buffer;
+    const ur_debug_glyph* glyphs;
+    uint32_t glyph_count;
+    const uint8_t* atlas;
+    uint32_t atlas_w, atlas_h;
+    uint32_t first_char, char_count; /* DebugPrintConstants.FirstChar / CharCount [32, 96] */
+} ur_frame_debug_print;
+int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

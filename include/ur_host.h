@@ -58,6 +58,14 @@ void ur_host_taa_jitter(uint32_t sample_index, float out[2]);
  * (elements 8 and 9); nothing when width or height is not positive. */
 void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width, float height);
 
+/* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
+ * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own
+ * design for codes 32..95 in 8 x 8 cells of a 64 x 64 R8 atlas; glyph quad = the cell, Size (8, 8), Offset (0, -7), Advance 8
+ * (kDebugPrintDefaultAdvance). info_out = {atlas_w, atlas_h, first_char, char_count} = {64, 64, 32, 64}; the glyph table is indexed by
+ * code and has first_char + char_count = 96 entries (codes below 32 zero). atlas_out == glyphs_out == NULL: info_out only. UR_EINVAL
+ * for a null info_out, one buffer without the other, atlas_capacity < atlas_w * atlas_h bytes or glyph_capacity < 96 entries. */
+int ur_host_debug_font(uint8_t* atlas_out, uint32_t atlas_capacity, ur_debug_glyph* glyphs_out, uint32_t glyph_capacity, uint32_t info_out[4]);
+
 /* Scene JSON conventions: BuildDirectionFromEulerDegrees (Scene/SceneJsonLoader.cpp:257-269); camera forward from
  * (pitch, yaw) degrees via RotationRollPitchYaw (Core/Application.cpp:896-902); and the light vector the renderer
  * ends up with after the app's asin/atan2 round trip (Core/Application.cpp:236-242,1225-1230), i.e. (d.x,-d.y,d.z). */

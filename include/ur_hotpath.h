@@ -531,6 +531,53 @@ int ur_temporal_aa_tonemap_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap
                                 const ur_half4* hist_below, ur_half4* resolved_above, ur_half4* resolved_below, float history_weight,
                                 uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows);
 
+/* ---- GpuDebugPrint: the reference's GPU-side text buffer, its stats printer and its draw (DeferredRenderer.cpp:1575-1598) --------
+ * Buffer (Shaders/DebugPrintCommon.hlsl): a u32 entry count, then UR_DEBUG_PRINT_MAX_ENTRIES entries {u32 x, y, code, color} of 16
+ * bytes. A printer takes a slot with one atomic add on the count and drops the entry when the slot is >= 4096; the count keeps
+ * growing. Device memory, 4-byte aligned, ur_debug_print_buffer_bytes() long. Any kernel of the caller's may print into it by the
+ * same rule. */
+#define UR_DEBUG_PRINT_MAX_ENTRIES 4096u
+uint64_t ur_debug_print_buffer_bytes(void);
+/* FDebugPrintGlyph (Source/Render/DebugPrintFont.h:11-19 == DebugGlyph of Shaders/GpuDebugPrint.hlsl:11-19), 40 bytes. UVs in
+ * [0, 1] of the atlas, Size / Offset / Advance in pixels. The table is indexed by the character code itself. */
+typedef struct ur_debug_glyph {
+    float UvMin[2];
+    float UvMax[2];
+    float Size[2];
+    float Offset[2];
+    float Advance;
+    float Padding;
+} ur_debug_glyph;
+/* DebugPrintConstants (Shaders/GpuDebugPrint.hlsl:4-9) */
+typedef struct ur_debug_print_constants {
+    float ScreenSize[2];
+    uint32_t FirstChar;
+    uint32_t CharCount;
+} ur_debug_print_constants;
+/* PrepareGpuDebugPrint (Renderer.cpp:474-527): zeroes the count word and, when stats is not null, the cull's two counters. */
+int ur_debug_print_reset(ur_ctx* ctx, void* buffer, uint32_t* stats /*nullable*/);
+/* GpuDebugPrintStats.hlsl, one thread: "FRUSTUM " at (8, 20) and "OCCLUDE " at (8, 36), stats[0] / stats[1] at x = 72 in five
+ * decimal places with leading zeros suppressed, colour 0xffffffff; a value >= 100000 makes the first "digit" exceed 9 (48 + digit),
+ * as in the reference. At most 26 entries. */
+int ur_debug_print_stats(ur_ctx* ctx, const uint32_t* stats, void* buffer);
+/* PrintString for a caller's string (host memory, read during the call): character i at (x + 8 i, y), stopping at `length` or at the
+ * first zero code. color: R in the low byte, A in the high byte. One launch per 256 characters. */
+int ur_debug_print_text(ur_ctx* ctx, void* buffer, uint32_t x, uint32_t y, uint32_t color, const char* text, uint32_t length);
+/* GpuDebugPrint.hlsl + its blend state, composited in place on rows [row0,row0+rows) of a w x h R8G8B8A8_UNORM image (ldr_inout is
+ * band-local). The first min(count, 4096) entries are applied in entry order. An entry whose code is outside
+ * [FirstChar, FirstChar + CharCount) or >= glyph_count, or whose quad is empty, negative or NaN, draws nothing. Per pixel (px, py):
+ *   quad      min = (float)pos + Offset, max = min + Size, in fp32
+ *   coverage  min.x <= px + 0.5 < max.x and min.y <= py + 0.5 < max.y
+ *   uv        UvMin + (centre - min) / Size * (UvMax - UvMin)
+ *   alpha     Color.a * bilinear tap of atlas_r8 (atlas_w x atlas_h R8_UNORM, row-major) at uv * size - 0.5, clamp addressing
+ *   blend     rgb = Color.rgb * alpha + dst.rgb * (1 - alpha), a = alpha, each rounded to 8 bits (nearest) before the next entry
+ * in fp32. A pixel no entry covers is not written; a 64 x 64 tile no entry touches is not read either. ScreenSize must be
+ * ((float)w, (float)h). UR_EINVAL, nothing launched: a null pointer, glyph_count == 0, a zero-sized atlas (or a side above 16384),
+ * row0 + rows > h, a ScreenSize that is not the frame's. */
+int ur_debug_print_draw(ur_ctx* ctx, const ur_debug_print_constants* constants, const ur_debug_glyph* glyphs, uint32_t glyph_count,
+                        const uint8_t* atlas_r8, uint32_t atlas_w, uint32_t atlas_h, const void* buffer, uint32_t* ldr_inout, uint32_t w,
+                        uint32_t h, uint32_t row0, uint32_t rows);
+
 /* ---- multi-GPU: gather the row bands of the HDR frame ------------------------------------------ */
 
 /* comm: an ncclComm_t (RCCL). hdr_full: device, w*h half4 on every rank; rank r has already written

@@ -17,6 +17,11 @@ UR_OPT_TAA_TONEMAP_HISTORY_STORE = 1, the plain history store), over the same ki
 Its batches ALTERNATE between the cases (pair, fused, fused with the plain store, pair, ...), so that a drift of the clocks during the
 run lands on all of them alike; the median over the batches of each case is reported, and the last line of a size gives the fused
 launch against the pair with the pair's own batch-to-batch spread. The strip kernel loads 10 current rows per 8 output rows.
+
+The "debugprint" leg (--legs debugprint): ur_debug_print_draw with the built-in font on rotating cold R8G8B8A8 images, with the two
+stats lines ("FRUSTUM 12345" / "OCCLUDE 67890", 26 entries) and with a full buffer of 4096 entries spread over the frame. The
+launch reads and writes only the 64 x 64 tiles the text touches, so no byte count is given: the claim to check is that the two stats
+lines cost the same at 4K and 8K (a launch, not a pass over the frame). The last line of the leg prints that ratio.
 """
 import argparse
 import json
@@ -68,13 +73,47 @@ def time_alternating(torch, fns, nsets, iters, batches, warm=10):
     return out
 
 
+def debugprint_leg(torch, hp, a, report):
+    from unclerenderer_amd import hostmath
+    from unclerenderer_amd.hotpath import debug_print_buffer, to_device
+    atlas, glyphs, first, count = hostmath.debug_font()
+    d_atlas, d_glyphs = torch.from_numpy(atlas).cuda(), to_device(glyphs)
+    stats_med = {}
+    for name in a.sizes.split(","):
+        w, h = SIZES[name]
+        nsets = max(2, -(-3 * CACHE_BYTES // (w * h * 4)))
+        g = torch.Generator(device="cuda").manual_seed(2)
+        img = [torch.randint(-2 ** 31, 2 ** 31 - 1, (h, w), dtype=torch.int32, device="cuda", generator=g) for _ in range(nsets)]
+        two = debug_print_buffer()
+        hp.debug_print_stats(to_device(np.array([12345, 67890], np.uint32)), two)
+        full = debug_print_buffer()
+        rng = np.random.default_rng(3)
+        for _ in range(4096 // 16):  # 256 strings of 16 characters all over the frame
+            hp.debug_print_text(full, int(rng.integers(0, w - 128)), int(rng.integers(8, h)), bytes(int(c) for c in rng.integers(33, 96, 16)),
+                                int(rng.integers(0, 1 << 32)))
+        torch.cuda.synchronize()
+        assert int(two[0]) == 26 and int(full[0]) == 4096
+
+        def draw(buf):
+            return lambda i: hp.debug_print_draw(buf, d_glyphs, d_atlas, img[i], w, h, first_char=first, char_count=count)
+
+        ts = time_alternating(torch, [draw(two), draw(full)], nsets, a.iters, a.batches)
+        stats_med[name] = report(name, w, h, "debug_draw/2 lines", 0, 0, ts[0], nsets)
+        report(name, w, h, "debug_draw/4096", 0, 0, ts[1], nsets)
+        del img
+        torch.cuda.empty_cache()
+    if "4k" in stats_med and "8k" in stats_med:
+        print(f"debug_draw, two stats lines: 8K / 4K = {stats_med['8k'] / stats_med['4k']:.2f} ({stats_med['4k']:.2f} us -> {stats_med['8k']:.2f} us)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1080p,4k,8k")
     ap.add_argument("--iters", type=int, default=200, help="launches per timed batch")
     ap.add_argument("--batches", type=int, default=7)
     ap.add_argument("--sharpness", type=float, default=0.5)
-    ap.add_argument("--legs", default="post,taa", help="post: Tonemap / CAS / AutoExposure; taa: TemporalAA + Tonemap against the fused launch")
+    ap.add_argument("--legs", default="post,taa", help="post: Tonemap / CAS / AutoExposure; taa: TemporalAA + Tonemap against the fused launch; "
+                                                       "debugprint: the GpuDebugPrint draw")
     ap.add_argument("--json", default="", help="also append one JSON line per measurement to this file")
     a = ap.parse_args()
     import torch
@@ -97,7 +136,7 @@ def main():
         print(f"{name:>5} {label:<18} {px * bpp / 1e6:8.1f} MB  {med:8.2f} us  [{min(t):.2f}, {max(t):.2f}]  {frac} of 8 TB/s"
               f"  (issued {px * issued / 1e6:6.1f} MB: {ifrac})", flush=True)
         return med
-    for name in a.sizes.split(","):
+    for name in a.sizes.split(",") if legs & {"post", "taa"} else []:
         w, h = SIZES[name]
         px = w * h
         set_bytes = px * (8 + 4 + 4 + 4)
@@ -173,6 +212,8 @@ def main():
             del hist, res, res1
         del hdr, ldr, out, fused
         torch.cuda.empty_cache()
+    if "debugprint" in legs:
+        debugprint_leg(torch, hp, a, report)
     if a.json:
         with open(a.json, "a") as f:
             for r in rows_out:

@@ -37,10 +37,12 @@ SOURCES = [
     ("tonemap.hip", EXACT),
     ("taa.hip", EXACT),
     ("post.hip", EXACT),
+    ("debug_print.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),
     ("host_math.cpp", ["-x", "hip"] + EXACT),
+    ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),
     ("frame/HotPathRenderer.cpp", ["-x", "hip"]),
 ]

@@ -57,6 +57,11 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         TaaFrame.Slots = GetTaaSlots(Cmd.GetCurrentFrameIndex(), TaaSlotCount);
     }
 
+    // GpuDebugPrint: the cull's two counters and the text buffer, written by "GPU Culling" (reset, then counted) and read by the last pass
+    const bool bDebugPrint = IsDebugPrintActive(Res, Options);
+    const FRGResourceHandle DebugStatsHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintStats", Res.CullStats, &Res.DebugPrintStatsState, {2, 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
+    const FRGResourceHandle DebugBufferHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintBuffer", Res.DebugPrintBuffer, &Res.DebugPrintState, {static_cast<uint32>(ur_debug_print_buffer_bytes() / 4u), 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
+
     const bool bHZBEnabled = Options.bHZBEnabled && Res.HZB != nullptr && Res.HZBMipCount != 0;
     if (!bHZBEnabled) bHZBReady = false; // :514-517
     const bool bUseHZBOcclusion = bHZBEnabled && bHZBReady; // ConfigureHZBOcclusion, :519-520
@@ -65,6 +70,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     struct FGpuCullingPassData
     {
         bool bEnabled = false;
+        bool bResetDebugPrint = false;
         uint32 Constants[UR_CULL_CONSTANT_DWORDS] = {};
     };
     Graph.AddPass<FGpuCullingPassData>("GPU Culling", [&](FGpuCullingPassData& Data, FRGPassBuilder& Builder)
@@ -76,6 +82,12 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         Data.Constants[42] = Res.HZBMipCount;
         Data.Constants[43] = HZBWidth;
         Data.Constants[44] = HZBHeight;
+        if (bDebugPrint) { // PrepareGpuDebugPrint (:390) and DebugPrintEnabled: the counters are zeroed, then counted, on this pass's stream
+            Data.bResetDebugPrint = true;
+            Data.Constants[45] = 1u;
+            Builder.WriteTexture(DebugStatsHandle, RG_STATE_UNORDERED_ACCESS);
+            Builder.WriteTexture(DebugBufferHandle, RG_STATE_UNORDERED_ACCESS);
+        }
         if (Data.bEnabled) {
             if (bUseHZBOcclusion) Builder.ReadTexture(HZBHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             Builder.KeepAlive();
@@ -85,6 +97,10 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         }
     }, [this, &Res](const FGpuCullingPassData& Data, FHIPCommandContext& Cmd)
     {
+        if (Data.bResetDebugPrint) {
+            const int rc = ur_debug_print_reset(Cmd.GetContext(), Res.DebugPrintBuffer, Res.CullStats);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        }
         if (!Data.bEnabled) return;
         // DispatchGpuCulling (Renderer.cpp:394-472): the UAV / INDIRECT_ARGUMENT transitions are stream order here.
         // With draw ranges the same call also places the visible commands of each range and writes its count (ur_cull_indirect_args_draws).
@@ -247,7 +263,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         return PassError;
     }
 
-    AddPostPasses(Graph, LightingHandle, Res, Constants, Options, 0);
+    AddPostPasses(Graph, LightingHandle, Res, Constants, Options, 0, DebugStatsHandle, DebugBufferHandle);
     Graph.Execute(Cmd);
     LastReport = Graph.GetLastExecutionReport();
     EndPostHistory(Options.bTonemap && Res.TonemapBand && Options.bAutoExposure);
@@ -269,7 +285,11 @@ int FHotPathRenderer::FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res
     Graph.SetResourceLifetimeLogging(PendingOptions.bGraphDump);
     Graph.SetBarrierLoggingEnabled(PendingOptions.bBarrierLogs);
     const FRGResourceHandle LightingHandle = Graph.ImportTexture("Lighting", Res.LightingBand, &Res.LightingState, {Res.Width, Res.Rows, RG_FORMAT_R16G16B16A16_FLOAT});
-    AddPostPasses(Graph, LightingHandle, Res, PendingConstants, PendingOptions, static_cast<uint32>(Cmd.GetWorldSize()));
+    // GpuDebugPrint behind the exchange: the counters are the ones the caller has summed over the ranks meanwhile (dist.allreduce_cull_stats)
+    const bool bDebugPrint = IsDebugPrintActive(Res, PendingOptions);
+    const FRGResourceHandle DebugStatsHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintStats", Res.CullStats, &Res.DebugPrintStatsState, {2, 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
+    const FRGResourceHandle DebugBufferHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintBuffer", Res.DebugPrintBuffer, &Res.DebugPrintState, {static_cast<uint32>(ur_debug_print_buffer_bytes() / 4u), 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
+    AddPostPasses(Graph, LightingHandle, Res, PendingConstants, PendingOptions, static_cast<uint32>(Cmd.GetWorldSize()), DebugStatsHandle, DebugBufferHandle);
     Graph.Execute(Cmd);
     const std::vector<FRenderGraph::FPassReport>& Tail = Graph.GetLastExecutionReport();
     LastReport.insert(LastReport.end(), Tail.begin(), Tail.end());
@@ -319,7 +339,7 @@ void FHotPathRenderer::EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 
 // neighbours' records in place. TemporalAA on the band (TaaFrame active in FinishPost) resolves from the neighbours' current rows in the
 // post records and, for CAS, also resolves the row on either side of the band from their TAA records into Res.TaaHaloRows: CAS's halo rows.
 void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
-                                     const FHotPathOptions& Options, uint32 RecordRanks)
+                                     const FHotPathOptions& Options, uint32 RecordRanks, FRGResourceHandle DebugStatsHandle, FRGResourceHandle DebugBufferHandle)
 {
     // (DeferredRenderer.cpp:1308-1573)
     // Without TemporalAA, AutoExposure and CAS this is the Tonemap pass alone, Lighting -> LDR band, as before they existed.
@@ -582,6 +602,33 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
                 if (rc != UR_OK && PassError == UR_OK) PassError = rc;
             });
         }
+        // ---- GpuDebugPrint (:1575-1598): last in the frame, DispatchGpuDebugPrintStats then RenderGpuDebugPrint onto the back buffer.
+        // On a band the draw composites the part of the text inside it.
+        struct FDebugPrintPassData
+        {
+            bool bEnabled = false;
+            ur_debug_print_constants K = {};
+        };
+        if (DebugBufferHandle) {
+            Graph.AddPass<FDebugPrintPassData>("GpuDebugPrint", [&](FDebugPrintPassData& Data, FRGPassBuilder& Builder)
+            {
+                Data.bEnabled = true;
+                Data.K.ScreenSize[0] = static_cast<float>(Res.Width);
+                Data.K.ScreenSize[1] = static_cast<float>(Res.Height);
+                Data.K.FirstChar = Res.DebugFirstChar;
+                Data.K.CharCount = Res.DebugCharCount;
+                Builder.ReadTexture(DebugStatsHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+                Builder.WriteTexture(DebugBufferHandle, RG_STATE_UNORDERED_ACCESS);
+                Builder.WriteTexture(TonemapHandle, RG_STATE_RENDER_TARGET);
+            }, [this, &Res](const FDebugPrintPassData& Data, FHIPCommandContext& Cmd)
+            {
+                int rc = ur_debug_print_stats(Cmd.GetContext(), Res.CullStats, Res.DebugPrintBuffer);
+                if (rc == UR_OK)
+                    rc = ur_debug_print_draw(Cmd.GetContext(), &Data.K, Res.DebugGlyphs, Res.DebugGlyphCount, Res.DebugAtlas, Res.DebugAtlasWidth, Res.DebugAtlasHeight,
+                                             Res.DebugPrintBuffer, Res.TonemapBand, Res.Width, Res.Height, Res.Row0, Res.Rows);
+                if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+            });
+        }
     }
 }
 
@@ -615,6 +662,7 @@ struct ur_frame
     const void* PostRecords = nullptr;
     void* TaaRecord = nullptr;         // ur_frame_set_taa_records
     const void* TaaRecords = nullptr;
+    ur_frame_debug_print DebugPrint = {}; // ur_frame_set_debug_print
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -760,6 +808,11 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
             f->TaaHaloWidth = r->width;
         }
     }
+    if (flags & UR_FRAME_DEBUG_PRINT) {
+        if (!(flags & UR_FRAME_TONEMAP) || !r->tonemap_band) { ur::set_error("ur_frame_render: DEBUG_PRINT needs UR_FRAME_TONEMAP and a tonemap_band"); return UR_EINVAL; }
+        if (!r->cull_stats) { ur::set_error("ur_frame_render: DEBUG_PRINT needs cull_stats"); return UR_EINVAL; }
+        if (!f->DebugPrint.buffer) { ur::set_error("ur_frame_render: DEBUG_PRINT needs ur_frame_set_debug_print's buffer and font"); return UR_EINVAL; }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -792,6 +845,14 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.DrawRanges = f->bDrawRanges ? &f->DrawRanges : nullptr;
     R.CullViews = f->CullViews;
     R.CullViewCount = (flags & UR_FRAME_CULL_VIEWS) ? f->CullViewCount : 0u;
+    R.DebugPrintBuffer = f->DebugPrint.buffer;
+    R.DebugGlyphs = f->DebugPrint.glyphs;
+    R.DebugGlyphCount = f->DebugPrint.glyph_count;
+    R.DebugAtlas = f->DebugPrint.atlas;
+    R.DebugAtlasWidth = f->DebugPrint.atlas_w;
+    R.DebugAtlasHeight = f->DebugPrint.atlas_h;
+    R.DebugFirstChar = f->DebugPrint.first_char;
+    R.DebugCharCount = f->DebugPrint.char_count;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -822,6 +883,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bTaa = (flags & UR_FRAME_TAA) != 0;
     O.bFuseTaaTonemap = (flags & UR_FRAME_FUSE_TAA_TONEMAP) != 0;
     O.bTaaBand = (flags & UR_FRAME_TAA_BAND) != 0;
+    O.bDebugPrint = (flags & UR_FRAME_DEBUG_PRINT) != 0;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -903,6 +965,17 @@ int ur_frame_set_cull_views(ur_frame* f, const ur_cull_view* views, uint32_t cou
         f->CullViews[v].draws = views[v].draws ? &f->ViewDraws[v] : nullptr;
     }
     f->CullViewCount = count;
+    return UR_OK;
+}
+
+int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp)
+{
+    if (!f) { ur::set_error("ur_frame_set_debug_print: null frame"); return UR_EINVAL; }
+    if (dp && (!dp->buffer || !dp->glyphs || dp->glyph_count == 0 || !dp->atlas || dp->atlas_w == 0 || dp->atlas_h == 0)) {
+        ur::set_error("ur_frame_set_debug_print: null buffer / glyphs / atlas, or an empty table or atlas");
+        return UR_EINVAL;
+    }
+    f->DebugPrint = dp ? *dp : ur_frame_debug_print{};
     return UR_OK;
 }
 

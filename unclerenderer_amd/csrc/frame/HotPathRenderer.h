@@ -2,7 +2,8 @@
 //
 // Reference wiring (Source/Render/DeferredRenderer.cpp): "GPU Culling" :508-542 (+ FRenderer::ConfigureHZBOcclusion /
 // DispatchGpuCulling, Renderer.cpp:384-472), "Build HZB" :982-1212, "Lighting" :1214-1255, "Sky" :1257-1296, and optionally the
-// post chain "TemporalAA" :1308-1361, "AutoExposure" :1363-1438, "Tonemap" :1440-1513, "CAS" :1515-1573. TemporalAA keeps the
+// post chain "TemporalAA" :1308-1361, "AutoExposure" :1363-1438, "Tonemap" :1440-1513, "CAS" :1515-1573, "GpuDebugPrint" :1575-1598
+// (with PrepareGpuDebugPrint, :390 / Renderer.cpp:474-527, at the head of the "GPU Culling" pass). TemporalAA keeps the
 // reference's history ring: FDeferredRenderer::OnFrameFenceSignaled (:2787-2799, called by FApplication::RenderFrame after every
 // submission) marks the slot a frame wrote as valid, so from the second frame on the pass runs with UseHistory = 1 and Tonemap reads
 // its output instead of Lighting (:1454-1459).
@@ -58,6 +59,13 @@ struct FHotPathResources
     const ur_draw_ranges* DrawRanges = nullptr; // optional (ur_frame_set_draw_ranges): compacted commands + a count per range
     const ur_cull_view* CullViews = nullptr;     // optional (ur_frame_set_cull_views + UR_FRAME_CULL_VIEWS): extra frustum-only views
     uint32 CullViewCount = 0;
+    // GpuDebugPrint (ur_frame_set_debug_print + UR_FRAME_DEBUG_PRINT): the text buffer, and the font the caller supplies
+    void* DebugPrintBuffer = nullptr;
+    const ur_debug_glyph* DebugGlyphs = nullptr;
+    uint32 DebugGlyphCount = 0;
+    const uint8_t* DebugAtlas = nullptr;
+    uint32 DebugAtlasWidth = 0, DebugAtlasHeight = 0;
+    uint32 DebugFirstChar = 0, DebugCharCount = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};
@@ -73,6 +81,8 @@ struct FHotPathResources
     uint32 TaaRecordState = RG_STATE_UNORDERED_ACCESS;
     uint32 TaaRecordsState = RG_STATE_UNORDERED_ACCESS;
     uint32 TaaHaloRowsState = RG_STATE_UNORDERED_ACCESS;
+    uint32 DebugPrintState = RG_STATE_UNORDERED_ACCESS;      // GpuDebugPrintState / GpuDebugPrintStatsState (Renderer.cpp:474-527)
+    uint32 DebugPrintStatsState = RG_STATE_UNORDERED_ACCESS;
 };
 
 struct FHotPathFrameConstants
@@ -105,6 +115,7 @@ struct FHotPathOptions
     bool bFuseTaaTonemap = false;     // with bTaa: TemporalAA + Tonemap in one launch (ur_temporal_aa_tonemap), TemporalAA pass culled
     bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
     bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
+    bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;
@@ -142,7 +153,11 @@ public:
 
 private:
     void AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
-                       const FHotPathOptions& Options, uint32 RecordRanks);
+                       const FHotPathOptions& Options, uint32 RecordRanks, FRGResourceHandle DebugStatsHandle, FRGResourceHandle DebugBufferHandle);
+    static bool IsDebugPrintActive(const FHotPathResources& Res, const FHotPathOptions& Options)
+    {
+        return Options.bDebugPrint && Options.bTonemap && Res.TonemapBand && Res.CullStats && Res.DebugPrintBuffer;
+    }
     void EndPostHistory(bool bAutoExposure);
     void EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 SlotCount);
 

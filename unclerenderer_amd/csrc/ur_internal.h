@@ -111,6 +111,13 @@ int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_c
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);
 enum { UR_MODE_LIGHTING = 0, UR_MODE_SKY = 1, UR_MODE_FUSED = 2 };
+// GpuDebugPrint (debug_print.hip); arguments checked by the C-ABI in ur_api.hip
+int launch_debug_print_reset(ur_ctx* ctx, void* buffer, uint32_t* stats);
+int launch_debug_print_stats(ur_ctx* ctx, const uint32_t* stats, void* buffer);
+int launch_debug_print_text(ur_ctx* ctx, void* buffer, uint32_t x, uint32_t y, uint32_t color, const char* text, uint32_t length);
+int launch_debug_print_draw(ur_ctx* ctx, const ur_debug_print_constants* constants, const ur_debug_glyph* glyphs, uint32_t glyph_count,
+                            const uint8_t* atlas_r8, uint32_t atlas_w, uint32_t atlas_h, const void* buffer, uint32_t* ldr_inout, uint32_t w,
+                            uint32_t row0, uint32_t rows);
 // the next {entry, exit} pair of the debug timeline (nullptr when it is off)
 inline unsigned long long* next_timeline_pair(ur_ctx* ctx)
 {

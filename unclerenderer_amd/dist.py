@@ -16,6 +16,9 @@ the GPU box, "gloo" in the CPU tests). The reference is single-GPU; this is new 
     second-last current rows and the first and last row of the history image it reads, hotpath.taa_record_bytes(W) = 32 W bytes -
     gathered the same way (allgather_taa_records); finish_post then resolves the band and, for CAS, the row on either side of it.
     Every rank must render the same flags every frame: the histories stay in step on that promise alone.
+  * GpuDebugPrint on the bands (UR_FRAME_DEBUG_PRINT with the post exchange): each rank's cull counts its own instance range;
+    allreduce_cull_stats sums the two counters over the ranks beside the record gathers, and finish_post prints the frame's totals on
+    every band.
   * BuildHZB: replicated (every rank builds the full chain from the full depth) — no exchange; or band-sharded
     (allgather_hzb_slices): a rank builds mips 0..4 for the 128x32 source pieces its rows own, the slices (5 contiguous runs of
     floats per rank) are exchanged peer to peer straight into place, and every rank runs the single-workgroup tail behind it.
@@ -141,6 +144,24 @@ def allgather_taa_records(all_records: torch.Tensor, own: torch.Tensor, group=No
     all_records[rank]). The collective of allgather_post_records on the second buffer; with async_op=True both may be in flight together
     (wait for both before Frame.finish_post)."""
     return allgather_post_records(all_records, own, group=group, async_op=async_op, mode=mode)
+
+
+def allreduce_cull_stats(cull_stats: torch.Tensor, group=None, async_op: bool = False):
+    """UR_FRAME_DEBUG_PRINT on row bands: each rank's cull counted its own instance range into `cull_stats` ([frustum-culled, occluded],
+    a 2-element 32-bit integer tensor); sum them in place over the ranks, beside the record gathers and before Frame.finish_post, so that
+    every band prints the frame's totals. The sum of the ranks' counts is the single-GPU count: every instance is culled by exactly one
+    rank. One rank, or no process group: nothing to do, None is returned. async_op=True otherwise returns a handle to wait() on, like the
+    gathers; for a device tensor over gloo (which moves host memory only) the tensor is staged through the host and copied back by wait()."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return None
+    staged = dist.get_backend(group) == "gloo" and cull_stats.is_cuda
+    buf = cull_stats.cpu() if staged else cull_stats
+    work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group, async_op=True)
+    w = _Works([work], (lambda: cull_stats.copy_(buf)) if staged else None)
+    if async_op:
+        return w
+    w.wait()
+    return None
 
 
 def allgather_visible(visible_idx: torch.Tensor, visible_count: torch.Tensor, group=None) -> tuple[torch.Tensor, int]:

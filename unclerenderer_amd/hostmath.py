@@ -75,6 +75,21 @@ def apply_taa_jitter(proj, jitter, width: float, height: float) -> np.ndarray:
     return out
 
 
+def debug_font():
+    """The built-in debug-print font (ur_host_debug_font): (atlas, glyphs, first_char, char_count) - atlas a (64, 64) uint8 array
+    (R8), glyphs a (96, 10) float32 array of ur_debug_glyph records {UvMin, UvMax, Size, Offset, Advance, Padding} indexed by code,
+    filled for codes first_char .. first_char + char_count - 1 = 32 .. 95."""
+    L = _lib.load()
+    info = (C.c_uint32 * 4)()
+    _lib.check(L.ur_host_debug_font(None, 0, None, 0, info), "ur_host_debug_font")
+    aw, ah, first, count = (int(v) for v in info)
+    atlas = np.zeros((ah, aw), np.uint8)
+    glyphs = np.zeros((first + count, 10), np.float32)
+    _lib.check(L.ur_host_debug_font(atlas.ctypes.data_as(C.c_void_p), atlas.size, glyphs.ctypes.data_as(C.c_void_p), glyphs.shape[0], info),
+               "ur_host_debug_font")
+    return atlas, glyphs, first, count
+
+
 def pack_culling_constants(view, proj, model_count: int, hzb_enabled: bool, hzb_mip_count: int, hzb_width: int,
                            hzb_height: int, debug_print: bool = False) -> np.ndarray:
     out = np.zeros(_lib.UR_CULL_CONSTANT_DWORDS, np.uint32)

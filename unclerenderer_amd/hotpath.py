@@ -617,6 +617,68 @@ HotPath.temporal_aa_halo = _temporal_aa_halo
 HotPath.temporal_aa_tonemap_halo = _temporal_aa_tonemap_halo
 
 
+# ---- GpuDebugPrint (include/ur_hotpath.h, ur_debug_print_*) ----
+
+def debug_print_buffer_bytes() -> int:
+    """Bytes of the debug-print buffer: the entry count, then 4096 entries {x, y, code, color} of 16 bytes."""
+    return int(_lib.load().ur_debug_print_buffer_bytes())
+
+
+def debug_print_buffer(device=0) -> torch.Tensor:
+    """A zeroed debug-print buffer as an int32 device tensor: [0] the count, [1 + 4 i : 5 + 4 i] entry i."""
+    return torch.zeros(debug_print_buffer_bytes() // 4, dtype=torch.int32, device=f"cuda:{device}")
+
+
+def _debug_print_reset(self, buffer, stats=None):
+    """Zero the buffer's count and, when given, the cull's two counters (PrepareGpuDebugPrint)."""
+    _lib.check(self._L.ur_debug_print_reset(self._ctx, _ptr(buffer), _ptr(stats)), "ur_debug_print_reset")
+
+
+def _debug_print_stats(self, stats, buffer):
+    """GpuDebugPrintStats.hlsl: "FRUSTUM n" / "OCCLUDE n" from stats[0] / stats[1] appended to the buffer."""
+    _lib.check(self._L.ur_debug_print_stats(self._ctx, _ptr(stats), _ptr(buffer)), "ur_debug_print_stats")
+
+
+def _debug_print_text(self, buffer, x, y, text, color=0xFFFFFFFF):
+    """PrintString of `text` (str, encoded latin-1, or bytes) at (x, y): 8 pixels a character, stopping at a zero code."""
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    _lib.check(self._L.ur_debug_print_text(self._ctx, _ptr(buffer), x, y, color, raw, len(raw)), "ur_debug_print_text")
+
+
+def _debug_print_draw(self, buffer, glyphs, atlas, ldr, w, h, row0=0, rows=None, first_char=32, char_count=96):
+    """GpuDebugPrint.hlsl's draw composited in place on rows [row0,row0+rows) of the w x h R8G8B8A8 image (ldr band-local).
+    glyphs: (n, 10) float32 device tensor of ur_debug_glyph records indexed by code; atlas: (atlas_h, atlas_w) uint8 device tensor."""
+    rows = h - row0 if rows is None else rows
+    assert glyphs.dtype == torch.float32 and glyphs.dim() == 2 and glyphs.shape[1] == 10 and atlas.dtype == torch.uint8 and atlas.dim() == 2
+    k = _lib.DebugPrintConstants((C.c_float * 2)(w, h), first_char, char_count)
+    _lib.check(self._L.ur_debug_print_draw(self._ctx, C.byref(k), _ptr(glyphs), glyphs.shape[0], _ptr(atlas), atlas.shape[1], atlas.shape[0],
+                                           _ptr(buffer), _ptr(ldr), w, h, row0, rows), "ur_debug_print_draw")
+
+
+HotPath.debug_print_buffer_bytes = staticmethod(debug_print_buffer_bytes)
+HotPath.debug_print_reset = _debug_print_reset
+HotPath.debug_print_stats = _debug_print_stats
+HotPath.debug_print_text = _debug_print_text
+HotPath.debug_print_draw = _debug_print_draw
+
+
+def _frame_set_debug_print(self, buffer=None, glyphs=None, atlas=None, first_char=32, char_count=96):
+    """ur_frame_set_debug_print: the text buffer and font (device tensors as in HotPath.debug_print_draw, kept alive here) of the frames
+    rendered with UR_FRAME_DEBUG_PRINT. No arguments: clear."""
+    if buffer is None and glyphs is None and atlas is None:
+        self._debug_print_keep = None
+        _lib.check(self._L.ur_frame_set_debug_print(self._f, None), "ur_frame_set_debug_print")
+        return
+    dp = _lib.FrameDebugPrint(buffer.data_ptr() if buffer is not None else None, glyphs.data_ptr() if glyphs is not None else None,
+                              glyphs.shape[0] if glyphs is not None else 0, atlas.data_ptr() if atlas is not None else None,
+                              atlas.shape[1] if atlas is not None else 0, atlas.shape[0] if atlas is not None else 0, first_char, char_count)
+    _lib.check(self._L.ur_frame_set_debug_print(self._f, C.byref(dp)), "ur_frame_set_debug_print")
+    self._debug_print_keep = (buffer, glyphs, atlas)
+
+
+Frame.set_debug_print = _frame_set_debug_print
+
+
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:
     """numpy -> device tensor, reinterpreting unsigned dtypes torch cannot hold (bit patterns are preserved)."""
     a = np.ascontiguousarray(a)

@@ -141,6 +141,26 @@ class FrameTaaInfo(C.Structure):
     _fields_ = [("read_slot", C.c_uint32), ("write_slot", C.c_uint32), ("use_history", C.c_uint32), ("jitter", C.c_float * 2)]
 
 
+class DebugGlyph(C.Structure):
+    """ur_debug_glyph (include/ur_hotpath.h) == FDebugPrintGlyph (Source/Render/DebugPrintFont.h:11-19), 40 bytes."""
+    _fields_ = [("UvMin", C.c_float * 2), ("UvMax", C.c_float * 2), ("Size", C.c_float * 2), ("Offset", C.c_float * 2),
+                ("Advance", C.c_float), ("Padding", C.c_float)]
+
+
+class DebugPrintConstants(C.Structure):
+    """ur_debug_print_constants == DebugPrintConstants (Shaders/GpuDebugPrint.hlsl:4-9)."""
+    _fields_ = [("ScreenSize", C.c_float * 2), ("FirstChar", C.c_uint32), ("CharCount", C.c_uint32)]
+
+
+class FrameDebugPrint(C.Structure):
+    """ur_frame_debug_print (include/ur_frame.h): the text buffer and font of UR_FRAME_DEBUG_PRINT (ur_frame_set_debug_print)."""
+    _fields_ = [("buffer", C.c_void_p), ("glyphs", C.c_void_p), ("glyph_count", C.c_uint32), ("atlas", C.c_void_p),
+                ("atlas_w", C.c_uint32), ("atlas_h", C.c_uint32), ("first_char", C.c_uint32), ("char_count", C.c_uint32)]
+
+
+UR_DEBUG_PRINT_MAX_ENTRIES = 4096
+
+
 class FrameResources(C.Structure):
     """ur_frame_resources (include/ur_frame.h)."""
     _fields_ = [
@@ -171,10 +191,12 @@ UR_FRAME_CULL_VIEWS = 0x400000
 UR_FRAME_TAA = 0x800000
 UR_FRAME_FUSE_TAA_TONEMAP = 0x1000000
 UR_FRAME_TAA_BAND = 0x2000000
+UR_FRAME_DEBUG_PRINT = 0x4000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
 assert C.sizeof(AutoExposureConstants) == 36 and C.sizeof(CasConstants) == 16
+assert C.sizeof(DebugGlyph) == 40 and C.sizeof(DebugPrintConstants) == 16
 
 # name -> (restype, argtypes); every symbol declared in include/*.h
 _VP, _U32, _F = C.c_void_p, C.c_uint32, C.c_float
@@ -231,6 +253,11 @@ SIGNATURES = {
     "ur_temporal_aa_halo": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _U32, _U32, _U32, _U32, _U32]),
     "ur_temporal_aa_tonemap_halo": (C.c_int, [_VP, C.POINTER(TonemapConstants), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F,
                                               _U32, _U32, _U32, _U32, _U32]),
+    "ur_debug_print_buffer_bytes": (C.c_uint64, []),
+    "ur_debug_print_reset": (C.c_int, [_VP, _VP, _VP]),
+    "ur_debug_print_stats": (C.c_int, [_VP, _VP, _VP]),
+    "ur_debug_print_text": (C.c_int, [_VP, _VP, _U32, _U32, _U32, C.c_char_p, _U32]),
+    "ur_debug_print_draw": (C.c_int, [_VP, C.POINTER(DebugPrintConstants), _VP, _U32, _VP, _U32, _U32, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes_ex": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.c_int]),
@@ -264,6 +291,7 @@ SIGNATURES = {
     "ur_frame_set_post_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_set_taa_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_finish_post": (C.c_int, [_VP]),
+    "ur_frame_set_debug_print": (C.c_int, [_VP, C.POINTER(FrameDebugPrint)]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
@@ -281,6 +309,7 @@ SIGNATURES = {
     "ur_host_fill_sky_constants": (None, [_FP, _FP, _FP, _F, _FP, _FP, C.POINTER(SkyConstants)]),
     "ur_host_taa_jitter": (None, [_U32, _FP]),
     "ur_host_apply_taa_jitter": (None, [_FP, _FP, _F, _F]),
+    "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_light_direction_roundtrip": (None, [_FP, _FP]),
