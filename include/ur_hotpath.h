@@ -246,7 +246,9 @@ int ur_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h
  * slices (ur_hzb_band_slices names them: one contiguous run of floats per level), and every rank runs the single-workgroup rest of
  * the chain (ur_build_hzb_tail: mips 5.. from mip 4) behind the exchange. Bit for bit ur_build_hzb's chain. Only for chains that are
  * one five-level launch plus the tail (frames of a few hundred pixels up to 8K); UR_EUNSUPPORTED otherwise (build it whole).
- * With ur_defer_hzb_tail(ctx, 2) the band's pieces ride the next streaming Lighting launch like the whole chain's do. */
+ * With ur_defer_hzb_tail(ctx, 2) the band's pieces ride the next streaming Lighting launch like the whole chain's do.
+ * ur_hzb_band_pieces needs equal bands, n_ranks | src_h (UR_EINVAL otherwise). ur_build_hzb_band writes the band's five slices and no
+ * other float of the HZB; ur_build_hzb_tail reads mip 4 and writes mips 5.. only; no call writes the floats between two mips. */
 typedef struct ur_hzb_slice {
     uint32_t offset; /* in floats from hzb_base */
     uint32_t count;  /* floats */
