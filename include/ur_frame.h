@@ -7,6 +7,7 @@
 #define UR_FRAME_H
 
 #include "ur_hotpath.h"
+#include "ur_raster.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -102,6 +103,13 @@ typedef struct ur_frame_resources {
  * Text the caller prints into the buffer between the cull and the pass (ur_debug_print_text, or its own kernels by the slot rule) comes
  * ahead of the two stats lines' entries in the buffer: it is blended first and lies beneath them where they overlap. Without the flag nothing of this happens: the frame is what it is today. */
 #define UR_FRAME_DEBUG_PRINT 0x4000000u
+/* "ShadowMap" pass directly behind "GPU Culling" (DeferredRenderer.cpp:551-633), with UR_FRAME_SHADOWS: ur_shadow_map of
+ * ur_frame_set_shadow_pass' draws with scene->LightViewProjection into its shadow_map, scene->ShadowMapSize texels, on the main stream
+ * (with UR_FRAME_ASYNC_COMPUTE behind a wait on the cull, whose lists and ranges it draws from); Lighting then reads that map:
+ * tables.shadow_map must be the pass's shadow_map and a pass must be set (else UR_EINVAL). Without UR_FRAME_SHADOWS the pass is listed
+ * and culled, as in the reference. On a row band every rank renders the whole map (a replicated side table, like the HZB). Without
+ * the flag nothing of this happens: the frame is what it is today. */
+#define UR_FRAME_SHADOW_PASS 0x8000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -198,6 +206,16 @@ typedef struct ur_frame_debug_print {
     uint32_t first_char, char_count; /* DebugPrintConstants.FirstChar / CharCount [32, 96] */
 } ur_frame_debug_print;
 int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp);
+/* The draws, the target and the optional counters (ur_shadow_map's stats4; the caller zeroes them) of the frames rendered with
+ * UR_FRAME_SHADOW_PASS. The frame keeps a copy of the struct and of the ur_draw_ranges it points to; the buffers stay the caller's and
+ * must stay valid while frames use them. NULL clears. UR_EINVAL for a null frame, a null shadow_map and what ur_shadow_map refuses
+ * in the draws (both selections, a list without its count, a null member of ranges, a misaligned buffer). */
+typedef struct ur_frame_shadow_pass {
+    ur_raster_draws draws;
+    float* shadow_map;
+    uint32_t* stats4;
+} ur_frame_shadow_pass;
+int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

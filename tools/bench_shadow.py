@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Timing of the ShadowMap pass (ur_shadow_map) on one GPU (development aid; bench.py is the contract benchmark and never draws).
+
+    python tools/bench_shadow.py [--batches 7] [--iters 10] [--json out.jsonl]
+    python tools/bench_shadow.py --quick     # each workload a few times: for a rocprofv3 --kernel-trace --stats run
+
+A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
+  small   1 M triangles of 1/8 px to 8 px in one command;
+  large   a soup of 256 map-spanning triangles;
+  mix     the two together, as two commands.
+Each time is one device-event pair around a batch of back-to-back calls over rotating buffer sets (cold maps), divided by the calls
+(launch gaps included). Beside them, measured in the same run, the yardstick that exists today: the clear alone (a call with no
+commands launches only the clear: 16.8 MB of stores). The per-launch split (clear / raster / large) comes from a separate rocprofv3
+--kernel-trace --stats run of --quick: the kernels are shadow_clear_kernel, shadow_raster_kernel and shadow_large_kernel. The second
+yardstick of the plan - a plain kernel issuing the same number of contiguous atomic-minimum bytes - needs a fragment count the pass
+does not keep and is not built.
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+SIZE = 2048
+
+
+def time_batch(torch, fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for k in range(iters):
+        fn(k)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def triangles(rng, n, lo, hi):
+    """n clockwise-on-target triangles (drawn) with edge lengths log-uniform in [lo, hi] px, as clip-space positions (n * 3, 3)."""
+    c = rng.uniform(0, SIZE, (n, 1, 2))
+    length = np.exp(rng.uniform(np.log(lo), np.log(hi), (n, 1, 1)))
+    p = c + rng.uniform(-0.5, 0.5, (n, 3, 2)) * length
+    e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    flip = e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1] < 0
+    p[flip] = p[flip][:, [0, 2, 1]]
+    z = rng.uniform(0.05, 0.95, (n, 3, 1))
+    return np.concatenate([p[..., :1] / (0.5 * SIZE) - 1.0, 1.0 - p[..., 1:] / (0.5 * SIZE), z], axis=2).reshape(-1, 3).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10, help="calls per timed batch")
+    ap.add_argument("--ring", type=int, default=4, help="maps cycled through so that every call meets a cold map")
+    ap.add_argument("--small", type=int, default=1_000_000)
+    ap.add_argument("--reserve", type=int, default=1 << 19)
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    if a.quick:
+        a.batches, a.iters, a.ring = 1, 2, 2
+    import torch
+    from unclerenderer_amd.hotpath import HotPath, pack_draw_commands, to_device
+    assert torch.cuda.is_available(), "bench_shadow needs a GPU"
+    hp = HotPath(0)
+    rng = np.random.default_rng(2048)
+    world = to_device(np.eye(4, dtype=np.float32).reshape(-1))
+    lvp = np.eye(4, dtype=np.float32).reshape(-1)
+
+    def mesh(pos):
+        v = np.zeros((pos.shape[0], 16), np.float32)
+        v[:, :3] = pos
+        vb, ib = to_device(v.reshape(-1)), to_device(np.arange(pos.shape[0], dtype=np.uint32))
+        return dict(vertices=vb, indices=ib, constants=world, stride=64)
+
+    small, large = mesh(triangles(rng, a.small, 0.125, 8.0)), mesh(triangles(rng, 256, SIZE, 2 * SIZE))
+    loads = {"small": [small], "large": [large], "mix": [small, large]}
+    cmds = {k: to_device(pack_draw_commands(v)) for k, v in loads.items()}
+    maps = [torch.empty((SIZE, SIZE), dtype=torch.float32, device="cuda") for _ in range(a.ring)]
+    stats = torch.zeros(4, dtype=torch.int32, device="cuda")
+    rows = []
+    for reserve in (a.reserve, 0):
+        hp.raster_reserve(reserve)
+        shapes = {"clear alone": None, **cmds}
+        fns = {k: (lambda i, c=c: hp.shadow_map(lvp, c, maps[i % a.ring], stats=stats if c is not None else None, command_count=None if c is not None else 0))
+               for k, c in shapes.items()}
+        seen = {}
+        for k, f in fns.items():
+            stats.zero_()
+            f(0)
+            torch.cuda.synchronize()
+            seen[k] = stats.cpu().numpy().view(np.uint32).tolist()
+        times = {k: [] for k in fns}
+        for _ in range(a.batches):
+            for k, f in fns.items():
+                times[k].append(time_batch(torch, f, a.iters))
+        for k, t in times.items():
+            rows.append({"shape": f"{SIZE}x{SIZE}, {k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
+                         "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
+    hp.raster_reserve(0)
+    hp.close()
+    for r in rows:
+        print(f"{r['shape']:48s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
+    if a.json:
+        with open(a.json, "a") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print(json.dumps({"tool": "bench_shadow", "quick": a.quick, "results": rows}))
+
+
+if __name__ == "__main__":
+    main()

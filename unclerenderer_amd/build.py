@@ -38,6 +38,7 @@ SOURCES = [
     ("taa.hip", EXACT),
     ("post.hip", EXACT),
     ("debug_print.hip", EXACT),
+    ("shadow_raster.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),

@@ -62,6 +62,16 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     const FRGResourceHandle DebugStatsHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintStats", Res.CullStats, &Res.DebugPrintStatsState, {2, 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
     const FRGResourceHandle DebugBufferHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintBuffer", Res.DebugPrintBuffer, &Res.DebugPrintState, {static_cast<uint32>(ur_debug_print_buffer_bytes() / 4u), 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
 
+    // ShadowMap: what the pass draws from (the light view's list or ranges, written by this frame's cull when it runs)
+    const bool bShadowPass = Options.bShadowPass && Res.ShadowDraws != nullptr && Res.ShadowMapTarget != nullptr;
+    const bool bCullEnabled = Options.bEnableIndirectDraw && Res.IndirectArgs && Res.ModelBounds && Res.IndirectCommandCount != 0;
+    FRGResourceHandle ShadowDrawsHandle;
+    if (bShadowPass) {
+        const ur_raster_draws& D = *Res.ShadowDraws;
+        const void* Draws = D.ranges ? D.ranges->commands : (D.visible_idx ? static_cast<const void*>(D.visible_idx) : D.commands);
+        ShadowDrawsHandle = Graph.ImportTexture("ShadowDraws", const_cast<void*>(Draws), &Res.ShadowDrawsState, {D.command_count, 1, RG_FORMAT_UNKNOWN});
+    }
+
     const bool bHZBEnabled = Options.bHZBEnabled && Res.HZB != nullptr && Res.HZBMipCount != 0;
     if (!bHZBEnabled) bHZBReady = false; // :514-517
     const bool bUseHZBOcclusion = bHZBEnabled && bHZBReady; // ConfigureHZBOcclusion, :519-520
@@ -90,6 +100,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         }
         if (Data.bEnabled) {
             if (bUseHZBOcclusion) Builder.ReadTexture(HZBHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
+            if (bShadowPass && Options.bRenderShadows) Builder.WriteTexture(ShadowDrawsHandle, RG_STATE_UNORDERED_ACCESS); // the light view's list / ranges
             Builder.KeepAlive();
             // Neither visibility pass shares a resource with Lighting/Sky inside a frame (the cull reads LAST frame's
             // HZB), so both can run beside the VALU-bound lighting kernel on the second stream.
@@ -112,6 +123,33 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
                                                    Res.CullViewCount != 0 ? Res.CullViews : nullptr, Res.CullViewCount);
         if (rc != UR_OK && PassError == UR_OK) PassError = rc;
     });
+
+    // ---- ShadowMap (:551-633): the light view's draws, depth only, into the map Lighting samples -----------------------
+    struct FShadowPassData
+    {
+        bool bEnabled = false;
+        float LightViewProjection[16] = {};
+        uint32 Width = 0, Height = 0;
+    };
+    if (bShadowPass) {
+        Graph.AddPass<FShadowPassData>("ShadowMap", [&](FShadowPassData& Data, FRGPassBuilder& Builder)
+        {
+            Data.bEnabled = Options.bRenderShadows;
+            std::memcpy(Data.LightViewProjection, Constants.Scene.LightViewProjection, sizeof(Data.LightViewProjection));
+            Data.Width = static_cast<uint32>(Constants.Scene.ShadowMapSize[0]);
+            Data.Height = static_cast<uint32>(Constants.Scene.ShadowMapSize[1]);
+            if (Data.bEnabled) {
+                if (bCullEnabled) Builder.ReadTexture(ShadowDrawsHandle, RG_STATE_INDIRECT_ARGUMENT); // (on the async lane: the wait on the cull)
+                Builder.WriteTexture(ShadowHandle, RG_STATE_DEPTH_WRITE);
+            }
+        }, [this, &Res](const FShadowPassData& Data, FHIPCommandContext& Cmd)
+        {
+            if (!Data.bEnabled) return;
+            // ClearDepth(1.0) and the draws of :571-631, on the stream the pass runs on (the main one: it is not an async-compute pass)
+            const int rc = ur_shadow_map(Cmd.GetContext(), Data.LightViewProjection, Res.ShadowDraws, Res.ShadowMapTarget, Data.Width, Data.Height, Res.ShadowStats);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
+    }
 
     // ---- Build HZB (after the G-buffer pass; only with HZB and depth prepass enabled, :996) ------------------------
     struct FHZBPassData
@@ -663,6 +701,9 @@ struct ur_frame
     void* TaaRecord = nullptr;         // ur_frame_set_taa_records
     const void* TaaRecords = nullptr;
     ur_frame_debug_print DebugPrint = {}; // ur_frame_set_debug_print
+    ur_frame_shadow_pass ShadowPass = {}; // ur_frame_set_shadow_pass (draws.ranges points into ShadowRanges)
+    ur_draw_ranges ShadowRanges = {};
+    bool bShadowPass = false;
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -813,6 +854,13 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
         if (!r->cull_stats) { ur::set_error("ur_frame_render: DEBUG_PRINT needs cull_stats"); return UR_EINVAL; }
         if (!f->DebugPrint.buffer) { ur::set_error("ur_frame_render: DEBUG_PRINT needs ur_frame_set_debug_print's buffer and font"); return UR_EINVAL; }
     }
+    if (flags & UR_FRAME_SHADOW_PASS) {
+        if (!f->bShadowPass) { ur::set_error("ur_frame_render: SHADOW_PASS needs ur_frame_set_shadow_pass"); return UR_EINVAL; }
+        if ((flags & UR_FRAME_SHADOWS) && r->tables.shadow_map != f->ShadowPass.shadow_map) {
+            ur::set_error("ur_frame_render: SHADOW_PASS renders into ur_frame_set_shadow_pass' shadow_map, Lighting reads tables.shadow_map: they must be the same buffer");
+            return UR_EINVAL;
+        }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -853,6 +901,10 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.DebugAtlasHeight = f->DebugPrint.atlas_h;
     R.DebugFirstChar = f->DebugPrint.first_char;
     R.DebugCharCount = f->DebugPrint.char_count;
+    const bool shadow_pass = (flags & UR_FRAME_SHADOW_PASS) != 0 && f->bShadowPass;
+    R.ShadowDraws = shadow_pass ? &f->ShadowPass.draws : nullptr;
+    R.ShadowMapTarget = shadow_pass ? f->ShadowPass.shadow_map : nullptr;
+    R.ShadowStats = shadow_pass ? f->ShadowPass.stats4 : nullptr;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -884,6 +936,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bFuseTaaTonemap = (flags & UR_FRAME_FUSE_TAA_TONEMAP) != 0;
     O.bTaaBand = (flags & UR_FRAME_TAA_BAND) != 0;
     O.bDebugPrint = (flags & UR_FRAME_DEBUG_PRINT) != 0;
+    O.bShadowPass = shadow_pass;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -976,6 +1029,34 @@ int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp)
         return UR_EINVAL;
     }
     f->DebugPrint = dp ? *dp : ur_frame_debug_print{};
+    return UR_OK;
+}
+
+int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass)
+{
+    if (!f) { ur::set_error("ur_frame_set_shadow_pass: null frame"); return UR_EINVAL; }
+    if (!pass) {
+        f->bShadowPass = false;
+        f->ShadowPass = ur_frame_shadow_pass{};
+        return UR_OK;
+    }
+    const ur_raster_draws& d = pass->draws;
+    const ur_draw_ranges* rg = d.ranges;
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
+    if (!pass->shadow_map) { ur::set_error("ur_frame_set_shadow_pass: null shadow_map"); return UR_EINVAL; }
+    if ((d.visible_idx != nullptr) != (d.visible_count != nullptr)) { ur::set_error("ur_frame_set_shadow_pass: a list needs visible_idx and visible_count"); return UR_EINVAL; }
+    if (d.visible_idx && rg) { ur::set_error("ur_frame_set_shadow_pass: a list and ranges at once"); return UR_EINVAL; }
+    if (rg && (!rg->offsets || !rg->commands || !rg->counts || rg->range_count == 0)) { ur::set_error("ur_frame_set_shadow_pass: a null member of ranges / no range"); return UR_EINVAL; }
+    if (!rg && !d.commands && d.command_count != 0) { ur::set_error("ur_frame_set_shadow_pass: null commands"); return UR_EINVAL; }
+    if (misaligned(rg ? rg->commands : d.commands, 16) || misaligned(pass->shadow_map, 4) || misaligned(pass->stats4, 4) || misaligned(d.visible_idx, 4) ||
+        misaligned(d.visible_count, 4) || (rg && (misaligned(rg->offsets, 4) || misaligned(rg->counts, 4)))) {
+        ur::set_error("ur_frame_set_shadow_pass: a misaligned buffer (commands 16 bytes, the others 4)");
+        return UR_EINVAL;
+    }
+    f->ShadowPass = *pass;
+    f->ShadowRanges = rg ? *rg : ur_draw_ranges{};
+    f->ShadowPass.draws.ranges = rg ? &f->ShadowRanges : nullptr;
+    f->bShadowPass = true;
     return UR_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../../include/ur_hotpath.h"
+#include "../../../include/ur_raster.h"
 #include "../rg/RenderGraph.h"
 
 // Device buffers owned by the caller (the renderer that rasterised the G-buffer). States mirror the variables the
@@ -66,6 +67,10 @@ struct FHotPathResources
     const uint8_t* DebugAtlas = nullptr;
     uint32 DebugAtlasWidth = 0, DebugAtlasHeight = 0;
     uint32 DebugFirstChar = 0, DebugCharCount = 0;
+    // ShadowMap (ur_frame_set_shadow_pass + UR_FRAME_SHADOW_PASS): the draws, the target (== Tables.shadow_map) and optional counters
+    const ur_raster_draws* ShadowDraws = nullptr;
+    float* ShadowMapTarget = nullptr;
+    uint32* ShadowStats = nullptr;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};
@@ -83,6 +88,7 @@ struct FHotPathResources
     uint32 TaaHaloRowsState = RG_STATE_UNORDERED_ACCESS;
     uint32 DebugPrintState = RG_STATE_UNORDERED_ACCESS;      // GpuDebugPrintState / GpuDebugPrintStatsState (Renderer.cpp:474-527)
     uint32 DebugPrintStatsState = RG_STATE_UNORDERED_ACCESS;
+    uint32 ShadowDrawsState = RG_STATE_UNORDERED_ACCESS;     // the list / ranges the cull writes and the ShadowMap pass draws from
 };
 
 struct FHotPathFrameConstants
@@ -116,6 +122,7 @@ struct FHotPathOptions
     bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
     bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
     bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
+    bool bShadowPass = false;         // with ShadowDraws: the "ShadowMap" pass behind "GPU Culling" (ur_shadow_map into Tables.shadow_map)
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;

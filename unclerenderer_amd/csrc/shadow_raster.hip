@@ -1,0 +1,417 @@
+// ShadowMap for gfx950 — a depth-only raster of indexed triangle lists under an orthographic light (include/ur_raster.h).
+//
+// Reference: the "ShadowMap" pass (DeferredRenderer.cpp:551-633), Shaders/ShadowMap.hlsl (position * World * LightViewProjection, no
+// pixel shader), its pipeline (Renderer.cpp:240-300: CULL_MODE_FRONT, FrontCounterClockwise, LESS_EQUAL, zero bias, depth clip) and
+// target (D32_FLOAT, cleared to 1.0). The result is a per-texel minimum, so it is specified to the bit: DESIGN.md section 3.7 is the
+// rule, tests/shadow_ref.py restates it in numpy, and this file computes the same bytes. Built with -ffp-contract=off.
+//
+// Three launches, nothing read back:
+//   clear   every texel = 1.0f (16-byte nontemporal stores), the large queue's count = 0;
+//   raster  a wave per (draw candidate, segment): it walks the 64-triangle chunks c = segment, segment + S, ... of its command, a lane
+//           per triangle (rules 1-3 and the bounding box), then serves the survivors: a triangle of at most 4 centres by its own lane,
+//           the others by the whole wave as an 8 x 8 pixel stamp, the triangle broadcast by readlane. Triangles of more than 64 stamps
+//           go to the queue, one (triangle, 64 x 64 tile) entry per tile under the bounding box, one atomic reservation per triangle;
+//           without room the wave rasterises the triangle itself (stats[3]);
+//   large   a fixed grid whose waves stride over the entries: a tile the triangle cannot touch is rejected at its corners, the rest
+//           is stamped.
+// A fragment is one device-scope atomic unsigned minimum of the depth's bit pattern (depths lie in [0, 1]); a plain load in front
+// skips it when the texel is already nearer (texels only decrease, so a stale value only costs an atomic, never a fragment).
+
+#include "ur_internal.h"
+
+#include "../../include/ur_raster.h"
+
+namespace {
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t kThreads = 256u, kWaves = kThreads / 64u;
+constexpr uint32_t kQueueHeaderDwords = 16u; // the count on a line of its own
+constexpr uint32_t kEntryDwords = 12u;       // x0 y0 x1 y1 | x2 y2 z0 k1 | k2 tile box_min box_max
+constexpr uint32_t kLargeStamps = 64u;       // a bounding box of more 8 x 8 stamps than this is a large triangle
+constexpr uint32_t kOwnPixels = 4u;          // a bounding box of at most this many centres is rasterised by the triangle's own lane
+constexpr uint32_t kNoTile = 0xFFFFFFFFu;
+constexpr float kGuardBand = (float)UR_RASTER_MAX_TARGET;
+
+struct RasterParams {
+    const uint8_t* commands;
+    uint32_t command_count;
+    uint32_t mode; // 0 every slot, 1 list, 2 ranges
+    const uint32_t* visible_idx;
+    const uint32_t* visible_count;
+    uint32_t index_base;
+    uint32_t range_count;
+    const uint32_t* offsets;
+    const uint32_t* counts;
+    float L[16];
+    uint32_t* map;
+    uint32_t w, h;
+    float half_w, half_h; // 0.5f * w, 0.5f * h
+    uint32_t* stats;
+    uint32_t* queue; // 64-bit count at [0..1], entries from kQueueHeaderDwords; null without room
+    uint32_t queue_cap;
+    uint32_t segments, items; // items = candidates * segments
+};
+
+struct Tri {
+    int x0, y0, x1, y1, x2, y2; // 24.8 target space, y down
+    float z0, k1, k2;
+};
+
+// Rule 4's tie-break as a bias: the edge a->b passes iff E - bias >= 0, bias 0 on a top (dy == 0 && dx > 0) or left (dy < 0) edge
+__device__ __forceinline__ int edge_bias(int ax, int ay, int bx, int by)
+{
+    const int dx = bx - ax, dy = by - ay;
+    return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
+}
+
+// Rules 4-6 for one pixel
+__device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, uint32_t* __restrict__ map, uint32_t w, int px, int py)
+{
+    const int sx = 256 * px + 128, sy = 256 * py + 128;
+    const long long e01 = (long long)(t.x1 - t.x0) * (sy - t.y0) - (long long)(t.y1 - t.y0) * (sx - t.x0);
+    const long long e12 = (long long)(t.x2 - t.x1) * (sy - t.y1) - (long long)(t.y2 - t.y1) * (sx - t.x1);
+    const long long e20 = (long long)(t.x0 - t.x2) * (sy - t.y2) - (long long)(t.y0 - t.y2) * (sx - t.x2);
+    if (((e01 - b01) | (e12 - b12) | (e20 - b20)) < 0) return;
+    const float z = t.z0 + ((float)e20 * t.k1 + (float)e01 * t.k2);
+    if (!(z >= 0.0f && z <= 1.0f)) return; // depth clip (a NaN goes too)
+    uint32_t bits = __float_as_uint(z);
+    if (bits == 0x80000000u) bits = 0u; // z += 0.0f
+    uint32_t* p = map + (size_t)py * w + (uint32_t)px;
+    if (bits >= __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
+    (void)__hip_atomic_fetch_min(p, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The whole wave stamps the pixels [px0, px1] x [py0, py1] (inside the target) of one triangle, uniform arguments
+__device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ map, uint32_t w, int px0, int py0, int px1, int py1, uint32_t lane)
+{
+    const int b01 = edge_bias(t.x0, t.y0, t.x1, t.y1), b12 = edge_bias(t.x1, t.y1, t.x2, t.y2), b20 = edge_bias(t.x2, t.y2, t.x0, t.y0);
+    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
+    for (int sy = py0 & ~7; sy <= py1; sy += 8) {
+        const int py = sy + ly;
+        for (int sx = px0 & ~7; sx <= px1; sx += 8) {
+            const int px = sx + lx;
+            if (px >= px0 && px <= px1 && py >= py0 && py <= py1) shade(t, b01, b12, b20, map, w, px, py);
+        }
+    }
+}
+
+__device__ __forceinline__ int rl(int v, uint32_t s) { return __builtin_amdgcn_readlane(v, (int)s); }
+__device__ __forceinline__ float rlf(float v, uint32_t s) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)s)); }
+
+__device__ __forceinline__ Tri broadcast(const Tri& t, uint32_t s)
+{
+    Tri r;
+    r.x0 = rl(t.x0, s); r.y0 = rl(t.y0, s); r.x1 = rl(t.x1, s); r.y1 = rl(t.y1, s); r.x2 = rl(t.x2, s); r.y2 = rl(t.y2, s);
+    r.z0 = rlf(t.z0, s); r.k1 = rlf(t.k1, s); r.k2 = rlf(t.k2, s);
+    return r;
+}
+
+// Rule 1 for one vertex: position * World * LightViewProjection, each a left-to-right sum of four products
+__device__ __forceinline__ void project(const float* __restrict__ pos, const float (&W)[16], const float (&L)[16], float (&clip)[4])
+{
+    const float x = pos[0], y = pos[1], z = pos[2];
+    float wv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wv[k] = ((x * W[k] + y * W[4 + k]) + z * W[8 + k]) + W[12 + k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) clip[k] = ((wv[0] * L[k] + wv[1] * L[4 + k]) + wv[2] * L[8 + k]) + wv[3] * L[12 + k];
+}
+
+__global__ __launch_bounds__(kThreads) void shadow_clear_kernel(float* __restrict__ map, uint32_t n, uint32_t head, uint32_t* __restrict__ queue)
+{
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i == 0u && queue != nullptr) queue[0] = queue[1] = 0u; // (a 64-bit count: it never wraps)
+    // `head` floats up to the first 16-byte boundary, then whole 16-byte groups, then what is left
+    const uint32_t groups = (n - head) / 4u, tail = head + groups * 4u;
+    if (i < head) map[i] = 1.0f;
+    if (i < n - tail) map[tail + i] = 1.0f;
+    f32x4_t* body = reinterpret_cast<f32x4_t*>(map + head);
+    const f32x4_t one = {1.0f, 1.0f, 1.0f, 1.0f};
+    for (uint32_t g = i; g < groups; g += gridDim.x * kThreads) __builtin_nontemporal_store(one, body + g);
+}
+
+__global__ __launch_bounds__(kThreads) void shadow_raster_kernel(RasterParams p)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    const uint32_t wave_count = gridDim.x * kWaves;
+    uint32_t n_drawn = 0, n_unsupported = 0, n_dropped = 0, n_unqueued = 0; // uniform; added to stats once per wave
+
+    for (uint32_t item = wave; item < p.items; item += wave_count) {
+        const uint32_t cand = item / p.segments, seg = item - cand * p.segments;
+        // ---- selection: the candidate's slot, or none
+        uint32_t slot = cand;
+        if (p.mode == 1u) {
+            if (cand >= *p.visible_count) continue;
+            slot = p.visible_idx[cand] - p.index_base;
+        } else if (p.mode == 2u) {
+            uint32_t lo = 0u, hi = p.range_count + 1u; // first k with offsets[k] > cand
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (p.offsets[mid] > cand) hi = mid; else lo = mid + 1u;
+            }
+            if (lo == 0u || lo > p.range_count) continue;
+            const uint32_t r = lo - 1u;
+            if (cand - p.offsets[r] >= p.counts[r]) continue;
+        }
+        slot = __builtin_amdgcn_readfirstlane(slot);
+        if (slot >= p.command_count) continue;
+        // ---- the command (uniform)
+        const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
+        const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
+        if (c2.w == 0u) continue; // InstanceCount
+        const uint64_t vb = (uint64_t)c0.x | ((uint64_t)c0.y << 32), ib = (uint64_t)c1.x | ((uint64_t)c1.y << 32), cb = (uint64_t)c2.x | ((uint64_t)c2.y << 32);
+        const uint32_t vb_size = c0.z, stride = c0.w, ib_size = c1.z, format = c1.w;
+        const uint32_t tri_count = c2.z / 3u, start_index = c3.x;
+        const long long base_vertex = (int)c3.y;
+        if (format != UR_RASTER_INDEX_FORMAT_R32_UINT || stride < 12u || (stride & 3u) != 0u || vb == 0u || (vb & 3u) != 0u || ib == 0u || (ib & 3u) != 0u ||
+            cb == 0u || (cb & 3u) != 0u) {
+            if (seg == 0u) n_unsupported += tri_count;
+            continue;
+        }
+        const uint32_t chunks = (tri_count + 63u) / 64u;
+        if (seg >= chunks) continue;
+        float W[16];
+        {
+            const float* wp = reinterpret_cast<const float*>(cb);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) W[k] = wp[k];
+        }
+        const uint32_t* indices = reinterpret_cast<const uint32_t*>(ib);
+        const uint8_t* vertices = reinterpret_cast<const uint8_t*>(vb);
+        const uint64_t index_slots = ib_size / 4u;
+
+        for (uint32_t chunk = seg; chunk < chunks; chunk += p.segments) {
+            const uint32_t t = chunk * 64u + lane;
+            // ---- a lane per triangle: rules 1-3 and the bounding box
+            Tri tri = {};
+            int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
+            uint32_t kind = 0u; // 0 nothing to draw, 1 own lane, 2 wave, 3 large
+            bool unsupported = false, dropped = false;
+            if (t < tri_count) {
+                const uint64_t first = (uint64_t)start_index + 3ull * t;
+                float X[3], Y[3], Z[3];
+                if (first + 2u >= index_slots) unsupported = true;
+                if (!unsupported) {
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const long long vi = base_vertex + (long long)indices[first + (uint32_t)v];
+                        if (vi < 0 || (uint64_t)vi * stride + 12u > (uint64_t)vb_size) { unsupported = true; X[v] = Y[v] = Z[v] = 0.0f; continue; }
+                        float clip[4];
+                        project(reinterpret_cast<const float*>(vertices + (uint64_t)vi * stride), W, p.L, clip);
+                        if (clip[3] != 1.0f) unsupported = true;
+                        X[v] = (clip[0] + 1.0f) * p.half_w; // rule 2
+                        Y[v] = (1.0f - clip[1]) * p.half_h;
+                        Z[v] = clip[2];
+                    }
+                }
+                if (!unsupported) {
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const bool finite = fabsf(X[v]) <= 3.402823466e38f && fabsf(Y[v]) <= 3.402823466e38f && fabsf(Z[v]) <= 3.402823466e38f; // (false for NaN)
+                        if (!finite || fabsf(X[v]) > kGuardBand || fabsf(Y[v]) > kGuardBand) dropped = true;
+                    }
+                }
+                if (!unsupported && !dropped) {
+                    tri.x0 = (int)rintf(X[0] * 256.0f); tri.y0 = (int)rintf(Y[0] * 256.0f);
+                    tri.x1 = (int)rintf(X[1] * 256.0f); tri.y1 = (int)rintf(Y[1] * 256.0f);
+                    tri.x2 = (int)rintf(X[2] * 256.0f); tri.y2 = (int)rintf(Y[2] * 256.0f);
+                    const long long A = (long long)(tri.x1 - tri.x0) * (tri.y2 - tri.y0) - (long long)(tri.x2 - tri.x0) * (tri.y1 - tri.y0); // rule 3
+                    if (A > 0) {
+                        kind = 1u;
+                        const float inv = 1.0f / (float)A; // rule 5
+                        tri.z0 = Z[0];
+                        tri.k1 = (Z[1] - Z[0]) * inv;
+                        tri.k2 = (Z[2] - Z[0]) * inv;
+                        // centres 256 p + 128 inside [min, max], clamped to the target
+                        const int minx = min(tri.x0, min(tri.x1, tri.x2)), maxx = max(tri.x0, max(tri.x1, tri.x2));
+                        const int miny = min(tri.y0, min(tri.y1, tri.y2)), maxy = max(tri.y0, max(tri.y1, tri.y2));
+                        bx0 = max((minx + 127) >> 8, 0); bx1 = min((maxx - 128) >> 8, (int)p.w - 1);
+                        by0 = max((miny + 127) >> 8, 0); by1 = min((maxy - 128) >> 8, (int)p.h - 1);
+                    }
+                }
+            }
+            const uint32_t drawn = kind;
+            if (kind != 0u) {
+                if (bx0 > bx1 || by0 > by1) kind = 0u; // no centre under the box
+                else {
+                    const uint32_t pixels = (uint32_t)(bx1 - bx0 + 1) * (uint32_t)(by1 - by0 + 1);
+                    const uint32_t stamps = (uint32_t)((bx1 >> 3) - (bx0 >> 3) + 1) * (uint32_t)((by1 >> 3) - (by0 >> 3) + 1);
+                    kind = pixels <= kOwnPixels ? 1u : (stamps <= kLargeStamps ? 2u : 3u);
+                }
+            }
+            n_drawn += (uint32_t)__popcll(__ballot(drawn != 0u));
+            n_unsupported += (uint32_t)__popcll(__ballot(unsupported));
+            n_dropped += (uint32_t)__popcll(__ballot(dropped));
+
+            // ---- the smallest by their own lanes
+            if (kind == 1u) {
+                const int b01 = edge_bias(tri.x0, tri.y0, tri.x1, tri.y1), b12 = edge_bias(tri.x1, tri.y1, tri.x2, tri.y2), b20 = edge_bias(tri.x2, tri.y2, tri.x0, tri.y0);
+                for (int py = by0; py <= by1; ++py)
+                    for (int px = bx0; px <= bx1; ++px) shade(tri, b01, b12, b20, p.map, p.w, px, py);
+            }
+            // ---- the middle ones by the wave
+            unsigned long long todo = __ballot(kind == 2u);
+            while (todo != 0ull) {
+                const uint32_t s = (uint32_t)__ffsll((long long)todo) - 1u;
+                todo &= todo - 1ull;
+                const Tri u = broadcast(tri, s);
+                stamp_rect(u, p.map, p.w, rl(bx0, s), rl(by0, s), rl(bx1, s), rl(by1, s), lane);
+            }
+            // ---- the large ones to the queue, or by the wave when there is no room
+            todo = __ballot(kind == 3u);
+            while (todo != 0ull) {
+                const uint32_t s = (uint32_t)__ffsll((long long)todo) - 1u;
+                todo &= todo - 1ull;
+                const Tri u = broadcast(tri, s);
+                const int x0 = rl(bx0, s), y0 = rl(by0, s), x1 = rl(bx1, s), y1 = rl(by1, s);
+                const uint32_t tx0 = (uint32_t)x0 >> 6, ty0 = (uint32_t)y0 >> 6, tnx = ((uint32_t)x1 >> 6) - tx0 + 1u, tny = ((uint32_t)y1 >> 6) - ty0 + 1u;
+                const uint32_t tiles = tnx * tny;
+                bool queued = false;
+                if (p.queue_cap != 0u) {
+                    unsigned long long at = 0ull;
+                    if (lane == 0u) at = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(p.queue), (unsigned long long)tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    at = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(at >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)at);
+                    queued = at + tiles <= p.queue_cap;
+                    // the slots this reservation took and cannot use are marked empty
+                    const uint32_t base = (uint32_t)min(at, (unsigned long long)p.queue_cap), end = (uint32_t)min(at + tiles, (unsigned long long)p.queue_cap);
+                    for (uint32_t e = base + lane; e < end; e += 64u) {
+                        const uint32_t k = e - base, tx = tx0 + k % tnx, ty = ty0 + k / tnx;
+                        u32x4_t* q = reinterpret_cast<u32x4_t*>(p.queue + kQueueHeaderDwords + (size_t)e * kEntryDwords);
+                        const u32x4_t q0 = {(uint32_t)u.x0, (uint32_t)u.y0, (uint32_t)u.x1, (uint32_t)u.y1};
+                        const u32x4_t q1 = {(uint32_t)u.x2, (uint32_t)u.y2, __float_as_uint(u.z0), __float_as_uint(u.k1)};
+                        const u32x4_t q2 = {__float_as_uint(u.k2), queued ? (tx | (ty << 16)) : kNoTile, (uint32_t)x0 | ((uint32_t)y0 << 16), (uint32_t)x1 | ((uint32_t)y1 << 16)};
+                        q[0] = q0; q[1] = q1; q[2] = q2;
+                    }
+                }
+                if (!queued) {
+                    ++n_unqueued;
+                    stamp_rect(u, p.map, p.w, x0, y0, x1, y1, lane);
+                }
+            }
+        }
+    }
+    if (p.stats != nullptr && lane == 0u) {
+        if (n_drawn) (void)__hip_atomic_fetch_add(p.stats + 0, n_drawn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_unsupported) (void)__hip_atomic_fetch_add(p.stats + 1, n_unsupported, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_dropped) (void)__hip_atomic_fetch_add(p.stats + 2, n_dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_unqueued) (void)__hip_atomic_fetch_add(p.stats + 3, n_unqueued, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The largest value of the edge function a->b over the centres of the pixels [px0, px1] x [py0, py1]: below zero, no centre passes
+__device__ __forceinline__ long long edge_max(int ax, int ay, int bx, int by, int px0, int py0, int px1, int py1)
+{
+    const int dx = bx - ax, dy = by - ay;
+    const int sy = 256 * (dx > 0 ? py1 : py0) + 128, sx = 256 * (dy > 0 ? px0 : px1) + 128;
+    return (long long)dx * (sy - ay) - (long long)dy * (sx - ax);
+}
+
+__global__ __launch_bounds__(kThreads) void shadow_large_kernel(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    const uint32_t wave_count = gridDim.x * kWaves;
+    const uint32_t count = (uint32_t)min(*reinterpret_cast<const unsigned long long*>(queue), (unsigned long long)queue_cap);
+    for (uint32_t e = wave; e < count; e += wave_count) {
+        const u32x4_t* q = reinterpret_cast<const u32x4_t*>(queue + kQueueHeaderDwords + (size_t)e * kEntryDwords);
+        const u32x4_t q0 = q[0], q1 = q[1], q2 = q[2];
+        if (q2.y == kNoTile) continue;
+        Tri t;
+        t.x0 = (int)q0.x; t.y0 = (int)q0.y; t.x1 = (int)q0.z; t.y1 = (int)q0.w; t.x2 = (int)q1.x; t.y2 = (int)q1.y;
+        t.z0 = __uint_as_float(q1.z); t.k1 = __uint_as_float(q1.w); t.k2 = __uint_as_float(q2.x);
+        const int tx = (int)(q2.y & 0xFFFFu) * 64, ty = (int)(q2.y >> 16) * 64;
+        const int px0 = max((int)(q2.z & 0xFFFFu), tx), py0 = max((int)(q2.z >> 16), ty);
+        const int px1 = min((int)(q2.w & 0xFFFFu), tx + 63), py1 = min((int)(q2.w >> 16), ty + 63);
+        if (edge_max(t.x0, t.y0, t.x1, t.y1, px0, py0, px1, py1) < 0 || edge_max(t.x1, t.y1, t.x2, t.y2, px0, py0, px1, py1) < 0 ||
+            edge_max(t.x2, t.y2, t.x0, t.y0, px0, py0, px1, py1) < 0)
+            continue;
+        stamp_rect(t, map, w, px0, py0, px1, py1, lane);
+    }
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0u; }
+
+} // namespace
+
+extern "C" {
+
+int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items)
+{
+    if (!ctx) { ur::set_error("ur_raster_reserve: null context"); return UR_EINVAL; }
+    if (max_large_work_items == ctx->raster_queue_cap) return UR_OK;
+    UR_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->raster_queue) (void)hipFree(ctx->raster_queue);
+    ctx->raster_queue = nullptr;
+    ctx->raster_queue_cap = 0;
+    if (max_large_work_items == 0u) return UR_OK;
+    const size_t bytes = ((size_t)kQueueHeaderDwords + (size_t)max_large_work_items * kEntryDwords) * sizeof(uint32_t);
+    if (hipMalloc(&ctx->raster_queue, bytes) != hipSuccess) {
+        ctx->raster_queue = nullptr;
+        ur::set_error("ur_raster_reserve: allocation of %u large work items failed", max_large_work_items);
+        return UR_ENOMEM;
+    }
+    ctx->raster_queue_cap = max_large_work_items;
+    return UR_OK;
+}
+
+int ur_shadow_map(ur_ctx* ctx, const float* lvp, const ur_raster_draws* draws, float* shadow_map, uint32_t w, uint32_t h, uint32_t* stats4)
+{
+    if (!ctx || !lvp || !draws || !shadow_map) { ur::set_error("ur_shadow_map: null context, matrix, draws or map"); return UR_EINVAL; }
+    if (w == 0u || h == 0u || w > UR_RASTER_MAX_TARGET || h > UR_RASTER_MAX_TARGET) { ur::set_error("ur_shadow_map: a %u x %u map (1..%u)", w, h, UR_RASTER_MAX_TARGET); return UR_EINVAL; }
+    const bool list = draws->visible_idx != nullptr || draws->visible_count != nullptr;
+    if (list && (!draws->visible_idx || !draws->visible_count)) { ur::set_error("ur_shadow_map: a list needs visible_idx and visible_count"); return UR_EINVAL; }
+    if (list && draws->ranges) { ur::set_error("ur_shadow_map: a list and ranges at once"); return UR_EINVAL; }
+    const ur_draw_ranges* rg = draws->ranges;
+    if (rg && (!rg->offsets || !rg->commands || !rg->counts || rg->range_count == 0u)) { ur::set_error("ur_shadow_map: a null member of ranges / no range"); return UR_EINVAL; }
+    const void* commands = rg ? rg->commands : draws->commands;
+    if (!commands && draws->command_count != 0u) { ur::set_error("ur_shadow_map: null commands"); return UR_EINVAL; }
+    if (!aligned(commands, 16) || !aligned(shadow_map, 4) || !aligned(stats4, 4) || !aligned(draws->visible_idx, 4) || !aligned(draws->visible_count, 4) ||
+        (rg && (!aligned(rg->offsets, 4) || !aligned(rg->counts, 4)))) {
+        ur::set_error("ur_shadow_map: a misaligned buffer (commands 16 bytes, the others 4)");
+        return UR_EINVAL;
+    }
+    if (!(lvp[3] == 0.0f && lvp[7] == 0.0f && lvp[11] == 0.0f && lvp[15] == 1.0f)) {
+        ur::set_error("ur_shadow_map: the light's fourth column is (%g, %g, %g, %g), not (0, 0, 0, 1): only orthographic lights are rasterised", lvp[3], lvp[7], lvp[11], lvp[15]);
+        return UR_EUNSUPPORTED;
+    }
+
+    const uint32_t n = w * h;
+    const uint32_t head = min((uint32_t)((16u - (reinterpret_cast<uintptr_t>(shadow_map) & 15u)) & 15u) / 4u, n);
+    uint32_t* queue = ctx->raster_queue_cap != 0u ? ctx->raster_queue : nullptr;
+    const uint32_t clear_blocks = min((n / 4u + kThreads - 1u) / kThreads + 1u, (uint32_t)ctx->cu_count * 16u);
+    hipLaunchKernelGGL(shadow_clear_kernel, dim3(clear_blocks), dim3(kThreads), 0, ctx->stream, shadow_map, n, head, queue);
+    UR_HIP_TRY(hipGetLastError());
+    if (draws->command_count == 0u) return UR_OK;
+
+    RasterParams p{};
+    p.commands = static_cast<const uint8_t*>(commands);
+    p.command_count = draws->command_count;
+    p.mode = list ? 1u : (rg ? 2u : 0u);
+    p.visible_idx = draws->visible_idx; p.visible_count = draws->visible_count; p.index_base = draws->index_base;
+    if (rg) { p.range_count = rg->range_count; p.offsets = rg->offsets; p.counts = rg->counts; }
+    for (int k = 0; k < 16; ++k) p.L[k] = lvp[k];
+    p.map = reinterpret_cast<uint32_t*>(shadow_map);
+    p.w = w; p.h = h;
+    p.half_w = 0.5f * (float)w; p.half_h = 0.5f * (float)h;
+    p.stats = stats4;
+    p.queue = queue; p.queue_cap = queue ? ctx->raster_queue_cap : 0u;
+    // enough (candidate, segment) waves to fill the device whatever the command count: index counts live on the device
+    const uint32_t want_waves = (uint32_t)ctx->cu_count * 16u;
+    p.segments = max(1u, min(1024u, want_waves / p.command_count));
+    const uint64_t items = (uint64_t)p.command_count * p.segments;
+    p.items = (uint32_t)items;
+    if (items > 0xFFFFFFFFull) { p.segments = 1u; p.items = p.command_count; }
+    const uint32_t blocks = min((p.items + kWaves - 1u) / kWaves, (uint32_t)ctx->cu_count * 32u);
+    hipLaunchKernelGGL(shadow_raster_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
+    UR_HIP_TRY(hipGetLastError());
+    if (queue) {
+        hipLaunchKernelGGL(shadow_large_kernel, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, queue, p.queue_cap, p.map, w);
+        UR_HIP_TRY(hipGetLastError());
+    }
+    return UR_OK;
+}
+
+} // extern "C"

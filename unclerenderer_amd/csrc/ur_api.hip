@@ -203,6 +203,7 @@ void ur_destroy(ur_ctx* ctx)
     if (ctx->srgb_table) (void)hipFree(ctx->srgb_table);
     if (ctx->block_counts) (void)hipFree(ctx->block_counts);
     if (ctx->wave_masks) (void)hipFree(ctx->wave_masks);
+    if (ctx->raster_queue) (void)hipFree(ctx->raster_queue);
     delete ctx;
 }
 

@@ -75,6 +75,9 @@ struct ur_ctx {
     // host-visible (mapped, coherent) word beside hzb_timed_out: a wave of a balanced launch gave up waiting for a claim
     volatile uint32_t* claim_timed_out = nullptr;
     uint32_t* claim_timed_out_dev = nullptr;
+    // ur_raster_reserve: the large-triangle queue of ur_shadow_map (csrc/shadow_raster.hip): a 64-byte header (the count) + entries
+    uint32_t* raster_queue = nullptr;
+    uint32_t raster_queue_cap = 0;
 };
 
 namespace ur {

@@ -679,6 +679,104 @@ def _frame_set_debug_print(self, buffer=None, glyphs=None, atlas=None, first_cha
 Frame.set_debug_print = _frame_set_debug_print
 
 
+# ---- ShadowMap (include/ur_raster.h) ----
+
+def pack_draw_commands(draws) -> np.ndarray:
+    """FIndirectDrawCommand slots (RendererUtils.h:102-111) as uint32[n, 16] from dicts of device tensors and numbers:
+    vertices (any contiguous tensor; the view is its whole storage unless vertex_bytes says less), stride (bytes of a vertex, 64 in the
+    reference), indices (int32 / uint32 tensor), constants (tensor whose first 64 bytes are World; constants_offset bytes into it),
+    index_count (default: every index behind start_index), instance_count (1), start_index (0), base_vertex (0), index_format (42 =
+    R32_UINT). Upload the result with to_device; the tensors must outlive the commands that point at them."""
+    out = np.zeros((len(draws), 16), np.uint32)
+    for row, d in zip(out, draws):
+        v, i, c = d["vertices"], d["indices"], d["constants"]
+        for t in (v, i, c):
+            assert t.is_cuda and t.is_contiguous(), "device tensors must be contiguous CUDA/HIP tensors"
+        va, ia, ca = v.data_ptr(), i.data_ptr(), c.data_ptr() + int(d.get("constants_offset", 0))
+        index_slots = i.numel() * i.element_size() // 4
+        start = int(d.get("start_index", 0))
+        row[0], row[1] = va & 0xFFFFFFFF, va >> 32
+        row[2] = int(d.get("vertex_bytes", v.numel() * v.element_size()))
+        row[3] = int(d.get("stride", 64))
+        row[4], row[5] = ia & 0xFFFFFFFF, ia >> 32
+        row[6] = int(d.get("index_bytes", index_slots * 4))
+        row[7] = int(d.get("index_format", _lib.UR_RASTER_INDEX_FORMAT_R32_UINT))
+        row[8], row[9] = ca & 0xFFFFFFFF, ca >> 32
+        row[10] = int(d.get("index_count", max(index_slots - start, 0)))
+        row[11] = int(d.get("instance_count", 1))
+        row[12] = start
+        row[13] = np.int64(d.get("base_vertex", 0)).astype(np.int32).view(np.uint32)
+    return out
+
+
+def raster_draws(commands, command_count=None, visible=None, ranges=None, index_base=0) -> _lib.RasterDraws:
+    """ur_raster_draws over device tensors. commands: n * 64 bytes (None with ranges). visible: (visible_idx, visible_count) device
+    tensors. ranges: a draw_ranges(...) result, or (offsets, commands, counts) device tensors. Keeps them alive."""
+    d = _lib.RasterDraws()
+    keep = [commands]
+    if commands is not None:
+        assert commands.is_cuda and commands.is_contiguous()
+        d.commands = commands.data_ptr()
+    if ranges is not None and not isinstance(ranges, _lib.DrawRanges):
+        ranges = draw_ranges(*ranges)
+    if command_count is None:
+        src = ranges._keep[1] if ranges is not None else commands
+        command_count = src.numel() * src.element_size() // _lib.UR_INDIRECT_COMMAND_STRIDE if src is not None else 0
+    d.command_count = int(command_count)
+    if visible is not None:
+        idx, cnt = visible
+        d.visible_idx = idx.data_ptr() if idx is not None else None
+        d.visible_count = cnt.data_ptr() if cnt is not None else None
+        keep += [idx, cnt]
+    d.index_base = int(index_base)
+    if ranges is not None:
+        d.ranges = C.pointer(ranges)
+        keep.append(ranges)
+    d._keep = keep
+    return d
+
+
+def _shadow_map(self, lvp, commands, shadow_map, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None, size=None):
+    """ur_shadow_map: clear shadow_map ((h, w) float32 device tensor, or flat with size=(w, h)) to 1.0 and rasterise the selected draws
+    of `commands` (pack_draw_commands, uploaded) under the orthographic light matrix lvp (16 floats, row-major, row-vector
+    convention). visible=(visible_idx, visible_count) or ranges=(offsets, commands, counts) select; stats: uint32[4] device tensor,
+    added to."""
+    w, h = size if size is not None else (int(shadow_map.shape[1]), int(shadow_map.shape[0]))
+    assert shadow_map.dtype == torch.float32 and shadow_map.numel() >= w * h
+    m = np.ascontiguousarray(lvp, np.float32).reshape(-1)
+    assert m.size == 16
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    _lib.check(self._L.ur_shadow_map(self._ctx, _lib.fptr(m), C.byref(d), _ptr(shadow_map), w, h, _ptr(stats)), "ur_shadow_map")
+
+
+def _raster_reserve(self, max_large_work_items: int):
+    """ur_raster_reserve: room for that many (triangle, 64 x 64 tile) entries of the large-triangle queue; 0 frees it."""
+    _lib.check(self._L.ur_raster_reserve(self._ctx, int(max_large_work_items)), "ur_raster_reserve")
+
+
+HotPath.shadow_map = _shadow_map
+HotPath.raster_reserve = _raster_reserve
+
+
+def _frame_set_shadow_pass(self, commands=None, shadow_map=None, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None):
+    """ur_frame_set_shadow_pass: the draws (as in HotPath.shadow_map), the map and the optional counters of the frames rendered with
+    UR_FRAME_SHADOW_PASS (device tensors, kept alive here). No arguments: clear."""
+    if commands is None and shadow_map is None and ranges is None:
+        self._shadow_pass_keep = None
+        _lib.check(self._L.ur_frame_set_shadow_pass(self._f, None), "ur_frame_set_shadow_pass")
+        return
+    sp = _lib.FrameShadowPass()
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    sp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
+    sp.shadow_map = shadow_map.data_ptr() if shadow_map is not None else None
+    sp.stats4 = stats.data_ptr() if stats is not None else None
+    _lib.check(self._L.ur_frame_set_shadow_pass(self._f, C.byref(sp)), "ur_frame_set_shadow_pass")
+    self._shadow_pass_keep = (d, shadow_map, stats)
+
+
+Frame.set_shadow_pass = _frame_set_shadow_pass
+
+
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:
     """numpy -> device tensor, reinterpreting unsigned dtypes torch cannot hold (bit patterns are preserved)."""
     a = np.ascontiguousarray(a)

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_host.h).
+"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_host.h).
 
 The shared library is the product; there is no Python or CPU fallback. If it is missing, importing the compute
 entry points raises — build it with `python -m unclerenderer_amd.build` (hipcc, gfx950).
@@ -45,6 +45,21 @@ class CullView(C.Structure):
     """ur_cull_view (include/ur_hotpath.h): one extra frustum-only view of ur_cull_indirect_args_views."""
     _fields_ = [("planes", C.c_float * 24), ("mask", C.c_void_p), ("visible_idx", C.c_void_p), ("visible_count", C.c_void_p),
                 ("draws", C.POINTER(DrawRanges))]
+
+
+class RasterDraws(C.Structure):
+    """ur_raster_draws (include/ur_raster.h): the command slots of a raster pass and which of them to draw."""
+    _fields_ = [("commands", C.c_void_p), ("command_count", C.c_uint32), ("visible_idx", C.c_void_p), ("visible_count", C.c_void_p),
+                ("index_base", C.c_uint32), ("ranges", C.POINTER(DrawRanges))]
+
+
+class FrameShadowPass(C.Structure):
+    """ur_frame_shadow_pass (include/ur_frame.h): the draws, target and optional counters of UR_FRAME_SHADOW_PASS."""
+    _fields_ = [("draws", RasterDraws), ("shadow_map", C.c_void_p), ("stats4", C.c_void_p)]
+
+
+UR_RASTER_MAX_TARGET = 16384
+UR_RASTER_INDEX_FORMAT_R32_UINT = 42
 
 
 class HzbSlice(C.Structure):
@@ -192,6 +207,7 @@ UR_FRAME_TAA = 0x800000
 UR_FRAME_FUSE_TAA_TONEMAP = 0x1000000
 UR_FRAME_TAA_BAND = 0x2000000
 UR_FRAME_DEBUG_PRINT = 0x4000000
+UR_FRAME_SHADOW_PASS = 0x8000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -261,6 +277,9 @@ SIGNATURES = {
     "ur_allgather_rows": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32]),
     "ur_allgather_rows_bytes_ex": (C.c_int, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.c_int]),
+    # ur_raster.h
+    "ur_shadow_map": (C.c_int, [_VP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _VP]),
+    "ur_raster_reserve": (C.c_int, [_VP, _U32]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
@@ -292,6 +311,7 @@ SIGNATURES = {
     "ur_frame_set_taa_records": (C.c_int, [_VP, _VP, _VP]),
     "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_set_debug_print": (C.c_int, [_VP, C.POINTER(FrameDebugPrint)]),
+    "ur_frame_set_shadow_pass": (C.c_int, [_VP, C.POINTER(FrameShadowPass)]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
