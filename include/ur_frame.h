@@ -110,6 +110,15 @@ typedef struct ur_frame_resources {
  * and culled, as in the reference. On a row band every rank renders the whole map (a replicated side table, like the HZB). Without
  * the flag nothing of this happens: the frame is what it is today. */
 #define UR_FRAME_SHADOW_PASS 0x8000000u
+/* "DepthPrepass" pass behind "ShadowMap" (behind "GPU Culling" when there is none) and in front of "Build HZB"
+ * (DeferredRenderer.cpp:635-718), with UR_FRAME_DEPTH_PREPASS: ur_depth_prepass of ur_frame_set_depth_pass' draws with scene->View and
+ * scene->Projection into its depth, width x height texels, on the main stream (with UR_FRAME_ASYNC_COMPUTE behind a wait on the cull,
+ * whose lists and ranges it draws from; Build HZB then waits for the pass). Build HZB reads that buffer: depth_full must be the pass's
+ * depth and a pass must be set (else UR_EINVAL). The frame then runs cull -> DepthPrepass -> Build HZB -> next frame's cull with no
+ * imported depth. Without UR_FRAME_DEPTH_PREPASS the pass is listed and culled, as in the reference when the prepass is off. On a row
+ * band every rank renders the whole buffer (replicated, like the HZB and the shadow map). Without the flag nothing of this happens:
+ * the frame is what it is today. */
+#define UR_FRAME_DEPTH_PASS 0x10000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -216,6 +225,17 @@ typedef struct ur_frame_shadow_pass {
     uint32_t* stats4;
 } ur_frame_shadow_pass;
 int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass);
+
+/* The draws, the target, the optional counters (ur_depth_prepass' stats6; the caller zeroes them) and ur_depth_prepass' flags of the
+ * frames rendered with UR_FRAME_DEPTH_PASS; kept as ur_frame_set_shadow_pass keeps its struct. NULL clears. UR_EINVAL for a null frame,
+ * a null depth and what ur_depth_prepass refuses in the draws, the alignment and the flags. */
+typedef struct ur_frame_depth_pass {
+    ur_raster_draws draws;
+    float* depth;
+    uint32_t* stats6;
+    uint32_t flags;
+} ur_frame_depth_pass;
+int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

@@ -2,6 +2,8 @@
  * ur_raster.h — C face of the raster passes: the ShadowMap pass (DeferredRenderer.cpp:551-633, Shaders/ShadowMap.hlsl), a depth-only
  * raster of indexed triangle lists under an orthographic light into an R32F map. The raster rule is DESIGN.md section 3.7; its numpy
  * restatement is tests/shadow_ref.py, and the two agree on every byte.
+ * The DepthPrepass pass (DeferredRenderer.cpp:635-718, Shaders/DeferredBasePass.hlsl:58-70): the same raster under a perspective camera
+ * with a near clip, reverse-Z, into the camera's depth buffer. Its rule is DESIGN.md section 3.8, restated in tests/depth_ref.py.
  */
 #ifndef UR_RASTER_H
 #define UR_RASTER_H
@@ -60,6 +62,33 @@ int ur_shadow_map(ur_ctx* ctx, const float light_view_projection[16], const ur_r
  * queue. Optional for correctness: without room every large triangle is rasterised where it is found and counted in stats4[3].
  * Synchronises the context's stream when it has to replace a queue (call it at set-up). UR_ENOMEM when the allocation fails. */
 int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items);
+
+#define UR_DEPTH_QUANTIZE_D24 0x1u /* every fragment stores (float)(rint((double)z * 16777215.0) / 16777215.0): a D24_UNORM target read through its R24 view */
+#define UR_DEPTH_GUARD_BAND 2097152u /* the DepthPrepass guard band in pixels (2^21): snapped coordinates stay below 2^29 */
+
+/* The DepthPrepass pass: every texel of depth (w x h floats, row-major, 4-byte aligned) is set to 0.0f, then the selected draws are
+ * rasterised by the rule of DESIGN.md 3.8 (position * World * View * Projection, the near clip z <= w, CULL_MODE_BACK with
+ * FrontCounterClockwise, GREATER_EQUAL on a reverse-Z target): a texel ends as the maximum depth, clamped to 1.0f, of the fragments that
+ * cover its centre. The bytes do not depend on the order of anything.
+ * view, projection: host, 16 floats each, row-major, row-vector convention - scene->View and scene->Projection; they are multiplied
+ * per vertex in that order, never with each other. Asynchronous on the context's stream; the host neither reads device memory nor
+ * synchronises; at most three launches (clear, raster, and the large-triangle queue when ur_raster_reserve gave one).
+ * Read: the selected command slots; of each drawn slot its index range, the 12 POSITION bytes of the vertices that range names and
+ * the first 64 bytes behind ConstantBufferAddress; visible_count[0] and the list entries in front of it, or the ranges' offsets and
+ * counts. Nothing else of these buffers is read, and none of them is written.
+ * Written: all w * h floats of depth, and nothing around them. stats6 is added to. The large-triangle queue is the context's own.
+ * flags: UR_DEPTH_QUANTIZE_D24 or 0.
+ * stats6: device u32[6] or NULL, added to (the caller zeroes): [0] emitted triangles rasterised (they passed every test below and
+ * face the camera: they may still cover no centre), [1] triangles skipped as unsupported - a vertex with a non-finite clip coordinate
+ * or clip z <= 0 (a projection that is not reverse-Z with an infinite far plane), and the command, index and vertex cases of
+ * ur_shadow_map -, [2] emitted triangles dropped for a non-finite target coordinate or a vertex outside the guard band (|X| or |Y| >
+ * 2^21 px: side planes are not clipped, the caller splits such triangles), [3] large triangles that did not fit the reserved queue
+ * and were rasterised by the wave that found them, [4] triangles cut by the near plane (one or two vertices behind it; one behind
+ * emits two triangles), [5] triangles wholly behind the near plane.
+ * UR_EINVAL, nothing launched: ur_shadow_map's cases (with view, projection and depth for the matrix and the map), and flag bits
+ * other than UR_DEPTH_QUANTIZE_D24. */
+int ur_depth_prepass(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                     float* depth, uint32_t w, uint32_t h, uint32_t flags, uint32_t* stats6);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 
     python tools/bench_shadow.py [--batches 7] [--iters 10] [--json out.jsonl]
     python tools/bench_shadow.py --quick     # each workload a few times: for a rocprofv3 --kernel-trace --stats run
+    python tools/bench_shadow.py --pass both # ShadowMap, then the DepthPrepass pass (ur_depth_prepass) over the same triangles
 
 A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
   small   1 M triangles of 1/8 px to 8 px in one command;
@@ -11,9 +12,14 @@ A 2048 x 2048 map over three workloads, each with and without a large-triangle q
 Each time is one device-event pair around a batch of back-to-back calls over rotating buffer sets (cold maps), divided by the calls
 (launch gaps included). Beside them, measured in the same run, the yardstick that exists today: the clear alone (a call with no
 commands launches only the clear: 16.8 MB of stores). The per-launch split (clear / raster / large) comes from a separate rocprofv3
---kernel-trace --stats run of --quick: the kernels are shadow_clear_kernel, shadow_raster_kernel and shadow_large_kernel. The second
-yardstick of the plan - a plain kernel issuing the same number of contiguous atomic-minimum bytes - needs a fragment count the pass
-does not keep and is not built.
+--kernel-trace --stats run of --quick: the kernels are shadow_clear_kernel, raster_kernel<ShadowPolicy> and large_kernel<ShadowPolicy>
+(<DepthPolicy<...>> for the prepass). The second yardstick of the plan - a plain kernel issuing the same number of contiguous
+atomic-minimum bytes - needs a fragment count the pass does not keep and is not built.
+
+The depth leg draws the same triangles under a perspective camera: a vertex at clip (x, y, z) becomes the view-space position
+(x * v, y * v, v) with v = NEAR / z, under View = identity and the projection clip = (x, y, NEAR, w = view z), its triangle's winding
+reversed (the prepass draws the other facing). It lands on the same pixel up to the rounding of x * v / v, with the same depth order
+reversed (reverse-Z): the same fragments, a maximum instead of a minimum, plus the three products, the near-plane test and the divides.
 """
 import argparse
 import json
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--small", type=int, default=1_000_000)
     ap.add_argument("--reserve", type=int, default=1 << 19)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both"), default="shadow")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     if a.quick:
@@ -75,34 +82,51 @@ def main():
         vb, ib = to_device(v.reshape(-1)), to_device(np.arange(pos.shape[0], dtype=np.uint32))
         return dict(vertices=vb, indices=ib, constants=world, stride=64)
 
-    small, large = mesh(triangles(rng, a.small, 0.125, 8.0)), mesh(triangles(rng, 256, SIZE, 2 * SIZE))
-    loads = {"small": [small], "large": [large], "mix": [small, large]}
-    cmds = {k: to_device(pack_draw_commands(v)) for k, v in loads.items()}
+    NEAR = 0.125
+    view = np.eye(4, dtype=np.float32).reshape(-1)
+    proj = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, NEAR, 0], np.float32)
+
+    def camera_space(pos):
+        v = NEAR / pos[:, 2:3].astype(np.float64)
+        p = np.concatenate([pos[:, :2] * v, v], axis=1).astype(np.float32)
+        return p.reshape(-1, 3, 3)[:, [0, 2, 1]].reshape(-1, 3)
+
+    small_pos, large_pos = triangles(rng, a.small, 0.125, 8.0), triangles(rng, 256, SIZE, 2 * SIZE)
+    legs = []
+    if a.which in ("shadow", "both"):
+        small, large = mesh(small_pos), mesh(large_pos)
+        legs.append(("", 4, {"small": [small], "large": [large], "mix": [small, large]},
+                     lambda c, m, st: hp.shadow_map(lvp, c, m, stats=st, command_count=None if c is not None else 0)))
+    if a.which in ("depth", "both"):
+        small, large = mesh(camera_space(small_pos)), mesh(camera_space(large_pos))
+        legs.append(("depth prepass, ", 6, {"small": [small], "large": [large], "mix": [small, large]},
+                     lambda c, m, st: hp.depth_prepass(view, proj, c, m, stats=st, command_count=None if c is not None else 0)))
     maps = [torch.empty((SIZE, SIZE), dtype=torch.float32, device="cuda") for _ in range(a.ring)]
-    stats = torch.zeros(4, dtype=torch.int32, device="cuda")
     rows = []
-    for reserve in (a.reserve, 0):
-        hp.raster_reserve(reserve)
-        shapes = {"clear alone": None, **cmds}
-        fns = {k: (lambda i, c=c: hp.shadow_map(lvp, c, maps[i % a.ring], stats=stats if c is not None else None, command_count=None if c is not None else 0))
-               for k, c in shapes.items()}
-        seen = {}
-        for k, f in fns.items():
-            stats.zero_()
-            f(0)
-            torch.cuda.synchronize()
-            seen[k] = stats.cpu().numpy().view(np.uint32).tolist()
-        times = {k: [] for k in fns}
-        for _ in range(a.batches):
+    for label, nstats, loads, call in legs:
+        cmds = {k: to_device(pack_draw_commands(v)) for k, v in loads.items()}
+        stats = torch.zeros(nstats, dtype=torch.int32, device="cuda")
+        for reserve in (a.reserve, 0):
+            hp.raster_reserve(reserve)
+            shapes = {"clear alone": None, **cmds}
+            fns = {k: (lambda i, c=c: call(c, maps[i % a.ring], stats if c is not None else None)) for k, c in shapes.items()}
+            seen = {}
             for k, f in fns.items():
-                times[k].append(time_batch(torch, f, a.iters))
-        for k, t in times.items():
-            rows.append({"shape": f"{SIZE}x{SIZE}, {k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
-                         "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
+                stats.zero_()
+                f(0)
+                torch.cuda.synchronize()
+                seen[k] = stats.cpu().numpy().view(np.uint32).tolist()
+            times = {k: [] for k in fns}
+            for _ in range(a.batches):
+                for k, f in fns.items():
+                    times[k].append(time_batch(torch, f, a.iters))
+            for k, t in times.items():
+                rows.append({"shape": f"{SIZE}x{SIZE}, {label}{k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
+                             "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
     hp.raster_reserve(0)
     hp.close()
     for r in rows:
-        print(f"{r['shape']:48s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
+        print(f"{r['shape']:64s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
     if a.json:
         with open(a.json, "a") as f:
             for r in rows:

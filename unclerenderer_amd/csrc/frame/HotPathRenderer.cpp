@@ -72,6 +72,15 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         ShadowDrawsHandle = Graph.ImportTexture("ShadowDraws", const_cast<void*>(Draws), &Res.ShadowDrawsState, {D.command_count, 1, RG_FORMAT_UNKNOWN});
     }
 
+    // DepthPrepass: the same for the camera's draws
+    const bool bDepthPass = Options.bDepthPass && Res.DepthDraws != nullptr && Res.DepthTarget != nullptr;
+    FRGResourceHandle DepthDrawsHandle;
+    if (bDepthPass) {
+        const ur_raster_draws& D = *Res.DepthDraws;
+        const void* Draws = D.ranges ? D.ranges->commands : (D.visible_idx ? static_cast<const void*>(D.visible_idx) : D.commands);
+        DepthDrawsHandle = Graph.ImportTexture("DepthDraws", const_cast<void*>(Draws), &Res.DepthDrawsState, {D.command_count, 1, RG_FORMAT_UNKNOWN});
+    }
+
     const bool bHZBEnabled = Options.bHZBEnabled && Res.HZB != nullptr && Res.HZBMipCount != 0;
     if (!bHZBEnabled) bHZBReady = false; // :514-517
     const bool bUseHZBOcclusion = bHZBEnabled && bHZBReady; // ConfigureHZBOcclusion, :519-520
@@ -101,6 +110,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         if (Data.bEnabled) {
             if (bUseHZBOcclusion) Builder.ReadTexture(HZBHandle, RG_STATE_NON_PIXEL_SHADER_RESOURCE);
             if (bShadowPass && Options.bRenderShadows) Builder.WriteTexture(ShadowDrawsHandle, RG_STATE_UNORDERED_ACCESS); // the light view's list / ranges
+            if (bDepthPass && Options.bDoDepthPrepass) Builder.WriteTexture(DepthDrawsHandle, RG_STATE_UNORDERED_ACCESS);   // the camera's list / ranges
             Builder.KeepAlive();
             // Neither visibility pass shares a resource with Lighting/Sky inside a frame (the cull reads LAST frame's
             // HZB), so both can run beside the VALU-bound lighting kernel on the second stream.
@@ -147,6 +157,35 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
             if (!Data.bEnabled) return;
             // ClearDepth(1.0) and the draws of :571-631, on the stream the pass runs on (the main one: it is not an async-compute pass)
             const int rc = ur_shadow_map(Cmd.GetContext(), Data.LightViewProjection, Res.ShadowDraws, Res.ShadowMapTarget, Data.Width, Data.Height, Res.ShadowStats);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
+    }
+
+    // ---- DepthPrepass (:635-718): the camera's draws, depth only, into the buffer Build HZB reads ---------------------------------
+    struct FDepthPrepassData
+    {
+        bool bEnabled = false;
+        float View[16] = {}, Projection[16] = {};
+        uint32 Width = 0, Height = 0, Flags = 0;
+    };
+    if (bDepthPass) {
+        Graph.AddPass<FDepthPrepassData>("DepthPrepass", [&](FDepthPrepassData& Data, FRGPassBuilder& Builder)
+        {
+            Data.bEnabled = Options.bDoDepthPrepass;
+            std::memcpy(Data.View, Constants.Scene.View, sizeof(Data.View));
+            std::memcpy(Data.Projection, Constants.Scene.Projection, sizeof(Data.Projection));
+            Data.Width = Res.Width;
+            Data.Height = Res.Height;
+            Data.Flags = Res.DepthPassFlags;
+            if (Data.bEnabled) {
+                if (bCullEnabled) Builder.ReadTexture(DepthDrawsHandle, RG_STATE_INDIRECT_ARGUMENT); // (on the async lane: the wait on the cull)
+                Builder.WriteTexture(DepthHandle, RG_STATE_DEPTH_WRITE);
+            }
+        }, [this, &Res](const FDepthPrepassData& Data, FHIPCommandContext& Cmd)
+        {
+            if (!Data.bEnabled) return;
+            // ClearDepth(0.0) and the draws of :655-716, on the main stream: Build HZB (on the async lane: behind a wait) reads what it wrote
+            const int rc = ur_depth_prepass(Cmd.GetContext(), Data.View, Data.Projection, Res.DepthDraws, Res.DepthTarget, Data.Width, Data.Height, Data.Flags, Res.DepthStats);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -704,6 +743,9 @@ struct ur_frame
     ur_frame_shadow_pass ShadowPass = {}; // ur_frame_set_shadow_pass (draws.ranges points into ShadowRanges)
     ur_draw_ranges ShadowRanges = {};
     bool bShadowPass = false;
+    ur_frame_depth_pass DepthPass = {};   // ur_frame_set_depth_pass (draws.ranges points into DepthRanges)
+    ur_draw_ranges DepthRanges = {};
+    bool bDepthPass = false;
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -861,6 +903,13 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
             return UR_EINVAL;
         }
     }
+    if (flags & UR_FRAME_DEPTH_PASS) {
+        if (!f->bDepthPass) { ur::set_error("ur_frame_render: DEPTH_PASS needs ur_frame_set_depth_pass"); return UR_EINVAL; }
+        if (r->depth_full != f->DepthPass.depth) {
+            ur::set_error("ur_frame_render: DEPTH_PASS renders into ur_frame_set_depth_pass' depth, Build HZB reads depth_full: they must be the same buffer");
+            return UR_EINVAL;
+        }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -905,6 +954,11 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.ShadowDraws = shadow_pass ? &f->ShadowPass.draws : nullptr;
     R.ShadowMapTarget = shadow_pass ? f->ShadowPass.shadow_map : nullptr;
     R.ShadowStats = shadow_pass ? f->ShadowPass.stats4 : nullptr;
+    const bool depth_pass = (flags & UR_FRAME_DEPTH_PASS) != 0 && f->bDepthPass;
+    R.DepthDraws = depth_pass ? &f->DepthPass.draws : nullptr;
+    R.DepthTarget = depth_pass ? f->DepthPass.depth : nullptr;
+    R.DepthStats = depth_pass ? f->DepthPass.stats6 : nullptr;
+    R.DepthPassFlags = depth_pass ? f->DepthPass.flags : 0u;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -937,6 +991,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bTaaBand = (flags & UR_FRAME_TAA_BAND) != 0;
     O.bDebugPrint = (flags & UR_FRAME_DEBUG_PRINT) != 0;
     O.bShadowPass = shadow_pass;
+    O.bDepthPass = depth_pass;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -1032,6 +1087,43 @@ int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp)
     return UR_OK;
 }
 
+// What ur_shadow_map / ur_depth_prepass refuse in a pass struct's draws, target and counters; `who` and `target_name` go into the error text
+static int check_raster_pass(const char* who, const char* target_name, const ur_raster_draws& d, const void* target, const void* stats)
+{
+    const ur_draw_ranges* rg = d.ranges;
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
+    if (!target) { ur::set_error("%s: null %s", who, target_name); return UR_EINVAL; }
+    if ((d.visible_idx != nullptr) != (d.visible_count != nullptr)) { ur::set_error("%s: a list needs visible_idx and visible_count", who); return UR_EINVAL; }
+    if (d.visible_idx && rg) { ur::set_error("%s: a list and ranges at once", who); return UR_EINVAL; }
+    if (rg && (!rg->offsets || !rg->commands || !rg->counts || rg->range_count == 0)) { ur::set_error("%s: a null member of ranges / no range", who); return UR_EINVAL; }
+    if (!rg && !d.commands && d.command_count != 0) { ur::set_error("%s: null commands", who); return UR_EINVAL; }
+    if (misaligned(rg ? rg->commands : d.commands, 16) || misaligned(target, 4) || misaligned(stats, 4) || misaligned(d.visible_idx, 4) ||
+        misaligned(d.visible_count, 4) || (rg && (misaligned(rg->offsets, 4) || misaligned(rg->counts, 4)))) {
+        ur::set_error("%s: a misaligned buffer (commands 16 bytes, the others 4)", who);
+        return UR_EINVAL;
+    }
+    return UR_OK;
+}
+
+int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass)
+{
+    if (!f) { ur::set_error("ur_frame_set_depth_pass: null frame"); return UR_EINVAL; }
+    if (!pass) {
+        f->bDepthPass = false;
+        f->DepthPass = ur_frame_depth_pass{};
+        return UR_OK;
+    }
+    const int rc = check_raster_pass("ur_frame_set_depth_pass", "depth", pass->draws, pass->depth, pass->stats6);
+    if (rc != UR_OK) return rc;
+    if (pass->flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_frame_set_depth_pass: unknown flag bits 0x%x", pass->flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    const ur_draw_ranges* rg = pass->draws.ranges;
+    f->DepthPass = *pass;
+    f->DepthRanges = rg ? *rg : ur_draw_ranges{};
+    f->DepthPass.draws.ranges = rg ? &f->DepthRanges : nullptr;
+    f->bDepthPass = true;
+    return UR_OK;
+}
+
 int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass)
 {
     if (!f) { ur::set_error("ur_frame_set_shadow_pass: null frame"); return UR_EINVAL; }
@@ -1040,19 +1132,9 @@ int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass)
         f->ShadowPass = ur_frame_shadow_pass{};
         return UR_OK;
     }
-    const ur_raster_draws& d = pass->draws;
-    const ur_draw_ranges* rg = d.ranges;
-    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
-    if (!pass->shadow_map) { ur::set_error("ur_frame_set_shadow_pass: null shadow_map"); return UR_EINVAL; }
-    if ((d.visible_idx != nullptr) != (d.visible_count != nullptr)) { ur::set_error("ur_frame_set_shadow_pass: a list needs visible_idx and visible_count"); return UR_EINVAL; }
-    if (d.visible_idx && rg) { ur::set_error("ur_frame_set_shadow_pass: a list and ranges at once"); return UR_EINVAL; }
-    if (rg && (!rg->offsets || !rg->commands || !rg->counts || rg->range_count == 0)) { ur::set_error("ur_frame_set_shadow_pass: a null member of ranges / no range"); return UR_EINVAL; }
-    if (!rg && !d.commands && d.command_count != 0) { ur::set_error("ur_frame_set_shadow_pass: null commands"); return UR_EINVAL; }
-    if (misaligned(rg ? rg->commands : d.commands, 16) || misaligned(pass->shadow_map, 4) || misaligned(pass->stats4, 4) || misaligned(d.visible_idx, 4) ||
-        misaligned(d.visible_count, 4) || (rg && (misaligned(rg->offsets, 4) || misaligned(rg->counts, 4)))) {
-        ur::set_error("ur_frame_set_shadow_pass: a misaligned buffer (commands 16 bytes, the others 4)");
-        return UR_EINVAL;
-    }
+    const int rc = check_raster_pass("ur_frame_set_shadow_pass", "shadow_map", pass->draws, pass->shadow_map, pass->stats4);
+    if (rc != UR_OK) return rc;
+    const ur_draw_ranges* rg = pass->draws.ranges;
     f->ShadowPass = *pass;
     f->ShadowRanges = rg ? *rg : ur_draw_ranges{};
     f->ShadowPass.draws.ranges = rg ? &f->ShadowRanges : nullptr;

@@ -71,6 +71,11 @@ struct FHotPathResources
     const ur_raster_draws* ShadowDraws = nullptr;
     float* ShadowMapTarget = nullptr;
     uint32* ShadowStats = nullptr;
+    // DepthPrepass (ur_frame_set_depth_pass + UR_FRAME_DEPTH_PASS): the draws, the target (== DepthFull), optional counters, flags
+    const ur_raster_draws* DepthDraws = nullptr;
+    float* DepthTarget = nullptr;
+    uint32* DepthStats = nullptr;
+    uint32 DepthPassFlags = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};
@@ -89,6 +94,7 @@ struct FHotPathResources
     uint32 DebugPrintState = RG_STATE_UNORDERED_ACCESS;      // GpuDebugPrintState / GpuDebugPrintStatsState (Renderer.cpp:474-527)
     uint32 DebugPrintStatsState = RG_STATE_UNORDERED_ACCESS;
     uint32 ShadowDrawsState = RG_STATE_UNORDERED_ACCESS;     // the list / ranges the cull writes and the ShadowMap pass draws from
+    uint32 DepthDrawsState = RG_STATE_UNORDERED_ACCESS;      // the same of the DepthPrepass pass
 };
 
 struct FHotPathFrameConstants
@@ -123,6 +129,7 @@ struct FHotPathOptions
     bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
     bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
     bool bShadowPass = false;         // with ShadowDraws: the "ShadowMap" pass behind "GPU Culling" (ur_shadow_map into Tables.shadow_map)
+    bool bDepthPass = false;          // with DepthDraws: the "DepthPrepass" pass in front of "Build HZB" (ur_depth_prepass into DepthFull)
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;

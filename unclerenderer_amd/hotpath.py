@@ -754,8 +754,22 @@ def _raster_reserve(self, max_large_work_items: int):
     _lib.check(self._L.ur_raster_reserve(self._ctx, int(max_large_work_items)), "ur_raster_reserve")
 
 
+def _depth_prepass(self, view, projection, commands, depth, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None, size=None,
+                   flags=0):
+    """ur_depth_prepass: clear depth ((h, w) float32 device tensor, or flat with size=(w, h)) to 0.0 and rasterise the selected draws of
+    `commands` under the camera's view and projection (16 floats each, row-major, row-vector convention; reverse-Z), keeping the
+    per-texel maximum. The selections are HotPath.shadow_map's; stats: uint32[6] device tensor, added to; flags: UR_DEPTH_QUANTIZE_D24."""
+    w, h = size if size is not None else (int(depth.shape[1]), int(depth.shape[0]))
+    assert depth.dtype == torch.float32 and depth.numel() >= w * h
+    v, p = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (view, projection))
+    assert v.size == 16 and p.size == 16
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    _lib.check(self._L.ur_depth_prepass(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), w, h, int(flags), _ptr(stats)), "ur_depth_prepass")
+
+
 HotPath.shadow_map = _shadow_map
 HotPath.raster_reserve = _raster_reserve
+HotPath.depth_prepass = _depth_prepass
 
 
 def _frame_set_shadow_pass(self, commands=None, shadow_map=None, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None):
@@ -775,6 +789,27 @@ def _frame_set_shadow_pass(self, commands=None, shadow_map=None, *, visible=None
 
 
 Frame.set_shadow_pass = _frame_set_shadow_pass
+
+
+def _frame_set_depth_pass(self, commands=None, depth=None, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None, flags=0):
+    """ur_frame_set_depth_pass: the draws (as in HotPath.depth_prepass), the depth buffer (the frame's depth_full), the optional counters
+    and the ur_depth_prepass flags of the frames rendered with UR_FRAME_DEPTH_PASS (device tensors, kept alive here). No arguments:
+    clear."""
+    if commands is None and depth is None and ranges is None:
+        self._depth_pass_keep = None
+        _lib.check(self._L.ur_frame_set_depth_pass(self._f, None), "ur_frame_set_depth_pass")
+        return
+    dp = _lib.FrameDepthPass()
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    dp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
+    dp.depth = depth.data_ptr() if depth is not None else None
+    dp.stats6 = stats.data_ptr() if stats is not None else None
+    dp.flags = int(flags)
+    _lib.check(self._L.ur_frame_set_depth_pass(self._f, C.byref(dp)), "ur_frame_set_depth_pass")
+    self._depth_pass_keep = (d, depth, stats)
+
+
+Frame.set_depth_pass = _frame_set_depth_pass
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

@@ -58,8 +58,15 @@ class FrameShadowPass(C.Structure):
     _fields_ = [("draws", RasterDraws), ("shadow_map", C.c_void_p), ("stats4", C.c_void_p)]
 
 
+class FrameDepthPass(C.Structure):
+    """ur_frame_depth_pass (include/ur_frame.h): the draws, target, optional counters and ur_depth_prepass flags of UR_FRAME_DEPTH_PASS."""
+    _fields_ = [("draws", RasterDraws), ("depth", C.c_void_p), ("stats6", C.c_void_p), ("flags", C.c_uint32)]
+
+
 UR_RASTER_MAX_TARGET = 16384
 UR_RASTER_INDEX_FORMAT_R32_UINT = 42
+UR_DEPTH_QUANTIZE_D24 = 0x1
+UR_DEPTH_GUARD_BAND = 2097152
 
 
 class HzbSlice(C.Structure):
@@ -208,6 +215,7 @@ UR_FRAME_FUSE_TAA_TONEMAP = 0x1000000
 UR_FRAME_TAA_BAND = 0x2000000
 UR_FRAME_DEBUG_PRINT = 0x4000000
 UR_FRAME_SHADOW_PASS = 0x8000000
+UR_FRAME_DEPTH_PASS = 0x10000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -280,6 +288,7 @@ SIGNATURES = {
     # ur_raster.h
     "ur_shadow_map": (C.c_int, [_VP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _VP]),
     "ur_raster_reserve": (C.c_int, [_VP, _U32]),
+    "ur_depth_prepass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _U32, _VP]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
@@ -312,6 +321,7 @@ SIGNATURES = {
     "ur_frame_finish_post": (C.c_int, [_VP]),
     "ur_frame_set_debug_print": (C.c_int, [_VP, C.POINTER(FrameDebugPrint)]),
     "ur_frame_set_shadow_pass": (C.c_int, [_VP, C.POINTER(FrameShadowPass)]),
+    "ur_frame_set_depth_pass": (C.c_int, [_VP, C.POINTER(FrameDepthPass)]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
