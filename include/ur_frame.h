@@ -119,6 +119,16 @@ typedef struct ur_frame_resources {
  * band every rank renders the whole buffer (replicated, like the HZB and the shadow map). Without the flag nothing of this happens:
  * the frame is what it is today. */
 #define UR_FRAME_DEPTH_PASS 0x10000000u
+/* "GBuffer" pass behind "DepthPrepass" and in front of "Build HZB" and Lighting (DeferredRenderer.cpp:720-865; with targets.object_id
+ * also the "ObjectId" pass, :867-980): ur_gbuffer_pass of ur_frame_set_gbuffer_pass' draws with scene->View and scene->Projection
+ * against the prepass' depth, over the band [row0, row0 + rows) of the resources, into gbuffer_a/b/c and - the (emissive, 1) start
+ * value Lighting adds to - lighting_band. Needs UR_FRAME_DEPTH_PASS and a pass set by ur_frame_set_gbuffer_pass whose flags equal the
+ * depth pass' (both quantise to D24 or neither) and whose targets are the resources' gbuffer_a, gbuffer_b, gbuffer_c and lighting_band
+ * (else UR_EINVAL); the depth it tests against is the depth pass' buffer. On the main stream, in stream order behind DepthPrepass
+ * (with UR_FRAME_ASYNC_COMPUTE that pass has waited for the cull). Without UR_FRAME_DEPTH_PREPASS the pass is listed and culled, like
+ * DepthPrepass. With it a frame goes from index and vertex buffers to pixels: no G-buffer is imported. Without the flag nothing of this
+ * happens: the frame is what it is today. */
+#define UR_FRAME_GBUFFER_PASS 0x20000000u
 #define UR_FRAME_DEFAULT (UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY)
 
 ur_frame* ur_frame_create(ur_ctx* ctx, void* stream, uint32_t frames_in_flight, int rank, int world_size);
@@ -236,6 +246,23 @@ typedef struct ur_frame_depth_pass {
     uint32_t flags;
 } ur_frame_depth_pass;
 int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass);
+
+/* The draws, the targets, the optional counters (ur_gbuffer_pass' stats6; the caller zeroes them), ur_gbuffer_pass' flags and its
+ * key_triangle_bits of the frames rendered with UR_FRAME_GBUFFER_PASS; kept as ur_frame_set_shadow_pass keeps its struct (the targets
+ * are copied, their images stay the caller's). NULL clears. UR_EINVAL for a null frame, a null target other than object_id, and what
+ * ur_gbuffer_pass refuses in the draws, the alignment, the flags and the key bits.
+ * Not checked, here or at render: that targets.keys and targets.object_id hold rows * w elements. The band is the resources' row0 and
+ * rows of the frame being rendered, which this call cannot know; gbuf_a/b/c and hdr are held to the resources' own images at render,
+ * keys and object_id are the caller's to size for every band rendered with this pass. A row0 / rows of the resources that does not
+ * fit their h is ur_gbuffer_pass' UR_EINVAL: ur_frame_render returns it (the first failing pass' code; the passes behind it still run). */
+typedef struct ur_frame_gbuffer_pass {
+    ur_raster_draws draws;
+    ur_gbuffer_targets targets;
+    uint32_t* stats6;
+    uint32_t flags;
+    uint32_t key_triangle_bits;
+} ur_frame_gbuffer_pass;
+int ur_frame_set_gbuffer_pass(ur_frame* f, const ur_frame_gbuffer_pass* pass);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

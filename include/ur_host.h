@@ -58,6 +58,11 @@ void ur_host_taa_jitter(uint32_t sample_index, float out[2]);
  * (elements 8 and 9); nothing when width or height is not positive. */
 void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width, float height);
 
+/* The linear -> sRGB8 encode of the GBuffer resolve (ur_gbuffer_pass) as 255 ascending fp32 thresholds: the code of x
+ * is the number of entries with x >= entry (a NaN gives 0). Entry c - 1, c = 1..255, is the linear value of sRGB (c - 0.5) / 255 by the
+ * IEC 61966-2-1 curve, evaluated in double and rounded to fp32: the device reads these very bytes. */
+void ur_host_srgb_encode_table(float out[255]);
+
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own
  * design for codes 32..95 in 8 x 8 cells of a 64 x 64 R8 atlas; glyph quad = the cell, Size (8, 8), Offset (0, -7), Advance 8

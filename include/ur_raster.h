@@ -4,6 +4,9 @@
  * restatement is tests/shadow_ref.py, and the two agree on every byte.
  * The DepthPrepass pass (DeferredRenderer.cpp:635-718, Shaders/DeferredBasePass.hlsl:58-70): the same raster under a perspective camera
  * with a near clip, reverse-Z, into the camera's depth buffer. Its rule is DESIGN.md section 3.8, restated in tests/depth_ref.py.
+ * The GBuffer pass (DeferredRenderer.cpp:720-865, Shaders/DeferredBasePass.hlsl, pipeline key 0: no texture maps, no alpha mask) and the
+ * ObjectId pass (:867-980, Shaders/ObjectId.hlsl): DepthPrepass' raster writing a visibility key per texel, and a per-texel resolve of
+ * the winning key into the render targets. Its rule is DESIGN.md section 3.9, restated in tests/gbuffer_ref.py.
  */
 #ifndef UR_RASTER_H
 #define UR_RASTER_H
@@ -60,7 +63,10 @@ int ur_shadow_map(ur_ctx* ctx, const float light_view_projection[16], const ur_r
 /* Room for max_large_work_items (triangle, 64 x 64 tile) entries of the large-triangle queue of this context: a triangle whose
  * bounding box covers more than 64 8 x 8 stamps is split over the tiles it touches and rasterised by a second launch. 0 frees the
  * queue. Optional for correctness: without room every large triangle is rasterised where it is found and counted in stats4[3].
- * Synchronises the context's stream when it has to replace a queue (call it at set-up). UR_ENOMEM when the allocation fails. */
+ * Synchronises the context's stream when it has to replace a queue (call it at set-up). UR_ENOMEM when the allocation fails.
+ * The allocation is 64 bytes per entry + 64: the 48 bytes a depth pass writes per entry, and 16 more that only ur_gbuffer_pass uses (the
+ * triangle's key), since one queue serves all three passes. Before ur_gbuffer_pass existed an entry cost 48 bytes: a caller of
+ * ur_shadow_map and ur_depth_prepass alone now pays a third more device memory for the same count (32 MiB instead of 24 at 2^19). */
 int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items);
 
 #define UR_DEPTH_QUANTIZE_D24 0x1u /* every fragment stores (float)(rint((double)z * 16777215.0) / 16777215.0): a D24_UNORM target read through its R24 view */
@@ -89,6 +95,60 @@ int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items);
  * other than UR_DEPTH_QUANTIZE_D24. */
 int ur_depth_prepass(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
                      float* depth, uint32_t w, uint32_t h, uint32_t flags, uint32_t* stats6);
+
+/* The targets of the GBuffer pass: the rows [row0, row0 + rows) of the frame, w texels wide, row-major (a band's own images). */
+typedef struct ur_gbuffer_targets {
+    ur_half4* gbuf_a; ur_half4* gbuf_b; uint32_t* gbuf_c; ur_half4* hdr;   /* rows [row0,row0+rows), w wide */
+    uint32_t* object_id;   /* nullable */
+    uint32_t* keys;        /* rows x w scratch owned by the caller; holds the winning keys afterwards */
+} ur_gbuffer_targets;
+
+/* The GBuffer pass (and, with targets->object_id, the ObjectId pass) over the rows [row0, row0 + rows) of a w x h frame, by the rule
+ * of DESIGN.md 3.9. The selected draws are rasterised exactly as ur_depth_prepass rasterises them (vertex, near clip, viewport, facing,
+ * coverage, depth plane, UR_DEPTH_QUANTIZE_D24); a fragment passes iff its value is >= depth[texel] (GREATER_EQUAL, depth is never
+ * written), and a texel of `keys` ends as the maximum key over its passing fragments: triangle t of the draw of ordinal o has the key
+ * ((o + 1) << T) | t, 0 = nothing; o is the slot index (every slot, ranges) or the position in the visible list, so among equal depths
+ * the draw and triangle that D3D draws last wins. T = key_triangle_bits, or 32 - bit_length(command_count) when that is 0. A resolve
+ * launch then writes EVERY texel of the band's targets: key 0 gives the clear values - gbuf_a = gbuf_b = hdr = fp16 (0, 0, 0, 1),
+ * gbuf_c = 0xFF000000, object_id = 0 -, any other key the base pass' pixel shader on perspective-correct attributes of that triangle:
+ * gbuf_a = fp16 (view normal, view depth), gbuf_b = fp16 (0.04, MetallicFactor, RoughnessFactor, 1), gbuf_c = sRGB8 of BaseColor *
+ * COLOR.rgb (R in the low byte, alpha byte 255; ur_host_srgb_encode_table), hdr = fp16 (EmissiveFactor, 1), object_id = ObjectId.
+ * With `depth` the result of ur_depth_prepass over the same draws, matrices and flags this is the reference's G-buffer. With any other
+ * depth it is still defined by the rule, but it is not that picture: a texel whose depth is above every fragment stays clear, one
+ * whose depth is below several fragments takes the last drawn of them, not the nearest.
+ * A vertex is 64 bytes: POSITION at byte 0, NORMAL at 12, TEXCOORD at 24, TANGENT at 32, COLOR at 48 (DeferredRenderer.cpp:1812-1816).
+ * ConstantBufferAddress points at a whole ur_scene_constants: World, BaseColor, EmissiveFactor, MetallicFactor, RoughnessFactor and
+ * ObjectId are read from it; view and projection come from the host as for ur_depth_prepass.
+ * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most four launches (clear of the
+ * keys, raster, the large-triangle queue when ur_raster_reserve gave one, resolve).
+ * Read: what ur_depth_prepass reads, with all 64 bytes of a named vertex and the 608 bytes behind ConstantBufferAddress; the w * h floats
+ * of depth (only rows [row0, row0 + rows) of them). None of these is written.
+ * Written: rows * w elements of gbuf_a, gbuf_b, gbuf_c, hdr, keys and (when given) object_id, every one of them, and nothing around
+ * them. stats6 is added to.
+ * stats6: ur_depth_prepass' meanings; [1] also counts every triangle of a command whose stride is below 64 or that has more than 2^T
+ * triangles (neither is drawn), and a triangle with a vertex whose 64 bytes do not lie inside its buffer view. Triangles are counted
+ * whether or not they touch the band.
+ * UR_EINVAL, nothing launched: ur_depth_prepass' cases; null targets or a null target other than object_id; a misaligned target
+ * (gbuf_a, gbuf_b, hdr 8 bytes, the others 4); rows == 0 or row0 + rows > h; key_triangle_bits > 31; command_count >= 2^(32 - T).
+ * UR_EUNSUPPORTED, nothing launched: key_triangle_bits == 0 with command_count >= 2^24. */
+int ur_gbuffer_pass(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                    const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                    uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6);
+
+#define UR_GBUFFER_PART_RASTER 0x1u  /* the clear of the keys, the raster and the large-triangle queue */
+#define UR_GBUFFER_PART_RESOLVE 0x2u /* the resolve */
+
+/* ur_gbuffer_pass in parts, for tools that time its two halves apart (tools/bench_shadow.py --pass gbuffer); ur_gbuffer_pass is this
+ * call with both parts. UR_GBUFFER_PART_RASTER alone launches the clear, the raster and the queue: it reads what ur_gbuffer_pass reads
+ * except the NORMAL..COLOR bytes of a vertex and the constants behind World, writes the rows * w keys and adds to stats6; the other
+ * targets are not touched. UR_GBUFFER_PART_RESOLVE alone launches the resolve over the keys as they are: they must be what the raster
+ * part left under the same draws, matrices, band, flags and key_triangle_bits (a key that names no triangle of these draws reads
+ * outside the caller's buffers); it reads the keys, the draws' buffers and the list, not depth, and writes the other targets; stats6 is
+ * not touched. Arguments, checks and return values are ur_gbuffer_pass', all of them in either part; parts == 0 or an unknown bit is
+ * UR_EINVAL. */
+int ur_gbuffer_pass_parts(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                          const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                          uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
     python tools/bench_shadow.py [--batches 7] [--iters 10] [--json out.jsonl]
     python tools/bench_shadow.py --quick     # each workload a few times: for a rocprofv3 --kernel-trace --stats run
     python tools/bench_shadow.py --pass both # ShadowMap, then the DepthPrepass pass (ur_depth_prepass) over the same triangles
+    python tools/bench_shadow.py --pass gbuffer # the GBuffer pass (ur_gbuffer_pass) at 3840 x 2160, its two halves timed apart
 
 A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
   small   1 M triangles of 1/8 px to 8 px in one command;
@@ -20,6 +21,15 @@ The depth leg draws the same triangles under a perspective camera: a vertex at c
 (x * v, y * v, v) with v = NEAR / z, under View = identity and the projection clip = (x, y, NEAR, w = view z), its triangle's winding
 reversed (the prepass draws the other facing). It lands on the same pixel up to the rounding of x * v / v, with the same depth order
 reversed (reverse-Z): the same fragments, a maximum instead of a minimum, plus the three products, the near-plane test and the divides.
+
+The gbuffer leg draws the small and the large workload, scaled to a 3840 x 2160 target, as the depth leg draws them, with 64-byte
+vertices (a unit normal, a seeded colour) and a whole constant block. Per workload every buffer set of the ring first gets its depth
+from ur_depth_prepass and its keys from the raster part; then, batch by batch in the same process, four times are taken over the ring:
+ur_depth_prepass on this input (the yardstick of clear + raster: what the pass adds is the depth load and compare, and the atomic on the
+key image), the clear + raster (+ queue) launches alone and the resolve launch alone (ur_gbuffer_pass_parts), and the whole pass. Beside
+the resolve, two yardsticks for its 4 B key + 28 B targets per texel (+4 with ObjectId): the resolve of an empty key image (a call
+without commands: the same loads and stores, no triangle), and the plain streaming kernel (ur_debug_stream_ceiling: four reads to one
+write) moving the same byte count.
 """
 import argparse
 import json
@@ -31,6 +41,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 SIZE = 2048
+GBUFFER_W, GBUFFER_H = 3840, 2160
 
 
 def time_batch(torch, fn, iters):
@@ -43,16 +54,103 @@ def time_batch(torch, fn, iters):
     return a.elapsed_time(b) * 1e3 / iters
 
 
-def triangles(rng, n, lo, hi):
+def triangles(rng, n, lo, hi, w=SIZE, h=SIZE):
     """n clockwise-on-target triangles (drawn) with edge lengths log-uniform in [lo, hi] px, as clip-space positions (n * 3, 3)."""
-    c = rng.uniform(0, SIZE, (n, 1, 2))
+    c = rng.uniform(0, (w, h), (n, 1, 2))
     length = np.exp(rng.uniform(np.log(lo), np.log(hi), (n, 1, 1)))
     p = c + rng.uniform(-0.5, 0.5, (n, 3, 2)) * length
     e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
     flip = e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1] < 0
     p[flip] = p[flip][:, [0, 2, 1]]
     z = rng.uniform(0.05, 0.95, (n, 3, 1))
-    return np.concatenate([p[..., :1] / (0.5 * SIZE) - 1.0, 1.0 - p[..., 1:] / (0.5 * SIZE), z], axis=2).reshape(-1, 3).astype(np.float32)
+    return np.concatenate([p[..., :1] / (0.5 * w) - 1.0, 1.0 - p[..., 1:] / (0.5 * h), z], axis=2).reshape(-1, 3).astype(np.float32)
+
+
+NEAR = 0.125
+VIEW = np.eye(4, dtype=np.float32).reshape(-1)
+PROJ = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, NEAR, 0], np.float32)
+
+
+def camera_space(pos):
+    v = NEAR / pos[:, 2:3].astype(np.float64)
+    p = np.concatenate([pos[:, :2] * v, v], axis=1).astype(np.float32)
+    return p.reshape(-1, 3, 3)[:, [0, 2, 1]].reshape(-1, 3)
+
+
+def gbuffer_leg(a, torch, hp):
+    """The rows of --pass gbuffer (the module's docstring says what is timed against what)."""
+    from unclerenderer_amd import lib
+    from unclerenderer_amd.hotpath import gbuffer_targets, pack_draw_commands, to_device
+    w, h = GBUFFER_W, GBUFFER_H
+    rng = np.random.default_rng(2160)
+    cb = np.zeros(152, np.float32)  # ur_scene_constants: World, BaseColor at float 64, EmissiveFactor at 80, Metallic / Roughness at 104 / 105, ObjectId at 148
+    cb[:16] = np.eye(4, dtype=np.float32).reshape(-1)
+    cb[64:68], cb[80:83], cb[104], cb[105] = (0.8, 0.7, 0.6, 1.0), (0.1, 0.2, 0.3), 0.25, 0.5
+    cb.view(np.uint32)[148] = 7
+    constants = to_device(cb)
+
+    def mesh(pos):
+        v = np.zeros((pos.shape[0], 16), np.float32)
+        v[:, :3], v[:, 5] = pos, -1.0
+        v[:, 12:15], v[:, 15] = rng.uniform(0.0, 1.0, (pos.shape[0], 3)), 1.0
+        return dict(vertices=to_device(v.reshape(-1)), indices=to_device(np.arange(pos.shape[0], dtype=np.uint32)), constants=constants, stride=64)
+
+    loads = {"small": mesh(camera_space(triangles(rng, a.small, 0.125, 8.0, w, h))), "large": mesh(camera_space(triangles(rng, 256, w, 2 * w, w, h)))}
+    cmds = {k: to_device(pack_draw_commands([v])) for k, v in loads.items()}
+    half = lambda: torch.empty((h, w, 4), dtype=torch.float16, device="cuda")  # noqa: E731
+    word = lambda: torch.zeros((h, w), dtype=torch.int32, device="cuda")  # noqa: E731
+    sets = []
+    for _ in range(a.ring):
+        ga, gb, hdr, gc, keys, oid = half(), half(), half(), word(), word(), word()
+        sets.append((torch.zeros((h, w), dtype=torch.float32, device="cuda"), gbuffer_targets(ga, gb, gc, hdr, keys), gbuffer_targets(ga, gb, gc, hdr, keys, oid)))
+    stats = torch.zeros(6, dtype=torch.int32, device="cuda")
+    RASTER, RESOLVE = lib.UR_GBUFFER_PART_RASTER, lib.UR_GBUFFER_PART_RESOLVE
+
+    def stream(nbytes):
+        n16 = nbytes // (5 * 16)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(1234)
+        ring = [([(torch.randint(0, 0x3FFF, (n16 * 8,), dtype=torch.int16, device="cuda", generator=gen) | 0x3000) for _ in range(4)],
+                 torch.empty(n16 * 8, dtype=torch.int16, device="cuda")) for _ in range(a.ring)]
+        fn = lambda i: hp.stream_ceiling(*ring[i % a.ring])  # noqa: E731
+        fn(0)
+        torch.cuda.synchronize()
+        return [time_batch(torch, fn, a.iters) for _ in range(a.batches)]
+
+    rows = []
+
+    def row(shape, t, seen=None, **more):
+        rows.append({"shape": f"{w}x{h}, gbuffer, {shape}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": seen or [],
+                     "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, **more})
+
+    for oid in (False, True):
+        nbytes = (36 if oid else 32) * w * h
+        row(f"streaming kernel of {nbytes} B (4 reads : 1 write), the resolve's bytes {'with' if oid else 'without'} ObjectId", stream(nbytes), bytes=nbytes)
+    for reserve in (a.reserve, 0):
+        hp.raster_reserve(reserve)
+        for name, c in {"no commands": None, **cmds}.items():
+            count = None if c is not None else 0
+            gb = lambda i, parts, oid=False, st=None: hp.gbuffer_pass(VIEW, PROJ, c, sets[i % a.ring][0], sets[i % a.ring][2 if oid else 1], w, h,  # noqa: E731
+                                                                      stats=st, command_count=count, parts=parts)
+            prepass = lambda i, st=None: hp.depth_prepass(VIEW, PROJ, c, sets[i % a.ring][0], stats=st, command_count=count)  # noqa: E731
+            # every set of the ring: the depth of these draws, and their keys (the resolve part reads the keys as they are: never another workload's)
+            for i in range(a.ring):
+                prepass(i)
+                gb(i, RASTER)
+            stats.zero_()
+            gb(0, RASTER, st=stats if c is not None else None)
+            torch.cuda.synchronize()
+            seen = stats.cpu().numpy().view(np.uint32).tolist()
+            drawn = int((sets[0][1]._keep[4] != 0).sum())
+            fns = {"DepthPrepass on this input": prepass, "clear + raster": lambda i: gb(i, RASTER), "resolve": lambda i: gb(i, RESOLVE),
+                   "resolve with ObjectId": lambda i: gb(i, RESOLVE, True), "whole pass": lambda i: gb(i, RASTER | RESOLVE)}
+            times = {k: [] for k in fns}
+            for _ in range(a.batches):
+                for k, f in fns.items():
+                    times[k].append(time_batch(torch, f, a.iters))
+            for k, t in times.items():
+                row(f"{name}, reserve {reserve}, {k}", t, seen, texels_drawn=drawn)
+    return rows
 
 
 def main():
@@ -63,7 +161,7 @@ def main():
     ap.add_argument("--small", type=int, default=1_000_000)
     ap.add_argument("--reserve", type=int, default=1 << 19)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both"), default="shadow")
+    ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer"), default="shadow")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     if a.quick:
@@ -82,14 +180,7 @@ def main():
         vb, ib = to_device(v.reshape(-1)), to_device(np.arange(pos.shape[0], dtype=np.uint32))
         return dict(vertices=vb, indices=ib, constants=world, stride=64)
 
-    NEAR = 0.125
-    view = np.eye(4, dtype=np.float32).reshape(-1)
-    proj = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, NEAR, 0], np.float32)
-
-    def camera_space(pos):
-        v = NEAR / pos[:, 2:3].astype(np.float64)
-        p = np.concatenate([pos[:, :2] * v, v], axis=1).astype(np.float32)
-        return p.reshape(-1, 3, 3)[:, [0, 2, 1]].reshape(-1, 3)
+    view, proj = VIEW, PROJ
 
     small_pos, large_pos = triangles(rng, a.small, 0.125, 8.0), triangles(rng, 256, SIZE, 2 * SIZE)
     legs = []
@@ -123,10 +214,12 @@ def main():
             for k, t in times.items():
                 rows.append({"shape": f"{SIZE}x{SIZE}, {label}{k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
                              "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
+    if a.which == "gbuffer":
+        rows += gbuffer_leg(a, torch, hp)
     hp.raster_reserve(0)
     hp.close()
     for r in rows:
-        print(f"{r['shape']:64s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
+        print(f"{r['shape']:{96 if a.which == 'gbuffer' else 64}s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
     if a.json:
         with open(a.json, "a") as f:
             for r in rows:

@@ -190,6 +190,34 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         });
     }
 
+    // ---- GBuffer (:720-865, with ObjectId :867-980 as its optional fifth output): the base pass against the prepass' depth ------------
+    struct FGBufferPassData
+    {
+        bool bEnabled = false;
+        float View[16] = {}, Projection[16] = {};
+    };
+    if (bDepthPass && Options.bGBufferPass && Res.GBufferDraws != nullptr && Res.GBufferTargets != nullptr) {
+        Graph.AddPass<FGBufferPassData>("GBuffer", [&](FGBufferPassData& Data, FRGPassBuilder& Builder)
+        {
+            Data.bEnabled = Options.bDoDepthPrepass; // (the base pass tests against the prepass' depth: without it the pass is listed and culled)
+            std::memcpy(Data.View, Constants.Scene.View, sizeof(Data.View));
+            std::memcpy(Data.Projection, Constants.Scene.Projection, sizeof(Data.Projection));
+            if (Data.bEnabled) {
+                Builder.ReadTexture(DepthHandle, RG_STATE_DEPTH_READ); // (main stream, behind DepthPrepass: the cull's lists and ranges are complete)
+                Builder.WriteTexture(GBufferHandles[0], RG_STATE_RENDER_TARGET);
+                Builder.WriteTexture(GBufferHandles[1], RG_STATE_RENDER_TARGET);
+                Builder.WriteTexture(GBufferHandles[2], RG_STATE_RENDER_TARGET);
+                Builder.WriteTexture(LightingHandle, RG_STATE_RENDER_TARGET); // SceneColor: (emissive, 1), what Lighting adds to
+            }
+        }, [this, &Res](const FGBufferPassData& Data, FHIPCommandContext& Cmd)
+        {
+            if (!Data.bEnabled) return;
+            const int rc = ur_gbuffer_pass(Cmd.GetContext(), Data.View, Data.Projection, Res.GBufferDraws, Res.DepthTarget, Res.GBufferTargets, Res.Width, Res.Height,
+                                           Res.Row0, Res.Rows, Res.DepthPassFlags, Res.GBufferKeyBits, Res.GBufferStats);
+            if (rc != UR_OK && PassError == UR_OK) PassError = rc;
+        });
+    }
+
     // ---- Build HZB (after the G-buffer pass; only with HZB and depth prepass enabled, :996) ------------------------
     struct FHZBPassData
     {
@@ -746,6 +774,9 @@ struct ur_frame
     ur_frame_depth_pass DepthPass = {};   // ur_frame_set_depth_pass (draws.ranges points into DepthRanges)
     ur_draw_ranges DepthRanges = {};
     bool bDepthPass = false;
+    ur_frame_gbuffer_pass GBufferPass = {}; // ur_frame_set_gbuffer_pass (draws.ranges points into GBufferRanges)
+    ur_draw_ranges GBufferRanges = {};
+    bool bGBufferPass = false;
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -910,6 +941,19 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
             return UR_EINVAL;
         }
     }
+    if (flags & UR_FRAME_GBUFFER_PASS) {
+        if (!(flags & UR_FRAME_DEPTH_PASS)) { ur::set_error("ur_frame_render: GBUFFER_PASS needs UR_FRAME_DEPTH_PASS: the base pass tests against the prepass' depth"); return UR_EINVAL; }
+        if (!f->bGBufferPass) { ur::set_error("ur_frame_render: GBUFFER_PASS needs ur_frame_set_gbuffer_pass"); return UR_EINVAL; }
+        if (f->GBufferPass.flags != f->DepthPass.flags) {
+            ur::set_error("ur_frame_render: GBUFFER_PASS and DEPTH_PASS must quantise alike (flags 0x%x and 0x%x)", f->GBufferPass.flags, f->DepthPass.flags);
+            return UR_EINVAL;
+        }
+        const ur_gbuffer_targets& T = f->GBufferPass.targets;
+        if (T.gbuf_a != r->gbuffer_a || T.gbuf_b != r->gbuffer_b || T.gbuf_c != r->gbuffer_c || T.hdr != r->lighting_band) {
+            ur::set_error("ur_frame_render: GBUFFER_PASS renders into ur_frame_set_gbuffer_pass' targets, Lighting reads gbuffer_a/b/c and adds to lighting_band: they must be the same buffers");
+            return UR_EINVAL;
+        }
+    }
     FHotPathResources& R = f->Res; // resource states persist across frames, like the renderer's member variables
     R.Width = r->width; R.Height = r->height; R.Row0 = r->row0; R.Rows = r->rows;
     R.GBufferA = const_cast<ur_half4*>(r->gbuffer_a);
@@ -959,6 +1003,11 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.DepthTarget = depth_pass ? f->DepthPass.depth : nullptr;
     R.DepthStats = depth_pass ? f->DepthPass.stats6 : nullptr;
     R.DepthPassFlags = depth_pass ? f->DepthPass.flags : 0u;
+    const bool gbuffer_pass = depth_pass && (flags & UR_FRAME_GBUFFER_PASS) != 0 && f->bGBufferPass;
+    R.GBufferDraws = gbuffer_pass ? &f->GBufferPass.draws : nullptr;
+    R.GBufferTargets = gbuffer_pass ? &f->GBufferPass.targets : nullptr;
+    R.GBufferStats = gbuffer_pass ? f->GBufferPass.stats6 : nullptr;
+    R.GBufferKeyBits = gbuffer_pass ? f->GBufferPass.key_triangle_bits : 0u;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -992,6 +1041,7 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bDebugPrint = (flags & UR_FRAME_DEBUG_PRINT) != 0;
     O.bShadowPass = shadow_pass;
     O.bDepthPass = depth_pass;
+    O.bGBufferPass = gbuffer_pass;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -1121,6 +1171,33 @@ int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass)
     f->DepthRanges = rg ? *rg : ur_draw_ranges{};
     f->DepthPass.draws.ranges = rg ? &f->DepthRanges : nullptr;
     f->bDepthPass = true;
+    return UR_OK;
+}
+
+int ur_frame_set_gbuffer_pass(ur_frame* f, const ur_frame_gbuffer_pass* pass)
+{
+    if (!f) { ur::set_error("ur_frame_set_gbuffer_pass: null frame"); return UR_EINVAL; }
+    if (!pass) {
+        f->bGBufferPass = false;
+        f->GBufferPass = ur_frame_gbuffer_pass{};
+        return UR_OK;
+    }
+    const ur_gbuffer_targets& T = pass->targets;
+    if (!T.gbuf_a || !T.gbuf_b || !T.gbuf_c || !T.hdr) { ur::set_error("ur_frame_set_gbuffer_pass: a null target other than object_id"); return UR_EINVAL; }
+    const int rc = check_raster_pass("ur_frame_set_gbuffer_pass", "keys", pass->draws, T.keys, pass->stats6);
+    if (rc != UR_OK) return rc;
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
+    if (misaligned(T.gbuf_a, 8) || misaligned(T.gbuf_b, 8) || misaligned(T.hdr, 8) || misaligned(T.gbuf_c, 4) || misaligned(T.object_id, 4)) {
+        ur::set_error("ur_frame_set_gbuffer_pass: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)");
+        return UR_EINVAL;
+    }
+    if (pass->flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_frame_set_gbuffer_pass: unknown flag bits 0x%x", pass->flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    if (pass->key_triangle_bits > 31u) { ur::set_error("ur_frame_set_gbuffer_pass: key_triangle_bits %u (0 = automatic, 1..31)", pass->key_triangle_bits); return UR_EINVAL; }
+    const ur_draw_ranges* rg = pass->draws.ranges;
+    f->GBufferPass = *pass;
+    f->GBufferRanges = rg ? *rg : ur_draw_ranges{};
+    f->GBufferPass.draws.ranges = rg ? &f->GBufferRanges : nullptr;
+    f->bGBufferPass = true;
     return UR_OK;
 }
 

@@ -76,6 +76,11 @@ struct FHotPathResources
     float* DepthTarget = nullptr;
     uint32* DepthStats = nullptr;
     uint32 DepthPassFlags = 0;
+    // GBuffer (ur_frame_set_gbuffer_pass + UR_FRAME_GBUFFER_PASS): the draws, the targets (== GBufferA/B/C and LightingBand), optional counters, key bits
+    const ur_raster_draws* GBufferDraws = nullptr;
+    const ur_gbuffer_targets* GBufferTargets = nullptr;
+    uint32* GBufferStats = nullptr;
+    uint32 GBufferKeyBits = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};
@@ -130,6 +135,7 @@ struct FHotPathOptions
     bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
     bool bShadowPass = false;         // with ShadowDraws: the "ShadowMap" pass behind "GPU Culling" (ur_shadow_map into Tables.shadow_map)
     bool bDepthPass = false;          // with DepthDraws: the "DepthPrepass" pass in front of "Build HZB" (ur_depth_prepass into DepthFull)
+    bool bGBufferPass = false;        // with bDepthPass and GBufferDraws: the "GBuffer" pass behind "DepthPrepass" (ur_gbuffer_pass into GBufferA/B/C and LightingBand)
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;

@@ -56,6 +56,14 @@ void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width
     proj[9] += (2.0f * jitter[1]) / height;
 }
 
+void ur_host_srgb_encode_table(float out[255])
+{
+    for (int c = 1; c <= 255; ++c) {
+        const double v = (c - 0.5) / 255.0;
+        out[c - 1] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
+    }
+}
+
 void ur_host_look_to_lh(const float eye[3], const float dir[3], const float up[3], float out[16])
 {
     const V3 r2 = normalize(load(dir));

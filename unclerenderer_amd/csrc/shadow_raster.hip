@@ -25,6 +25,7 @@
 // e = (S0, S[1 + e], S[2 + e]). The wave serves emitted triangle 0 of every lane, then, when a ballot finds a lane that was cut into
 // two, runs the same code once more over emitted triangle 1.
 
+#include "ur_device.h"
 #include "ur_internal.h"
 
 #include "../../include/ur_raster.h"
@@ -37,6 +38,7 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 constexpr uint32_t kThreads = 256u, kWaves = kThreads / 64u;
 constexpr uint32_t kQueueHeaderDwords = 16u; // the count on a line of its own
 constexpr uint32_t kEntryDwords = 12u;       // x0 y0 x1 y1 | x2 y2 z0 k1 | k2 tile box_min box_max
+constexpr uint32_t kKeyedEntryDwords = 16u;  // GBuffer: | key - - - behind them; the queue is allocated for entries of this size
 constexpr uint32_t kLargeStamps = 64u;       // a bounding box of more 8 x 8 stamps than this is a large triangle
 constexpr uint32_t kOwnPixels = 4u;          // a bounding box of at most this many centres is rasterised by the triangle's own lane
 constexpr uint32_t kNoTile = 0xFFFFFFFFu;
@@ -61,6 +63,9 @@ struct RasterParams {
     uint32_t* queue; // 64-bit count at [0..1], entries from kQueueHeaderDwords; null without room
     uint32_t queue_cap;
     uint32_t segments, items; // items = candidates * segments
+    // GBuffer: `map` is the key image of the band [row0, row0 + rows); depth is the whole target, read only
+    const float* depth;
+    uint32_t row0, rows, key_bits;
 };
 
 struct Tri {
@@ -77,7 +82,8 @@ __device__ __forceinline__ int edge_bias(int ax, int ay, int bx, int by)
 
 // Rules 4-6 for one pixel
 template <class P>
-__device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, uint32_t* __restrict__ map, uint32_t w, int px, int py)
+__device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, uint32_t* __restrict__ map, uint32_t w, int px, int py,
+                                      const float* __restrict__ depth, uint32_t row0, uint32_t key)
 {
     const int sx = 256 * px + 128, sy = 256 * py + 128;
     const long long e01 = (long long)(t.x1 - t.x0) * (sy - t.y0) - (long long)(t.y1 - t.y0) * (sx - t.x0);
@@ -85,6 +91,16 @@ __device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, u
     const long long e20 = (long long)(t.x0 - t.x2) * (sy - t.y2) - (long long)(t.y0 - t.y2) * (sx - t.x2);
     if (((e01 - b01) | (e12 - b12) | (e20 - b20)) < 0) return;
     float z = t.z0 + ((float)e20 * t.k1 + (float)e01 * t.k2);
+    if constexpr (P::kKeyed) {
+        if (!(z >= 0.0f)) return; // the value ur_depth_prepass stores ...
+        if (z > 1.0f) z = 1.0f;
+        if constexpr (P::kD24) z = (float)(__builtin_rint((double)z * 16777215.0) / 16777215.0);
+        if (!(z >= depth[(size_t)py * w + (uint32_t)px])) return; // ... under GREATER_EQUAL against the prepass' maximum
+        uint32_t* k = map + (size_t)((uint32_t)py - row0) * w + (uint32_t)px;
+        if (key <= __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return; // (keys only increase)
+        (void)__hip_atomic_fetch_max(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
     uint32_t* p = map + (size_t)py * w + (uint32_t)px;
     if constexpr (P::kNearest) {
         if (!(z >= 0.0f && z <= 1.0f)) return; // depth clip (a NaN goes too)
@@ -104,7 +120,8 @@ __device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, u
 
 // The whole wave stamps the pixels [px0, px1] x [py0, py1] (inside the target) of one triangle, uniform arguments
 template <class P>
-__device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ map, uint32_t w, int px0, int py0, int px1, int py1, uint32_t lane)
+__device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ map, uint32_t w, int px0, int py0, int px1, int py1, uint32_t lane,
+                                           const float* __restrict__ depth, uint32_t row0, uint32_t key)
 {
     const int b01 = edge_bias(t.x0, t.y0, t.x1, t.y1), b12 = edge_bias(t.x1, t.y1, t.x2, t.y2), b20 = edge_bias(t.x2, t.y2, t.x0, t.y0);
     const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
@@ -112,7 +129,7 @@ __device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ 
         const int py = sy + ly;
         for (int sx = px0 & ~7; sx <= px1; sx += 8) {
             const int px = sx + lx;
-            if (px >= px0 && px <= px1 && py >= py0 && py <= py1) shade<P>(t, b01, b12, b20, map, w, px, py);
+            if (px >= px0 && px <= px1 && py >= py0 && py <= py1) shade<P>(t, b01, b12, b20, map, w, px, py, depth, row0, key);
         }
     }
 }
@@ -135,8 +152,8 @@ __device__ __forceinline__ Tri broadcast(const Tri& t, uint32_t s)
 
 // ShadowMap: orthographic, drawn iff A > 0, a per-texel minimum over a map cleared to 1.0
 struct ShadowPolicy {
-    static constexpr bool kNearest = true, kSwap12 = false;
-    static constexpr uint32_t kEmit = 1u;
+    static constexpr bool kNearest = true, kSwap12 = false, kKeyed = false;
+    static constexpr uint32_t kEmit = 1u, kVertexBytes = 12u, kEntryDwords = ::kEntryDwords;
     static constexpr float kGuardBand = (float)UR_RASTER_MAX_TARGET;
 
     // position * World * LightViewProjection, each a left-to-right sum of four products
@@ -170,8 +187,8 @@ __device__ __forceinline__ float sel3(uint32_t r, float u0, float u1, float u2) 
 // drawn iff A > 0 as above), a per-texel maximum over a target cleared to 0.0, optionally quantised to D24
 template <bool D24>
 struct DepthPolicy {
-    static constexpr bool kNearest = false, kD24 = D24, kSwap12 = true;
-    static constexpr uint32_t kEmit = 2u;
+    static constexpr bool kNearest = false, kD24 = D24, kSwap12 = true, kKeyed = false;
+    static constexpr uint32_t kEmit = 2u, kVertexBytes = 12u, kEntryDwords = ::kEntryDwords;
     static constexpr float kGuardBand = 2097152.0f; // 2^21 px: snapped coordinates below 2^29, edge functions exact in 64 bits
 
     // position * World * View * Projection, in the order the vertex shader multiplies
@@ -236,6 +253,15 @@ struct DepthPolicy {
     }
 };
 
+// GBuffer's raster: DepthPrepass' vertex, near clip, facing, coverage and depth plane; a fragment whose depth passes
+// GREATER_EQUAL against the prepass' result raises the texel of the key image to the triangle's key ((ordinal + 1) << T) | t. The key
+// rides with the triangle: the lane's own in the own-lane path, a readlane in the stamp paths, a dword of the queue's record.
+template <bool D24>
+struct VisPolicy : DepthPolicy<D24> {
+    static constexpr bool kKeyed = true;
+    static constexpr uint32_t kVertexBytes = 64u, kEntryDwords = kKeyedEntryDwords;
+};
+
 __global__ __launch_bounds__(kThreads) void shadow_clear_kernel(float* __restrict__ map, uint32_t n, uint32_t head, uint32_t* __restrict__ queue, float value)
 {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -284,7 +310,9 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
         const uint32_t vb_size = c0.z, stride = c0.w, ib_size = c1.z, format = c1.w;
         const uint32_t tri_count = c2.z / 3u, start_index = c3.x;
         const long long base_vertex = (int)c3.y;
-        if (format != UR_RASTER_INDEX_FORMAT_R32_UINT || stride < 12u || (stride & 3u) != 0u || vb == 0u || (vb & 3u) != 0u || ib == 0u || (ib & 3u) != 0u ||
+        bool too_many = false;
+        if constexpr (P::kKeyed) too_many = tri_count > (1u << p.key_bits);
+        if (too_many || format != UR_RASTER_INDEX_FORMAT_R32_UINT || stride < P::kVertexBytes || (stride & 3u) != 0u || vb == 0u || (vb & 3u) != 0u || ib == 0u || (ib & 3u) != 0u ||
             cb == 0u || (cb & 3u) != 0u) {
             if (seg == 0u) n_unsupported += tri_count;
             continue;
@@ -303,6 +331,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
 
         for (uint32_t chunk = seg; chunk < chunks; chunk += p.segments) {
             const uint32_t t = chunk * 64u + lane;
+            const uint32_t key = P::kKeyed ? (((cand + 1u) << p.key_bits) | t) : 0u; // (cand is the ordinal under every selection)
             // ---- a lane per triangle: rules 1-2 (and the near clip), up to four target-space vertices
             float SX[4] = {}, SY[4] = {}, SZ[4] = {};
             uint32_t emit = 0u;
@@ -315,7 +344,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
 #pragma unroll
                     for (int v = 0; v < 3; ++v) {
                         const long long vi = base_vertex + (long long)indices[first + (uint32_t)v];
-                        if (vi < 0 || (uint64_t)vi * stride + 12u > (uint64_t)vb_size) { unsupported = true; continue; }
+                        if (vi < 0 || (uint64_t)vi * stride + P::kVertexBytes > (uint64_t)vb_size) { unsupported = true; continue; }
                         P::project(reinterpret_cast<const float*>(vertices + (uint64_t)vi * stride), W, p, clip[v]);
                     }
                 }
@@ -363,6 +392,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                             const int miny = min(tri.y0, min(tri.y1, tri.y2)), maxy = max(tri.y0, max(tri.y1, tri.y2));
                             bx0 = max((minx + 127) >> 8, 0); bx1 = min((maxx - 128) >> 8, (int)p.w - 1);
                             by0 = max((miny + 127) >> 8, 0); by1 = min((maxy - 128) >> 8, (int)p.h - 1);
+                            if constexpr (P::kKeyed) { by0 = max(by0, (int)p.row0); by1 = min(by1, (int)(p.row0 + p.rows) - 1); } // the band scissor
                         }
                     }
                 }
@@ -382,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                 if (kind == 1u) {
                     const int b01 = edge_bias(tri.x0, tri.y0, tri.x1, tri.y1), b12 = edge_bias(tri.x1, tri.y1, tri.x2, tri.y2), b20 = edge_bias(tri.x2, tri.y2, tri.x0, tri.y0);
                     for (int py = by0; py <= by1; ++py)
-                        for (int px = bx0; px <= bx1; ++px) shade<P>(tri, b01, b12, b20, p.map, p.w, px, py);
+                        for (int px = bx0; px <= bx1; ++px) shade<P>(tri, b01, b12, b20, p.map, p.w, px, py, p.depth, p.row0, key);
                 }
                 // ---- the middle ones by the wave
                 unsigned long long todo = __ballot(kind == 2u);
@@ -390,7 +420,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                     const uint32_t s = (uint32_t)__ffsll((long long)todo) - 1u;
                     todo &= todo - 1ull;
                     const Tri u = broadcast(tri, s);
-                    stamp_rect<P>(u, p.map, p.w, rl(bx0, s), rl(by0, s), rl(bx1, s), rl(by1, s), lane);
+                    stamp_rect<P>(u, p.map, p.w, rl(bx0, s), rl(by0, s), rl(bx1, s), rl(by1, s), lane, p.depth, p.row0, (uint32_t)rl((int)key, s));
                 }
                 // ---- the large ones to the queue, or by the wave when there is no room
                 todo = __ballot(kind == 3u);
@@ -399,6 +429,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                     todo &= todo - 1ull;
                     const Tri u = broadcast(tri, s);
                     const int x0 = rl(bx0, s), y0 = rl(by0, s), x1 = rl(bx1, s), y1 = rl(by1, s);
+                    const uint32_t ukey = (uint32_t)rl((int)key, s);
                     const uint32_t tx0 = (uint32_t)x0 >> 6, ty0 = (uint32_t)y0 >> 6, tnx = ((uint32_t)x1 >> 6) - tx0 + 1u, tny = ((uint32_t)y1 >> 6) - ty0 + 1u;
                     const uint32_t tiles = tnx * tny;
                     bool queued = false;
@@ -411,16 +442,17 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                         const uint32_t base = (uint32_t)min(at, (unsigned long long)p.queue_cap), end = (uint32_t)min(at + tiles, (unsigned long long)p.queue_cap);
                         for (uint32_t q_at = base + lane; q_at < end; q_at += 64u) {
                             const uint32_t k = q_at - base, tx = tx0 + k % tnx, ty = ty0 + k / tnx;
-                            u32x4_t* q = reinterpret_cast<u32x4_t*>(p.queue + kQueueHeaderDwords + (size_t)q_at * kEntryDwords);
+                            u32x4_t* q = reinterpret_cast<u32x4_t*>(p.queue + kQueueHeaderDwords + (size_t)q_at * P::kEntryDwords);
                             const u32x4_t q0 = {(uint32_t)u.x0, (uint32_t)u.y0, (uint32_t)u.x1, (uint32_t)u.y1};
                             const u32x4_t q1 = {(uint32_t)u.x2, (uint32_t)u.y2, __float_as_uint(u.z0), __float_as_uint(u.k1)};
                             const u32x4_t q2 = {__float_as_uint(u.k2), queued ? (tx | (ty << 16)) : kNoTile, (uint32_t)x0 | ((uint32_t)y0 << 16), (uint32_t)x1 | ((uint32_t)y1 << 16)};
                             q[0] = q0; q[1] = q1; q[2] = q2;
+                            if constexpr (P::kKeyed) q[3] = u32x4_t{ukey, 0u, 0u, 0u};
                         }
                     }
                     if (!queued) {
                         ++n_unqueued;
-                        stamp_rect<P>(u, p.map, p.w, x0, y0, x1, y1, lane);
+                        stamp_rect<P>(u, p.map, p.w, x0, y0, x1, y1, lane, p.depth, p.row0, ukey);
                     }
                 }
             }
@@ -447,15 +479,18 @@ __device__ __forceinline__ long long edge_max(int ax, int ay, int bx, int by, in
 }
 
 template <class P>
-__global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w)
+__global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w,
+                                                         const float* __restrict__ depth, uint32_t row0)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
     const uint32_t wave_count = gridDim.x * kWaves;
     const uint32_t count = (uint32_t)min(*reinterpret_cast<const unsigned long long*>(queue), (unsigned long long)queue_cap);
     for (uint32_t e = wave; e < count; e += wave_count) {
-        const u32x4_t* q = reinterpret_cast<const u32x4_t*>(queue + kQueueHeaderDwords + (size_t)e * kEntryDwords);
+        const u32x4_t* q = reinterpret_cast<const u32x4_t*>(queue + kQueueHeaderDwords + (size_t)e * P::kEntryDwords);
         const u32x4_t q0 = q[0], q1 = q[1], q2 = q[2];
+        uint32_t key = 0u;
+        if constexpr (P::kKeyed) key = q[3].x;
         if (q2.y == kNoTile) continue;
         Tri t;
         t.x0 = (int)q0.x; t.y0 = (int)q0.y; t.x1 = (int)q0.z; t.y1 = (int)q0.w; t.x2 = (int)q1.x; t.y2 = (int)q1.y;
@@ -466,8 +501,209 @@ __global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restr
         if (edge_max(t.x0, t.y0, t.x1, t.y1, px0, py0, px1, py1) < 0 || edge_max(t.x1, t.y1, t.x2, t.y2, px0, py0, px1, py1) < 0 ||
             edge_max(t.x2, t.y2, t.x0, t.y0, px0, py0, px1, py1) < 0)
             continue;
-        stamp_rect<P>(t, map, w, px0, py0, px1, py1, lane);
+        stamp_rect<P>(t, map, w, px0, py0, px1, py1, lane, depth, row0, key);
     }
+}
+
+// ---- GBuffer's resolve: a lane per texel of the band turns the winning key into the render targets --------------------
+struct ResolveParams {
+    const uint8_t* commands;
+    uint32_t mode; // 0 every slot / ranges (the ordinal is the slot), 1 list (the ordinal is the position in the list)
+    const uint32_t* visible_idx;
+    uint32_t index_base;
+    float V[16], Pr[16];
+    const uint32_t* keys;
+    uint2* gbuf_a; uint2* gbuf_b; uint32_t* gbuf_c; uint2* hdr; uint32_t* object_id;
+    const float* table; // 255 thresholds of the sRGB encode
+    uint32_t w, row0, n;  // n = rows * w
+    float half_w, half_h;
+    uint32_t key_bits;
+};
+
+typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes of a vertex: 4-byte aligned
+
+__device__ __forceinline__ uint32_t half_bits(float v)
+{
+    const _Float16 h = (_Float16)v; // round to nearest even
+    return (uint32_t)__builtin_bit_cast(unsigned short, h);
+}
+__device__ __forceinline__ ur::once_u32x2_t pack_half4(float x, float y, float z, float w)
+{
+    return ur::once_u32x2_t{half_bits(x) | (half_bits(y) << 16), half_bits(z) | (half_bits(w) << 16)};
+}
+
+// the number of thresholds with x >= entry (ascending entries: a binary search; every compare is false for a NaN: 0)
+__device__ __forceinline__ uint32_t srgb_code(const float* table, float x)
+{
+    uint32_t lo = 0u, hi = 255u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool ge = lo < hi && x >= table[min(mid, 254u)];
+        if (lo < hi) { if (ge) lo = mid + 1u; else hi = mid; }
+    }
+    return lo;
+}
+
+// Rules 3-4 at one centre for the target-space triangle (X, Y)[0..2], already reordered: false when it is dropped, culled or does not
+// cover (sx, sy); else the exact edge values l0 = E12, l1 = E20, l2 = E01
+__device__ __forceinline__ bool cover(const float (&X)[3], const float (&Y)[3], int sx, int sy, long long& l0, long long& l1, long long& l2)
+{
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const bool finite = fabsf(X[v]) <= kFloatMax && fabsf(Y[v]) <= kFloatMax;
+        if (!finite || fabsf(X[v]) > DepthPolicy<false>::kGuardBand || fabsf(Y[v]) > DepthPolicy<false>::kGuardBand) return false;
+    }
+    const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
+    const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
+    const long long A = (long long)(x1 - x0) * (y2 - y0) - (long long)(x2 - x0) * (y1 - y0);
+    if (A <= 0) return false;
+    const long long e01 = (long long)(x1 - x0) * (sy - y0) - (long long)(y1 - y0) * (sx - x0);
+    const long long e12 = (long long)(x2 - x1) * (sy - y1) - (long long)(y2 - y1) * (sx - x1);
+    const long long e20 = (long long)(x0 - x2) * (sy - y2) - (long long)(y0 - y2) * (sx - x2);
+    l0 = e12; l1 = e20; l2 = e01;
+    return ((e01 - edge_bias(x0, y0, x1, y1)) | (e12 - edge_bias(x1, y1, x2, y2)) | (e20 - edge_bias(x2, y2, x0, y0))) >= 0;
+}
+
+template <bool OBJECT_ID>
+__global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams p)
+{
+    __shared__ float table[256];
+    table[threadIdx.x] = p.table[min(threadIdx.x, 254u)];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const uint32_t key = p.keys[i];
+    if (key == 0u) { // the clear values
+        const ur::once_u32x2_t clear = {0u, 0x3C000000u}; // fp16 (0, 0, 0, 1)
+        ur::store_once_b64(p.gbuf_a + i, clear);
+        ur::store_once_b64(p.gbuf_b + i, clear);
+        ur::store_once_b32(p.gbuf_c + i, 0xFF000000u);
+        ur::store_once_b64(p.hdr + i, clear);
+        if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, 0u);
+        return;
+    }
+    const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
+    const uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
+    const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
+    const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
+    const uint32_t* indices = reinterpret_cast<const uint32_t*>((uint64_t)c1.x | ((uint64_t)c1.y << 32));
+    const float* cb = reinterpret_cast<const float*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
+    const uint32_t stride = c0.w;
+    const uint64_t first = (uint64_t)c3.x + 3ull * t;
+    const long long base_vertex = (int)c3.y;
+    float W[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) W[k] = cb[k];
+
+    // ---- the three vertices: rule 1 (world and clip position), the world normal, the colour
+    float c[3][4], wp[3][3], wn[3][3], col[3][3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
+        const f32x4u_t* vp = reinterpret_cast<const f32x4u_t*>(vertices + vi * stride);
+        const f32x4u_t v0 = vp[0], v1 = vp[1], v3 = vp[3];
+        const float x = v0.x, y = v0.y, z = v0.z, nx = v0.w, ny = v1.x, nz = v1.y;
+        float wv[4], vv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wv[k] = ((x * W[k] + y * W[4 + k]) + z * W[8 + k]) + W[12 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) vv[k] = ((wv[0] * p.V[k] + wv[1] * p.V[4 + k]) + wv[2] * p.V[8 + k]) + wv[3] * p.V[12 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[v][k] = ((vv[0] * p.Pr[k] + vv[1] * p.Pr[4 + k]) + vv[2] * p.Pr[8 + k]) + vv[3] * p.Pr[12 + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            wp[v][k] = wv[k];
+            wn[v][k] = (nx * W[k] + ny * W[4 + k]) + nz * W[8 + k];
+        }
+        col[v][0] = v3.x; col[v][1] = v3.y; col[v][2] = v3.z;
+    }
+
+    // ---- rule 2 again (DepthPolicy::assemble), every polygon vertex with its weight row over the original three
+    const float d0 = c[0][3] - c[0][2], d1 = c[1][3] - c[1][2], d2 = c[2][3] - c[2][2];
+    const bool o0 = d0 < 0.0f, o1 = d1 < 0.0f, o2 = d2 < 0.0f;
+    const uint32_t n_out = (o0 ? 1u : 0u) + (o1 ? 1u : 0u) + (o2 ? 1u : 0u);
+    const uint32_t rot = n_out == 1u ? (o0 ? 1u : (o1 ? 2u : 0u)) : (n_out == 2u ? (!o0 ? 0u : (!o1 ? 1u : 2u)) : 0u);
+    const uint32_t ia = rot, ib = rot == 2u ? 0u : rot + 1u, ic = rot == 0u ? 2u : rot - 1u;
+    const float ax = sel3(rot, c[0][0], c[1][0], c[2][0]), ay = sel3(rot, c[0][1], c[1][1], c[2][1]);
+    const float aw = sel3(rot, c[0][3], c[1][3], c[2][3]), ad = sel3(rot, d0, d1, d2);
+    const float bx = sel3(rot, c[1][0], c[2][0], c[0][0]), by = sel3(rot, c[1][1], c[2][1], c[0][1]);
+    const float bw = sel3(rot, c[1][3], c[2][3], c[0][3]), bd = sel3(rot, d1, d2, d0);
+    const float cx = sel3(rot, c[2][0], c[0][0], c[1][0]), cy = sel3(rot, c[2][1], c[0][1], c[1][1]);
+    const float cw = sel3(rot, c[2][3], c[0][3], c[1][3]), cd = sel3(rot, d2, d0, d1);
+    const bool one = n_out == 1u, two = n_out == 2u, whole = n_out == 0u;
+    const float ix = one ? bx : ax, iy = one ? by : ay, iw = one ? bw : aw, id = one ? bd : ad;
+    const float ox = one ? cx : bx, oy = one ? cy : by, ow = one ? cw : bw, od = one ? cd : bd;
+    const uint32_t ii = one ? ib : ia, io = one ? ic : ib;
+    const float tp = id / (id - od), tq = ad / (ad - cd);
+    const float px = ix + tp * (ox - ix), py = iy + tp * (oy - iy), pw = iw + tp * (ow - iw);
+    const float qx = ax + tq * (cx - ax), qy = ay + tq * (cy - ay), qw = aw + tq * (cw - aw);
+    float vx[4], vy[4], vw[4], B[4][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float ua = (uint32_t)j == ia ? 1.0f : 0.0f, ub = (uint32_t)j == ib ? 1.0f : 0.0f, uc = (uint32_t)j == ic ? 1.0f : 0.0f;
+        const float up = (uint32_t)j == ii ? 1.0f - tp : ((uint32_t)j == io ? tp : 0.0f);
+        const float uq = (uint32_t)j == ia ? 1.0f - tq : ((uint32_t)j == ic ? tq : 0.0f);
+        B[0][j] = ua;
+        B[1][j] = two ? up : ub;
+        B[2][j] = whole ? uc : (one ? up : uq);
+        B[3][j] = uq;
+    }
+    vx[0] = ax; vy[0] = ay; vw[0] = aw;
+    vx[1] = two ? px : bx; vy[1] = two ? py : by; vw[1] = two ? pw : bw;
+    vx[2] = whole ? cx : (one ? px : qx); vy[2] = whole ? cy : (one ? py : qy); vw[2] = whole ? cw : (one ? pw : qw);
+    vx[3] = qx; vy[3] = qy; vw[3] = qw;
+    float SX[4], SY[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        SX[k] = (vx[k] / vw[k] + 1.0f) * p.half_w;
+        SY[k] = (1.0f - vy[k] / vw[k]) * p.half_h;
+    }
+
+    // ---- the piece that covers this centre: emitted triangle 0 if rule 4 says so, else 1; reordered (r0, r1, r2) = (S0, S[2 + e], S[1 + e])
+    const uint32_t row = i / p.w, column = i - row * p.w;
+    const int sx = 256 * (int)column + 128, sy = 256 * (int)(p.row0 + row) + 128;
+    long long l0 = 0, l1 = 0, l2 = 0;
+    float X[3] = {SX[0], SX[2], SX[1]}, Y[3] = {SY[0], SY[2], SY[1]};
+    bool second = false;
+    if (!cover(X, Y, sx, sy, l0, l1, l2) && one) {
+        second = true;
+        X[1] = SX[3]; Y[1] = SY[3]; X[2] = SX[2]; Y[2] = SY[2];
+        (void)cover(X, Y, sx, sy, l0, l1, l2);
+    }
+    const float cw0 = vw[0], cw1 = second ? vw[3] : vw[2], cw2 = second ? vw[2] : vw[1];
+    const float q0 = (float)l0 / cw0, q1 = (float)l1 / cw1, q2 = (float)l2 / cw2;
+    const float s = (q0 + q1) + q2;
+    const float g0 = q0 / s, g1 = q1 / s, g2 = q2 / s;
+    float b[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
+        b[j] = (g0 * B[0][j] + g1 * B1) + g2 * B2;
+    }
+    float n[3], wpos[3], colour[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        n[k] = (b[0] * wn[0][k] + b[1] * wn[1][k]) + b[2] * wn[2][k];
+        wpos[k] = (b[0] * wp[0][k] + b[1] * wp[1][k]) + b[2] * wp[2][k];
+        colour[k] = (b[0] * col[0][k] + b[1] * col[1][k]) + b[2] * col[2][k];
+    }
+
+    // ---- the pixel shader (DeferredBasePass.hlsl:80-149 without maps)
+    const float nl = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    const float vn0 = n[0] / nl, vn1 = n[1] / nl, vn2 = n[2] / nl;
+    float m[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = (vn0 * p.V[k] + vn1 * p.V[4 + k]) + vn2 * p.V[8 + k];
+    const float ml = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+    const float view_depth = -(((wpos[0] * p.V[2] + wpos[1] * p.V[6]) + wpos[2] * p.V[10]) + p.V[14]);
+    const uint32_t r8 = srgb_code(table, cb[64] * colour[0]), g8 = srgb_code(table, cb[65] * colour[1]), b8 = srgb_code(table, cb[66] * colour[2]);
+    ur::store_once_b64(p.gbuf_a + i, pack_half4(m[0] / ml, m[1] / ml, m[2] / ml, view_depth));
+    ur::store_once_b64(p.gbuf_b + i, pack_half4(0.04f, cb[104], cb[105], 1.0f));
+    ur::store_once_b32(p.gbuf_c + i, r8 | (g8 << 8) | (b8 << 16) | 0xFF000000u);
+    ur::store_once_b64(p.hdr + i, pack_half4(cb[80], cb[81], cb[82], 1.0f));
+    if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
 }
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0u; }
@@ -493,17 +729,24 @@ int check_arguments(const char* who, const ur_ctx* ctx, const float* m0, const f
     return UR_OK;
 }
 
-// clear, raster, large: the launches of a pass. m1 is null for ShadowMap.
+// What GBuffer's raster has beside a depth pass': the depth it tests against, its band and the key's triangle bits
+struct VisArgs {
+    const float* depth;
+    uint32_t row0, rows, key_bits;
+};
+
+// clear, raster, large: the launches every pass shares. `map` holds n = w * (rows of the map) dwords: the whole target of a depth pass
+// (vis null), GBuffer's key image of its band. m1 is null for ShadowMap.
 template <class P>
-int launch(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, float* target, uint32_t w, uint32_t h, float clear, uint32_t* stats)
+int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, uint32_t* map, uint32_t n, uint32_t w, uint32_t h, float clear,
+                  uint32_t* stats, const VisArgs* vis)
 {
     const ur_draw_ranges* rg = draws->ranges;
     const bool list = draws->visible_idx != nullptr;
-    const uint32_t n = w * h;
-    const uint32_t head = min((uint32_t)((16u - (reinterpret_cast<uintptr_t>(target) & 15u)) & 15u) / 4u, n);
+    const uint32_t head = min((uint32_t)((16u - (reinterpret_cast<uintptr_t>(map) & 15u)) & 15u) / 4u, n);
     uint32_t* queue = ctx->raster_queue_cap != 0u ? ctx->raster_queue : nullptr;
     const uint32_t clear_blocks = min((n / 4u + kThreads - 1u) / kThreads + 1u, (uint32_t)ctx->cu_count * 16u);
-    hipLaunchKernelGGL(shadow_clear_kernel, dim3(clear_blocks), dim3(kThreads), 0, ctx->stream, target, n, head, queue, clear);
+    hipLaunchKernelGGL(shadow_clear_kernel, dim3(clear_blocks), dim3(kThreads), 0, ctx->stream, reinterpret_cast<float*>(map), n, head, queue, clear);
     UR_HIP_TRY(hipGetLastError());
     if (draws->command_count == 0u) return UR_OK;
 
@@ -514,11 +757,12 @@ int launch(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws*
     p.visible_idx = draws->visible_idx; p.visible_count = draws->visible_count; p.index_base = draws->index_base;
     if (rg) { p.range_count = rg->range_count; p.offsets = rg->offsets; p.counts = rg->counts; }
     for (int k = 0; k < 16; ++k) { p.L[k] = m0[k]; p.Pr[k] = m1 ? m1[k] : 0.0f; }
-    p.map = reinterpret_cast<uint32_t*>(target);
+    p.map = map;
     p.w = w; p.h = h;
     p.half_w = 0.5f * (float)w; p.half_h = 0.5f * (float)h;
     p.stats = stats;
     p.queue = queue; p.queue_cap = queue ? ctx->raster_queue_cap : 0u;
+    if (vis) { p.depth = vis->depth; p.row0 = vis->row0; p.rows = vis->rows; p.key_bits = vis->key_bits; }
     // enough (candidate, segment) waves to fill the device whatever the command count: index counts live on the device
     const uint32_t want_waves = (uint32_t)ctx->cu_count * 16u;
     p.segments = max(1u, min(1024u, want_waves / p.command_count));
@@ -529,15 +773,95 @@ int launch(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws*
     hipLaunchKernelGGL(raster_kernel<P>, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     if (queue) {
-        hipLaunchKernelGGL(large_kernel<P>, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, queue, p.queue_cap, p.map, w);
+        hipLaunchKernelGGL(large_kernel<P>, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, queue, p.queue_cap, p.map, w, p.depth, p.row0);
         UR_HIP_TRY(hipGetLastError());
     }
+    return UR_OK;
+}
+
+// The launches of a depth pass
+template <class P>
+int launch(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, float* target, uint32_t w, uint32_t h, float clear, uint32_t* stats)
+{
+    return launch_raster<P>(ctx, m0, m1, draws, reinterpret_cast<uint32_t*>(target), w * h, w, h, clear, stats, nullptr);
+}
+
+// The launches of the GBuffer pass: launch_raster over the key image (UR_GBUFFER_PART_RASTER), then the resolve (UR_GBUFFER_PART_RESOLVE)
+template <bool D24>
+int launch_gbuffer(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* tg,
+                   uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, uint32_t* stats, uint32_t parts)
+{
+    const uint32_t n = w * rows;
+    if (parts & UR_GBUFFER_PART_RASTER) {
+        const VisArgs vis{depth, row0, rows, key_bits};
+        const int rc = launch_raster<VisPolicy<D24>>(ctx, view, projection, draws, tg->keys, n, w, h, 0.0f, stats, &vis);
+        if (rc != UR_OK) return rc;
+    }
+    if (!(parts & UR_GBUFFER_PART_RESOLVE)) return UR_OK;
+    ResolveParams r{};
+    r.commands = static_cast<const uint8_t*>(draws->ranges ? draws->ranges->commands : draws->commands);
+    r.mode = draws->visible_idx != nullptr ? 1u : 0u;
+    r.visible_idx = draws->visible_idx; r.index_base = draws->index_base;
+    for (int k = 0; k < 16; ++k) { r.V[k] = view[k]; r.Pr[k] = projection[k]; }
+    r.keys = tg->keys;
+    r.gbuf_a = reinterpret_cast<uint2*>(tg->gbuf_a); r.gbuf_b = reinterpret_cast<uint2*>(tg->gbuf_b); r.gbuf_c = tg->gbuf_c;
+    r.hdr = reinterpret_cast<uint2*>(tg->hdr); r.object_id = tg->object_id;
+    r.table = ctx->srgb_encode_table;
+    r.w = w; r.row0 = row0; r.n = n;
+    r.half_w = 0.5f * (float)w; r.half_h = 0.5f * (float)h;
+    r.key_bits = key_bits;
+    const uint32_t blocks = (n + kThreads - 1u) / kThreads;
+    if (tg->object_id) hipLaunchKernelGGL(gbuffer_resolve_kernel<true>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+    else hipLaunchKernelGGL(gbuffer_resolve_kernel<false>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+    UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }
 
 } // namespace
 
 extern "C" {
+
+int ur_gbuffer_pass_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts)
+{
+    const int rc = check_arguments("ur_gbuffer_pass", ctx, view, projection, draws, depth, w, h, stats6);
+    if (rc != UR_OK) return rc;
+    if (flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_gbuffer_pass: unknown flag bits 0x%x", flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    if (!targets || !targets->gbuf_a || !targets->gbuf_b || !targets->gbuf_c || !targets->hdr || !targets->keys) {
+        ur::set_error("ur_gbuffer_pass: null targets, or a null target other than object_id");
+        return UR_EINVAL;
+    }
+    if (!aligned(targets->gbuf_a, 8) || !aligned(targets->gbuf_b, 8) || !aligned(targets->hdr, 8) || !aligned(targets->gbuf_c, 4) || !aligned(targets->object_id, 4) ||
+        !aligned(targets->keys, 4)) {
+        ur::set_error("ur_gbuffer_pass: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)");
+        return UR_EINVAL;
+    }
+    if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("ur_gbuffer_pass: rows [%u, %u + %u) of a target %u high", row0, row0, rows, h); return UR_EINVAL; }
+    if (parts == 0u || (parts & ~(UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE))) { ur::set_error("ur_gbuffer_pass_parts: parts 0x%x (UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE)", parts); return UR_EINVAL; }
+    if (key_triangle_bits > 31u) { ur::set_error("ur_gbuffer_pass: key_triangle_bits %u (0 = automatic, 1..31)", key_triangle_bits); return UR_EINVAL; }
+    uint32_t key_bits = key_triangle_bits;
+    if (key_bits == 0u) {
+        if (draws->command_count >= (1u << 24)) {
+            ur::set_error("ur_gbuffer_pass: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", draws->command_count);
+            return UR_EUNSUPPORTED;
+        }
+        uint32_t length = 0u;
+        while ((draws->command_count >> length) != 0u) ++length;
+        key_bits = min(32u - length, 31u);
+    } else if ((uint64_t)draws->command_count >= (1ull << (32u - key_bits))) {
+        ur::set_error("ur_gbuffer_pass: %u command slots do not fit the %u key bits beside key_triangle_bits %u", draws->command_count, 32u - key_bits, key_bits);
+        return UR_EINVAL;
+    }
+    if (flags & UR_DEPTH_QUANTIZE_D24) return launch_gbuffer<true>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts);
+    return launch_gbuffer<false>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts);
+}
+
+int ur_gbuffer_pass(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                    uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6)
+{
+    return ur_gbuffer_pass_parts(ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6,
+                                 UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE);
+}
 
 int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items)
 {
@@ -548,7 +872,7 @@ int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items)
     ctx->raster_queue = nullptr;
     ctx->raster_queue_cap = 0;
     if (max_large_work_items == 0u) return UR_OK;
-    const size_t bytes = ((size_t)kQueueHeaderDwords + (size_t)max_large_work_items * kEntryDwords) * sizeof(uint32_t);
+    const size_t bytes = ((size_t)kQueueHeaderDwords + (size_t)max_large_work_items * kKeyedEntryDwords) * sizeof(uint32_t);
     if (hipMalloc(&ctx->raster_queue, bytes) != hipSuccess) {
         ctx->raster_queue = nullptr;
         ur::set_error("ur_raster_reserve: allocation of %u large work items failed", max_large_work_items);

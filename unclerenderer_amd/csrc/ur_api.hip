@@ -11,6 +11,8 @@
 
 #include "ur_internal.h"
 
+#include "../../include/ur_host.h"
+
 namespace ur {
 
 static thread_local char g_error[512] = "";
@@ -154,6 +156,14 @@ ur_ctx* ur_create(int device, void* stream)
         ur_destroy(ctx);
         return nullptr;
     }
+    float encode[255];
+    ur_host_srgb_encode_table(encode);
+    if (hipMalloc(&ctx->srgb_encode_table, sizeof(encode)) != hipSuccess ||
+        hipMemcpy(ctx->srgb_encode_table, encode, sizeof(encode), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("ur_create: sRGB encode table upload failed");
+        ur_destroy(ctx);
+        return nullptr;
+    }
     if (hipMalloc(&ctx->hzb_done, 64) != hipSuccess || hipMemset(ctx->hzb_done, 0, 64) != hipSuccess) {
         set_error("ur_create: HZB arrival counter allocation failed");
         ur_destroy(ctx);
@@ -201,6 +211,7 @@ void ur_destroy(ur_ctx* ctx)
     if (ctx->claim_words) (void)hipFree(ctx->claim_words);
     if (ctx->hzb_timed_out) (void)hipHostFree(const_cast<uint32_t*>(ctx->hzb_timed_out));
     if (ctx->srgb_table) (void)hipFree(ctx->srgb_table);
+    if (ctx->srgb_encode_table) (void)hipFree(ctx->srgb_encode_table);
     if (ctx->block_counts) (void)hipFree(ctx->block_counts);
     if (ctx->wave_masks) (void)hipFree(ctx->wave_masks);
     if (ctx->raster_queue) (void)hipFree(ctx->raster_queue);

@@ -68,6 +68,14 @@ def taa_jitter(sample_index: int) -> np.ndarray:
     return out
 
 
+def srgb_encode_table() -> np.ndarray:
+    """ur_host_srgb_encode_table: the 255 ascending fp32 thresholds of the GBuffer resolve's sRGB encode (code = the number of entries
+    with x >= entry)."""
+    out = np.zeros(255, np.float32)
+    _lib.load().ur_host_srgb_encode_table(_lib.fptr(out))
+    return out
+
+
 def apply_taa_jitter(proj, jitter, width: float, height: float) -> np.ndarray:
     """A copy of the projection with _31 += 2 jx / width, _32 += 2 jy / height (elements 8 and 9), as the reference jitters it."""
     out = _f(*proj)

@@ -767,6 +767,40 @@ def _depth_prepass(self, view, projection, commands, depth, *, visible=None, ran
     _lib.check(self._L.ur_depth_prepass(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), w, h, int(flags), _ptr(stats)), "ur_depth_prepass")
 
 
+def gbuffer_targets(gbuf_a, gbuf_b, gbuf_c, hdr, keys, object_id=None) -> _lib.GBufferTargets:
+    """ur_gbuffer_targets over device tensors of the band (rows x w): gbuf_a, gbuf_b, hdr float16 (..., 4), gbuf_c, keys and the optional
+    object_id int32. Keeps them alive."""
+    for t in (gbuf_a, gbuf_b, hdr):
+        assert t.dtype == torch.float16 and t.is_contiguous()
+    for t in (gbuf_c, keys) + ((object_id,) if object_id is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    tg = _lib.GBufferTargets(gbuf_a.data_ptr(), gbuf_b.data_ptr(), gbuf_c.data_ptr(), hdr.data_ptr(),
+                             object_id.data_ptr() if object_id is not None else None, keys.data_ptr())
+    tg._keep = (gbuf_a, gbuf_b, gbuf_c, hdr, keys, object_id)
+    return tg
+
+
+def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0, rows=None, *, visible=None, ranges=None, index_base=0, stats=None,
+                  command_count=None, flags=0, key_triangle_bits=0, parts=None):
+    """ur_gbuffer_pass: rasterise the selected draws of `commands` (64-byte vertices, whole ur_scene_constants behind the constant address)
+    into visibility keys against `depth` (the w x h result of depth_prepass, read only) and resolve the rows [row0, row0 + rows) into
+    `targets` (gbuffer_targets(...)). The selections are HotPath.shadow_map's; stats: uint32[6] device tensor, added to; flags:
+    UR_DEPTH_QUANTIZE_D24; key_triangle_bits: the key's triangle bits, 0 = 32 - bit_length(command_count). parts: None, or for a timing tool
+    UR_GBUFFER_PART_RASTER and / or UR_GBUFFER_PART_RESOLVE through ur_gbuffer_pass_parts (the resolve part alone trusts targets.keys)."""
+    rows = h - row0 if rows is None else rows
+    assert depth.dtype == torch.float32 and depth.numel() >= w * h
+    v, p = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (view, projection))
+    assert v.size == 16 and p.size == 16
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    args = (self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), C.byref(targets), w, h, int(row0), int(rows), int(flags), int(key_triangle_bits),
+            _ptr(stats))
+    if parts is None:
+        _lib.check(self._L.ur_gbuffer_pass(*args), "ur_gbuffer_pass")
+    else:
+        _lib.check(self._L.ur_gbuffer_pass_parts(*args, int(parts)), "ur_gbuffer_pass_parts")
+
+
+HotPath.gbuffer_pass = _gbuffer_pass
 HotPath.shadow_map = _shadow_map
 HotPath.raster_reserve = _raster_reserve
 HotPath.depth_prepass = _depth_prepass
@@ -810,6 +844,29 @@ def _frame_set_depth_pass(self, commands=None, depth=None, *, visible=None, rang
 
 
 Frame.set_depth_pass = _frame_set_depth_pass
+
+
+def _frame_set_gbuffer_pass(self, commands=None, targets=None, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None, flags=0,
+                            key_triangle_bits=0):
+    """ur_frame_set_gbuffer_pass: the draws (as in HotPath.gbuffer_pass), the targets (gbuffer_targets(...): the frame's gbuffer_a/b/c and
+    lighting_band), the optional counters, the ur_gbuffer_pass flags and the key bits of the frames rendered with UR_FRAME_GBUFFER_PASS
+    (device tensors, kept alive here). No arguments: clear."""
+    if commands is None and targets is None and ranges is None:
+        self._gbuffer_pass_keep = None
+        _lib.check(self._L.ur_frame_set_gbuffer_pass(self._f, None), "ur_frame_set_gbuffer_pass")
+        return
+    gp = _lib.FrameGBufferPass()
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    gp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
+    if targets is not None:
+        gp.targets = targets
+    gp.stats6 = stats.data_ptr() if stats is not None else None
+    gp.flags, gp.key_triangle_bits = int(flags), int(key_triangle_bits)
+    _lib.check(self._L.ur_frame_set_gbuffer_pass(self._f, C.byref(gp)), "ur_frame_set_gbuffer_pass")
+    self._gbuffer_pass_keep = (d, targets, stats)
+
+
+Frame.set_gbuffer_pass = _frame_set_gbuffer_pass
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

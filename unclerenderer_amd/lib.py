@@ -63,10 +63,22 @@ class FrameDepthPass(C.Structure):
     _fields_ = [("draws", RasterDraws), ("depth", C.c_void_p), ("stats6", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class GBufferTargets(C.Structure):
+    """ur_gbuffer_targets (include/ur_raster.h): the band's render targets, the optional ObjectId image and the key scratch of ur_gbuffer_pass."""
+    _fields_ = [("gbuf_a", C.c_void_p), ("gbuf_b", C.c_void_p), ("gbuf_c", C.c_void_p), ("hdr", C.c_void_p), ("object_id", C.c_void_p),
+                ("keys", C.c_void_p)]
+
+
+class FrameGBufferPass(C.Structure):
+    """ur_frame_gbuffer_pass (include/ur_frame.h): the draws, targets, optional counters, ur_gbuffer_pass flags and key bits of UR_FRAME_GBUFFER_PASS."""
+    _fields_ = [("draws", RasterDraws), ("targets", GBufferTargets), ("stats6", C.c_void_p), ("flags", C.c_uint32), ("key_triangle_bits", C.c_uint32)]
+
+
 UR_RASTER_MAX_TARGET = 16384
 UR_RASTER_INDEX_FORMAT_R32_UINT = 42
 UR_DEPTH_QUANTIZE_D24 = 0x1
 UR_DEPTH_GUARD_BAND = 2097152
+UR_GBUFFER_PART_RASTER, UR_GBUFFER_PART_RESOLVE = 0x1, 0x2
 
 
 class HzbSlice(C.Structure):
@@ -216,6 +228,7 @@ UR_FRAME_TAA_BAND = 0x2000000
 UR_FRAME_DEBUG_PRINT = 0x4000000
 UR_FRAME_SHADOW_PASS = 0x8000000
 UR_FRAME_DEPTH_PASS = 0x10000000
+UR_FRAME_GBUFFER_PASS = 0x20000000
 UR_FRAME_DEFAULT = UR_FRAME_INDIRECT_DRAW | UR_FRAME_HZB | UR_FRAME_DEPTH_PREPASS | UR_FRAME_SHADOWS | UR_FRAME_SKY
 
 assert C.sizeof(SceneConstants) == 608 and C.sizeof(SkyConstants) == 240
@@ -289,6 +302,8 @@ SIGNATURES = {
     "ur_shadow_map": (C.c_int, [_VP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _VP]),
     "ur_raster_reserve": (C.c_int, [_VP, _U32]),
     "ur_depth_prepass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _U32, _VP]),
+    "ur_gbuffer_pass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP]),
+    "ur_gbuffer_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
@@ -322,6 +337,7 @@ SIGNATURES = {
     "ur_frame_set_debug_print": (C.c_int, [_VP, C.POINTER(FrameDebugPrint)]),
     "ur_frame_set_shadow_pass": (C.c_int, [_VP, C.POINTER(FrameShadowPass)]),
     "ur_frame_set_depth_pass": (C.c_int, [_VP, C.POINTER(FrameDepthPass)]),
+    "ur_frame_set_gbuffer_pass": (C.c_int, [_VP, C.POINTER(FrameGBufferPass)]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
@@ -339,6 +355,7 @@ SIGNATURES = {
     "ur_host_fill_sky_constants": (None, [_FP, _FP, _FP, _F, _FP, _FP, C.POINTER(SkyConstants)]),
     "ur_host_taa_jitter": (None, [_U32, _FP]),
     "ur_host_apply_taa_jitter": (None, [_FP, _FP, _F, _F]),
+    "ur_host_srgb_encode_table": (None, [_FP]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
