@@ -263,6 +263,13 @@ typedef struct ur_frame_gbuffer_pass {
     uint32_t key_triangle_bits;
 } ur_frame_gbuffer_pass;
 int ur_frame_set_gbuffer_pass(ur_frame* f, const ur_frame_gbuffer_pass* pass);
+
+/* The material table of the "GBuffer" pass (ur_material, include/ur_raster.h): with UR_FRAME_GBUFFER_PASS and a table
+ * set, the pass is ur_gbuffer_pass_materials with it - one record per command slot of ur_frame_set_gbuffer_pass' draws, slots
+ * >= material_count resolve as key 0. materials: device, 16-byte aligned, read at render by every following frame until it is replaced;
+ * NULL clears it (material_count is then ignored). Without a table the pass list, the launches and the bytes are what they are without
+ * this call. There is no flag and ur_frame_gbuffer_pass has no member for it. UR_EINVAL: a null frame, a misaligned table. */
+int ur_frame_set_gbuffer_materials(ur_frame* f, const ur_material* materials, uint32_t material_count);
 /* Last execution: one line per pass "name|culled(0/1)|transitions|async(0/1)|cross-stream waits". Returns bytes needed (incl. NUL). */
 uint32_t ur_frame_report(const ur_frame* f, char* buf, uint32_t cap);
 /* Sliding-window GPU timing (FRenderGraph::GetGpuTimingStats): "name|avg_ms|min_ms|max_ms|samples" lines. */

@@ -63,6 +63,16 @@ void ur_host_apply_taa_jitter(float proj[16], const float jitter[2], float width
  * IEC 61966-2-1 curve, evaluated in double and rounded to fp32: the device reads these very bytes. */
 void ur_host_srgb_encode_table(float out[255]);
 
+/* The sRGB8 -> linear decode of a UR_TEXTURE_R8G8B8A8_UNORM_SRGB texel's R, G and B (ur_gbuffer_pass_materials): entry c,
+ * c = 0..255, is the linear value of sRGB c / 255 by the IEC 61966-2-1 curve, evaluated in double and rounded to fp32: the device reads
+ * these very bytes. */
+void ur_host_srgb_decode_table(float out[256]);
+
+/* The level-of-detail thresholds of the textured GBuffer resolve: entry j - 1, j = 1..127, is 2^(j / 128), evaluated in
+ * double and rounded to fp32, ascending. With rho^2 = m * 2^e, m in [1, 2) from the float's bits, the 8.8 fixed-point level is
+ * 128 e + (the number of entries with m >= entry) = floor(256 log2 rho): the device reads these very bytes. */
+void ur_host_lod_table(float out[127]);
+
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own
  * design for codes 32..95 in 8 x 8 cells of a 64 x 64 R8 atlas; glyph quad = the cell, Size (8, 8), Offset (0, -7), Advance 8

@@ -150,6 +150,58 @@ int ur_gbuffer_pass_parts(ur_ctx* ctx, const float view[16], const float project
                           const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
                           uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts);
 
+#define UR_TEXTURE_R8G8B8A8_UNORM 28u      /* DXGI_FORMAT_R8G8B8A8_UNORM */
+#define UR_TEXTURE_R8G8B8A8_UNORM_SRGB 29u /* DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: R, G and B decode through ur_host_srgb_decode_table, alpha never */
+
+/* A texture of the textured GBuffer resolve: `mips` levels packed tightly one behind the other from `texels` (device, 4-byte aligned),
+ * level k = max(1, width >> k) x max(1, height >> k) texels of 4 bytes, row-major, R in the low byte. Any size 1..65535, powers of two
+ * or not. */
+typedef struct ur_texture2d {
+    uint64_t texels;
+    uint16_t width, height;
+    uint8_t  mips, format;
+    uint16_t reserved;
+} ur_texture2d; /* 16 bytes */
+
+#define UR_MATERIAL_NORMAL_MAP 0x1u             /* BuildPipelineKey (DeferredRenderer.cpp:28-36): USE_NORMAL_MAP, texture t2 */
+#define UR_MATERIAL_METALLIC_ROUGHNESS_MAP 0x2u /* USE_METALLIC_ROUGHNESS_MAP, t1 */
+#define UR_MATERIAL_BASE_COLOR_MAP 0x4u         /* USE_BASE_COLOR_MAP, t0 */
+#define UR_MATERIAL_EMISSIVE_MAP 0x8u           /* USE_EMISSIVE_MAP, t3 */
+
+/* What the reference binds per draw range (DeferredRenderer.cpp:800): the descriptor table t0-t3 and the pipeline key. One record per
+ * command slot. Key bits 4 and above are ignored (USE_ALPHA_MASK is not drawn: the caller's ranges keep such models out). A set bit is
+ * treated as clear when its texture has a null address, an address that is not 4-byte aligned, a zero dimension, zero mips or a format
+ * other than the two above. */
+typedef struct ur_material {
+    ur_texture2d base_color, metallic_roughness, normal, emissive; /* t0, t1, t2, t3 */
+    uint32_t pipeline_key;
+    uint32_t reserved[3];
+} ur_material; /* 80 bytes, 16-byte aligned */
+
+/* ur_gbuffer_pass with texture maps: pipeline keys 0-15 of DeferredBasePass.hlsl by the rule of DESIGN.md 3.10, restated in
+ * tests/gbuffer_tex_ref.py. The raster is ur_gbuffer_pass'; the resolve of a texel whose winning key names command slot s evaluates the
+ * pixel shader under materials[s].pipeline_key: each map is sampled at its own ApplyTextureTransform of the interpolated TEXCOORD with
+ * the base pass' static sampler (anisotropic, MaxAnisotropy 4, wrap, every mip, no LOD bias) as 3.10 defines it - derivatives from the
+ * texel's 2 x 2 quad partners on its own triangle, up to four trilinear probes along the major axis. gbuf_a's normal goes through
+ * ComputeViewNormal with the interpolated TANGENT, gbuf_c's albedo is multiplied by the base-colour sample's rgb, gbuf_b's metallic and
+ * roughness by the metallic-roughness sample's b and g, hdr's emissive by the emissive sample's rgb. Key 0 gives ur_gbuffer_pass' bytes.
+ * materials: device, 16-byte aligned, material_count records; NULL is ur_gbuffer_pass (material_count is then not looked at). A slot
+ * >= material_count resolves as key 0.
+ * Read: what ur_gbuffer_pass reads; materials[s] (80 bytes) for every slot s < material_count that a winning key names; of a texture
+ * whose bit is set and whose descriptor is valid, 4-byte texels inside its `mips` levels (width, height and mips as the record gives
+ * them) and nothing around them. None of these is written.
+ * Written, launches, stats6: ur_gbuffer_pass'.
+ * UR_EINVAL, nothing launched: ur_gbuffer_pass' cases; materials not 16-byte aligned. */
+int ur_gbuffer_pass_materials(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                              const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                              uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, const ur_material* materials, uint32_t material_count);
+
+/* ur_gbuffer_pass_materials in parts, as ur_gbuffer_pass_parts: the raster part reads no material, the resolve part reads them. */
+int ur_gbuffer_pass_materials_parts(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                                    const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                                    uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
+                                    const ur_material* materials, uint32_t material_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@
     python tools/bench_shadow.py --quick     # each workload a few times: for a rocprofv3 --kernel-trace --stats run
     python tools/bench_shadow.py --pass both # ShadowMap, then the DepthPrepass pass (ur_depth_prepass) over the same triangles
     python tools/bench_shadow.py --pass gbuffer # the GBuffer pass (ur_gbuffer_pass) at 3840 x 2160, its two halves timed apart
+    python tools/bench_shadow.py --pass gbuffer --textured # the textured resolve (key 15) beside the untextured one and a streaming kernel
 
 A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
   small   1 M triangles of 1/8 px to 8 px in one command;
@@ -153,6 +154,100 @@ def gbuffer_leg(a, torch, hp):
     return rows
 
 
+def gbuffer_textured_leg(a, torch, hp):
+    """The rows of --pass gbuffer --textured: at 3840 x 2160 over cold buffer sets, the resolve part alone (ur_gbuffer_pass_materials_parts)
+    with the one command on pipeline key 15 - two 1024 x 1024 sRGB (base colour, emissive) and two UNORM (metallic-roughness, normal)
+    textures with full chains of random bytes -, interleaved in the same process with the untextured resolve over the same keys (the
+    yardstick) and the streaming kernel of the resolve's 32 bytes per texel. TEXCOORD is the target position / 256 px in u and 2.5 x
+    that in v: about 4 x 10 texels per pixel, so the nominal footprint is N = 3 probes between levels 2 and 3 (the perspective of each
+    triangle moves it a little; the mean probe count of a row is computed on the host by the numpy restatement over every 64th texel of the
+    keys the device rasterised). Only the targets are ringed: the four 5.6 MB texture chains are shared by every set of the ring, so
+    they stay warm in the L2 and the Infinity Cache, as a frame's textures would between passes but not as a streamed scene's would."""
+    from unclerenderer_amd import lib
+    from unclerenderer_amd.hotpath import gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, to_device
+    w, h = GBUFFER_W, GBUFFER_H
+    rng = np.random.default_rng(2161)
+    cb = np.zeros(152, np.float32)
+    cb[:16] = np.eye(4, dtype=np.float32).reshape(-1)
+    cb[64:68], cb[80:83], cb[104], cb[105] = (0.8, 0.7, 0.6, 1.0), (0.1, 0.2, 0.3), 0.25, 0.5
+    for at in (112, 120, 128, 136):  # the four texture transforms: identity
+        cb[at + 2], cb[at + 3], cb[at + 4] = 1.0, 1.0, 1.0
+    constants = to_device(cb)
+
+    def mesh(pos):
+        v = np.zeros((pos.shape[0], 16), np.float32)
+        v[:, :3], v[:, 5] = pos, -1.0
+        v[:, 6] = pos[:, 0] / pos[:, 2] * (0.5 * w / 256.0)
+        v[:, 7] = pos[:, 1] / pos[:, 2] * (0.5 * h / 256.0 * 2.5)
+        v[:, 8], v[:, 11] = 1.0, 1.0
+        v[:, 12:15], v[:, 15] = rng.uniform(0.0, 1.0, (pos.shape[0], 3)), 1.0
+        return dict(vertices=to_device(v.reshape(-1)), indices=to_device(np.arange(pos.shape[0], dtype=np.uint32)), constants=constants, stride=64)
+
+    chain = lambda: [rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)]  # noqa: E731
+    chains = {"base_color": (chain(), True), "emissive": (chain(), True), "metallic_roughness": (chain(), False), "normal": (chain(), False)}
+    materials = pack_materials([{"key": 15, **{k: pack_texture(*v) for k, v in chains.items()}}])
+    host_vertices = {}
+
+    def mesh_kept(name, pos):
+        m = mesh(pos)
+        host_vertices[name] = m["vertices"].cpu().numpy().view(np.uint8)
+        return m
+
+    def mean_probes(name, keys):
+        """The mean probe count per sampled map of every 8th texel of every 8th row, by the numpy restatement (tests/gbuffer_tex_ref.py)
+        on the keys the device rasterised: the restatement is byte-equal to the kernel, so these are the kernel's probe counts."""
+        from tests import gbuffer_tex_ref as X
+        sampled = np.zeros_like(keys)
+        sampled[::8, ::8] = keys[::8, ::8]
+        v = host_vertices[name]
+        d = X.TexDraw(v, np.arange(v.size // 64, dtype=np.uint32))
+        g = X.gather([d], VIEW, PROJ, sampled, w, h, {0: 0}, X.G.key_bits(1))
+        r = X.shade(g, VIEW, [{"key": 15, **{k: X.Tex(lv, srgb) for k, (lv, srgb) in chains.items()}}])
+        n = np.concatenate([N for runs in r["info"].values() for (_, N, _, _, _) in runs])
+        lod = np.concatenate([L for runs in r["info"].values() for (_, _, L, _, _) in runs])
+        return float(n.mean()), float(lod.mean()) / 256.0, int(g["at"].size)
+
+    loads = {"small": mesh_kept("small", camera_space(triangles(rng, a.small, 0.125, 8.0, w, h))),
+             "large": mesh_kept("large", camera_space(triangles(rng, 256, w, 2 * w, w, h)))}
+    cmds = {k: to_device(pack_draw_commands([v])) for k, v in loads.items()}
+    sets = []
+    for _ in range(a.ring):
+        ga, gb, hdr = (torch.empty((h, w, 4), dtype=torch.float16, device="cuda") for _ in range(3))
+        gc, keys = (torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(2))
+        sets.append((torch.zeros((h, w), dtype=torch.float32, device="cuda"), gbuffer_targets(ga, gb, gc, hdr, keys)))
+    RASTER, RESOLVE = lib.UR_GBUFFER_PART_RASTER, lib.UR_GBUFFER_PART_RESOLVE
+    n16 = (32 * w * h) // (5 * 16)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(1234)
+    ring = [([(torch.randint(0, 0x3FFF, (n16 * 8,), dtype=torch.int16, device="cuda", generator=gen) | 0x3000) for _ in range(4)],
+             torch.empty(n16 * 8, dtype=torch.int16, device="cuda")) for _ in range(a.ring)]
+    rows = []
+    hp.raster_reserve(a.reserve)
+    for name, c in cmds.items():
+        gb = lambda i, parts, m=None: hp.gbuffer_pass(VIEW, PROJ, c, sets[i % a.ring][0], sets[i % a.ring][1], w, h, parts=parts, materials=m)  # noqa: E731
+        for i in range(a.ring):
+            hp.depth_prepass(VIEW, PROJ, c, sets[i][0])
+            gb(i, RASTER)
+        torch.cuda.synchronize()
+        drawn = int((sets[0][1]._keep[4] != 0).sum())
+        probes, level, sampled = mean_probes(name, sets[0][1]._keep[4].cpu().numpy().view(np.uint32)) if not a.no_probe_count else (None, None, 0)
+        fns = {"streaming kernel of the resolve's 32 B per texel": lambda i: hp.stream_ceiling(*ring[i % a.ring]),
+               "resolve, untextured": lambda i: gb(i, RESOLVE), "resolve, key 15 (four 1024 x 1024 maps)": lambda i: gb(i, RESOLVE, materials)}
+        times = {k: [] for k in fns}
+        for f in fns.values():
+            f(0)
+        torch.cuda.synchronize()
+        for _ in range(a.batches):
+            for k, f in fns.items():
+                times[k].append(time_batch(torch, f, a.iters))
+        base = float(np.median(times["resolve, untextured"]))
+        for k, t in times.items():
+            rows.append({"shape": f"{w}x{h}, gbuffer textured, {name}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": [],
+                         "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, "texels_drawn": drawn, "ratio_to_untextured": float(np.median(t)) / base,
+                         "mean_probes_per_map": probes, "mean_level": level, "texels_sampled_for_probes": sampled})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=7)
@@ -162,6 +257,8 @@ def main():
     ap.add_argument("--reserve", type=int, default=1 << 19)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer"), default="shadow")
+    ap.add_argument("--textured", action="store_true", help="with --pass gbuffer: the textured resolve beside the untextured one")
+    ap.add_argument("--no-probe-count", action="store_true", help="with --textured: skip the host-side mean probe count")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     if a.quick:
@@ -215,7 +312,7 @@ def main():
                 rows.append({"shape": f"{SIZE}x{SIZE}, {label}{k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
                              "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
     if a.which == "gbuffer":
-        rows += gbuffer_leg(a, torch, hp)
+        rows += gbuffer_textured_leg(a, torch, hp) if a.textured else gbuffer_leg(a, torch, hp)
     hp.raster_reserve(0)
     hp.close()
     for r in rows:

@@ -212,8 +212,10 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         }, [this, &Res](const FGBufferPassData& Data, FHIPCommandContext& Cmd)
         {
             if (!Data.bEnabled) return;
-            const int rc = ur_gbuffer_pass(Cmd.GetContext(), Data.View, Data.Projection, Res.GBufferDraws, Res.DepthTarget, Res.GBufferTargets, Res.Width, Res.Height,
-                                           Res.Row0, Res.Rows, Res.DepthPassFlags, Res.GBufferKeyBits, Res.GBufferStats);
+            // (a null table is ur_gbuffer_pass)
+            const int rc = ur_gbuffer_pass_materials(Cmd.GetContext(), Data.View, Data.Projection, Res.GBufferDraws, Res.DepthTarget, Res.GBufferTargets, Res.Width,
+                                                     Res.Height, Res.Row0, Res.Rows, Res.DepthPassFlags, Res.GBufferKeyBits, Res.GBufferStats, Res.GBufferMaterials,
+                                                     Res.GBufferMaterialCount);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -777,6 +779,8 @@ struct ur_frame
     ur_frame_gbuffer_pass GBufferPass = {}; // ur_frame_set_gbuffer_pass (draws.ranges points into GBufferRanges)
     ur_draw_ranges GBufferRanges = {};
     bool bGBufferPass = false;
+    const ur_material* GBufferMaterials = nullptr; // ur_frame_set_gbuffer_materials: the "GBuffer" pass resolves with them
+    uint32_t GBufferMaterialCount = 0;
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
@@ -1008,6 +1012,8 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.GBufferTargets = gbuffer_pass ? &f->GBufferPass.targets : nullptr;
     R.GBufferStats = gbuffer_pass ? f->GBufferPass.stats6 : nullptr;
     R.GBufferKeyBits = gbuffer_pass ? f->GBufferPass.key_triangle_bits : 0u;
+    R.GBufferMaterials = gbuffer_pass ? f->GBufferMaterials : nullptr;
+    R.GBufferMaterialCount = gbuffer_pass ? f->GBufferMaterialCount : 0u;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -1171,6 +1177,15 @@ int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass)
     f->DepthRanges = rg ? *rg : ur_draw_ranges{};
     f->DepthPass.draws.ranges = rg ? &f->DepthRanges : nullptr;
     f->bDepthPass = true;
+    return UR_OK;
+}
+
+int ur_frame_set_gbuffer_materials(ur_frame* f, const ur_material* materials, uint32_t material_count)
+{
+    if (!f) { ur::set_error("ur_frame_set_gbuffer_materials: null frame"); return UR_EINVAL; }
+    if ((reinterpret_cast<uintptr_t>(materials) & 15u) != 0u) { ur::set_error("ur_frame_set_gbuffer_materials: a misaligned material table (16 bytes)"); return UR_EINVAL; }
+    f->GBufferMaterials = materials;
+    f->GBufferMaterialCount = materials ? material_count : 0u;
     return UR_OK;
 }
 

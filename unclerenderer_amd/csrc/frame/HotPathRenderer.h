@@ -80,6 +80,8 @@ struct FHotPathResources
     const ur_raster_draws* GBufferDraws = nullptr;
     const ur_gbuffer_targets* GBufferTargets = nullptr;
     uint32* GBufferStats = nullptr;
+    const ur_material* GBufferMaterials = nullptr; // ur_frame_set_gbuffer_materials: null = the untextured resolve
+    uint32 GBufferMaterialCount = 0;
     uint32 GBufferKeyBits = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;

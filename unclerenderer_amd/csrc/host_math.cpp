@@ -64,6 +64,19 @@ void ur_host_srgb_encode_table(float out[255])
     }
 }
 
+void ur_host_srgb_decode_table(float out[256])
+{
+    for (int c = 0; c < 256; ++c) {
+        const double v = c / 255.0;
+        out[c] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4));
+    }
+}
+
+void ur_host_lod_table(float out[127])
+{
+    for (int j = 1; j <= 127; ++j) out[j - 1] = (float)std::exp2(j / 128.0);
+}
+
 void ur_host_look_to_lh(const float eye[3], const float dir[3], const float up[3], float out[16])
 {
     const V3 r2 = normalize(load(dir));

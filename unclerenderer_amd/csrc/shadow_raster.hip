@@ -506,6 +506,8 @@ __global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restr
 }
 
 // ---- GBuffer's resolve: a lane per texel of the band turns the winning key into the render targets --------------------
+static_assert(sizeof(ur_texture2d) == 16 && sizeof(ur_material) == 80, "ur_material is 80 bytes");
+
 struct ResolveParams {
     const uint8_t* commands;
     uint32_t mode; // 0 every slot / ranges (the ordinal is the slot), 1 list (the ordinal is the position in the list)
@@ -518,6 +520,11 @@ struct ResolveParams {
     uint32_t w, row0, n;  // n = rows * w
     float half_w, half_h;
     uint32_t key_bits;
+    // the textured resolve
+    const ur_material* materials;
+    uint32_t material_count;
+    const float* decode; // 256 entries of the sRGB decode
+    const float* lod;    // 127 thresholds of the level of detail
 };
 
 typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes of a vertex: 4-byte aligned
@@ -565,11 +572,131 @@ __device__ __forceinline__ bool cover(const float (&X)[3], const float (&Y)[3], 
     return ((e01 - edge_bias(x0, y0, x1, y1)) | (e12 - edge_bias(x1, y1, x2, y2)) | (e20 - edge_bias(x2, y2, x0, y0))) >= 0;
 }
 
-template <bool OBJECT_ID>
+// ---- the textured resolve's sampler ----------------------------------------------------------------------------------
+constexpr uint32_t kLdsDecode = 0u, kLdsUnorm = 256u, kLdsLod = 512u, kLdsFloats = 640u; // the sampler's tables in LDS, in floats
+
+// (i + 0.5) / N - 0.5 for N = 1, 2, 3, 4, i ascending
+__constant__ float kProbeOffset[10] = {0.0f, -0.25f, 0.25f, -0.33333334f, 0.0f, 0.33333334f, -0.375f, -0.125f, 0.125f, 0.375f};
+
+// ApplyTextureTransform with the constant vectors at cb[at .. at + 8)
+__device__ __forceinline__ void texture_transform(const float* __restrict__ cb, uint32_t at, float u, float v, float& tu, float& tv)
+{
+    const float su = u * cb[at + 2u], sv = v * cb[at + 3u];
+    const float ru = su * cb[at + 4u] - sv * cb[at + 5u], rv = su * cb[at + 5u] + sv * cb[at + 4u];
+    tu = ru + cb[at + 0u];
+    tv = rv + cb[at + 1u];
+}
+
+// x = u * size - 0.5 -> the two wrapped texel indices and the weight; a coordinate that is not finite, or beyond 2^30 texels, counts as 0
+__device__ __forceinline__ void wrap_pair(float u, uint32_t size, uint32_t& i0, uint32_t& i1, float& f)
+{
+    float x = u * (float)size - 0.5f;
+    if (!(fabsf(x) <= 1073741824.0f)) x = 0.0f;
+    const float x0 = floorf(x);
+    f = x - x0;
+    int r = (int)x0 % (int)size;
+    if (r < 0) r += (int)size;
+    i0 = (uint32_t)r;
+    i1 = i0 + 1u == size ? 0u : i0 + 1u;
+}
+
+// One bilinear sample of a level: R, G, B decoded through `tab` (LDS: the sRGB decode or code / 255)
+__device__ __forceinline__ void bilinear(const uint32_t* __restrict__ level, uint32_t wd, uint32_t hd, float u, float v, const float* tab, float (&out)[3])
+{
+    uint32_t x0, x1, y0, y1;
+    float fx, fy;
+    wrap_pair(u, wd, x0, x1, fx);
+    wrap_pair(v, hd, y0, y1, fy);
+    const uint32_t* r0 = level + (size_t)y0 * wd;
+    const uint32_t* r1 = level + (size_t)y1 * wd;
+    const uint32_t t00 = r0[x0], t10 = r0[x1], t01 = r1[x0], t11 = r1[x1];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = tab[(t00 >> (8 * c)) & 255u], b = tab[(t10 >> (8 * c)) & 255u];
+        const float d = tab[(t01 >> (8 * c)) & 255u], e = tab[(t11 >> (8 * c)) & 255u];
+        const float top = a + fx * (b - a), bottom = d + fx * (e - d);
+        out[c] = top + fy * (bottom - top);
+    }
+}
+
+// The static sampler on one map: footprint, level of detail, up to four trilinear probes. (u, v) the centre's coordinate, (dxu, dxv) and
+// (dyu, dyv) the quad's differences; `desc` a valid descriptor's four dwords; `lds` the tables
+__device__ __forceinline__ void sample_map(const u32x4_t desc, float u, float v, float dxu, float dxv, float dyu, float dyv, const float* lds, float (&out)[3])
+{
+    const uint32_t* texels = reinterpret_cast<const uint32_t*>((uint64_t)desc.x | ((uint64_t)desc.y << 32));
+    const uint32_t width = desc.z & 0xFFFFu, height = desc.z >> 16, mips = desc.w & 0xFFu, format = (desc.w >> 8) & 0xFFu;
+    const float fw = (float)width, fh = (float)height;
+    const float axu = dxu * fw, axv = dxv * fh, ayu = dyu * fw, ayv = dyv * fh;
+    const float px2 = axu * axu + axv * axv, py2 = ayu * ayu + ayv * ayv;
+    const bool ymajor = py2 > px2; // a tie goes to x
+    const float pmax2 = ymajor ? py2 : px2, pmin2 = ymajor ? px2 : py2;
+    const uint32_t n = pmax2 <= pmin2 ? 1u : (pmax2 <= 4.0f * pmin2 ? 2u : (pmax2 <= 9.0f * pmin2 ? 3u : 4u));
+    const float rho2 = pmax2 / (float)(n * n);
+    // L = floor(256 log2 rho), 8.8 fixed point
+    const uint32_t bits = __float_as_uint(rho2), ef = (bits >> 23) & 255u;
+    const int lmax = 256 * ((int)mips - 1);
+    int L = 0;
+    if (ef == 255u) L = lmax;
+    else if (ef != 0u) {
+        const float m = __uint_as_float((bits & 0x007FFFFFu) | 0x3F800000u);
+        uint32_t lo = 0u, hi = 127u;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const uint32_t mid = (lo + hi) >> 1;
+            const bool ge = lo < hi && m >= lds[kLdsLod + min(mid, 126u)];
+            if (lo < hi) { if (ge) lo = mid + 1u; else hi = mid; }
+        }
+        L = min(max(128 * ((int)ef - 127) + (int)lo, 0), lmax);
+    }
+    const uint32_t d = (uint32_t)L >> 8;
+    const float f = (float)(L & 255) * 0.00390625f;
+    size_t offset = 0u;
+    for (uint32_t k = 0u; k < d; ++k) offset += (size_t)max(1u, width >> k) * max(1u, height >> k);
+    const uint32_t wd = max(1u, width >> d), hd = max(1u, height >> d);
+    const uint32_t d1 = min(d + 1u, mips - 1u);
+    const uint32_t we = max(1u, width >> d1), he = max(1u, height >> d1);
+    const uint32_t* level0 = texels + offset;
+    const uint32_t* level1 = d1 == d ? level0 : level0 + (size_t)wd * hd;
+    const float* tab = lds + (format == UR_TEXTURE_R8G8B8A8_UNORM_SRGB ? kLdsDecode : kLdsUnorm);
+    const float mu = ymajor ? dyu : dxu, mv = ymajor ? dyv : dxv;
+    float sum[3] = {0.0f, 0.0f, 0.0f};
+    for (uint32_t i = 0u; i < n; ++i) {
+        const float o = kProbeOffset[n * (n - 1u) / 2u + i];
+        const float pu = u + mu * o, pv = v + mv * o;
+        float s[3];
+        bilinear(level0, wd, hd, pu, pv, tab, s);
+        if (f != 0.0f) { // (lo + 0 * (hi - lo) is lo: every value here is finite and no zero is negative)
+            float t[3];
+            bilinear(level1, we, he, pu, pv, tab, t);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[c] = s[c] + f * (t[c] - s[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) sum[c] = i == 0u ? s[c] : sum[c] + s[c];
+    }
+    const float fn = (float)n;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = sum[c] / fn;
+}
+
+__device__ __forceinline__ bool valid_texture(const u32x4_t desc)
+{
+    const uint32_t format = (desc.w >> 8) & 0xFFu;
+    return (desc.x | desc.y) != 0u && (desc.x & 3u) == 0u && (desc.z & 0xFFFFu) != 0u && (desc.z >> 16) != 0u && (desc.w & 0xFFu) != 0u &&
+           (format == UR_TEXTURE_R8G8B8A8_UNORM || format == UR_TEXTURE_R8G8B8A8_UNORM_SRGB);
+}
+
+template <bool OBJECT_ID, bool MAPS = false>
 __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams p)
 {
     __shared__ float table[256];
+    __shared__ float sampler_tables[MAPS ? kLdsFloats : 1u];
     table[threadIdx.x] = p.table[min(threadIdx.x, 254u)];
+    if constexpr (MAPS) {
+        sampler_tables[kLdsDecode + threadIdx.x] = p.decode[threadIdx.x];
+        sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
+        if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.lod[min(threadIdx.x, 126u)];
+    }
     __syncthreads();
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= p.n) return;
@@ -599,6 +726,7 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
 
     // ---- the three vertices: rule 1 (world and clip position), the world normal, the colour
     float c[3][4], wp[3][3], wn[3][3], col[3][3];
+    [[maybe_unused]] float uv[3][2], tg[3][4]; // MAPS: TEXCOORD and the vertex shader's tangent
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
         const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
@@ -618,6 +746,15 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
             wn[v][k] = (nx * W[k] + ny * W[4 + k]) + nz * W[8 + k];
         }
         col[v][0] = v3.x; col[v][1] = v3.y; col[v][2] = v3.z;
+        if constexpr (MAPS) {
+            const f32x4u_t v2 = vp[2];
+            uv[v][0] = v1.z; uv[v][1] = v1.w;
+            float wt[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wt[k] = (v2.x * W[k] + v2.y * W[4 + k]) + v2.z * W[8 + k];
+            const float tl = sqrtf((wt[0] * wt[0] + wt[1] * wt[1]) + wt[2] * wt[2]);
+            tg[v][0] = wt[0] / tl; tg[v][1] = wt[1] / tl; tg[v][2] = wt[2] / tl; tg[v][3] = v2.w;
+        }
     }
 
     // ---- rule 2 again (DepthPolicy::assemble), every polygon vertex with its weight row over the original three
@@ -688,6 +825,105 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
         n[k] = (b[0] * wn[0][k] + b[1] * wn[1][k]) + b[2] * wn[2][k];
         wpos[k] = (b[0] * wp[0][k] + b[1] * wp[1][k]) + b[2] * wp[2][k];
         colour[k] = (b[0] * col[0][k] + b[1] * col[1][k]) + b[2] * col[2][k];
+    }
+
+    if constexpr (MAPS) {
+        // ---- the material of the slot, its valid maps, and the samples
+        uint32_t bits = 0u;
+        if (slot < p.material_count) bits = reinterpret_cast<const uint32_t*>(p.materials + slot)[16] & 15u;
+        float base[3] = {1.0f, 1.0f, 1.0f}, mr[3] = {1.0f, 1.0f, 1.0f}, nm[3] = {0.5f, 0.5f, 1.0f}, em[3] = {1.0f, 1.0f, 1.0f};
+        if (__ballot(bits != 0u) != 0ull) {
+            // the quad partners' weights: the edge functions are affine, so a step of one pixel adds the coefficient times 256
+            const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
+            const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
+            const bool odd_column = (column & 1u) != 0u, odd_row = ((p.row0 + row) & 1u) != 0u;
+            const long long step_x = odd_column ? -256 : 256, step_y = odd_row ? -256 : 256;
+            float pu[3], pv[3]; // TEXCOORD at the centre, the horizontal and the vertical partner
+#pragma unroll
+            for (int point = 0; point < 3; ++point) {
+                long long m0 = l0, m1 = l1, m2 = l2;
+                if (point == 1) { m0 -= step_x * (y2 - y1); m1 -= step_x * (y0 - y2); m2 -= step_x * (y1 - y0); }
+                if (point == 2) { m0 += step_y * (x2 - x1); m1 += step_y * (x0 - x2); m2 += step_y * (x1 - x0); }
+                const float r0 = (float)m0 / cw0, r1 = (float)m1 / cw1, r2 = (float)m2 / cw2;
+                const float rs = (r0 + r1) + r2;
+                const float h0 = r0 / rs, h1 = r1 / rs, h2 = r2 / rs;
+                float bb[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
+                    bb[j] = (h0 * B[0][j] + h1 * B1) + h2 * B2;
+                }
+                pu[point] = (bb[0] * uv[0][0] + bb[1] * uv[1][0]) + bb[2] * uv[2][0];
+                pv[point] = (bb[0] * uv[0][1] + bb[1] * uv[1][1]) + bb[2] * uv[2][1];
+            }
+#pragma unroll 1
+            for (uint32_t map = 0u; map < 4u; ++map) { // t0 base colour, t1 metallic-roughness, t2 normal, t3 emissive
+                const uint32_t bit = map == 0u ? UR_MATERIAL_BASE_COLOR_MAP : (map == 1u ? UR_MATERIAL_METALLIC_ROUGHNESS_MAP : (map == 2u ? UR_MATERIAL_NORMAL_MAP : UR_MATERIAL_EMISSIVE_MAP));
+                if (__ballot((bits & bit) != 0u) == 0ull) continue;
+                if ((bits & bit) == 0u) continue;
+                const u32x4_t desc = reinterpret_cast<const u32x4_t*>(p.materials + slot)[map];
+                if (!valid_texture(desc)) { bits &= ~bit; continue; }
+                const uint32_t at = 112u + 8u * map; // the map's OffsetScale and Rotation in ur_scene_constants
+                float tu[3], tv[3];
+#pragma unroll
+                for (int point = 0; point < 3; ++point) texture_transform(cb, at, pu[point], pv[point], tu[point], tv[point]);
+                // value(odd) - value(even)
+                const float dxu = odd_column ? tu[0] - tu[1] : tu[1] - tu[0], dxv = odd_column ? tv[0] - tv[1] : tv[1] - tv[0];
+                const float dyu = odd_row ? tu[0] - tu[2] : tu[2] - tu[0], dyv = odd_row ? tv[0] - tv[2] : tv[2] - tv[0];
+                float s[3];
+                sample_map(desc, tu[0], tv[0], dxu, dxv, dyu, dyv, sampler_tables, s);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (map == 0u) base[k] = s[k];
+                    if (map == 1u) mr[k] = s[k];
+                    if (map == 2u) nm[k] = s[k];
+                    if (map == 3u) em[k] = s[k];
+                }
+            }
+        }
+        // ---- the pixel shader (DeferredBasePass.hlsl:80-148)
+        const float nl = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        const float vn[3] = {n[0] / nl, n[1] / nl, n[2] / nl};
+        float wnrm[3] = {vn[0], vn[1], vn[2]};
+        if (bits & UR_MATERIAL_NORMAL_MAP) {
+            float tan4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tan4[k] = (b[0] * tg[0][k] + b[1] * tg[1][k]) + b[2] * tg[2][k];
+            const float dt = (vn[0] * tan4[0] + vn[1] * tan4[1]) + vn[2] * tan4[2];
+            const float u0 = tan4[0] - vn[0] * dt, u1 = tan4[1] - vn[1] * dt, u2 = tan4[2] - vn[2] * dt;
+            const float ul = sqrtf((u0 * u0 + u1 * u1) + u2 * u2);
+            const float t0 = u0 / ul, t1 = u1 / ul, t2 = u2 / ul;
+            const float c0 = vn[1] * t2 - vn[2] * t1, c1 = vn[2] * t0 - vn[0] * t2, c2 = vn[0] * t1 - vn[1] * t0;
+            const float cl = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
+            const float bt0 = (c0 / cl) * tan4[3], bt1 = (c1 / cl) * tan4[3], bt2 = (c2 / cl) * tan4[3];
+            const float nr = nm[0] * 2.0f - 1.0f, ng = nm[1] * 2.0f - 1.0f;
+            const float one_minus = 1.0f - (nr * nr + ng * ng);
+            const float nz = sqrtf(one_minus > 0.0f ? fminf(one_minus, 1.0f) : 0.0f); // saturate
+            const float tl = sqrtf((nr * nr + ng * ng) + nz * nz);
+            const bool flat = tl < 1e-5f;
+            const float e0 = flat ? 0.0f : nr, e1 = flat ? 0.0f : ng, e2 = flat ? 1.0f : nz;
+            const float w0 = (e0 * t0 + e1 * bt0) + e2 * vn[0], w1 = (e0 * t1 + e1 * bt1) + e2 * vn[1], w2 = (e0 * t2 + e1 * bt2) + e2 * vn[2];
+            const float wl = sqrtf((w0 * w0 + w1 * w1) + w2 * w2);
+            wnrm[0] = w0 / wl; wnrm[1] = w1 / wl; wnrm[2] = w2 / wl;
+        }
+        float m[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = (wnrm[0] * p.V[k] + wnrm[1] * p.V[4 + k]) + wnrm[2] * p.V[8 + k];
+        const float ml = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+        const float view_depth = -(((wpos[0] * p.V[2] + wpos[1] * p.V[6]) + wpos[2] * p.V[10]) + p.V[14]);
+        float albedo[3] = {cb[64] * colour[0], cb[65] * colour[1], cb[66] * colour[2]};
+        float metallic = cb[104], roughness = cb[105];
+        float emissive[3] = {cb[80], cb[81], cb[82]};
+        if (bits & UR_MATERIAL_BASE_COLOR_MAP) { albedo[0] = albedo[0] * base[0]; albedo[1] = albedo[1] * base[1]; albedo[2] = albedo[2] * base[2]; }
+        if (bits & UR_MATERIAL_METALLIC_ROUGHNESS_MAP) { metallic = metallic * mr[2]; roughness = roughness * mr[1]; }
+        if (bits & UR_MATERIAL_EMISSIVE_MAP) { emissive[0] = emissive[0] * em[0]; emissive[1] = emissive[1] * em[1]; emissive[2] = emissive[2] * em[2]; }
+        const uint32_t r8 = srgb_code(table, albedo[0]), g8 = srgb_code(table, albedo[1]), b8 = srgb_code(table, albedo[2]);
+        ur::store_once_b64(p.gbuf_a + i, pack_half4(m[0] / ml, m[1] / ml, m[2] / ml, view_depth));
+        ur::store_once_b64(p.gbuf_b + i, pack_half4(0.04f, metallic, roughness, 1.0f));
+        ur::store_once_b32(p.gbuf_c + i, r8 | (g8 << 8) | (b8 << 16) | 0xFF000000u);
+        ur::store_once_b64(p.hdr + i, pack_half4(emissive[0], emissive[1], emissive[2], 1.0f));
+        if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
+        return;
     }
 
     // ---- the pixel shader (DeferredBasePass.hlsl:80-149 without maps)
@@ -789,7 +1025,8 @@ int launch(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws*
 // The launches of the GBuffer pass: launch_raster over the key image (UR_GBUFFER_PART_RASTER), then the resolve (UR_GBUFFER_PART_RESOLVE)
 template <bool D24>
 int launch_gbuffer(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* tg,
-                   uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, uint32_t* stats, uint32_t parts)
+                   uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, uint32_t* stats, uint32_t parts, const ur_material* materials,
+                   uint32_t material_count)
 {
     const uint32_t n = w * rows;
     if (parts & UR_GBUFFER_PART_RASTER) {
@@ -811,56 +1048,90 @@ int launch_gbuffer(ur_ctx* ctx, const float* view, const float* projection, cons
     r.half_w = 0.5f * (float)w; r.half_h = 0.5f * (float)h;
     r.key_bits = key_bits;
     const uint32_t blocks = (n + kThreads - 1u) / kThreads;
+    if (materials) { // the textured resolve
+        r.materials = materials; r.material_count = material_count;
+        r.decode = ctx->srgb_table; r.lod = ctx->lod_table;
+        if (tg->object_id) hipLaunchKernelGGL((gbuffer_resolve_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        else hipLaunchKernelGGL((gbuffer_resolve_kernel<false, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        UR_HIP_TRY(hipGetLastError());
+        return UR_OK;
+    }
     if (tg->object_id) hipLaunchKernelGGL(gbuffer_resolve_kernel<true>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
     else hipLaunchKernelGGL(gbuffer_resolve_kernel<false>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int ur_gbuffer_pass_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
-                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts)
+// The checks and the launches behind the four GBuffer entry points; `who` names the caller in the error text, `who_parts` its _parts form
+int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
+                  const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
+                  uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count)
 {
-    const int rc = check_arguments("ur_gbuffer_pass", ctx, view, projection, draws, depth, w, h, stats6);
+    const int rc = check_arguments(who, ctx, view, projection, draws, depth, w, h, stats6);
     if (rc != UR_OK) return rc;
-    if (flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_gbuffer_pass: unknown flag bits 0x%x", flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    if (flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("%s: unknown flag bits 0x%x", who, flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
     if (!targets || !targets->gbuf_a || !targets->gbuf_b || !targets->gbuf_c || !targets->hdr || !targets->keys) {
-        ur::set_error("ur_gbuffer_pass: null targets, or a null target other than object_id");
+        ur::set_error("%s: null targets, or a null target other than object_id", who);
         return UR_EINVAL;
     }
     if (!aligned(targets->gbuf_a, 8) || !aligned(targets->gbuf_b, 8) || !aligned(targets->hdr, 8) || !aligned(targets->gbuf_c, 4) || !aligned(targets->object_id, 4) ||
         !aligned(targets->keys, 4)) {
-        ur::set_error("ur_gbuffer_pass: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)");
+        ur::set_error("%s: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)", who);
         return UR_EINVAL;
     }
-    if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("ur_gbuffer_pass: rows [%u, %u + %u) of a target %u high", row0, row0, rows, h); return UR_EINVAL; }
-    if (parts == 0u || (parts & ~(UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE))) { ur::set_error("ur_gbuffer_pass_parts: parts 0x%x (UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE)", parts); return UR_EINVAL; }
-    if (key_triangle_bits > 31u) { ur::set_error("ur_gbuffer_pass: key_triangle_bits %u (0 = automatic, 1..31)", key_triangle_bits); return UR_EINVAL; }
+    if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("%s: rows [%u, %u + %u) of a target %u high", who, row0, row0, rows, h); return UR_EINVAL; }
+    if (parts == 0u || (parts & ~(UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE))) { ur::set_error("%s: parts 0x%x (UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE)", who_parts, parts); return UR_EINVAL; }
+    if (key_triangle_bits > 31u) { ur::set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, key_triangle_bits); return UR_EINVAL; }
     uint32_t key_bits = key_triangle_bits;
     if (key_bits == 0u) {
         if (draws->command_count >= (1u << 24)) {
-            ur::set_error("ur_gbuffer_pass: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", draws->command_count);
+            ur::set_error("%s: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", who, draws->command_count);
             return UR_EUNSUPPORTED;
         }
         uint32_t length = 0u;
         while ((draws->command_count >> length) != 0u) ++length;
         key_bits = min(32u - length, 31u);
     } else if ((uint64_t)draws->command_count >= (1ull << (32u - key_bits))) {
-        ur::set_error("ur_gbuffer_pass: %u command slots do not fit the %u key bits beside key_triangle_bits %u", draws->command_count, 32u - key_bits, key_bits);
+        ur::set_error("%s: %u command slots do not fit the %u key bits beside key_triangle_bits %u", who, draws->command_count, 32u - key_bits, key_bits);
         return UR_EINVAL;
     }
-    if (flags & UR_DEPTH_QUANTIZE_D24) return launch_gbuffer<true>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts);
-    return launch_gbuffer<false>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts);
+    if (!aligned(materials, 16)) { ur::set_error("%s: a misaligned material table (16 bytes)", who); return UR_EINVAL; }
+    if (flags & UR_DEPTH_QUANTIZE_D24) return launch_gbuffer<true>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts, materials, material_count);
+    return launch_gbuffer<false>(ctx, view, projection, draws, depth, targets, w, h, row0, rows, key_bits, stats6, parts, materials, material_count);
+}
+
+} // namespace
+
+extern "C" {
+
+int ur_gbuffer_pass_materials_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
+                                    const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
+                                    uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count)
+{
+    return gbuffer_entry("ur_gbuffer_pass_materials", "ur_gbuffer_pass_materials_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags,
+                         key_triangle_bits, stats6, parts, materials, material_count);
+}
+
+int ur_gbuffer_pass_materials(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                              uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6,
+                              const ur_material* materials, uint32_t material_count)
+{
+    return gbuffer_entry("ur_gbuffer_pass_materials", "ur_gbuffer_pass_materials_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags,
+                         key_triangle_bits, stats6, UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, materials, material_count);
+}
+
+int ur_gbuffer_pass_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts)
+{
+    return gbuffer_entry("ur_gbuffer_pass", "ur_gbuffer_pass_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6, parts,
+                         nullptr, 0u);
 }
 
 int ur_gbuffer_pass(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
                     uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6)
 {
-    return ur_gbuffer_pass_parts(ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6,
-                                 UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE);
+    return gbuffer_entry("ur_gbuffer_pass", "ur_gbuffer_pass_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6,
+                         UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, nullptr, 0u);
 }
 
 int ur_raster_reserve(ur_ctx* ctx, uint32_t max_large_work_items)

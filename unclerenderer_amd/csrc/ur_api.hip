@@ -146,10 +146,7 @@ ur_ctx* ur_create(int device, void* stream)
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     // sRGB8 -> linear (exact IEC 61966-2-1 curve, evaluated in double)
     float table[256];
-    for (int i = 0; i < 256; ++i) {
-        const double c = i / 255.0;
-        table[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
-    }
+    ur_host_srgb_decode_table(table);
     if (hipMalloc(&ctx->srgb_table, sizeof(table)) != hipSuccess ||
         hipMemcpy(ctx->srgb_table, table, sizeof(table), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("ur_create: sRGB table upload failed");
@@ -161,6 +158,13 @@ ur_ctx* ur_create(int device, void* stream)
     if (hipMalloc(&ctx->srgb_encode_table, sizeof(encode)) != hipSuccess ||
         hipMemcpy(ctx->srgb_encode_table, encode, sizeof(encode), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("ur_create: sRGB encode table upload failed");
+        ur_destroy(ctx);
+        return nullptr;
+    }
+    float lod[127];
+    ur_host_lod_table(lod);
+    if (hipMalloc(&ctx->lod_table, sizeof(lod)) != hipSuccess || hipMemcpy(ctx->lod_table, lod, sizeof(lod), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("ur_create: level-of-detail table upload failed");
         ur_destroy(ctx);
         return nullptr;
     }
@@ -212,6 +216,7 @@ void ur_destroy(ur_ctx* ctx)
     if (ctx->hzb_timed_out) (void)hipHostFree(const_cast<uint32_t*>(ctx->hzb_timed_out));
     if (ctx->srgb_table) (void)hipFree(ctx->srgb_table);
     if (ctx->srgb_encode_table) (void)hipFree(ctx->srgb_encode_table);
+    if (ctx->lod_table) (void)hipFree(ctx->lod_table);
     if (ctx->block_counts) (void)hipFree(ctx->block_counts);
     if (ctx->wave_masks) (void)hipFree(ctx->wave_masks);
     if (ctx->raster_queue) (void)hipFree(ctx->raster_queue);

@@ -37,6 +37,8 @@ struct ur_ctx {
     float* srgb_table = nullptr;
     // linear -> sRGB8 thresholds (255 floats, ur_host_srgb_encode_table), uploaded once: the GBuffer resolve's encode
     float* srgb_encode_table = nullptr;
+    // 127 thresholds 2^(j / 128) (ur_host_lod_table), uploaded once: the textured GBuffer resolve's level of detail
+    float* lod_table = nullptr;
     int cu_count = 256;
     // The HZB tail may ride along with the next streaming Lighting launch as one extra workgroup (ur_defer_hzb_tail):
     // its single workgroup is ~5 us of latency during which the other 255 CUs would idle.

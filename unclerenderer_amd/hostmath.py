@@ -76,6 +76,20 @@ def srgb_encode_table() -> np.ndarray:
     return out
 
 
+def srgb_decode_table() -> np.ndarray:
+    """ur_host_srgb_decode_table: the 256 fp32 linear values of the sRGB codes 0..255, the textured GBuffer resolve's texel decode."""
+    out = np.zeros(256, np.float32)
+    _lib.load().ur_host_srgb_decode_table(_lib.fptr(out))
+    return out
+
+
+def lod_table() -> np.ndarray:
+    """ur_host_lod_table: the 127 ascending fp32 thresholds 2^(j / 128), j = 1..127, of the textured GBuffer resolve's level of detail."""
+    out = np.zeros(127, np.float32)
+    _lib.load().ur_host_lod_table(_lib.fptr(out))
+    return out
+
+
 def apply_taa_jitter(proj, jitter, width: float, height: float) -> np.ndarray:
     """A copy of the projection with _31 += 2 jx / width, _32 += 2 jy / height (elements 8 and 9), as the reference jitters it."""
     out = _f(*proj)

@@ -780,13 +780,58 @@ def gbuffer_targets(gbuf_a, gbuf_b, gbuf_c, hdr, keys, object_id=None) -> _lib.G
     return tg
 
 
+class Texture:
+    """A texture on the device: the packed levels (`buffer`, kept alive here) and their ur_texture2d descriptor (`desc`)."""
+
+    def __init__(self, buffer, desc):
+        self.buffer, self.desc = buffer, desc
+
+
+def pack_texture(levels, srgb: bool) -> Texture:
+    """A list of (h, w, 4) uint8 arrays, level 0 first, level k max(1, w >> k) x max(1, h >> k), becomes one device buffer of tightly
+    packed texels and its descriptor (UR_TEXTURE_R8G8B8A8_UNORM_SRGB when srgb, else UR_TEXTURE_R8G8B8A8_UNORM)."""
+    levels = [np.ascontiguousarray(a, np.uint8) for a in levels]
+    h0, w0 = levels[0].shape[:2]
+    assert 1 <= len(levels) <= 255 and 1 <= w0 <= 65535 and 1 <= h0 <= 65535
+    for k, a in enumerate(levels):
+        assert a.shape == (max(1, h0 >> k), max(1, w0 >> k), 4), f"level {k} is {a.shape}"
+    buffer = to_device(np.concatenate([a.reshape(-1) for a in levels]).view(np.uint32))
+    desc = _lib.Texture2D(buffer.data_ptr(), w0, h0, len(levels), _lib.UR_TEXTURE_R8G8B8A8_UNORM_SRGB if srgb else _lib.UR_TEXTURE_R8G8B8A8_UNORM, 0)
+    return Texture(buffer, desc)
+
+
+class Materials:
+    """A ur_material table on the device: `table` (int32 tensor, 20 dwords per record), `count`, and the textures it points to."""
+
+    def __init__(self, table, count, keep):
+        self.table, self.count, self._keep = table, count, keep
+
+
+def pack_materials(materials) -> Materials:
+    """[{"key": pipeline key, "base_color" / "metallic_roughness" / "normal" / "emissive": a Texture, a lib.Texture2D or None}, ...], one
+    per command slot, becomes the device table HotPath.gbuffer_pass(materials=) and Frame.set_gbuffer_materials take."""
+    rec = (_lib.Material * max(len(materials), 1))()
+    keep = []
+    for r, m in zip(rec, materials):
+        r.pipeline_key = int(m.get("key", 0))
+        for name in ("base_color", "metallic_roughness", "normal", "emissive"):
+            t = m.get(name)
+            if t is None:
+                continue
+            keep.append(t)
+            setattr(r, name, t.desc if isinstance(t, Texture) else t)
+    host = np.frombuffer(bytes(rec), np.uint32).copy()
+    return Materials(to_device(host), len(materials), keep)
+
+
 def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0, rows=None, *, visible=None, ranges=None, index_base=0, stats=None,
-                  command_count=None, flags=0, key_triangle_bits=0, parts=None):
+                  command_count=None, flags=0, key_triangle_bits=0, parts=None, materials=None):
     """ur_gbuffer_pass: rasterise the selected draws of `commands` (64-byte vertices, whole ur_scene_constants behind the constant address)
     into visibility keys against `depth` (the w x h result of depth_prepass, read only) and resolve the rows [row0, row0 + rows) into
     `targets` (gbuffer_targets(...)). The selections are HotPath.shadow_map's; stats: uint32[6] device tensor, added to; flags:
     UR_DEPTH_QUANTIZE_D24; key_triangle_bits: the key's triangle bits, 0 = 32 - bit_length(command_count). parts: None, or for a timing tool
-    UR_GBUFFER_PART_RASTER and / or UR_GBUFFER_PART_RESOLVE through ur_gbuffer_pass_parts (the resolve part alone trusts targets.keys)."""
+    UR_GBUFFER_PART_RASTER and / or UR_GBUFFER_PART_RESOLVE through ur_gbuffer_pass_parts (the resolve part alone trusts targets.keys).
+    materials: a pack_materials(...) table, one record per command slot: the textured resolve of ur_gbuffer_pass_materials."""
     rows = h - row0 if rows is None else rows
     assert depth.dtype == torch.float32 and depth.numel() >= w * h
     v, p = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (view, projection))
@@ -794,7 +839,13 @@ def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0
     d = raster_draws(commands, command_count, visible, ranges, index_base)
     args = (self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), C.byref(targets), w, h, int(row0), int(rows), int(flags), int(key_triangle_bits),
             _ptr(stats))
-    if parts is None:
+    if materials is not None:
+        table, count = (materials.table, materials.count) if isinstance(materials, Materials) else materials
+        if parts is None:
+            _lib.check(self._L.ur_gbuffer_pass_materials(*args, _ptr(table), int(count)), "ur_gbuffer_pass_materials")
+        else:
+            _lib.check(self._L.ur_gbuffer_pass_materials_parts(*args, int(parts), _ptr(table), int(count)), "ur_gbuffer_pass_materials_parts")
+    elif parts is None:
         _lib.check(self._L.ur_gbuffer_pass(*args), "ur_gbuffer_pass")
     else:
         _lib.check(self._L.ur_gbuffer_pass_parts(*args, int(parts)), "ur_gbuffer_pass_parts")
@@ -867,6 +918,19 @@ def _frame_set_gbuffer_pass(self, commands=None, targets=None, *, visible=None, 
 
 
 Frame.set_gbuffer_pass = _frame_set_gbuffer_pass
+
+
+def _frame_set_gbuffer_materials(self, materials=None):
+    """ur_frame_set_gbuffer_materials: the pack_materials(...) table the "GBuffer" pass of the following frames resolves with
+    (ur_gbuffer_pass_materials); None clears it. Kept alive here."""
+    self._gbuffer_materials_keep = materials
+    if materials is None:
+        _lib.check(self._L.ur_frame_set_gbuffer_materials(self._f, None, 0), "ur_frame_set_gbuffer_materials")
+    else:
+        _lib.check(self._L.ur_frame_set_gbuffer_materials(self._f, _ptr(materials.table), int(materials.count)), "ur_frame_set_gbuffer_materials")
+
+
+Frame.set_gbuffer_materials = _frame_set_gbuffer_materials
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:

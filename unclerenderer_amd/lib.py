@@ -69,6 +69,22 @@ class GBufferTargets(C.Structure):
                 ("keys", C.c_void_p)]
 
 
+class Texture2D(C.Structure):
+    """ur_texture2d (include/ur_raster.h): `mips` tightly packed levels of R8G8B8A8 texels from the device address `texels`."""
+    _fields_ = [("texels", C.c_uint64), ("width", C.c_uint16), ("height", C.c_uint16), ("mips", C.c_uint8), ("format", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class Material(C.Structure):
+    """ur_material (include/ur_raster.h): the textures t0-t3 and the pipeline key of one command slot, 80 bytes."""
+    _fields_ = [("base_color", Texture2D), ("metallic_roughness", Texture2D), ("normal", Texture2D), ("emissive", Texture2D),
+                ("pipeline_key", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+UR_TEXTURE_R8G8B8A8_UNORM = 28
+UR_TEXTURE_R8G8B8A8_UNORM_SRGB = 29
+UR_MATERIAL_NORMAL_MAP, UR_MATERIAL_METALLIC_ROUGHNESS_MAP, UR_MATERIAL_BASE_COLOR_MAP, UR_MATERIAL_EMISSIVE_MAP = 1, 2, 4, 8
+
+
 class FrameGBufferPass(C.Structure):
     """ur_frame_gbuffer_pass (include/ur_frame.h): the draws, targets, optional counters, ur_gbuffer_pass flags and key bits of UR_FRAME_GBUFFER_PASS."""
     _fields_ = [("draws", RasterDraws), ("targets", GBufferTargets), ("stats6", C.c_void_p), ("flags", C.c_uint32), ("key_triangle_bits", C.c_uint32)]
@@ -304,6 +320,9 @@ SIGNATURES = {
     "ur_depth_prepass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _U32, _VP]),
     "ur_gbuffer_pass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP]),
     "ur_gbuffer_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32]),
+    "ur_gbuffer_pass_materials": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _U32]),
+    "ur_gbuffer_pass_materials_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
+                                                  _VP, _U32]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
@@ -338,6 +357,7 @@ SIGNATURES = {
     "ur_frame_set_shadow_pass": (C.c_int, [_VP, C.POINTER(FrameShadowPass)]),
     "ur_frame_set_depth_pass": (C.c_int, [_VP, C.POINTER(FrameDepthPass)]),
     "ur_frame_set_gbuffer_pass": (C.c_int, [_VP, C.POINTER(FrameGBufferPass)]),
+    "ur_frame_set_gbuffer_materials": (C.c_int, [_VP, _VP, _U32]),
     "ur_frame_report": (_U32, [_VP, C.c_char_p, _U32]),
     "ur_rg_timing_stats": (_U32, [C.c_char_p, _U32]),
     # ur_host.h
@@ -356,6 +376,8 @@ SIGNATURES = {
     "ur_host_taa_jitter": (None, [_U32, _FP]),
     "ur_host_apply_taa_jitter": (None, [_FP, _FP, _F, _F]),
     "ur_host_srgb_encode_table": (None, [_FP]),
+    "ur_host_srgb_decode_table": (None, [_FP]),
+    "ur_host_lod_table": (None, [_FP]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
