@@ -155,7 +155,8 @@ int ur_gbuffer_pass_parts(ur_ctx* ctx, const float view[16], const float project
 
 /* A texture of the textured GBuffer resolve: `mips` levels packed tightly one behind the other from `texels` (device, 4-byte aligned),
  * level k = max(1, width >> k) x max(1, height >> k) texels of 4 bytes, row-major, R in the low byte. Any size 1..65535, powers of two
- * or not. */
+ * or not. `mips` may be anything 1..255: levels past the end of the chain (every level from 16 on) are 1 x 1 texels packed one behind
+ * the other like any level. */
 typedef struct ur_texture2d {
     uint64_t texels;
     uint16_t width, height;

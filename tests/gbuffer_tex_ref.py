@@ -375,6 +375,9 @@ def accuracy(out):
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------
 
 TEXTURE_SHAPES = [(16, 16, 5), (13, 7, 4), (1, 1, 1), (8, 4, 1)]
+# (w, h, mips) at the ends of ur_texture2d's ranges: the largest dimension each way, a chain one level longer than its last shrinking
+# level, sizes that are no power of two, and the largest texture the tests upload (8 MB at level 0)
+EDGE_SHAPES = [(65535, 1, 1), (1, 65535, 16), (65535, 2, 17), (1000, 600, 10), (2048, 1024, 12), (3, 4099, 13)]
 SOUPS = [(64, 64, 1), (257, 130, 2)]
 SOUP_DRAWS = 18
 UV_SEED = 2000  # (chosen so that float64 takes other taps than fp32 on at most 2 % of the textured texels of both soups)
@@ -430,15 +433,16 @@ class TexDraw(G.GDraw):
         return c
 
 
-def soup_materials(seed: int, count: int = SOUP_DRAWS):
-    """A material per command cycling through keys 0-15 (command k: key k % 16), its four textures cycling through TEXTURE_SHAPES, sRGB
-    for base colour and emissive."""
+def soup_materials(seed: int, count: int = SOUP_DRAWS, shapes=None):
+    """A material per command cycling through keys 0-15 (command k: key k % 16), its four textures cycling through `shapes`
+    (TEXTURE_SHAPES unless given), sRGB for base colour and emissive."""
+    shapes = TEXTURE_SHAPES if shapes is None else shapes
     rng = np.random.default_rng(seed + 3000)
     out = []
     for k in range(count):
         m = {"key": k % 16}
         for j, (name, _, _) in enumerate(MAPS):
-            tw, th, mips = TEXTURE_SHAPES[(k + j) % len(TEXTURE_SHAPES)]
+            tw, th, mips = shapes[(k + j) % len(shapes)]
             m[name] = random_texture(tw, th, mips, name in ("base_color", "emissive"), rng)
         out.append(m)
     return out

@@ -10,7 +10,7 @@ from tests.gbuffer_gpu import device_draws, run, same
 from tests.gbuffer_tex_gpu import device_materials
 from tests.test_gbuffer_tex_ref import H as HAND_H
 from tests.test_gbuffer_tex_ref import W as HAND_W
-from tests.test_gbuffer_tex_ref import hand_cases, soup_reference
+from tests.test_gbuffer_tex_ref import edge_soup_reference, hand_cases, soup_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +47,21 @@ def test_soups(hotpath, w, h, seed):
                 if h > 78:
                     band = run(hotpath, dd, view, proj, dev_depth, w, h, 37, 41, object_id=oid, materials=dm)
                     same(band, want, f"soup {w}x{h} rows [37, 78), reserve {reserve}, ObjectId {oid}", 37, 41)
+    finally:
+        hotpath.raster_reserve(0)
+
+
+def test_edge_shape_soup(hotpath):
+    """The 64 x 64 soup under textures at the ends of ur_texture2d's ranges (gbuffer_tex_ref.EDGE_SHAPES: 65535 texels each way, chains of
+    16 and 17 levels, sizes that are no power of two, 8 MB at level 0), with a 65536-entry queue and without one, ObjectId on."""
+    w, h, _ = X.SOUPS[0]
+    draws, view, proj, depth, mats, want = edge_soup_reference()
+    dd, dm, dev_depth = device_draws(draws), device_materials(mats), _depth(depth)
+    try:
+        for reserve in (1 << 16, 0):
+            hotpath.raster_reserve(reserve)
+            got = run(hotpath, dd, view, proj, dev_depth, w, h, materials=dm)
+            same(got, want, f"edge shapes, reserve {reserve}")
     finally:
         hotpath.raster_reserve(0)
 

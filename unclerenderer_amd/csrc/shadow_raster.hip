@@ -650,11 +650,12 @@ __device__ __forceinline__ void sample_map(const u32x4_t desc, float u, float v,
     }
     const uint32_t d = (uint32_t)L >> 8;
     const float f = (float)(L & 255) * 0.00390625f;
+    // a dimension is at most 65535, so every level from 16 on is 1 x 1: the shift count stays below the word's width for any `mips`
     size_t offset = 0u;
-    for (uint32_t k = 0u; k < d; ++k) offset += (size_t)max(1u, width >> k) * max(1u, height >> k);
-    const uint32_t wd = max(1u, width >> d), hd = max(1u, height >> d);
+    for (uint32_t k = 0u; k < d; ++k) offset += (size_t)max(1u, width >> min(k, 16u)) * max(1u, height >> min(k, 16u));
+    const uint32_t wd = max(1u, width >> min(d, 16u)), hd = max(1u, height >> min(d, 16u));
     const uint32_t d1 = min(d + 1u, mips - 1u);
-    const uint32_t we = max(1u, width >> d1), he = max(1u, height >> d1);
+    const uint32_t we = max(1u, width >> min(d1, 16u)), he = max(1u, height >> min(d1, 16u));
     const uint32_t* level0 = texels + offset;
     const uint32_t* level1 = d1 == d ? level0 : level0 + (size_t)wd * hd;
     const float* tab = lds + (format == UR_TEXTURE_R8G8B8A8_UNORM_SRGB ? kLdsDecode : kLdsUnorm);
