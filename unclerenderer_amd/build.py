@@ -38,7 +38,8 @@ SOURCES = [
     ("taa.hip", EXACT),
     ("post.hip", EXACT),
     ("debug_print.hip", EXACT),
-    ("shadow_raster.hip", EXACT),
+    ("raster.hip", EXACT),
+    ("gbuffer_resolve.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),

@@ -62,24 +62,17 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
     const FRGResourceHandle DebugStatsHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintStats", Res.CullStats, &Res.DebugPrintStatsState, {2, 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
     const FRGResourceHandle DebugBufferHandle = bDebugPrint ? Graph.ImportTexture("DebugPrintBuffer", Res.DebugPrintBuffer, &Res.DebugPrintState, {static_cast<uint32>(ur_debug_print_buffer_bytes() / 4u), 1, RG_FORMAT_UNKNOWN}) : FRGResourceHandle{};
 
-    // ShadowMap: what the pass draws from (the light view's list or ranges, written by this frame's cull when it runs)
-    const bool bShadowPass = Options.bShadowPass && Res.ShadowDraws != nullptr && Res.ShadowMapTarget != nullptr;
+    // What a raster pass draws from, written by this frame's cull when it runs: its list, else the commands of its ranges or its own
+    const auto ImportDraws = [&Graph](const char* Name, const ur_raster_draws& D, uint32* State) {
+        const void* Draws = D.visible_idx ? static_cast<const void*>(D.visible_idx) : ur::raster_commands(D);
+        return Graph.ImportTexture(Name, const_cast<void*>(Draws), State, {D.command_count, 1, RG_FORMAT_UNKNOWN});
+    };
+    // ShadowMap: the light view's draws; DepthPrepass: the camera's
+    const bool bShadowPass = Res.ShadowPass.Draws != nullptr && Res.ShadowPass.Map != nullptr;
+    const bool bDepthPass = Res.DepthPass.Draws != nullptr && Res.DepthPass.Depth != nullptr;
     const bool bCullEnabled = Options.bEnableIndirectDraw && Res.IndirectArgs && Res.ModelBounds && Res.IndirectCommandCount != 0;
-    FRGResourceHandle ShadowDrawsHandle;
-    if (bShadowPass) {
-        const ur_raster_draws& D = *Res.ShadowDraws;
-        const void* Draws = D.ranges ? D.ranges->commands : (D.visible_idx ? static_cast<const void*>(D.visible_idx) : D.commands);
-        ShadowDrawsHandle = Graph.ImportTexture("ShadowDraws", const_cast<void*>(Draws), &Res.ShadowDrawsState, {D.command_count, 1, RG_FORMAT_UNKNOWN});
-    }
-
-    // DepthPrepass: the same for the camera's draws
-    const bool bDepthPass = Options.bDepthPass && Res.DepthDraws != nullptr && Res.DepthTarget != nullptr;
-    FRGResourceHandle DepthDrawsHandle;
-    if (bDepthPass) {
-        const ur_raster_draws& D = *Res.DepthDraws;
-        const void* Draws = D.ranges ? D.ranges->commands : (D.visible_idx ? static_cast<const void*>(D.visible_idx) : D.commands);
-        DepthDrawsHandle = Graph.ImportTexture("DepthDraws", const_cast<void*>(Draws), &Res.DepthDrawsState, {D.command_count, 1, RG_FORMAT_UNKNOWN});
-    }
+    const FRGResourceHandle ShadowDrawsHandle = bShadowPass ? ImportDraws("ShadowDraws", *Res.ShadowPass.Draws, &Res.ShadowDrawsState) : FRGResourceHandle{};
+    const FRGResourceHandle DepthDrawsHandle = bDepthPass ? ImportDraws("DepthDraws", *Res.DepthPass.Draws, &Res.DepthDrawsState) : FRGResourceHandle{};
 
     const bool bHZBEnabled = Options.bHZBEnabled && Res.HZB != nullptr && Res.HZBMipCount != 0;
     if (!bHZBEnabled) bHZBReady = false; // :514-517
@@ -156,7 +149,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         {
             if (!Data.bEnabled) return;
             // ClearDepth(1.0) and the draws of :571-631, on the stream the pass runs on (the main one: it is not an async-compute pass)
-            const int rc = ur_shadow_map(Cmd.GetContext(), Data.LightViewProjection, Res.ShadowDraws, Res.ShadowMapTarget, Data.Width, Data.Height, Res.ShadowStats);
+            const int rc = ur_shadow_map(Cmd.GetContext(), Data.LightViewProjection, Res.ShadowPass.Draws, Res.ShadowPass.Map, Data.Width, Data.Height, Res.ShadowPass.Stats);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -176,7 +169,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
             std::memcpy(Data.Projection, Constants.Scene.Projection, sizeof(Data.Projection));
             Data.Width = Res.Width;
             Data.Height = Res.Height;
-            Data.Flags = Res.DepthPassFlags;
+            Data.Flags = Res.DepthPass.Flags;
             if (Data.bEnabled) {
                 if (bCullEnabled) Builder.ReadTexture(DepthDrawsHandle, RG_STATE_INDIRECT_ARGUMENT); // (on the async lane: the wait on the cull)
                 Builder.WriteTexture(DepthHandle, RG_STATE_DEPTH_WRITE);
@@ -185,7 +178,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         {
             if (!Data.bEnabled) return;
             // ClearDepth(0.0) and the draws of :655-716, on the main stream: Build HZB (on the async lane: behind a wait) reads what it wrote
-            const int rc = ur_depth_prepass(Cmd.GetContext(), Data.View, Data.Projection, Res.DepthDraws, Res.DepthTarget, Data.Width, Data.Height, Data.Flags, Res.DepthStats);
+            const int rc = ur_depth_prepass(Cmd.GetContext(), Data.View, Data.Projection, Res.DepthPass.Draws, Res.DepthPass.Depth, Data.Width, Data.Height, Data.Flags, Res.DepthPass.Stats);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -196,7 +189,7 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         bool bEnabled = false;
         float View[16] = {}, Projection[16] = {};
     };
-    if (bDepthPass && Options.bGBufferPass && Res.GBufferDraws != nullptr && Res.GBufferTargets != nullptr) {
+    if (bDepthPass && Res.GBufferPass.Draws != nullptr) {
         Graph.AddPass<FGBufferPassData>("GBuffer", [&](FGBufferPassData& Data, FRGPassBuilder& Builder)
         {
             Data.bEnabled = Options.bDoDepthPrepass; // (the base pass tests against the prepass' depth: without it the pass is listed and culled)
@@ -213,9 +206,9 @@ int FHotPathRenderer::RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Re
         {
             if (!Data.bEnabled) return;
             // (a null table is ur_gbuffer_pass)
-            const int rc = ur_gbuffer_pass_materials(Cmd.GetContext(), Data.View, Data.Projection, Res.GBufferDraws, Res.DepthTarget, Res.GBufferTargets, Res.Width,
-                                                     Res.Height, Res.Row0, Res.Rows, Res.DepthPassFlags, Res.GBufferKeyBits, Res.GBufferStats, Res.GBufferMaterials,
-                                                     Res.GBufferMaterialCount);
+            const int rc = ur_gbuffer_pass_materials(Cmd.GetContext(), Data.View, Data.Projection, Res.GBufferPass.Draws, Res.DepthPass.Depth, &Res.GBufferPass.Targets,
+                                                     Res.Width, Res.Height, Res.Row0, Res.Rows, Res.DepthPass.Flags, Res.GBufferPass.KeyBits, Res.GBufferPass.Stats,
+                                                     Res.GBufferMaterials, Res.GBufferMaterialCount);
             if (rc != UR_OK && PassError == UR_OK) PassError = rc;
         });
     }
@@ -742,6 +735,18 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
 // ---------------------------------------------------------------------------------------------------------------------
 // C face
 // ---------------------------------------------------------------------------------------------------------------------
+// The draws of a raster pass as the frame keeps them: the caller's struct and a copy of its ranges, which Draws.ranges refers to. It points
+// into itself: it lives in ur_frame, which is never copied.
+struct FRasterPassBinding
+{
+    ur_raster_draws Draws = {};
+    ur_draw_ranges Ranges = {};
+    bool bSet = false;
+    void Set(const ur_raster_draws& In) { Draws = In; Ranges = In.ranges ? *In.ranges : ur_draw_ranges{}; Draws.ranges = In.ranges ? &Ranges : nullptr; bSet = true; }
+    void Clear() { Draws = ur_raster_draws{}; Ranges = ur_draw_ranges{}; bSet = false; }
+    bool IsSet() const { return bSet; }
+};
+
 struct ur_frame
 {
     FHIPDevice Device;
@@ -770,20 +775,17 @@ struct ur_frame
     void* TaaRecord = nullptr;         // ur_frame_set_taa_records
     const void* TaaRecords = nullptr;
     ur_frame_debug_print DebugPrint = {}; // ur_frame_set_debug_print
-    ur_frame_shadow_pass ShadowPass = {}; // ur_frame_set_shadow_pass (draws.ranges points into ShadowRanges)
-    ur_draw_ranges ShadowRanges = {};
-    bool bShadowPass = false;
-    ur_frame_depth_pass DepthPass = {};   // ur_frame_set_depth_pass (draws.ranges points into DepthRanges)
-    ur_draw_ranges DepthRanges = {};
-    bool bDepthPass = false;
-    ur_frame_gbuffer_pass GBufferPass = {}; // ur_frame_set_gbuffer_pass (draws.ranges points into GBufferRanges)
-    ur_draw_ranges GBufferRanges = {};
-    bool bGBufferPass = false;
+    FRasterPassBinding ShadowDraws, DepthDraws, GBufferDraws; // ur_frame_set_shadow_pass / _depth_pass / _gbuffer_pass: the draws ...
+    FShadowPassResources ShadowPass;                          // ... and the rest of each pass (Draws points at its binding's)
+    FDepthPassResources DepthPass;
+    FGBufferPassResources GBufferPass;
     const ur_material* GBufferMaterials = nullptr; // ur_frame_set_gbuffer_materials: the "GBuffer" pass resolves with them
     uint32_t GBufferMaterialCount = 0;
     ur_half4* TaaHaloRows = nullptr;   // the frame's own: 2 x TaaHaloWidth texels, the resolved rows around the band (UR_FRAME_TAA_BAND with CAS)
     uint32_t TaaHaloWidth = 0;
     ur_frame(ur_ctx* Ctx, hipStream_t Stream, uint32 Frames, int Rank, int World) : Cmd(Ctx, Stream, Frames, Rank, World), Renderer(&Device) {}
+    ur_frame(const ur_frame&) = delete; // (CullViews and the bindings point into the frame)
+    ur_frame& operator=(const ur_frame&) = delete;
 };
 
 extern "C" {
@@ -932,27 +934,27 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
         if (!f->DebugPrint.buffer) { ur::set_error("ur_frame_render: DEBUG_PRINT needs ur_frame_set_debug_print's buffer and font"); return UR_EINVAL; }
     }
     if (flags & UR_FRAME_SHADOW_PASS) {
-        if (!f->bShadowPass) { ur::set_error("ur_frame_render: SHADOW_PASS needs ur_frame_set_shadow_pass"); return UR_EINVAL; }
-        if ((flags & UR_FRAME_SHADOWS) && r->tables.shadow_map != f->ShadowPass.shadow_map) {
+        if (!f->ShadowDraws.IsSet()) { ur::set_error("ur_frame_render: SHADOW_PASS needs ur_frame_set_shadow_pass"); return UR_EINVAL; }
+        if ((flags & UR_FRAME_SHADOWS) && r->tables.shadow_map != f->ShadowPass.Map) {
             ur::set_error("ur_frame_render: SHADOW_PASS renders into ur_frame_set_shadow_pass' shadow_map, Lighting reads tables.shadow_map: they must be the same buffer");
             return UR_EINVAL;
         }
     }
     if (flags & UR_FRAME_DEPTH_PASS) {
-        if (!f->bDepthPass) { ur::set_error("ur_frame_render: DEPTH_PASS needs ur_frame_set_depth_pass"); return UR_EINVAL; }
-        if (r->depth_full != f->DepthPass.depth) {
+        if (!f->DepthDraws.IsSet()) { ur::set_error("ur_frame_render: DEPTH_PASS needs ur_frame_set_depth_pass"); return UR_EINVAL; }
+        if (r->depth_full != f->DepthPass.Depth) {
             ur::set_error("ur_frame_render: DEPTH_PASS renders into ur_frame_set_depth_pass' depth, Build HZB reads depth_full: they must be the same buffer");
             return UR_EINVAL;
         }
     }
     if (flags & UR_FRAME_GBUFFER_PASS) {
         if (!(flags & UR_FRAME_DEPTH_PASS)) { ur::set_error("ur_frame_render: GBUFFER_PASS needs UR_FRAME_DEPTH_PASS: the base pass tests against the prepass' depth"); return UR_EINVAL; }
-        if (!f->bGBufferPass) { ur::set_error("ur_frame_render: GBUFFER_PASS needs ur_frame_set_gbuffer_pass"); return UR_EINVAL; }
-        if (f->GBufferPass.flags != f->DepthPass.flags) {
-            ur::set_error("ur_frame_render: GBUFFER_PASS and DEPTH_PASS must quantise alike (flags 0x%x and 0x%x)", f->GBufferPass.flags, f->DepthPass.flags);
+        if (!f->GBufferDraws.IsSet()) { ur::set_error("ur_frame_render: GBUFFER_PASS needs ur_frame_set_gbuffer_pass"); return UR_EINVAL; }
+        if (f->GBufferPass.Flags != f->DepthPass.Flags) {
+            ur::set_error("ur_frame_render: GBUFFER_PASS and DEPTH_PASS must quantise alike (flags 0x%x and 0x%x)", f->GBufferPass.Flags, f->DepthPass.Flags);
             return UR_EINVAL;
         }
-        const ur_gbuffer_targets& T = f->GBufferPass.targets;
+        const ur_gbuffer_targets& T = f->GBufferPass.Targets;
         if (T.gbuf_a != r->gbuffer_a || T.gbuf_b != r->gbuffer_b || T.gbuf_c != r->gbuffer_c || T.hdr != r->lighting_band) {
             ur::set_error("ur_frame_render: GBUFFER_PASS renders into ur_frame_set_gbuffer_pass' targets, Lighting reads gbuffer_a/b/c and adds to lighting_band: they must be the same buffers");
             return UR_EINVAL;
@@ -998,22 +1000,11 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     R.DebugAtlasHeight = f->DebugPrint.atlas_h;
     R.DebugFirstChar = f->DebugPrint.first_char;
     R.DebugCharCount = f->DebugPrint.char_count;
-    const bool shadow_pass = (flags & UR_FRAME_SHADOW_PASS) != 0 && f->bShadowPass;
-    R.ShadowDraws = shadow_pass ? &f->ShadowPass.draws : nullptr;
-    R.ShadowMapTarget = shadow_pass ? f->ShadowPass.shadow_map : nullptr;
-    R.ShadowStats = shadow_pass ? f->ShadowPass.stats4 : nullptr;
-    const bool depth_pass = (flags & UR_FRAME_DEPTH_PASS) != 0 && f->bDepthPass;
-    R.DepthDraws = depth_pass ? &f->DepthPass.draws : nullptr;
-    R.DepthTarget = depth_pass ? f->DepthPass.depth : nullptr;
-    R.DepthStats = depth_pass ? f->DepthPass.stats6 : nullptr;
-    R.DepthPassFlags = depth_pass ? f->DepthPass.flags : 0u;
-    const bool gbuffer_pass = depth_pass && (flags & UR_FRAME_GBUFFER_PASS) != 0 && f->bGBufferPass;
-    R.GBufferDraws = gbuffer_pass ? &f->GBufferPass.draws : nullptr;
-    R.GBufferTargets = gbuffer_pass ? &f->GBufferPass.targets : nullptr;
-    R.GBufferStats = gbuffer_pass ? f->GBufferPass.stats6 : nullptr;
-    R.GBufferKeyBits = gbuffer_pass ? f->GBufferPass.key_triangle_bits : 0u;
-    R.GBufferMaterials = gbuffer_pass ? f->GBufferMaterials : nullptr;
-    R.GBufferMaterialCount = gbuffer_pass ? f->GBufferMaterialCount : 0u;
+    R.ShadowPass = (flags & UR_FRAME_SHADOW_PASS) ? f->ShadowPass : FShadowPassResources{}; // (a flag without its pass, or GBUFFER_PASS without DEPTH_PASS, was refused above)
+    R.DepthPass = (flags & UR_FRAME_DEPTH_PASS) ? f->DepthPass : FDepthPassResources{};
+    R.GBufferPass = (flags & UR_FRAME_GBUFFER_PASS) ? f->GBufferPass : FGBufferPassResources{};
+    R.GBufferMaterials = f->GBufferMaterials; // (read by the "GBuffer" pass alone)
+    R.GBufferMaterialCount = f->GBufferMaterialCount;
 
     FHotPathFrameConstants K;
     std::memcpy(K.CullingConstants, culling_constants, sizeof(K.CullingConstants));
@@ -1045,9 +1036,6 @@ int ur_frame_render(ur_frame* f, const ur_frame_resources* r, const uint32_t* cu
     O.bFuseTaaTonemap = (flags & UR_FRAME_FUSE_TAA_TONEMAP) != 0;
     O.bTaaBand = (flags & UR_FRAME_TAA_BAND) != 0;
     O.bDebugPrint = (flags & UR_FRAME_DEBUG_PRINT) != 0;
-    O.bShadowPass = shadow_pass;
-    O.bDepthPass = depth_pass;
-    O.bGBufferPass = gbuffer_pass;
     O.bShardHZB = (flags & UR_FRAME_HZB_SHARD) != 0 && f->Cmd.GetWorldSize() > 1;
     O.bAsyncCompute = (flags & UR_FRAME_ASYNC_COMPUTE) != 0;
     if (O.bAsyncCompute && !f->AsyncCtx) { // second stream + a context bound to it, created on first use
@@ -1143,40 +1131,15 @@ int ur_frame_set_debug_print(ur_frame* f, const ur_frame_debug_print* dp)
     return UR_OK;
 }
 
-// What ur_shadow_map / ur_depth_prepass refuse in a pass struct's draws, target and counters; `who` and `target_name` go into the error text
-static int check_raster_pass(const char* who, const char* target_name, const ur_raster_draws& d, const void* target, const void* stats)
-{
-    const ur_draw_ranges* rg = d.ranges;
-    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
-    if (!target) { ur::set_error("%s: null %s", who, target_name); return UR_EINVAL; }
-    if ((d.visible_idx != nullptr) != (d.visible_count != nullptr)) { ur::set_error("%s: a list needs visible_idx and visible_count", who); return UR_EINVAL; }
-    if (d.visible_idx && rg) { ur::set_error("%s: a list and ranges at once", who); return UR_EINVAL; }
-    if (rg && (!rg->offsets || !rg->commands || !rg->counts || rg->range_count == 0)) { ur::set_error("%s: a null member of ranges / no range", who); return UR_EINVAL; }
-    if (!rg && !d.commands && d.command_count != 0) { ur::set_error("%s: null commands", who); return UR_EINVAL; }
-    if (misaligned(rg ? rg->commands : d.commands, 16) || misaligned(target, 4) || misaligned(stats, 4) || misaligned(d.visible_idx, 4) ||
-        misaligned(d.visible_count, 4) || (rg && (misaligned(rg->offsets, 4) || misaligned(rg->counts, 4)))) {
-        ur::set_error("%s: a misaligned buffer (commands 16 bytes, the others 4)", who);
-        return UR_EINVAL;
-    }
-    return UR_OK;
-}
-
 int ur_frame_set_depth_pass(ur_frame* f, const ur_frame_depth_pass* pass)
 {
     if (!f) { ur::set_error("ur_frame_set_depth_pass: null frame"); return UR_EINVAL; }
-    if (!pass) {
-        f->bDepthPass = false;
-        f->DepthPass = ur_frame_depth_pass{};
-        return UR_OK;
-    }
-    const int rc = check_raster_pass("ur_frame_set_depth_pass", "depth", pass->draws, pass->depth, pass->stats6);
+    if (!pass) { f->DepthDraws.Clear(); f->DepthPass = {}; return UR_OK; }
+    int rc = ur::check_raster_draws("ur_frame_set_depth_pass", pass->draws, pass->depth, "depth", pass->stats6);
+    if (rc == UR_OK) rc = ur::check_depth_flags("ur_frame_set_depth_pass", pass->flags);
     if (rc != UR_OK) return rc;
-    if (pass->flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_frame_set_depth_pass: unknown flag bits 0x%x", pass->flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
-    const ur_draw_ranges* rg = pass->draws.ranges;
-    f->DepthPass = *pass;
-    f->DepthRanges = rg ? *rg : ur_draw_ranges{};
-    f->DepthPass.draws.ranges = rg ? &f->DepthRanges : nullptr;
-    f->bDepthPass = true;
+    f->DepthDraws.Set(pass->draws);
+    f->DepthPass = {&f->DepthDraws.Draws, pass->depth, pass->stats6, pass->flags};
     return UR_OK;
 }
 
@@ -1192,45 +1155,25 @@ int ur_frame_set_gbuffer_materials(ur_frame* f, const ur_material* materials, ui
 int ur_frame_set_gbuffer_pass(ur_frame* f, const ur_frame_gbuffer_pass* pass)
 {
     if (!f) { ur::set_error("ur_frame_set_gbuffer_pass: null frame"); return UR_EINVAL; }
-    if (!pass) {
-        f->bGBufferPass = false;
-        f->GBufferPass = ur_frame_gbuffer_pass{};
-        return UR_OK;
-    }
-    const ur_gbuffer_targets& T = pass->targets;
-    if (!T.gbuf_a || !T.gbuf_b || !T.gbuf_c || !T.hdr) { ur::set_error("ur_frame_set_gbuffer_pass: a null target other than object_id"); return UR_EINVAL; }
-    const int rc = check_raster_pass("ur_frame_set_gbuffer_pass", "keys", pass->draws, T.keys, pass->stats6);
+    if (!pass) { f->GBufferDraws.Clear(); f->GBufferPass = {}; return UR_OK; }
+    int rc = ur::check_gbuffer_targets("ur_frame_set_gbuffer_pass", &pass->targets); // (the keys are the target the raster writes: never null from here on)
+    if (rc == UR_OK) rc = ur::check_raster_draws("ur_frame_set_gbuffer_pass", pass->draws, pass->targets.keys, "keys", pass->stats6);
+    if (rc == UR_OK) rc = ur::check_depth_flags("ur_frame_set_gbuffer_pass", pass->flags);
+    if (rc == UR_OK) rc = ur::check_key_triangle_bits("ur_frame_set_gbuffer_pass", pass->key_triangle_bits);
     if (rc != UR_OK) return rc;
-    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
-    if (misaligned(T.gbuf_a, 8) || misaligned(T.gbuf_b, 8) || misaligned(T.hdr, 8) || misaligned(T.gbuf_c, 4) || misaligned(T.object_id, 4)) {
-        ur::set_error("ur_frame_set_gbuffer_pass: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)");
-        return UR_EINVAL;
-    }
-    if (pass->flags & ~UR_DEPTH_QUANTIZE_D24) { ur::set_error("ur_frame_set_gbuffer_pass: unknown flag bits 0x%x", pass->flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
-    if (pass->key_triangle_bits > 31u) { ur::set_error("ur_frame_set_gbuffer_pass: key_triangle_bits %u (0 = automatic, 1..31)", pass->key_triangle_bits); return UR_EINVAL; }
-    const ur_draw_ranges* rg = pass->draws.ranges;
-    f->GBufferPass = *pass;
-    f->GBufferRanges = rg ? *rg : ur_draw_ranges{};
-    f->GBufferPass.draws.ranges = rg ? &f->GBufferRanges : nullptr;
-    f->bGBufferPass = true;
+    f->GBufferDraws.Set(pass->draws);
+    f->GBufferPass = {&f->GBufferDraws.Draws, pass->targets, pass->stats6, pass->flags, pass->key_triangle_bits};
     return UR_OK;
 }
 
 int ur_frame_set_shadow_pass(ur_frame* f, const ur_frame_shadow_pass* pass)
 {
     if (!f) { ur::set_error("ur_frame_set_shadow_pass: null frame"); return UR_EINVAL; }
-    if (!pass) {
-        f->bShadowPass = false;
-        f->ShadowPass = ur_frame_shadow_pass{};
-        return UR_OK;
-    }
-    const int rc = check_raster_pass("ur_frame_set_shadow_pass", "shadow_map", pass->draws, pass->shadow_map, pass->stats4);
+    if (!pass) { f->ShadowDraws.Clear(); f->ShadowPass = {}; return UR_OK; }
+    const int rc = ur::check_raster_draws("ur_frame_set_shadow_pass", pass->draws, pass->shadow_map, "shadow_map", pass->stats4);
     if (rc != UR_OK) return rc;
-    const ur_draw_ranges* rg = pass->draws.ranges;
-    f->ShadowPass = *pass;
-    f->ShadowRanges = rg ? *rg : ur_draw_ranges{};
-    f->ShadowPass.draws.ranges = rg ? &f->ShadowRanges : nullptr;
-    f->bShadowPass = true;
+    f->ShadowDraws.Set(pass->draws);
+    f->ShadowPass = {&f->ShadowDraws.Draws, pass->shadow_map, pass->stats4};
     return UR_OK;
 }
 

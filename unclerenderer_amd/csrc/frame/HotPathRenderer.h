@@ -23,6 +23,11 @@
 
 // Device buffers owned by the caller (the renderer that rasterised the G-buffer). States mirror the variables the
 // reference keeps next to each resource (DepthBufferState, GBufferStates[], HZBState, LightingBufferState, ...).
+// What a raster pass of the frame works on (ur_frame_set_*_pass + UR_FRAME_*_PASS): the draws, the target, the optional counters and the entry point's own arguments
+struct FShadowPassResources { const ur_raster_draws* Draws = nullptr; float* Map = nullptr; uint32* Stats = nullptr; };                    // Map == Tables.shadow_map
+struct FDepthPassResources { const ur_raster_draws* Draws = nullptr; float* Depth = nullptr; uint32* Stats = nullptr; uint32 Flags = 0; }; // Depth == DepthFull
+struct FGBufferPassResources { const ur_raster_draws* Draws = nullptr; ur_gbuffer_targets Targets = {}; uint32* Stats = nullptr; uint32 Flags = 0, KeyBits = 0; }; // Targets == GBufferA/B/C, LightingBand
+
 struct FHotPathResources
 {
     uint32 Width = 0, Height = 0;      // full frame
@@ -67,22 +72,12 @@ struct FHotPathResources
     const uint8_t* DebugAtlas = nullptr;
     uint32 DebugAtlasWidth = 0, DebugAtlasHeight = 0;
     uint32 DebugFirstChar = 0, DebugCharCount = 0;
-    // ShadowMap (ur_frame_set_shadow_pass + UR_FRAME_SHADOW_PASS): the draws, the target (== Tables.shadow_map) and optional counters
-    const ur_raster_draws* ShadowDraws = nullptr;
-    float* ShadowMapTarget = nullptr;
-    uint32* ShadowStats = nullptr;
-    // DepthPrepass (ur_frame_set_depth_pass + UR_FRAME_DEPTH_PASS): the draws, the target (== DepthFull), optional counters, flags
-    const ur_raster_draws* DepthDraws = nullptr;
-    float* DepthTarget = nullptr;
-    uint32* DepthStats = nullptr;
-    uint32 DepthPassFlags = 0;
-    // GBuffer (ur_frame_set_gbuffer_pass + UR_FRAME_GBUFFER_PASS): the draws, the targets (== GBufferA/B/C and LightingBand), optional counters, key bits
-    const ur_raster_draws* GBufferDraws = nullptr;
-    const ur_gbuffer_targets* GBufferTargets = nullptr;
-    uint32* GBufferStats = nullptr;
+    // The raster passes, each there iff its Draws are: "ShadowMap" behind "GPU Culling", "DepthPrepass" in front of "Build HZB", with it "GBuffer" behind it
+    FShadowPassResources ShadowPass;
+    FDepthPassResources DepthPass;
+    FGBufferPassResources GBufferPass;
     const ur_material* GBufferMaterials = nullptr; // ur_frame_set_gbuffer_materials: null = the untextured resolve
     uint32 GBufferMaterialCount = 0;
-    uint32 GBufferKeyBits = 0;
 
     uint32 DepthState = RG_STATE_DEPTH_WRITE;
     uint32 GBufferStates[3] = {RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET, RG_STATE_RENDER_TARGET};
@@ -135,9 +130,6 @@ struct FHotPathOptions
     bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
     bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
     bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
-    bool bShadowPass = false;         // with ShadowDraws: the "ShadowMap" pass behind "GPU Culling" (ur_shadow_map into Tables.shadow_map)
-    bool bDepthPass = false;          // with DepthDraws: the "DepthPrepass" pass in front of "Build HZB" (ur_depth_prepass into DepthFull)
-    bool bGBufferPass = false;        // with bDepthPass and GBufferDraws: the "GBuffer" pass behind "DepthPrepass" (ur_gbuffer_pass into GBufferA/B/C and LightingBand)
     bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
     bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
     bool bGpuTiming = false;

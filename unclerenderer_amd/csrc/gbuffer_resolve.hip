@@ -1,0 +1,445 @@
+// GBuffer's resolve for gfx950 — a lane per texel of the band turns the winning visibility key (csrc/raster.hip) into the render
+// targets: it fetches the key's triangle again, restates the near clip with a weight row per polygon vertex, interpolates the attributes
+// perspective-correct and runs the base pass' pixel shader (Shaders/DeferredBasePass.hlsl), with or without ObjectId and texture maps
+// (csrc/texture_sample.h). DESIGN.md sections 3.9 and 3.10 are its rule, tests/gbuffer_ref.py the restatement. Built with -ffp-contract=off.
+
+#include "raster_rule.h"
+#include "texture_sample.h"
+#include "ur_device.h"
+#include "ur_internal.h"
+
+namespace {
+
+using namespace ur_raster;
+
+static_assert(sizeof(ur_texture2d) == 16 && sizeof(ur_material) == 80, "ur_material is 80 bytes");
+
+struct ResolveParams {
+    const uint8_t* commands;
+    uint32_t mode; // 0 every slot / ranges (the ordinal is the slot), 1 list (the ordinal is the position in the list)
+    const uint32_t* visible_idx;
+    uint32_t index_base;
+    float V[16], Pr[16];
+    const uint32_t* keys;
+    uint2* gbuf_a; uint2* gbuf_b; uint32_t* gbuf_c; uint2* hdr; uint32_t* object_id;
+    const float* table; // 255 thresholds of the sRGB encode
+    uint32_t w, row0, n;  // n = rows * w
+    float half_w, half_h;
+    uint32_t key_bits;
+    // the textured resolve
+    const ur_material* materials;
+    uint32_t material_count;
+    const float* decode; // 256 entries of the sRGB decode
+    const float* lod;    // 127 thresholds of the level of detail
+};
+
+typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes of a vertex: 4-byte aligned
+
+__device__ __forceinline__ uint32_t half_bits(float v)
+{
+    const _Float16 h = (_Float16)v; // round to nearest even
+    return (uint32_t)__builtin_bit_cast(unsigned short, h);
+}
+__device__ __forceinline__ ur::once_u32x2_t pack_half4(float x, float y, float z, float w)
+{
+    return ur::once_u32x2_t{half_bits(x) | (half_bits(y) << 16), half_bits(z) | (half_bits(w) << 16)};
+}
+
+// the number of thresholds with x >= entry (ascending entries: a binary search; every compare is false for a NaN: 0)
+__device__ __forceinline__ uint32_t srgb_code(const float* table, float x)
+{
+    uint32_t lo = 0u, hi = 255u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool ge = lo < hi && x >= table[min(mid, 254u)];
+        if (lo < hi) { if (ge) lo = mid + 1u; else hi = mid; }
+    }
+    return lo;
+}
+
+// Rules 3-4 at one centre for the target-space triangle (X, Y)[0..2], already reordered: false when it is dropped, culled or does not
+// cover (sx, sy); else the exact edge values l0 = E12, l1 = E20, l2 = E01
+__device__ __forceinline__ bool cover(const float (&X)[3], const float (&Y)[3], int sx, int sy, long long& l0, long long& l1, long long& l2)
+{
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const bool finite = fabsf(X[v]) <= kFloatMax && fabsf(Y[v]) <= kFloatMax;
+        if (!finite || fabsf(X[v]) > kDepthGuardBand || fabsf(Y[v]) > kDepthGuardBand) return false;
+    }
+    const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
+    const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
+    const long long A = (long long)(x1 - x0) * (y2 - y0) - (long long)(x2 - x0) * (y1 - y0);
+    if (A <= 0) return false;
+    const long long e01 = (long long)(x1 - x0) * (sy - y0) - (long long)(y1 - y0) * (sx - x0);
+    const long long e12 = (long long)(x2 - x1) * (sy - y1) - (long long)(y2 - y1) * (sx - x1);
+    const long long e20 = (long long)(x0 - x2) * (sy - y2) - (long long)(y0 - y2) * (sx - x2);
+    l0 = e12; l1 = e20; l2 = e01;
+    return ((e01 - edge_bias(x0, y0, x1, y1)) | (e12 - edge_bias(x1, y1, x2, y2)) | (e20 - edge_bias(x2, y2, x0, y0))) >= 0;
+}
+
+template <bool OBJECT_ID, bool MAPS = false>
+__global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams p)
+{
+    __shared__ float table[256];
+    __shared__ float sampler_tables[MAPS ? kLdsFloats : 1u];
+    table[threadIdx.x] = p.table[min(threadIdx.x, 254u)];
+    if constexpr (MAPS) {
+        sampler_tables[kLdsDecode + threadIdx.x] = p.decode[threadIdx.x];
+        sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
+        if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.lod[min(threadIdx.x, 126u)];
+    }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const uint32_t key = p.keys[i];
+    if (key == 0u) { // the clear values
+        const ur::once_u32x2_t clear = {0u, 0x3C000000u}; // fp16 (0, 0, 0, 1)
+        ur::store_once_b64(p.gbuf_a + i, clear);
+        ur::store_once_b64(p.gbuf_b + i, clear);
+        ur::store_once_b32(p.gbuf_c + i, 0xFF000000u);
+        ur::store_once_b64(p.hdr + i, clear);
+        if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, 0u);
+        return;
+    }
+    const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
+    const uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
+    const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
+    const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
+    const uint32_t* indices = reinterpret_cast<const uint32_t*>((uint64_t)c1.x | ((uint64_t)c1.y << 32));
+    const float* cb = reinterpret_cast<const float*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
+    const uint32_t stride = c0.w;
+    const uint64_t first = (uint64_t)c3.x + 3ull * t;
+    const long long base_vertex = (int)c3.y;
+    float W[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) W[k] = cb[k];
+
+    // ---- the three vertices: rule 1 (world and clip position), the world normal, the colour
+    float c[3][4], wp[3][3], wn[3][3], col[3][3];
+    [[maybe_unused]] float uv[3][2], tg[3][4]; // MAPS: TEXCOORD and the vertex shader's tangent
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
+        const f32x4u_t* vp = reinterpret_cast<const f32x4u_t*>(vertices + vi * stride);
+        const f32x4u_t v0 = vp[0], v1 = vp[1], v3 = vp[3];
+        const float x = v0.x, y = v0.y, z = v0.z, nx = v0.w, ny = v1.x, nz = v1.y;
+        float wv[4], vv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wv[k] = ((x * W[k] + y * W[4 + k]) + z * W[8 + k]) + W[12 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) vv[k] = ((wv[0] * p.V[k] + wv[1] * p.V[4 + k]) + wv[2] * p.V[8 + k]) + wv[3] * p.V[12 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[v][k] = ((vv[0] * p.Pr[k] + vv[1] * p.Pr[4 + k]) + vv[2] * p.Pr[8 + k]) + vv[3] * p.Pr[12 + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            wp[v][k] = wv[k];
+            wn[v][k] = (nx * W[k] + ny * W[4 + k]) + nz * W[8 + k];
+        }
+        col[v][0] = v3.x; col[v][1] = v3.y; col[v][2] = v3.z;
+        if constexpr (MAPS) {
+            const f32x4u_t v2 = vp[2];
+            uv[v][0] = v1.z; uv[v][1] = v1.w;
+            float wt[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) wt[k] = (v2.x * W[k] + v2.y * W[4 + k]) + v2.z * W[8 + k];
+            const float tl = sqrtf((wt[0] * wt[0] + wt[1] * wt[1]) + wt[2] * wt[2]);
+            tg[v][0] = wt[0] / tl; tg[v][1] = wt[1] / tl; tg[v][2] = wt[2] / tl; tg[v][3] = v2.w;
+        }
+    }
+
+    // ---- rule 2 again (DepthPolicy::assemble), every polygon vertex with its weight row over the original three
+    const float d0 = c[0][3] - c[0][2], d1 = c[1][3] - c[1][2], d2 = c[2][3] - c[2][2];
+    const bool o0 = d0 < 0.0f, o1 = d1 < 0.0f, o2 = d2 < 0.0f;
+    const uint32_t n_out = (o0 ? 1u : 0u) + (o1 ? 1u : 0u) + (o2 ? 1u : 0u);
+    const uint32_t rot = n_out == 1u ? (o0 ? 1u : (o1 ? 2u : 0u)) : (n_out == 2u ? (!o0 ? 0u : (!o1 ? 1u : 2u)) : 0u);
+    const uint32_t ia = rot, ib = rot == 2u ? 0u : rot + 1u, ic = rot == 0u ? 2u : rot - 1u;
+    const float ax = sel3(rot, c[0][0], c[1][0], c[2][0]), ay = sel3(rot, c[0][1], c[1][1], c[2][1]);
+    const float aw = sel3(rot, c[0][3], c[1][3], c[2][3]), ad = sel3(rot, d0, d1, d2);
+    const float bx = sel3(rot, c[1][0], c[2][0], c[0][0]), by = sel3(rot, c[1][1], c[2][1], c[0][1]);
+    const float bw = sel3(rot, c[1][3], c[2][3], c[0][3]), bd = sel3(rot, d1, d2, d0);
+    const float cx = sel3(rot, c[2][0], c[0][0], c[1][0]), cy = sel3(rot, c[2][1], c[0][1], c[1][1]);
+    const float cw = sel3(rot, c[2][3], c[0][3], c[1][3]), cd = sel3(rot, d2, d0, d1);
+    const bool one = n_out == 1u, two = n_out == 2u, whole = n_out == 0u;
+    const float ix = one ? bx : ax, iy = one ? by : ay, iw = one ? bw : aw, id = one ? bd : ad;
+    const float ox = one ? cx : bx, oy = one ? cy : by, ow = one ? cw : bw, od = one ? cd : bd;
+    const uint32_t ii = one ? ib : ia, io = one ? ic : ib;
+    const float tp = id / (id - od), tq = ad / (ad - cd);
+    const float px = ix + tp * (ox - ix), py = iy + tp * (oy - iy), pw = iw + tp * (ow - iw);
+    const float qx = ax + tq * (cx - ax), qy = ay + tq * (cy - ay), qw = aw + tq * (cw - aw);
+    float vx[4], vy[4], vw[4], B[4][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float ua = (uint32_t)j == ia ? 1.0f : 0.0f, ub = (uint32_t)j == ib ? 1.0f : 0.0f, uc = (uint32_t)j == ic ? 1.0f : 0.0f;
+        const float up = (uint32_t)j == ii ? 1.0f - tp : ((uint32_t)j == io ? tp : 0.0f);
+        const float uq = (uint32_t)j == ia ? 1.0f - tq : ((uint32_t)j == ic ? tq : 0.0f);
+        B[0][j] = ua;
+        B[1][j] = two ? up : ub;
+        B[2][j] = whole ? uc : (one ? up : uq);
+        B[3][j] = uq;
+    }
+    vx[0] = ax; vy[0] = ay; vw[0] = aw;
+    vx[1] = two ? px : bx; vy[1] = two ? py : by; vw[1] = two ? pw : bw;
+    vx[2] = whole ? cx : (one ? px : qx); vy[2] = whole ? cy : (one ? py : qy); vw[2] = whole ? cw : (one ? pw : qw);
+    vx[3] = qx; vy[3] = qy; vw[3] = qw;
+    float SX[4], SY[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        SX[k] = (vx[k] / vw[k] + 1.0f) * p.half_w;
+        SY[k] = (1.0f - vy[k] / vw[k]) * p.half_h;
+    }
+
+    // ---- the piece that covers this centre: emitted triangle 0 if rule 4 says so, else 1; reordered (r0, r1, r2) = (S0, S[2 + e], S[1 + e])
+    const uint32_t row = i / p.w, column = i - row * p.w;
+    const int sx = 256 * (int)column + 128, sy = 256 * (int)(p.row0 + row) + 128;
+    long long l0 = 0, l1 = 0, l2 = 0;
+    float X[3] = {SX[0], SX[2], SX[1]}, Y[3] = {SY[0], SY[2], SY[1]};
+    bool second = false;
+    if (!cover(X, Y, sx, sy, l0, l1, l2) && one) {
+        second = true;
+        X[1] = SX[3]; Y[1] = SY[3]; X[2] = SX[2]; Y[2] = SY[2];
+        (void)cover(X, Y, sx, sy, l0, l1, l2);
+    }
+    const float cw0 = vw[0], cw1 = second ? vw[3] : vw[2], cw2 = second ? vw[2] : vw[1];
+    const float q0 = (float)l0 / cw0, q1 = (float)l1 / cw1, q2 = (float)l2 / cw2;
+    const float s = (q0 + q1) + q2;
+    const float g0 = q0 / s, g1 = q1 / s, g2 = q2 / s;
+    float b[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
+        b[j] = (g0 * B[0][j] + g1 * B1) + g2 * B2;
+    }
+    float n[3], wpos[3], colour[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        n[k] = (b[0] * wn[0][k] + b[1] * wn[1][k]) + b[2] * wn[2][k];
+        wpos[k] = (b[0] * wp[0][k] + b[1] * wp[1][k]) + b[2] * wp[2][k];
+        colour[k] = (b[0] * col[0][k] + b[1] * col[1][k]) + b[2] * col[2][k];
+    }
+
+    if constexpr (MAPS) {
+        // ---- the material of the slot, its valid maps, and the samples
+        uint32_t bits = 0u;
+        if (slot < p.material_count) bits = reinterpret_cast<const uint32_t*>(p.materials + slot)[16] & 15u;
+        float base[3] = {1.0f, 1.0f, 1.0f}, mr[3] = {1.0f, 1.0f, 1.0f}, nm[3] = {0.5f, 0.5f, 1.0f}, em[3] = {1.0f, 1.0f, 1.0f};
+        if (__ballot(bits != 0u) != 0ull) {
+            // the quad partners' weights: the edge functions are affine, so a step of one pixel adds the coefficient times 256
+            const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
+            const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
+            const bool odd_column = (column & 1u) != 0u, odd_row = ((p.row0 + row) & 1u) != 0u;
+            const long long step_x = odd_column ? -256 : 256, step_y = odd_row ? -256 : 256;
+            float pu[3], pv[3]; // TEXCOORD at the centre, the horizontal and the vertical partner
+#pragma unroll
+            for (int point = 0; point < 3; ++point) {
+                long long m0 = l0, m1 = l1, m2 = l2;
+                if (point == 1) { m0 -= step_x * (y2 - y1); m1 -= step_x * (y0 - y2); m2 -= step_x * (y1 - y0); }
+                if (point == 2) { m0 += step_y * (x2 - x1); m1 += step_y * (x0 - x2); m2 += step_y * (x1 - x0); }
+                const float r0 = (float)m0 / cw0, r1 = (float)m1 / cw1, r2 = (float)m2 / cw2;
+                const float rs = (r0 + r1) + r2;
+                const float h0 = r0 / rs, h1 = r1 / rs, h2 = r2 / rs;
+                float bb[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
+                    bb[j] = (h0 * B[0][j] + h1 * B1) + h2 * B2;
+                }
+                pu[point] = (bb[0] * uv[0][0] + bb[1] * uv[1][0]) + bb[2] * uv[2][0];
+                pv[point] = (bb[0] * uv[0][1] + bb[1] * uv[1][1]) + bb[2] * uv[2][1];
+            }
+#pragma unroll 1
+            for (uint32_t map = 0u; map < 4u; ++map) { // t0 base colour, t1 metallic-roughness, t2 normal, t3 emissive
+                const uint32_t bit = map == 0u ? UR_MATERIAL_BASE_COLOR_MAP : (map == 1u ? UR_MATERIAL_METALLIC_ROUGHNESS_MAP : (map == 2u ? UR_MATERIAL_NORMAL_MAP : UR_MATERIAL_EMISSIVE_MAP));
+                if (__ballot((bits & bit) != 0u) == 0ull) continue;
+                if ((bits & bit) == 0u) continue;
+                const u32x4_t desc = reinterpret_cast<const u32x4_t*>(p.materials + slot)[map];
+                if (!valid_texture(desc)) { bits &= ~bit; continue; }
+                const uint32_t at = 112u + 8u * map; // the map's OffsetScale and Rotation in ur_scene_constants
+                float tu[3], tv[3];
+#pragma unroll
+                for (int point = 0; point < 3; ++point) texture_transform(cb, at, pu[point], pv[point], tu[point], tv[point]);
+                // value(odd) - value(even)
+                const float dxu = odd_column ? tu[0] - tu[1] : tu[1] - tu[0], dxv = odd_column ? tv[0] - tv[1] : tv[1] - tv[0];
+                const float dyu = odd_row ? tu[0] - tu[2] : tu[2] - tu[0], dyv = odd_row ? tv[0] - tv[2] : tv[2] - tv[0];
+                float s[3];
+                sample_map(desc, tu[0], tv[0], dxu, dxv, dyu, dyv, sampler_tables, s);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (map == 0u) base[k] = s[k];
+                    if (map == 1u) mr[k] = s[k];
+                    if (map == 2u) nm[k] = s[k];
+                    if (map == 3u) em[k] = s[k];
+                }
+            }
+        }
+        // ---- the pixel shader (DeferredBasePass.hlsl:80-148)
+        const float nl = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        const float vn[3] = {n[0] / nl, n[1] / nl, n[2] / nl};
+        float wnrm[3] = {vn[0], vn[1], vn[2]};
+        if (bits & UR_MATERIAL_NORMAL_MAP) {
+            float tan4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tan4[k] = (b[0] * tg[0][k] + b[1] * tg[1][k]) + b[2] * tg[2][k];
+            const float dt = (vn[0] * tan4[0] + vn[1] * tan4[1]) + vn[2] * tan4[2];
+            const float u0 = tan4[0] - vn[0] * dt, u1 = tan4[1] - vn[1] * dt, u2 = tan4[2] - vn[2] * dt;
+            const float ul = sqrtf((u0 * u0 + u1 * u1) + u2 * u2);
+            const float t0 = u0 / ul, t1 = u1 / ul, t2 = u2 / ul;
+            const float c0 = vn[1] * t2 - vn[2] * t1, c1 = vn[2] * t0 - vn[0] * t2, c2 = vn[0] * t1 - vn[1] * t0;
+            const float cl = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
+            const float bt0 = (c0 / cl) * tan4[3], bt1 = (c1 / cl) * tan4[3], bt2 = (c2 / cl) * tan4[3];
+            const float nr = nm[0] * 2.0f - 1.0f, ng = nm[1] * 2.0f - 1.0f;
+            const float one_minus = 1.0f - (nr * nr + ng * ng);
+            const float nz = sqrtf(one_minus > 0.0f ? fminf(one_minus, 1.0f) : 0.0f); // saturate
+            const float tl = sqrtf((nr * nr + ng * ng) + nz * nz);
+            const bool flat = tl < 1e-5f;
+            const float e0 = flat ? 0.0f : nr, e1 = flat ? 0.0f : ng, e2 = flat ? 1.0f : nz;
+            const float w0 = (e0 * t0 + e1 * bt0) + e2 * vn[0], w1 = (e0 * t1 + e1 * bt1) + e2 * vn[1], w2 = (e0 * t2 + e1 * bt2) + e2 * vn[2];
+            const float wl = sqrtf((w0 * w0 + w1 * w1) + w2 * w2);
+            wnrm[0] = w0 / wl; wnrm[1] = w1 / wl; wnrm[2] = w2 / wl;
+        }
+        float m[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = (wnrm[0] * p.V[k] + wnrm[1] * p.V[4 + k]) + wnrm[2] * p.V[8 + k];
+        const float ml = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+        const float view_depth = -(((wpos[0] * p.V[2] + wpos[1] * p.V[6]) + wpos[2] * p.V[10]) + p.V[14]);
+        float albedo[3] = {cb[64] * colour[0], cb[65] * colour[1], cb[66] * colour[2]};
+        float metallic = cb[104], roughness = cb[105];
+        float emissive[3] = {cb[80], cb[81], cb[82]};
+        if (bits & UR_MATERIAL_BASE_COLOR_MAP) { albedo[0] = albedo[0] * base[0]; albedo[1] = albedo[1] * base[1]; albedo[2] = albedo[2] * base[2]; }
+        if (bits & UR_MATERIAL_METALLIC_ROUGHNESS_MAP) { metallic = metallic * mr[2]; roughness = roughness * mr[1]; }
+        if (bits & UR_MATERIAL_EMISSIVE_MAP) { emissive[0] = emissive[0] * em[0]; emissive[1] = emissive[1] * em[1]; emissive[2] = emissive[2] * em[2]; }
+        const uint32_t r8 = srgb_code(table, albedo[0]), g8 = srgb_code(table, albedo[1]), b8 = srgb_code(table, albedo[2]);
+        ur::store_once_b64(p.gbuf_a + i, pack_half4(m[0] / ml, m[1] / ml, m[2] / ml, view_depth));
+        ur::store_once_b64(p.gbuf_b + i, pack_half4(0.04f, metallic, roughness, 1.0f));
+        ur::store_once_b32(p.gbuf_c + i, r8 | (g8 << 8) | (b8 << 16) | 0xFF000000u);
+        ur::store_once_b64(p.hdr + i, pack_half4(emissive[0], emissive[1], emissive[2], 1.0f));
+        if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
+        return;
+    }
+
+    // ---- the pixel shader (DeferredBasePass.hlsl:80-149 without maps)
+    const float nl = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    const float vn0 = n[0] / nl, vn1 = n[1] / nl, vn2 = n[2] / nl;
+    float m[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = (vn0 * p.V[k] + vn1 * p.V[4 + k]) + vn2 * p.V[8 + k];
+    const float ml = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+    const float view_depth = -(((wpos[0] * p.V[2] + wpos[1] * p.V[6]) + wpos[2] * p.V[10]) + p.V[14]);
+    const uint32_t r8 = srgb_code(table, cb[64] * colour[0]), g8 = srgb_code(table, cb[65] * colour[1]), b8 = srgb_code(table, cb[66] * colour[2]);
+    ur::store_once_b64(p.gbuf_a + i, pack_half4(m[0] / ml, m[1] / ml, m[2] / ml, view_depth));
+    ur::store_once_b64(p.gbuf_b + i, pack_half4(0.04f, cb[104], cb[105], 1.0f));
+    ur::store_once_b32(p.gbuf_c + i, r8 | (g8 << 8) | (b8 << 16) | 0xFF000000u);
+    ur::store_once_b64(p.hdr + i, pack_half4(cb[80], cb[81], cb[82], 1.0f));
+    if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
+}
+
+// The checks and the launches behind the four GBuffer entry points; `who` names the caller in the error text, `who_parts` its _parts form
+int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
+                  const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
+                  uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count)
+{
+    int rc = ur::check_raster_call(who, ctx, view, projection, draws, depth, "depth", w, h, stats6);
+    if (rc == UR_OK) rc = ur::check_depth_flags(who, flags);
+    if (rc == UR_OK) rc = ur::check_gbuffer_targets(who, targets);
+    if (rc == UR_OK) rc = ur::check_key_triangle_bits(who, key_triangle_bits);
+    if (rc != UR_OK) return rc;
+    if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("%s: rows [%u, %u + %u) of a target %u high", who, row0, row0, rows, h); return UR_EINVAL; }
+    if (parts == 0u || (parts & ~(UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE))) { ur::set_error("%s: parts 0x%x (UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE)", who_parts, parts); return UR_EINVAL; }
+    uint32_t key_bits = key_triangle_bits;
+    if (key_bits == 0u) {
+        if (draws->command_count >= (1u << 24)) {
+            ur::set_error("%s: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", who, draws->command_count);
+            return UR_EUNSUPPORTED;
+        }
+        uint32_t length = 0u;
+        while ((draws->command_count >> length) != 0u) ++length;
+        key_bits = min(32u - length, 31u);
+    } else if ((uint64_t)draws->command_count >= (1ull << (32u - key_bits))) {
+        ur::set_error("%s: %u command slots do not fit the %u key bits beside key_triangle_bits %u", who, draws->command_count, 32u - key_bits, key_bits);
+        return UR_EINVAL;
+    }
+    if (!aligned(materials, 16)) { ur::set_error("%s: a misaligned material table (16 bytes)", who); return UR_EINVAL; }
+    // ---- the launches: the raster over the key image (UR_GBUFFER_PART_RASTER), then the resolve (UR_GBUFFER_PART_RESOLVE)
+    const uint32_t n = w * rows;
+    if (parts & UR_GBUFFER_PART_RASTER) {
+        rc = ur::launch_visibility_raster(ctx, view, projection, draws, depth, targets->keys, w, h, row0, rows, key_bits, (flags & UR_DEPTH_QUANTIZE_D24) != 0u, stats6);
+        if (rc != UR_OK) return rc;
+    }
+    if (!(parts & UR_GBUFFER_PART_RESOLVE)) return UR_OK;
+    ResolveParams r{};
+    r.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
+    r.mode = draws->visible_idx != nullptr ? 1u : 0u;
+    r.visible_idx = draws->visible_idx; r.index_base = draws->index_base;
+    for (int k = 0; k < 16; ++k) { r.V[k] = view[k]; r.Pr[k] = projection[k]; }
+    r.keys = targets->keys;
+    r.gbuf_a = reinterpret_cast<uint2*>(targets->gbuf_a); r.gbuf_b = reinterpret_cast<uint2*>(targets->gbuf_b); r.gbuf_c = targets->gbuf_c;
+    r.hdr = reinterpret_cast<uint2*>(targets->hdr); r.object_id = targets->object_id;
+    r.table = ctx->srgb_encode_table;
+    r.w = w; r.row0 = row0; r.n = n;
+    r.half_w = 0.5f * (float)w; r.half_h = 0.5f * (float)h;
+    r.key_bits = key_bits;
+    const uint32_t blocks = (n + kThreads - 1u) / kThreads;
+    if (materials) { // the textured resolve
+        r.materials = materials; r.material_count = material_count;
+        r.decode = ctx->srgb_table; r.lod = ctx->lod_table;
+        if (targets->object_id) hipLaunchKernelGGL((gbuffer_resolve_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        else hipLaunchKernelGGL((gbuffer_resolve_kernel<false, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        UR_HIP_TRY(hipGetLastError());
+        return UR_OK;
+    }
+    if (targets->object_id) hipLaunchKernelGGL(gbuffer_resolve_kernel<true>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+    else hipLaunchKernelGGL(gbuffer_resolve_kernel<false>, dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+} // namespace
+
+int ur::check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets)
+{
+    if (!targets || !targets->gbuf_a || !targets->gbuf_b || !targets->gbuf_c || !targets->hdr || !targets->keys) {
+        ur::set_error("%s: null targets, or a null target other than object_id", who);
+        return UR_EINVAL;
+    }
+    if (!aligned(targets->gbuf_a, 8) || !aligned(targets->gbuf_b, 8) || !aligned(targets->hdr, 8) || !aligned(targets->gbuf_c, 4) || !aligned(targets->object_id, 4) ||
+        !aligned(targets->keys, 4)) {
+        ur::set_error("%s: a misaligned target (gbuf_a, gbuf_b, hdr 8 bytes, the others 4)", who);
+        return UR_EINVAL;
+    }
+    return UR_OK;
+}
+
+extern "C" {
+
+int ur_gbuffer_pass_materials_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
+                                    const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
+                                    uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count)
+{
+    return gbuffer_entry("ur_gbuffer_pass_materials", "ur_gbuffer_pass_materials_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags,
+                         key_triangle_bits, stats6, parts, materials, material_count);
+}
+
+int ur_gbuffer_pass_materials(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                              uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6,
+                              const ur_material* materials, uint32_t material_count)
+{
+    return gbuffer_entry("ur_gbuffer_pass_materials", "ur_gbuffer_pass_materials_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags,
+                         key_triangle_bits, stats6, UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, materials, material_count);
+}
+
+int ur_gbuffer_pass_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts)
+{
+    return gbuffer_entry("ur_gbuffer_pass", "ur_gbuffer_pass_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6, parts,
+                         nullptr, 0u);
+}
+
+int ur_gbuffer_pass(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, const ur_gbuffer_targets* targets,
+                    uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6)
+{
+    return gbuffer_entry("ur_gbuffer_pass", "ur_gbuffer_pass_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6,
+                         UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, nullptr, 0u);
+}
+
+} // extern "C"

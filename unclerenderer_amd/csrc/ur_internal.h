@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "../../include/ur_hotpath.h"
+#include "../../include/ur_raster.h"
 
 namespace ur {
 // Arguments of the single-workgroup tail of the HZB chain (csrc/hzb_tail.h): the levels from `first_mip` on.
@@ -79,7 +80,7 @@ struct ur_ctx {
     // host-visible (mapped, coherent) word beside hzb_timed_out: a wave of a balanced launch gave up waiting for a claim
     volatile uint32_t* claim_timed_out = nullptr;
     uint32_t* claim_timed_out_dev = nullptr;
-    // ur_raster_reserve: the large-triangle queue of ur_shadow_map (csrc/shadow_raster.hip): a 64-byte header (the count) + entries
+    // ur_raster_reserve: the large-triangle queue of the raster passes (csrc/raster.hip): a 64-byte header (the count) + entries
     uint32_t* raster_queue = nullptr;
     uint32_t raster_queue_cap = 0;
 };
@@ -114,6 +115,28 @@ int launch_cull_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* b
                       uint32_t view_count);
 // ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
 int check_cull_views(const ur_cull_view* views, uint32_t view_count);
+// The raster passes: one set of checks for the direct calls and the frame's setters; `who`, the entry point called, goes into the error text.
+// Where the command slots live: the ranges' commands if ranges are set, else the draws' own
+inline const void* raster_commands(const ur_raster_draws& draws) { return draws.ranges ? draws.ranges->commands : draws.commands; }
+// (raster.hip) `target` not null; a list has both pointers; no list beside ranges; ranges whole; commands (unless command_count == 0) 16-byte, the rest 4-byte aligned
+int check_raster_draws(const char* who, const ur_raster_draws& draws, const void* target, const char* target_name, const void* stats);
+// ... behind what a direct call adds: the context, the matrices (ShadowMap passes its one twice), draws, w and h
+int check_raster_call(const char* who, const ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, const void* target, const char* target_name,
+                      uint32_t w, uint32_t h, const void* stats);
+inline int check_depth_flags(const char* who, uint32_t flags)
+{
+    if (flags & ~UR_DEPTH_QUANTIZE_D24) { set_error("%s: unknown flag bits 0x%x", who, flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    return UR_OK;
+}
+int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_resolve.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
+inline int check_key_triangle_bits(const char* who, uint32_t bits)
+{
+    if (bits > 31u) { set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, bits); return UR_EINVAL; }
+    return UR_OK;
+}
+// GBuffer's raster (UR_GBUFFER_PART_RASTER): clears the key image of the band [row0, row0 + rows) and raises it to the winning keys
+int launch_visibility_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, uint32_t* keys, uint32_t w,
+                             uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats);
 int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_constants* sky, const ur_half4* gbuf_a,
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);

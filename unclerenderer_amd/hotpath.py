@@ -711,7 +711,8 @@ def pack_draw_commands(draws) -> np.ndarray:
 
 def raster_draws(commands, command_count=None, visible=None, ranges=None, index_base=0) -> _lib.RasterDraws:
     """ur_raster_draws over device tensors. commands: n * 64 bytes (None with ranges). visible: (visible_idx, visible_count) device
-    tensors. ranges: a draw_ranges(...) result, or (offsets, commands, counts) device tensors. Keeps them alive."""
+    tensors. ranges: a draw_ranges(...) result, or (offsets, commands, counts) device tensors. Keeps them alive. The slots, and so the
+    default command_count, live where the native ur::raster_commands says: in the ranges' commands if ranges are given, else in `commands`."""
     d = _lib.RasterDraws()
     keep = [commands]
     if commands is not None:
@@ -736,6 +737,13 @@ def raster_draws(commands, command_count=None, visible=None, ranges=None, index_
     return d
 
 
+def _matrix16(m) -> np.ndarray:
+    """16 contiguous floats of a 4 x 4 matrix (row-major, row-vector convention)."""
+    a = np.ascontiguousarray(m, np.float32).reshape(-1)
+    assert a.size == 16
+    return a
+
+
 def _shadow_map(self, lvp, commands, shadow_map, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None, size=None):
     """ur_shadow_map: clear shadow_map ((h, w) float32 device tensor, or flat with size=(w, h)) to 1.0 and rasterise the selected draws
     of `commands` (pack_draw_commands, uploaded) under the orthographic light matrix lvp (16 floats, row-major, row-vector
@@ -743,8 +751,7 @@ def _shadow_map(self, lvp, commands, shadow_map, *, visible=None, ranges=None, i
     added to."""
     w, h = size if size is not None else (int(shadow_map.shape[1]), int(shadow_map.shape[0]))
     assert shadow_map.dtype == torch.float32 and shadow_map.numel() >= w * h
-    m = np.ascontiguousarray(lvp, np.float32).reshape(-1)
-    assert m.size == 16
+    m = _matrix16(lvp)
     d = raster_draws(commands, command_count, visible, ranges, index_base)
     _lib.check(self._L.ur_shadow_map(self._ctx, _lib.fptr(m), C.byref(d), _ptr(shadow_map), w, h, _ptr(stats)), "ur_shadow_map")
 
@@ -761,8 +768,7 @@ def _depth_prepass(self, view, projection, commands, depth, *, visible=None, ran
     per-texel maximum. The selections are HotPath.shadow_map's; stats: uint32[6] device tensor, added to; flags: UR_DEPTH_QUANTIZE_D24."""
     w, h = size if size is not None else (int(depth.shape[1]), int(depth.shape[0]))
     assert depth.dtype == torch.float32 and depth.numel() >= w * h
-    v, p = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (view, projection))
-    assert v.size == 16 and p.size == 16
+    v, p = _matrix16(view), _matrix16(projection)
     d = raster_draws(commands, command_count, visible, ranges, index_base)
     _lib.check(self._L.ur_depth_prepass(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), w, h, int(flags), _ptr(stats)), "ur_depth_prepass")
 
@@ -834,8 +840,7 @@ def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0
     materials: a pack_materials(...) table, one record per command slot: the textured resolve of ur_gbuffer_pass_materials."""
     rows = h - row0 if rows is None else rows
     assert depth.dtype == torch.float32 and depth.numel() >= w * h
-    v, p = (np.ascontiguousarray(m, np.float32).reshape(-1) for m in (view, projection))
-    assert v.size == 16 and p.size == 16
+    v, p = _matrix16(view), _matrix16(projection)
     d = raster_draws(commands, command_count, visible, ranges, index_base)
     args = (self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), C.byref(targets), w, h, int(row0), int(rows), int(flags), int(key_triangle_bits),
             _ptr(stats))
@@ -857,20 +862,28 @@ HotPath.raster_reserve = _raster_reserve
 HotPath.depth_prepass = _depth_prepass
 
 
+def _frame_set_raster_pass(self, call, keep, record, target, stats, draws, **fields):
+    """The three setters below: `call` is the library's ur_frame_set_*_pass, `keep` the attribute that keeps the tensors alive, `draws`
+    raster_draws' arguments. Without commands, target and ranges: clear. Else `record`, the pass' empty struct, takes the draws and those of
+    `fields` that are not None, a tensor as its address."""
+    if draws[0] is None and target is None and draws[3] is None:
+        setattr(self, keep, None)
+        _lib.check(call(self._f, None), call.__name__)
+        return
+    d = raster_draws(*draws)
+    record.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
+    for field, value in fields.items():
+        if value is not None:
+            setattr(record, field, value.data_ptr() if isinstance(value, torch.Tensor) else value)
+    _lib.check(call(self._f, C.byref(record)), call.__name__)
+    setattr(self, keep, (d, target, stats))
+
+
 def _frame_set_shadow_pass(self, commands=None, shadow_map=None, *, visible=None, ranges=None, index_base=0, stats=None, command_count=None):
     """ur_frame_set_shadow_pass: the draws (as in HotPath.shadow_map), the map and the optional counters of the frames rendered with
     UR_FRAME_SHADOW_PASS (device tensors, kept alive here). No arguments: clear."""
-    if commands is None and shadow_map is None and ranges is None:
-        self._shadow_pass_keep = None
-        _lib.check(self._L.ur_frame_set_shadow_pass(self._f, None), "ur_frame_set_shadow_pass")
-        return
-    sp = _lib.FrameShadowPass()
-    d = raster_draws(commands, command_count, visible, ranges, index_base)
-    sp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
-    sp.shadow_map = shadow_map.data_ptr() if shadow_map is not None else None
-    sp.stats4 = stats.data_ptr() if stats is not None else None
-    _lib.check(self._L.ur_frame_set_shadow_pass(self._f, C.byref(sp)), "ur_frame_set_shadow_pass")
-    self._shadow_pass_keep = (d, shadow_map, stats)
+    _frame_set_raster_pass(self, self._L.ur_frame_set_shadow_pass, "_shadow_pass_keep", _lib.FrameShadowPass(), shadow_map, stats,
+                           (commands, command_count, visible, ranges, index_base), shadow_map=shadow_map, stats4=stats)
 
 
 Frame.set_shadow_pass = _frame_set_shadow_pass
@@ -880,18 +893,8 @@ def _frame_set_depth_pass(self, commands=None, depth=None, *, visible=None, rang
     """ur_frame_set_depth_pass: the draws (as in HotPath.depth_prepass), the depth buffer (the frame's depth_full), the optional counters
     and the ur_depth_prepass flags of the frames rendered with UR_FRAME_DEPTH_PASS (device tensors, kept alive here). No arguments:
     clear."""
-    if commands is None and depth is None and ranges is None:
-        self._depth_pass_keep = None
-        _lib.check(self._L.ur_frame_set_depth_pass(self._f, None), "ur_frame_set_depth_pass")
-        return
-    dp = _lib.FrameDepthPass()
-    d = raster_draws(commands, command_count, visible, ranges, index_base)
-    dp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
-    dp.depth = depth.data_ptr() if depth is not None else None
-    dp.stats6 = stats.data_ptr() if stats is not None else None
-    dp.flags = int(flags)
-    _lib.check(self._L.ur_frame_set_depth_pass(self._f, C.byref(dp)), "ur_frame_set_depth_pass")
-    self._depth_pass_keep = (d, depth, stats)
+    _frame_set_raster_pass(self, self._L.ur_frame_set_depth_pass, "_depth_pass_keep", _lib.FrameDepthPass(), depth, stats,
+                           (commands, command_count, visible, ranges, index_base), depth=depth, stats6=stats, flags=int(flags))
 
 
 Frame.set_depth_pass = _frame_set_depth_pass
@@ -902,19 +905,9 @@ def _frame_set_gbuffer_pass(self, commands=None, targets=None, *, visible=None, 
     """ur_frame_set_gbuffer_pass: the draws (as in HotPath.gbuffer_pass), the targets (gbuffer_targets(...): the frame's gbuffer_a/b/c and
     lighting_band), the optional counters, the ur_gbuffer_pass flags and the key bits of the frames rendered with UR_FRAME_GBUFFER_PASS
     (device tensors, kept alive here). No arguments: clear."""
-    if commands is None and targets is None and ranges is None:
-        self._gbuffer_pass_keep = None
-        _lib.check(self._L.ur_frame_set_gbuffer_pass(self._f, None), "ur_frame_set_gbuffer_pass")
-        return
-    gp = _lib.FrameGBufferPass()
-    d = raster_draws(commands, command_count, visible, ranges, index_base)
-    gp.draws = d  # (a copy: the tensors and the ur_draw_ranges it points to are kept through d)
-    if targets is not None:
-        gp.targets = targets
-    gp.stats6 = stats.data_ptr() if stats is not None else None
-    gp.flags, gp.key_triangle_bits = int(flags), int(key_triangle_bits)
-    _lib.check(self._L.ur_frame_set_gbuffer_pass(self._f, C.byref(gp)), "ur_frame_set_gbuffer_pass")
-    self._gbuffer_pass_keep = (d, targets, stats)
+    _frame_set_raster_pass(self, self._L.ur_frame_set_gbuffer_pass, "_gbuffer_pass_keep", _lib.FrameGBufferPass(), targets, stats,
+                           (commands, command_count, visible, ranges, index_base), targets=targets, stats6=stats, flags=int(flags),
+                           key_triangle_bits=int(key_triangle_bits))
 
 
 Frame.set_gbuffer_pass = _frame_set_gbuffer_pass
