@@ -1,11 +1,11 @@
 // Sanitizer driver (CPU build only: -fsanitize=address,undefined): runs the host-side code of the product (DDS/BC6H decode,
-// scene -> ModelBounds extraction, host constant math) and the CPU oracle (test infrastructure) over the shipped fixtures,
-// random inputs and hostile inputs (truncated files, garbage blocks, empty and ragged sizes). Any report from ASan/UBSan
+// scene -> ModelBounds extraction, host constant math, the Lighting launch's planner) and the CPU oracle (test infrastructure) over the
+// shipped fixtures, random inputs and hostile inputs (truncated files, garbage blocks, empty and ragged sizes). Any report from ASan/UBSan
 // ends the process with a non-zero status. SURVEY.md section 5, "Race detection / sanitizers": the reference has only the D3D12
 // debug layer (Source/RHI/DX12Device.cpp:82-91).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -I include \
-//       tests/cpp/sanitize_main.cpp csrc/dds.cpp csrc/scene.cpp csrc/host_math.cpp oracle/ur_oracle.cpp -pthread
+//       tests/cpp/sanitize_main.cpp csrc/dds.cpp csrc/scene.cpp csrc/host_math.cpp csrc/lighting_plan.cpp oracle/ur_oracle.cpp -pthread
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +20,8 @@
 #include "ur_host.h"
 #include "ur_hotpath.h"
 #include "ur_scene.h"
+
+#include "lighting_plan_sweep.h"
 
 extern "C" {
 uint32_t uro_hzb_layout(uint32_t w, uint32_t h, ur_mip_desc* mips, uint32_t* mip_count);
@@ -197,12 +199,27 @@ static void test_oracle_and_host_math()
     }
 }
 
+// csrc/lighting_plan.cpp: the sweep of tests/cpp/test_lighting_plan.cpp (its shifts, divisions and magic numbers are what UBSan is for),
+// and the cube layouts the entry points accept or refuse, the absurd ones included
+static void test_lighting_plan()
+{
+    CHECK(plan_sweep::sweep() > 100000);
+    CHECK(plan_sweep::g_fail == 0);
+    for (uint32_t base : {0u, 1u, 2u, 3u, 255u, 256u, 4096u, 0x7FFFFFFFu, 0xFFFFFFFEu, 0xFFFFFFFFu})
+        for (uint32_t mips = 0; mips <= 18; ++mips) {
+            const ur::CubeLayout L = ur::cube_layout(base, mips);
+            CHECK((L.mips == 0) == (base == 0 || mips == 0 || mips > 16));
+            if (L.mips != 0) CHECK(ur::cube_first_mip_within(L, ur::kLdsCubeBytes) <= L.mips);
+        }
+}
+
 int main(int argc, char** argv)
 {
     const std::string assets = argc > 1 ? argv[1] : "tests/golden/assets";
     test_dds(assets);
     test_scene(assets);
     test_oracle_and_host_math();
+    test_lighting_plan();
     if (g_fail) { std::printf("%d check(s) failed\n", g_fail); return 1; }
     std::printf("OK sanitized host + oracle run clean\n");
     return 0;

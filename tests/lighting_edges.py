@@ -7,7 +7,7 @@ tests/lighting_ref64.py state them:
   * a tap outside the map reads the opaque-white border, depth 1.0, and is compared like any other;
   * the sky is drawn where sphereDepth >= the stored depth (GREATER_EQUAL): a NaN depth is not sky, a depth <= 0 is.
 
-The emulations restate, in exact arithmetic rounded once to fp32 where the instruction rounds, what csrc/lighting.hip computes for
+The emulations restate, in exact arithmetic rounded once to fp32 where the instruction rounds, what csrc/lighting.hip and csrc/lighting_tiled.hip compute for
 those decisions, and a few plain mutants next to them. The hardware clamp is assumed to send NaN to 0 (DX10 clamp).
 """
 from __future__ import annotations

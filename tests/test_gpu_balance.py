@@ -1,4 +1,4 @@
-"""Inter-workgroup balancing of the streaming lighting launch (UR_OPT_LIGHTING_BALANCE, csrc/lighting.hip struct Balance): the
+"""Inter-workgroup balancing of the streaming lighting launch (UR_OPT_LIGHTING_BALANCE, struct Balance in csrc/lighting_params.h, planned in csrc/lighting_plan.cpp, claimed in csrc/lighting.hip): the
 last part of a launch's tiles is claimed by the workgroups at run time instead of being dealt statically. Which workgroup
 shades a tile must not change a bit of it: every schedule is compared byte for byte with the all-static one, over launches in
 a row (the claim words must be back at zero after each), with the Build HZB chain riding, and on a band."""

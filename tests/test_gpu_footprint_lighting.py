@@ -1,4 +1,4 @@
-"""Footprints of DeferredLighting, SkyAtmosphere and the fused launch (csrc/lighting.hip) under the rules of tests/footprint.py: both
+"""Footprints of DeferredLighting, SkyAtmosphere and the fused launch (csrc/lighting.hip, csrc/lighting_tiled.hip) under the rules of tests/footprint.py: both
 kernels, the twelve-wave workgroups, a balanced schedule, shadow maps down to 1x1, every irradiance table form, shapes whose last
 tile row hangs over the band, bands, one 4K frame; G-buffer A/B/C, depth, shadow map, staged cube and BRDF LUT each between poisoned
 guards, the HDR target between hashed ones. Nothing here judges a value."""

@@ -1,4 +1,4 @@
-"""The decision forms of csrc/lighting.hip held to the shaders' semantics on edge and special values, on the CPU: fp32 emulations
+"""The decision forms of the lighting kernels (csrc/lighting.hip, csrc/lighting_tiled.hip) held to the shaders' semantics on edge and special values, on the CPU: fp32 emulations
 of each form (tests/lighting_edges.py) against LESS_EQUAL / GREATER_EQUAL, the mutant table that shows every former form and every
 plain mutant caught, the edge frames' generators, and the oracle against the float64 restatement on those frames.
 tests/test_gpu_lighting_edges.py runs the same frames through the kernels."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic builds of libur_hotpath.so that differ from the product in the lighting kernel only. Outputs go to
+"""Diagnostic builds of libur_hotpath.so that differ from the product in the streaming lighting kernel's unit (csrc/lighting.hip) only. Outputs go to
 unclerenderer_amd/csrc/_build/variants/ (git-ignored, shipped to the GPU box by gpurun); select one with UR_HOTPATH_LIB=<path>.
 
     python tools/build_variants.py name=-DFLAG=1 name2="-DA=1 -DB=2" ...          # the product source + defines
@@ -51,7 +51,10 @@ def one(spec: str) -> Path:
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"{name}: {r.stderr}")
-    objs = [str(b.OUT / (s.replace("/", "_") + ".o")) for s, _ in b.SOURCES if s != "lighting.hip"] + [str(obj)]
+    # the round-2 file is the whole pass (ur::launch_lighting and both kernels): it replaces the three lighting units, not the planner
+    # (ur_api.hip sizes and stages the cube by it)
+    replaced = {"lighting.hip"} if BASE is None else {"lighting.hip", "lighting_tiled.hip", "lighting_host.hip"}
+    objs = [str(b.OUT / (s.replace("/", "_") + ".o")) for s, _ in b.SOURCES if s not in replaced] + [str(obj)]
     r = subprocess.run([b.hipcc(), f"--offload-arch={b.ARCH}", "-shared", "-fPIC", "-o", str(lib)] + objs + ["-ldl", "-lpthread"], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"{name}: link: {r.stderr}")

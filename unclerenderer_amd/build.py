@@ -25,15 +25,19 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-fno-gpu-rdc"
 # exact-arithmetic translation units: no FMA contraction, IEEE divide (hipcc's default)
 EXACT = ["-ffp-contract=off"]
 
+# packed fp32 VALU ops are not faster on gfx950 and cost v_mov traffic; the atomic optimizer would turn the one-lane LDS
+# work-counter claim into a scan + broadcast with an immediate wait
+LIGHTING = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+
 # (source relative to csrc, extra flags)
 SOURCES = [
     ("ur_api.hip", []),
     ("hzb.hip", EXACT),
     ("cull.hip", EXACT),
     ("cull_views.hip", EXACT),
-    # packed fp32 VALU ops are not faster on gfx950 and cost v_mov traffic; the atomic optimizer would turn the one-lane LDS
-    # work-counter claim into a scan + broadcast with an immediate wait
-    ("lighting.hip", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]),
+    ("lighting.hip", LIGHTING),
+    ("lighting_tiled.hip", LIGHTING),
+    ("lighting_host.hip", LIGHTING),  # host code only; the kernels' bits depend on its arithmetic, so it keeps their flags
     ("tonemap.hip", EXACT),
     ("taa.hip", EXACT),
     ("post.hip", EXACT),
@@ -44,6 +48,7 @@ SOURCES = [
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),
     ("host_math.cpp", ["-x", "hip"] + EXACT),
+    ("lighting_plan.cpp", ["-x", "hip"] + EXACT),
     ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),
     ("frame/HotPathRenderer.cpp", ["-x", "hip"]),

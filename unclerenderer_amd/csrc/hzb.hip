@@ -148,7 +148,7 @@ int launch_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t s
     while (mip < mip_count) {
         if (mip > 0 && (uint64_t)mips[mip].width * mips[mip].height <= kTailTexels && mip_count - mip <= kTailMaxLevels) {
             const HzbTail t = make_tail(hzb, mips, mip_count, mip);
-            if (ctx->defer_hzb_tail) { // the next streaming Lighting launch takes it along (lighting.hip); ur_flush otherwise
+            if (ctx->defer_hzb_tail) { // the next streaming Lighting launch takes it along (lighting.hip, planned in lighting_plan.cpp); ur_flush otherwise
                 ctx->pending_tail = t;
                 ctx->hzb_tail_pending = true;
                 break;
@@ -193,7 +193,7 @@ int launch_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t s
         const dim3 grid((d.W[0] + 63u) / 64u, (d.H[0] + 15u) / 16u);
         // ur_defer_hzb_tail(ctx, 2): a chain that is ONE five-level launch from the depth buffer plus the single-workgroup tail
         // (1080p, 4K and 8K all are) is held back as a whole: the next streaming Lighting launch takes its 128x32 pieces
-        // along (lighting.hip), ur_flush / a cull / another build launch it the ordinary way
+        // along (lighting.hip, if lighting_plan.cpp finds that they can ride), ur_flush / a cull / another build launch it the ordinary way
         if (mip == 0 && n == 5u && ctx->defer_hzb_tail && ctx->defer_hzb_wide && mip_count > 5u &&
             (uint64_t)mips[5].width * mips[5].height <= kTailTexels && mip_count - 5u <= kTailMaxLevels && ctx->hzb_done != nullptr) {
             ctx->pending_wide = d;

@@ -1,5 +1,5 @@
 // The wide launch of the HZB chain (depth -> mips 0..4) as device code shared by two launch forms: `hzb_reduce4_kernel`
-// (csrc/hzb.hip: one 256-thread workgroup per 128x32 source tile) and the streaming lighting kernel (csrc/lighting.hip), whose
+// (csrc/hzb.hip: one 256-thread workgroup per 128x32 source tile) and the streaming lighting kernel (csrc/lighting.hip; csrc/lighting_plan.cpp decides when and how many waves walk), whose
 // workgroups take the same 128x32 pieces along — ONE wave walks a piece in four passes of 128x8 source texels — when the
 // frame driver lets the whole chain ride with the Lighting launch (ur_defer_hzb_tail(ctx, 2)). Not installed.
 //

@@ -1,4 +1,4 @@
-// DeferredLighting (GGX + IBL) and SkyAtmosphere for gfx950: per-pixel compute kernels with three modes (lighting, sky, fused).
+// DeferredLighting (GGX + IBL) and SkyAtmosphere for gfx950: the streaming kernel, the default of the pass.
 //
 // Reference: Shaders/DeferredLighting.hlsl:35-94 + Shaders/PBRCommon.hlsl:1-48 (fullscreen-triangle pixel shader,
 // additive ONE/ONE blend into RGBA16F, Source/Render/DeferredRenderer.cpp:1219-1255,1997-2005) and
@@ -8,177 +8,25 @@
 // the G-buffer rows are contiguous 128-byte segments and the shadow / cube gathers of neighbouring lanes land on
 // neighbouring texels. The PCF, the trilinear cube lookups and the BRDF LUT are filtered in ALU.
 //
-// Two kernels share that arithmetic:
-//   * lighting_stream_kernel (second half of this file, the default): persistent workgroups, G-buffer tiles prefetched into
-//     LDS by DMA, side tables in LDS, work claimed from an LDS counter, instruction selection tuned to gfx950's VALU issue
-//     rules (DESIGN.md section 3.3 has the measurements behind every choice). A launch may carry one extra workgroup
-//     that runs the held-back tail of the HZB chain on a CU of its own (ur_defer_hzb_tail, csrc/hzb_tail.h);
-//   * lighting_kernel (first half): one workgroup per 64 x 4 pixels, plain loads; sky-only launches and every
-//     configuration the streaming kernel declines (launch_lighting() at the end decides per launch, never per row).
+// lighting_stream_kernel: persistent workgroups, G-buffer tiles prefetched into LDS by DMA, side tables in LDS, work claimed from
+// an LDS counter, instruction selection tuned to gfx950's VALU issue rules (DESIGN.md section 3.3 has the measurements behind
+// every choice). A launch may carry one extra workgroup that runs the held-back tail of the HZB chain on a CU of its own
+// (ur_defer_hzb_tail, csrc/hzb_tail.h). Sky-only launches and every configuration this kernel declines take the per-tile kernel
+// (lighting_tiled.hip); launch_lighting() (lighting_host.hip) decides per launch, never per row, and derives the launch uniforms;
+// the schedule of a launch (workgroups, riding HZB work, the static / run-time split) is planned in lighting_plan.cpp.
 // Every per-launch uniform the HLSL recomputes per pixel is folded on the host: gfx950 has no scalar fp32 ALU. The view
 // matrix is rigid (XMMatrixLookToLH, Scene/Camera.cpp:23-31), so world-space vectors are view-space ones rotated by
 // ViewInverse. Tolerance against the oracle: max(1e-3, 1 ulp fp16) per channel; fp32 math, one RTE to fp16.
 
-#include "ur_internal.h"
+#include "lighting_device.h"
 #include "ur_device.h"
 #include "hzb_tail.h"
 
-#include <hip/hip_ext.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstddef>
 #include <cstring>
-#include <type_traits>
 
 namespace {
 
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-
-// The launch-uniform values of the streaming kernel's loop. The hot ones stay in SGPRs across the loop; cold paths (sky
-// constants, shadow slow path, partial tiles) re-read theirs from the kernarg segment when they run (fresh_params()).
-struct StreamHot {
-    uint32_t groups; // lighting workgroups of the launch (a workgroup with this index, if any, runs the deferred HZB tail)
-    uint32_t tilesX, numTiles, tilesXMagic, W, rows, row0, irrN0, irrRowBytes; // tilesXMagic: tile / tilesX = (tile * magic) >> 32
-    uint32_t staticClaims; // a workgroup's claims c < staticClaims are dealt statically (above); from there on they index the chunks the
-                           // workgroup claims at run time (Balance). 0xFFFFFFFF: every tile is dealt statically
-    float invW2, invH2, invP11, nInvP22;      // ray: ra = ndc.x * invP11, rb = ndc.y * nInvP22 (= -1/P22)
-    float skyInvP11, nSkyInvP22, skyNearOverR2, maxMip;
-    float envMaxLevel, irrNf, irrEf, irrEEf, irrOfff; // irradiance mip: N, N+2, (N+2)^2, texel offset — as floats (exact)
-    float shadowWm3, shadowHm3, shadowWf;     // W-3, H-3, W as floats
-    float shadowXmax, shadowYmax, shadowStrength, shadowQuarterStrength, shadowOneMinusStrength; // W - 0.5, H - 0.5, s, s/4, 1 - s
-    uint32_t shadowRowBytes;
-    int32_t shadowWi, shadowHi;
-    const void* env;
-    const float* shadow;
-    void* hdr;
-    float skyDepthMax;   // no sphere depth of the frame exceeds it
-    // the cube's small mips in LDS: a pixel whose prefiltered level is >= cubeLdsLevel takes both footprints from the workgroup's
-    // copy of the RGB row-pair entries of mips [cubeLdsLevel, last] (byte address = global byte offset - cubeLdsAdj)
-    float cubeLdsLevel;  // (16.0: nothing is in LDS)
-    uint32_t cubeLdsBase, cubeLdsBytes; // where those mips' entries start in the staged buffer (bytes), and how many bytes they are
-    // read once per wave into VGPRs
-    float R[9];          // (float3x3)ViewInverse, row-major
-    float Lw[3];         // light direction, world space
-    float WA[3], WB[3], WC[3]; // world-space camera ray through the pixel = ndc.x * WA + ndc.y * WB + WC
-    float lightRGB[3];
-    float shA[3], shB[3], shC[3], shT[3]; // (su * W - 0.5, sv * H - 0.5, depth - bias)[k] = viewZ * (ndc.x * shA[k] + ndc.y * shB[k] + shC[k]) + shT[k]
-};
-
-// Inter-workgroup balancing of a streaming launch (UR_OPT_LIGHTING_BALANCE). Equal static shares leave the mean wave idle for the
-// last ~5 us of a 4K launch: XCDs differ by up to 8 % in speed on the same work (profiles/r03_wave_exit_stamps.txt). So only the tiles
-// [0, staticTiles) are dealt statically; the rest is a pool of chunks of 2^dynShift consecutive tiles that workgroups claim at run
-// time, one returning device-scope atomic per chunk, `lookahead` chunks ahead of use (the first `lookahead` of a workgroup are
-// pre-assigned). The pool is cut into kClaimWords sub-pools, word q serving workgroups 8q .. 8q+7 - one per XCD under round-robin
-// placement, which is what evens out the XCDs; any placement is correct. Per workgroup the claims are strictly sequential (the chunk
-// of slot k is claimed only after slot k - 1 has been published in LDS), so its slots are valid up to the first failed claim and
-// END from there on: exactly one failed claim per workgroup, after which it adds one to words[kClaimWords * stride]; the
-// workgroup whose add comes last puts every word back to zero for the next launch (also under hipGraph replay).
-struct Balance {
-    uint32_t poolChunks;   // 0: off
-    uint32_t staticTiles, dynShift, lookahead;
-    unsigned long long poolMagic; // first chunk of the share of workgroups [0, x) = (x * poolMagic) >> 32 (= x * poolChunks / groups, rounded up)
-    uint32_t* words;
-    uint32_t* timedOut;    // host-visible (mapped, coherent): a wave gave up waiting for a slot of its workgroup (ur_ctx::claim_timed_out)
-};
-
-struct LightingParams {
-    // frame
-    uint32_t W, H, row0, rows;
-    float invW2, invH2;  // 2/W, 2/H
-    // lighting
-    float invP11, invP22;
-    float L[3];          // normalize(mul(float4(LightDirection,0), View).xyz)
-    float R[9];          // (float3x3)ViewInverse, row-major
-    float SQ[12];        // rows 0..2 of (ViewInverse * LightViewProjection), columns x,y,z,w : applied to the camera ray (a,b,1)
-    float VIt[3], camPos[3]; // row 3 of ViewInverse, CameraPosition: the general path below (general != 0)
-    uint32_t general;    // ViewInverse is not a rigid transform, or CameraPosition is not its origin: world vectors are formed literally
-    uint32_t shadowSmall; // a shadow map below 3x3 texels: every pixel takes the bordered PCF
-    float ST[4];         // row 3 of the same matrix
-    float lightRGB[3];   // LightIntensity * LightColor
-    float shadowStrength, shadowBias;
-    float shadowW, shadowH, shadowTexelX, shadowTexelY;
-    int32_t shadowWi, shadowHi;
-    float maxMip;        // max(0, EnvMapMipCount-1)
-    uint32_t envBase, envMips;
-    uint32_t envMipOffset[16]; // in half4 texels
-    uint32_t irrOffset0, irrOffset1, irrN0, irrN1; // mip pair of the irradiance lookup (level == maxMip, launch-uniform)
-    float irrFrac;
-    uint32_t lutW, lutH;
-    // sky
-    float skyRot[9];     // rows of View's 3x3: world_j = dot(skyRot[3j..3j+2], v)
-    float skyInvP11, skyInvP22;
-    float skyNearOverR;  // Projection[14] / World[0]
-    float sunDir[3];     // normalize(LightDirection)
-    float skyScatterR[3];// rayleighColor * rayleighDensity * 3/(16 pi)
-    float skyMie[3];     // LightColor * mieDensity * 0.8 * (1-g^2)/(4 pi)
-    float sunAttenuation;
-    StreamHot hot;       // streaming kernel: everything one loop iteration reads
-    Balance bal;         // ... and what its run-time tile claims read (cold)
-    unsigned long long* timeline; // debug: {first entry, last exit} of this launch (ur_debug_timeline), else null
-    // buffers
-    const half4_t* A;
-    const half4_t* B;
-    const uint32_t* C;
-    const float* depth;
-    const float* shadow;
-    const half4_t* env;
-    const uint32_t* lut; // RG16 texel = one dword
-    const float* srgb;
-    half4_t* hdr;
-};
-
-__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
-__device__ __forceinline__ float sat(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
-__device__ __forceinline__ float mix(float a, float b, float t) { return fmaf(t, b - a, a); }
-
-// base + 32-bit unsigned BYTE offset: lets the compiler use the SGPR-base + VGPR-offset addressing mode of global_load
-// instead of 64-bit VALU address arithmetic (v_lshl_add_u64 per access).
-// (The pointers are global memory by contract; saying so keeps pointers that were themselves loaded from memory off the
-// flat_load path.)
-#define UR_GLOBAL __attribute__((address_space(1)))
-template <class T>
-__device__ __forceinline__ T ld(const void* base, uint32_t byte_offset)
-{
-    return *reinterpret_cast<const UR_GLOBAL T*>((const UR_GLOBAL char*)base + byte_offset);
-}
-template <class T>
-__device__ __forceinline__ void st(void* base, uint32_t byte_offset, T v)
-{
-    *reinterpret_cast<UR_GLOBAL T*>((UR_GLOBAL char*)base + byte_offset) = v;
-}
-
-// HDR out of the per-tile kernel: written once, write-through + nontemporal like the streaming kernel's store (store_hdr below)
-__device__ __forceinline__ void st_hdr_once(void* base, uint32_t byte_offset, half4_t v)
-{
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    u32x2_t u;
-    __builtin_memcpy(&u, &v, 8);
-    asm volatile("global_store_dwordx2 %0, %1, %2 sc1 nt" ::"v"(byte_offset), "v"(u), "s"(base) : "memory");
-}
-
-struct uint4u { uint32_t x, y, z, w; };  // 16 bytes loaded from an 8-byte-aligned address
-struct float3u { float x, y, z; };       // 12 bytes loaded from a 4-byte-aligned address
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x3_t __attribute__((ext_vector_type(3)));
-typedef u32x4_t u32x4_a8 __attribute__((aligned(8)));
-typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
-typedef u32x3_t u32x3_a4 __attribute__((aligned(4)));
-typedef f32x3_t f32x3_a4 __attribute__((aligned(4)));
-template <>
-__device__ __forceinline__ uint4u ld<uint4u>(const void* base, uint32_t byte_offset)
-{
-    const u32x4_t v = *reinterpret_cast<const UR_GLOBAL u32x4_a8*>((const UR_GLOBAL char*)base + byte_offset);
-    return {v.x, v.y, v.z, v.w};
-}
-template <>
-__device__ __forceinline__ float3u ld<float3u>(const void* base, uint32_t byte_offset)
-{
-    const f32x3_t v = *reinterpret_cast<const UR_GLOBAL f32x3_a4*>((const UR_GLOBAL char*)base + byte_offset);
-    return {v.x, v.y, v.z};
-}
+using namespace ur;
 
 // The x, y halves of a vector as a pair. Packed fp32 arithmetic on such pairs (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 through
 // the vector type: hipcc pairs the registers and broadcasts scalar operands through op_sel without a move) was built for every
@@ -188,176 +36,8 @@ __device__ __forceinline__ float3u ld<float3u>(const void* base, uint32_t byte_o
 typedef float f2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2_t f2(float x, float y) { return f2_t{x, y}; }
 
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 f3(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ float dot(F3 a, F3 b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
-__device__ __forceinline__ F3 mix(F3 a, F3 b, float t) { return {mix(a.x, b.x, t), mix(a.y, b.y, t), mix(a.z, b.z, t)}; }
-// v * M for a row-major 3x3
-__device__ __forceinline__ F3 rot(F3 v, const float* M)
-{
-    return f3(fmaf(v.z, M[6], fmaf(v.y, M[3], v.x * M[0])), fmaf(v.z, M[7], fmaf(v.y, M[4], v.x * M[1])),
-              fmaf(v.z, M[8], fmaf(v.y, M[5], v.x * M[2])));
-}
-
-// ---- bordered cube: face f of mip m is (N+2)^2 texels, border = seamless neighbours (ur_stage_env_cube) -----------
-struct CubeUV { uint32_t face; float u, v; };
-// D3D cube addressing (+X,-X,+Y,-Y,+Z,-Z; ties z > y > x; uc/vc table of the oracle's SelectCubeFace) is exactly what
-// gfx950's v_cubeid/v_cubesc/v_cubetc/v_cubema compute (cubema = 2 * signed major axis), four instructions instead of a
-// compare/select ladder.
-__device__ __forceinline__ CubeUV cube_face(F3 d)
-{
-    CubeUV r;
-    r.face = (uint32_t)__builtin_amdgcn_cubeid(d.x, d.y, d.z);
-    const float inv = rcp(fabsf(__builtin_amdgcn_cubema(d.x, d.y, d.z))); // 1 / (2 |major|)
-    r.u = fmaf(__builtin_amdgcn_cubesc(d.x, d.y, d.z), inv, 0.5f);
-    r.v = fmaf(__builtin_amdgcn_cubetc(d.x, d.y, d.z), inv, 0.5f);
-    return r;
-}
-
-// acc += w * f16(lo/hi half of a packed dword): one mixed-precision FMA, no unpack/convert instructions
-__device__ __forceinline__ float mix_lo(float acc, uint32_t packed, float w)
-{
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(packed), "v"(w));
-    return acc;
-}
-__device__ __forceinline__ float mix_hi(float acc, uint32_t packed, float w)
-{
-    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(packed), "v"(w));
-    return acc;
-}
-// the same without an addend (first tap of a sum: no zero-initialised accumulator register)
-__device__ __forceinline__ float mul_lo(uint32_t packed, float w)
-{
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(packed), "v"(w));
-    return r;
-}
-__device__ __forceinline__ float mul_hi(uint32_t packed, float w)
-{
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(packed), "v"(w));
-    return r;
-}
-
-// ---- gathers are split into "issue the loads" and "filter" so one pixel has every independent gather in flight
-// before the BRDF math starts (the math hides their latency; no branch separates them) -----------------------------
-struct CubeTaps { uint4u r0, r1; float fx, fy; };
-
-// u,v in [0,1] (a NaN direction gives index 0 and NaN weights, i.e. a NaN result, like the reference).
-__device__ __forceinline__ CubeTaps cube_taps_load(const void* __restrict__ env, uint32_t mipOffset, uint32_t N, const CubeUV& c)
-{
-    const uint32_t E = N + 2u;
-    const float fN = (float)N;
-    const float x = fmaf(c.u, fN, 0.5f), y = fmaf(c.v, fN, 0.5f); // bordered coordinates, in [0.5, N + 0.5]
-    const uint32_t i0 = (uint32_t)x, j0 = (uint32_t)y;            // truncation == floor for x >= 0; NaN -> 0
-    CubeTaps t;
-    t.fx = x - (float)i0;
-    t.fy = y - (float)j0;
-    const uint32_t off = (mipOffset + (c.face * E + j0) * E + i0) * 8u, row = E * 8u;
-    // the two taps of a row are adjacent in memory: one 16-byte load per row (8-byte aligned; gfx950 loads may be unaligned)
-    t.r0 = ld<uint4u>(env, off);
-    t.r1 = ld<uint4u>(env, off + row);
-    return t;
-}
-
-// scale * bilinear(taps) [+ r when ACC]: 12 mixed-precision FMAs straight from the packed fp16 texels
-template <bool ACC>
-__device__ __forceinline__ void cube_taps_filter(F3& r, const CubeTaps& t, float scale)
-{
-    const float wy1 = t.fy * scale, wy0 = scale - wy1;
-    const float w10 = wy0 * t.fx, w00 = wy0 - w10, w11 = wy1 * t.fx, w01 = wy1 - w11;
-    const float x0 = ACC ? mix_lo(r.x, t.r0.x, w00) : mul_lo(t.r0.x, w00);
-    const float y0 = ACC ? mix_hi(r.y, t.r0.x, w00) : mul_hi(t.r0.x, w00);
-    const float z0 = ACC ? mix_lo(r.z, t.r0.y, w00) : mul_lo(t.r0.y, w00);
-    r.x = mix_lo(mix_lo(mix_lo(x0, t.r0.z, w10), t.r1.x, w01), t.r1.z, w11);
-    r.y = mix_hi(mix_hi(mix_hi(y0, t.r0.z, w10), t.r1.x, w01), t.r1.z, w11);
-    r.z = mix_lo(mix_lo(mix_lo(z0, t.r0.w, w10), t.r1.y, w01), t.r1.w, w11);
-}
-
-struct LutTaps { uint32_t t00, t10, t01, t11; float fx, fy; };
-__device__ __forceinline__ LutTaps lut_taps_load(const LightingParams& p, float u, float v)
-{
-    const float x = fmaf(u, (float)p.lutW, -0.5f), y = fmaf(v, (float)p.lutH, -0.5f);
-    const float x0 = floorf(x), y0 = floorf(y);
-    LutTaps t;
-    t.fx = x - x0;
-    t.fy = y - y0;
-    const int W1 = (int)p.lutW - 1, H1 = (int)p.lutH - 1;
-    const int i0 = min(max((int)x0, 0), W1), i1 = min(max((int)x0 + 1, 0), W1); // clamp addressing
-    const int j0 = min(max((int)y0, 0), H1), j1 = min(max((int)y0 + 1, 0), H1);
-    const uint32_t r0 = (uint32_t)j0 * p.lutW, r1 = (uint32_t)j1 * p.lutW;
-    t.t00 = ld<uint32_t>(p.lut, (r0 + i0) * 4u);
-    t.t10 = ld<uint32_t>(p.lut, (r0 + i1) * 4u);
-    t.t01 = ld<uint32_t>(p.lut, (r1 + i0) * 4u);
-    t.t11 = ld<uint32_t>(p.lut, (r1 + i1) * 4u);
-    return t;
-}
-__device__ __forceinline__ void lut_taps_filter(const LutTaps& t, float& a, float& b)
-{
-    const float s = 1.0f / 65535.0f;
-    const float wy1 = t.fy * s, wy0 = s - wy1;
-    const float w10 = wy0 * t.fx, w00 = wy0 - w10, w11 = wy1 * t.fx, w01 = wy1 - w11;
-    a = fmaf(w11, (float)(t.t11 & 0xFFFFu), fmaf(w01, (float)(t.t01 & 0xFFFFu), fmaf(w10, (float)(t.t10 & 0xFFFFu), w00 * (float)(t.t00 & 0xFFFFu))));
-    b = fmaf(w11, (float)(t.t11 >> 16), fmaf(w01, (float)(t.t01 >> 16), fmaf(w10, (float)(t.t10 >> 16), w00 * (float)(t.t00 >> 16))));
-}
-
-// step(t) = (cmp <= t), LESS_EQUAL as the shader states it (a NaN on either side fails). A compare, not
-// saturate((t - cmp) * 2^126 + 1): that form returns a fraction when 0 < |t - cmp| < 2^-126 (cmp = 0, t = -2^-149).
-__device__ __forceinline__ float step_le(float cmp, float t)
-{
-    return cmp <= t ? 1.0f : 0.0f;
-}
-
-// The four PCF samples of DeferredLighting.hlsl:62-70: SampleCmpLevelZero (bilinear blend of four LESS_EQUAL results,
-// border = 1.0) at (u, u + 1 texel) x (v, v + 1 texel). The second sample's footprint is the first's shifted by exactly
-// one texel, so the union is a 3x3 block and the sum of the four bilinear blends factors into separable weights
-// (1-f, 1, f) per axis: 9 loads, 9 compares. (The oracle evaluates the shifted coordinate (u + 1/W) * W - 0.5 in fp32;
-// its fraction differs from f by O(1e-4), i.e. O(1e-5) in the result — far inside the HDR tolerance.)
-struct ShadowTaps { float3u ra, rb, rc; float fx, fy; int ia, ja; };
-__device__ __forceinline__ ShadowTaps shadow_taps_load(const LightingParams& p, float su, float sv)
-{
-    const float xa = fmaf(su, p.shadowW, -0.5f), ya = fmaf(sv, p.shadowH, -0.5f);
-    const float xa0 = floorf(xa), ya0 = floorf(ya);
-    ShadowTaps t;
-    t.fx = xa - xa0;
-    t.fy = ya - ya0;
-    t.ia = (int)xa0;
-    t.ja = (int)ya0;
-    // clamped block origin: always a valid address (the host rejects shadow maps smaller than 3x3)
-    const uint32_t ic = (uint32_t)min(max(t.ia, 0), p.shadowWi - 3), jc = (uint32_t)min(max(t.ja, 0), p.shadowHi - 3);
-    const uint32_t W = (uint32_t)p.shadowWi;
-    const uint32_t o0 = (jc * W + ic) * 4u, o1 = o0 + W * 4u, o2 = o1 + W * 4u;
-    t.ra = ld<float3u>(p.shadow, o0); // one 12-byte load per row
-    t.rb = ld<float3u>(p.shadow, o1);
-    t.rc = ld<float3u>(p.shadow, o2);
-    return t;
-}
-__device__ __forceinline__ float shadow_taps_filter(const ShadowTaps& t, float cmp)
-{
-    const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
-    const float r0 = fmaf(step_le(cmp, t.ra.z), t.fx, fmaf(step_le(cmp, t.ra.x), wx0, step_le(cmp, t.ra.y)));
-    const float r1 = fmaf(step_le(cmp, t.rb.z), t.fx, fmaf(step_le(cmp, t.rb.x), wx0, step_le(cmp, t.rb.y)));
-    const float r2 = fmaf(step_le(cmp, t.rc.z), t.fx, fmaf(step_le(cmp, t.rc.x), wx0, step_le(cmp, t.rc.y)));
-    return 0.25f * fmaf(t.fy, r2, fmaf(wy0, r0, r1));
-}
-// footprint touches the border (or the map is tiny): out-of-range taps read the border colour 1.0
-__device__ __noinline__ float shadow_pcf_border(const float* __restrict__ map, int W, int H, int ia, int ja, float fx, float fy, float cmp)
-{
-    float acc = 0.0f;
-    for (int r = 0; r < 3; ++r) {
-        float s = 0.0f;
-        for (int c = 0; c < 3; ++c) {
-            const int xi = ia + c, yj = ja + r;
-            const bool in = xi >= 0 && yj >= 0 && xi < W && yj < H;
-            const float t = in ? map[(uint32_t)yj * (uint32_t)W + (uint32_t)xi] : 1.0f;
-            s += cmp <= t ? (c == 0 ? 1.0f - fx : (c == 1 ? 1.0f : fx)) : 0.0f;
-        }
-        acc = fmaf(r == 0 ? 1.0f - fy : (r == 1 ? 1.0f : fy), s, acc);
-    }
-    return 0.25f * acc;
-}
-
-// the same, inlined (the streaming kernel keeps no call in its loop: a call pins live values to callee-saved registers)
+// footprint touches the border (or the map is tiny): out-of-range taps read the border colour 1.0. shadow_pcf_border of
+// lighting_tiled.hip, inlined (the streaming kernel keeps no call in its loop: a call pins live values to callee-saved registers)
 __device__ __forceinline__ float shadow_pcf_border_inline(const float* __restrict__ map, int W, int H, int ia, int ja, float fx, float fy, float cmp)
 {
     float acc = 0.0f;
@@ -379,216 +59,6 @@ __device__ __forceinline__ float shadow_pcf_border_inline(const float* __restric
     return 0.25f * acc;
 }
 
-// DeferredLighting.hlsl:35-94 for one pixel. (a,b) = camera ray (ndc.x/P11, -ndc.y/P22); viewPos = viewZ * (a, b, 1).
-template <bool SHADOWS>
-__device__ __forceinline__ F3 shade_pixel(const LightingParams& p, const float* srgb, const uint32_t* mipOffset, float ra, float rb, half4_t ga, half4_t gb,
-                                          uint32_t gc)
-{
-    // ---- decode, view vectors ------------------------------------------------------------------------------------------
-    const float nx = (float)ga.x, ny = (float)ga.y, nz = (float)ga.z;
-    const float nr = rsq(fmaf(nz, nz, fmaf(ny, ny, nx * nx))); // normalize(0) = NaN, as in the reference
-    const F3 N = f3(nx * nr, ny * nr, nz * nr);
-    const float viewZ = -(float)ga.w;
-    const float spec0 = (float)gb.x, metallic = (float)gb.y, roughness = (float)gb.z;
-    // V = normalize(-viewPos) = -sign(viewZ) * (a,b,1)/|(a,b,1)|
-    const float rl = rsq(fmaf(ra, ra, fmaf(rb, rb, 1.0f)));
-    const float vs = viewZ > 0.0f ? -rl : (viewZ < 0.0f ? rl : __builtin_nanf("")); // normalize(0) = NaN
-    const F3 V = f3(ra * vs, rb * vs, vs);
-    const F3 L = f3(p.L[0], p.L[1], p.L[2]);
-    const float NdotVraw = dot(N, V);
-    const float NdotV = sat(NdotVraw);
-
-    // ---- issue every gather ------------------------------------------------------------------------------------------
-    // IBL: world vectors are the view-space ones rotated by (float3x3)ViewInverse; reflect(-V, N) = 2 N (N.V) - V
-    // With a rigid view matrix whose origin is CameraPosition (every camera the reference builds) that rotation keeps lengths and
-    // angles, worldView is the rotated V and dot(worldNormal, worldView) = N.V. Otherwise (uniform, p.general) the vectors are formed
-    // as the shader writes them: worldPos = viewPos * ViewInverse, worldView = normalize(CameraPosition - worldPos),
-    // worldNormal = normalize(normal * (float3x3)ViewInverse) (DeferredLighting.hlsl:55,76-78,84).
-    F3 wR = f3(0.0f, 0.0f, 0.0f), wN = f3(0.0f, 0.0f, 0.0f);
-    float NdotVibl = NdotV;
-    if (p.general == 0u) {
-        const float t2 = 2.0f * NdotVraw;
-        wR = rot(f3(fmaf(t2, N.x, -V.x), fmaf(t2, N.y, -V.y), fmaf(t2, N.z, -V.z)), p.R);
-        wN = rot(N, p.R);
-    } else {
-        const F3 wp = rot(f3(ra * viewZ, rb * viewZ, viewZ), p.R);
-        F3 wv = f3(p.camPos[0] - (wp.x + p.VIt[0]), p.camPos[1] - (wp.y + p.VIt[1]), p.camPos[2] - (wp.z + p.VIt[2]));
-        const float wvr = rsq(dot(wv, wv));
-        wv = f3(wv.x * wvr, wv.y * wvr, wv.z * wvr);
-        wN = rot(N, p.R);
-        const float wnr = rsq(dot(wN, wN));
-        wN = f3(wN.x * wnr, wN.y * wnr, wN.z * wnr);
-        const float nv = dot(wN, wv);
-        wR = f3(fmaf(2.0f * nv, wN.x, -wv.x), fmaf(2.0f * nv, wN.y, -wv.y), fmaf(2.0f * nv, wN.z, -wv.z)); // reflect(-worldView, worldNormal)
-        NdotVibl = sat(nv);
-    }
-    const CubeUV cr = cube_face(wR);
-    const CubeUV cn = cube_face(wN);
-    const float lvl = fminf(fmaxf(roughness * p.maxMip, 0.0f), (float)(p.envMips - 1u));
-    const uint32_t m0 = (uint32_t)lvl, m1 = min(m0 + 1u, p.envMips - 1u);
-    const float fl = lvl - (float)m0; // m1 == m0 only when fl == 0: the second mip then carries weight 0
-    const CubeTaps pre0 = cube_taps_load(p.env, mipOffset[m0], max(1u, p.envBase >> m0), cr);
-    const CubeTaps pre1 = cube_taps_load(p.env, mipOffset[m1], max(1u, p.envBase >> m1), cr);
-    const CubeTaps irr0 = cube_taps_load(p.env, p.irrOffset0, p.irrN0, cn);
-    const LutTaps lut = lut_taps_load(p, NdotVibl, roughness);
-    // The shadow term multiplies NdotL: a wave whose every pixel faces away from the light skips the PCF altogether
-    // (same result: direct = 0). Coherent G-buffers make this common (ceilings, walls turned from the sun).
-    const float NdotL = sat(dot(N, L));
-    const bool wave_lit = SHADOWS && __any(NdotL > 0.0f);
-    float su = 0.0f, sv = 0.0f, cmp = 0.0f;
-    bool lit = false;
-    ShadowTaps sh;
-    if (wave_lit) {
-        // shadow clip = viewZ * ((a,b,1) * M3) + M[3]
-        const float qx = fmaf(rb, p.SQ[4], fmaf(ra, p.SQ[0], p.SQ[8]));
-        const float qy = fmaf(rb, p.SQ[5], fmaf(ra, p.SQ[1], p.SQ[9]));
-        const float qz = fmaf(rb, p.SQ[6], fmaf(ra, p.SQ[2], p.SQ[10]));
-        const float qw = fmaf(rb, p.SQ[7], fmaf(ra, p.SQ[3], p.SQ[11]));
-        const float iw = rcp(fmaf(viewZ, qw, p.ST[3]));
-        su = fmaf(fmaf(viewZ, qx, p.ST[0]) * iw, 0.5f, 0.5f);
-        sv = fmaf(fmaf(viewZ, qy, p.ST[1]) * iw, -0.5f, 0.5f);
-        cmp = fmaf(viewZ, qz, p.ST[2]) * iw - p.shadowBias;
-        lit = su >= 0.0f && sv >= 0.0f && su <= 1.0f && sv <= 1.0f;
-        if (p.shadowSmall == 0u) sh = shadow_taps_load(p, su, sv); // (uniform; the 3x3 block needs a map of at least 3x3 texels)
-        else sh = ShadowTaps{};
-    }
-    const F3 albedo = f3(srgb[gc & 0xFFu], srgb[(gc >> 8) & 0xFFu], srgb[(gc >> 16) & 0xFFu]);
-
-    // ---- EvaluatePBR, PBRCommon.hlsl:24-48 (runs while the gathers are in flight) --------------------------------------------
-    const F3 F0 = mix(f3(spec0, spec0, spec0), albedo, metallic);
-    F3 Hv = f3(V.x + L.x, V.y + L.y, V.z + L.z);
-    const float hr = rsq(dot(Hv, Hv));
-    const float NdotH = sat(dot(N, Hv) * hr);
-    const float VdotH = dot(V, Hv) * hr; // = (1 + V.L)/|V + L| in [0,1]: saturate is the identity up to rounding
-    const float alpha = roughness * roughness;
-    const float alpha2 = alpha * alpha;
-    const float denom = fmaf(NdotH * NdotH, alpha2 - 1.0f, 1.0f);
-    const float D = alpha2 * rcp(fmaxf(3.14159265f * denom * denom, 1e-4f));
-    float k = roughness + 1.0f;
-    k = (k * k) * 0.125f;
-    const float omk = 1.0f - k;
-    // G / max(4 NdotL NdotV, 1e-4) * D, one reciprocal for the three denominators
-    const float gv = fmaf(NdotV, omk, k), gl = fmaf(NdotL, omk, k);
-    const float sc = (D * NdotV * NdotL) * rcp(gv * gl * fmaxf(4.0f * NdotL * NdotV, 1e-4f));
-    const float om = 1.0f - VdotH;
-    const float om2 = om * om;
-    const float p5 = om2 * om2 * om;
-    const float kdm = 1.0f - metallic;
-
-    // ---- filter ---------------------------------------------------------------------------------------------------------------
-    float shadow = 1.0f;
-    if (wave_lit) {
-        const bool fast = p.shadowSmall == 0u && sh.ia >= 0 && sh.ja >= 0 && sh.ia + 2 < p.shadowWi && sh.ja + 2 < p.shadowHi;
-        float s = shadow_taps_filter(sh, cmp);
-        if (__builtin_expect(lit && !fast, 0)) {
-            const float xa = fmaf(su, p.shadowW, -0.5f), ya = fmaf(sv, p.shadowH, -0.5f);
-            const float xa0 = floorf(xa), ya0 = floorf(ya);
-            s = shadow_pcf_border(p.shadow, p.shadowWi, p.shadowHi, (int)xa0, (int)ya0, xa - xa0, ya - ya0, cmp);
-        }
-        shadow = lit ? mix(1.0f, s, p.shadowStrength) : 1.0f;
-    }
-    const float sh_l = shadow * NdotL;
-    F3 prefiltered, irradiance;
-    cube_taps_filter<false>(prefiltered, pre0, 1.0f - fl);
-    cube_taps_filter<true>(prefiltered, pre1, fl);
-    cube_taps_filter<false>(irradiance, irr0, 1.0f - p.irrFrac);
-    if (p.irrFrac != 0.0f) cube_taps_filter<true>(irradiance, cube_taps_load(p.env, p.irrOffset1, p.irrN1, cn), p.irrFrac); // uniform
-    float ba, bb;
-    lut_taps_filter(lut, ba, bb);
-
-    F3 color;
-#define UR_CHANNEL(ch, i)                                                                                     \
-    {                                                                                                         \
-        const float A = kdm * albedo.ch;                     /* (1 - metallic) * albedo: diffuse weight, also irradiance's */ \
-        const float F = fmaf(1.0f - F0.ch, p5, F0.ch);                                                        \
-        const float direct = fmaf(F, sc - A, A);             /* (1-F) A + F sc */                            \
-        const float ambient = fmaf(irradiance.ch, A, prefiltered.ch * fmaf(F0.ch, ba, bb));                   \
-        color.ch = fmaf(direct, p.lightRGB[i] * sh_l, ambient);                                               \
-    }
-    UR_CHANNEL(x, 0)
-    UR_CHANNEL(y, 1)
-    UR_CHANNEL(z, 2)
-#undef UR_CHANNEL
-    return color;
-}
-
-// SkyAtmosphere.hlsl:58-93 with the camera-height densities, phase constants and sun attenuation folded on the host.
-// P: pointer to the parameters (generic for the per-tile kernel; a re-read kernarg pointer in the streaming kernel)
-template <class P>
-__device__ __forceinline__ F3 sky_pixel(P p, float vx, float vy)
-{
-    const auto* Q = p->skyRot;
-    F3 w = f3(fmaf(vy, Q[1], fmaf(vx, Q[0], Q[2])), fmaf(vy, Q[4], fmaf(vx, Q[3], Q[5])), fmaf(vy, Q[7], fmaf(vx, Q[6], Q[8])));
-    const float wr = rsq(dot(w, w));
-    w = f3(w.x * wr, w.y * wr, w.z * wr);
-    const float h = 1.0f - sat(fmaf(w.y, 0.5f, 0.5f));
-    const float falloff = sat(h * h * h);
-    const float cosSunView = dot(w, f3(p->sunDir[0], p->sunDir[1], p->sunDir[2]));
-    const float rayleighPhase = fmaf(cosSunView, cosSunView, 1.0f);
-    const float g = 0.76f, g2 = g * g;
-    const float mb = fmaf(-2.0f * g, cosSunView, 1.0f + g2);
-    const float denom = mb * __builtin_amdgcn_sqrtf(mb); // pow(x, 1.5)
-    const float miePhase = rcp(fmaxf(denom, 1e-3f));
-    F3 c;
-    c.x = fmaf(fmaf(p->skyMie[0], miePhase, p->skyScatterR[0] * rayleighPhase), p->sunAttenuation, mix(0.05f, 0.52f, falloff));
-    c.y = fmaf(fmaf(p->skyMie[1], miePhase, p->skyScatterR[1] * rayleighPhase), p->sunAttenuation, mix(0.12f, 0.68f, falloff));
-    c.z = fmaf(fmaf(p->skyMie[2], miePhase, p->skyScatterR[2] * rayleighPhase), p->sunAttenuation, mix(0.22f, 0.86f, falloff));
-    return c;
-}
-
-// A workgroup is 4 waves; a wave covers TW x TH pixels; the four waves sit side by side in x.
-template <int MODE, bool SHADOWS, int TW, int WAVES>
-__global__ __launch_bounds__(256, WAVES) void lighting_kernel(LightingParams p)
-{
-    constexpr int TH = 64 / TW;
-    __shared__ float srgb[256];
-    if (MODE != ur::UR_MODE_SKY) {
-        srgb[threadIdx.x] = p.srgb[threadIdx.x];
-        __syncthreads();
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t px = (blockIdx.x * 4u + wave) * TW + (lane % TW);
-    const uint32_t r = blockIdx.y * TH + (lane / TW); // row inside the band
-    if (px >= p.W || r >= p.rows) return;
-    const uint32_t py = p.row0 + r;
-    const uint32_t i = r * p.W + px; // pixel index inside the band (< 2^29: byte offsets below stay 32-bit)
-    // ndc.x in the streaming kernel's two-step form (16-pixel tile origin, then the column inside the tile): the same bits
-    // in both kernels, so a fused streaming launch equals Lighting followed by this kernel's Sky launch bit for bit
-    const float ndcx = fmaf((float)(px & ~15u), p.invW2, fmaf((float)(px & 15u), p.invW2, 0.5f * p.invW2 - 1.0f));
-    const float ndcy = fmaf((float)py + 0.5f, p.invH2, -1.0f);
-
-    if (MODE != ur::UR_MODE_LIGHTING) {
-        const float vx = ndcx * p.skyInvP11, vy = -ndcy * p.skyInvP22;
-        const float len = __builtin_amdgcn_sqrtf(fmaf(vx, vx, fmaf(vy, vy, 1.0f)));
-        const float skyDepth = p.skyNearOverR * len; // Near / (R * unit_dir.z), unit_dir.z = 1/len
-        if (skyDepth >= ld<float>(p.depth, i * 4u)) {
-            F3 sky = sky_pixel(&p, vx, vy);
-            // the colour is an fp32 value rounded to fp16 in a second step, as in the oracle and in the streaming kernel: kept
-            // apart from the conversion, or hipcc fuses the last FMA with it (v_fma_mixlo_f16: ONE rounding, a different bit in
-            // about one sky pixel in seven thousand)
-            asm volatile("" : "+v"(sky.x), "+v"(sky.y), "+v"(sky.z));
-            half4_t o;
-            o.x = (_Float16)sky.x; o.y = (_Float16)sky.y; o.z = (_Float16)sky.z; o.w = (_Float16)1.0f;
-            st_hdr_once(p.hdr, i * 8u, o);
-            return;
-        }
-        if (MODE == ur::UR_MODE_SKY) return;
-    }
-    const half4_t ga = ld<half4_t>(p.A, i * 8u), gb = ld<half4_t>(p.B, i * 8u);
-    const uint32_t gc = ld<uint32_t>(p.C, i * 4u);
-    const half4_t d = ld<half4_t>(p.hdr, i * 8u);
-    const F3 col = shade_pixel<SHADOWS>(p, srgb, p.envMipOffset, ndcx * p.invP11, -ndcy * p.invP22, ga, gb, gc);
-    // blend in fp32, then ONE conversion to fp16 (not a fused mixed-precision add: see the sky branch above)
-    float bx = (float)d.x + col.x, by = (float)d.y + col.y, bz = (float)d.z + col.z, bw = (float)d.w + 1.0f;
-    asm volatile("" : "+v"(bx), "+v"(by), "+v"(bz), "+v"(bw));
-    half4_t o;
-    o.x = (_Float16)bx;
-    o.y = (_Float16)by;
-    o.z = (_Float16)bz;
-    o.w = (_Float16)bw;
-    st_hdr_once(p.hdr, i * 8u, o);
-}
-
 // =====================================================================================================================
 // Streaming form (the default for full-tile regions): persistent waves, each looping over 16x4-pixel tiles.
 //
@@ -605,13 +75,12 @@ __global__ __launch_bounds__(256, WAVES) void lighting_kernel(LightingParams p)
 //    min/max, no unpack/convert per tap), the launch-uniform irradiance mip as per-cell fp32 polynomials, the sRGB table as before.
 //  * The shadow transform of the (orthographic) light is folded on the host into three affine forms of the camera ray.
 // =====================================================================================================================
-constexpr uint32_t kLutW = 128, kLutH = 32, kLutE = kLutW + 2;    // streaming kernel: LUT dimensions are compile-time
-constexpr uint32_t kChunkShift = 2;                                 // static deal: chunks of 4 consecutive tiles (4K, round 1: chunks of 16 / 4 / 1 tiles -> 75.4 / 74.6 / 79.1 us)
+constexpr uint32_t kLutE = kLutW + 2;
 constexpr uint32_t kLdsSrgb = 0;                                    // 256 floats
 constexpr uint32_t kLdsIrrBytes = 6 * 9 * 64;                       // 54 cells x 64 B
 constexpr uint32_t kLdsWork = 1024 + 17 * 32 + kLdsIrrBytes;        // [0] the workgroup's tile counter, [1] waves that left the loop, [2] HZB walkers done,
                                                                     // [4] first run-time chunk of the workgroup's claim word, [5] how many follow (32 bytes reserved)
-constexpr uint32_t kDynSlots = 256;                                 // run-time chunk slots of a workgroup: tile index of the chunk's first tile, or:
+// A workgroup has kDynSlots (lighting_plan.h) run-time chunk slots. A slot holds the tile index of its chunk's first tile, or one of:
 constexpr uint32_t kDynNotReady = 0xFFFFFFFFu, kDynEnd = 0xFFFF0000u; // not published yet / nothing left to claim (any value >= kDynEnd)
 constexpr uint32_t kLdsDyn = kLdsWork + 32;
 constexpr uint32_t kLdsMip = 1024;                                  // 17 x 16 B: per-mip cube constants (MipEntry)
@@ -620,8 +89,7 @@ constexpr uint32_t kLdsHzb = kLdsDyn + kDynSlots * 4;               // 80 floats
 constexpr uint32_t kLdsLut = kLdsHzb + 16 * 80 * 4;                 // (kLutW + 2) x (kLutH + 2) float2
 constexpr uint32_t kLdsTiles = kLdsLut + kLutE * (kLutH + 2) * 8;   // per wave: 2 x 2 KB
 constexpr uint32_t kTileBytes = 2048;                               // A 512 | B 512 | HDR 512 | C 256 | depth 256
-constexpr uint32_t kLdsCubeBytes = 32768;                           // behind the waves' tile buffers: RGB row-pair entries of the cube's small mips
-                                                                    // (the shipped 256^2 cube: mips 4..8 = 31 968 bytes)
+// Behind the waves' tile buffers come kLdsCubeBytes (lighting_plan.h): the RGB row-pair entries of the cube's small mips.
 static_assert(kLdsTiles % 16 == 0, "tile buffers are 16-byte aligned");
 
 __device__ __forceinline__ uint32_t lds_address(const void* p)
@@ -1480,406 +948,60 @@ __global__ __launch_bounds__(64 * WPB, 1) void lighting_stream_kernel(LightingPa
     }
 }
 
-void mat4_mul(const float* a, const float* b, float* o)
-{
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            float s = 0.0f;
-            for (int k = 0; k < 4; ++k) s += a[i * 4 + k] * b[k * 4 + j];
-            o[i * 4 + j] = s;
-        }
-}
-
-// One Lighting launch. With a pair of events waiting on the context (ur_time_next_lighting) the dispatch itself carries
-// them (hipExtLaunchKernelGGL): their distance is the kernel's own begin -> end interval, no event record in the queue.
-template <class K, class... Args>
-void launch_timed(ur_ctx* ctx, K kern, dim3 grid, dim3 block, uint32_t lds, Args... args)
-{
-    if (ctx->time_stop != nullptr) {
-        hipExtLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ctx->time_start, ctx->time_stop, 0, args...);
-        ctx->time_start = ctx->time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, args...);
-    }
-}
-
-// Per-tile kernel (one 64x4-pixel workgroup per tile): partial tiles, sky-only launches and configurations the streaming
-// kernel does not cover.
-template <int MODE, bool SHADOWS>
-void launch_tiled(ur_ctx* ctx, const LightingParams& p)
-{
-    constexpr int TW = 16; // pixels per wave = 16 x 4: 128-byte G-buffer row segments and compact gather footprints
-    const uint32_t tilesX = (p.W + 4 * TW - 1) / (4 * TW), tilesY = (p.rows + (64 / TW) - 1) / (64 / TW);
-    // register budget: waves/SIMD the kernel is compiled for (6 -> 80 VGPRs, the most that does not spill; 4 -> no cap)
-    if (ctx->opt.tiled_waves >= 6) /* UR_OPT_LIGHTING_TILED_WAVES */ launch_timed(ctx, lighting_kernel<MODE, SHADOWS, TW, 6>, dim3(tilesX, tilesY), dim3(256), 0u, p);
-    else launch_timed(ctx, lighting_kernel<MODE, SHADOWS, TW, 4>, dim3(tilesX, tilesY), dim3(256), 0u, p);
-}
-
-
-template <int MODE, bool SHADOWS, bool IRR_LDS, int WPB>
-int launch_stream_wpb(ur_ctx* ctx, LightingParams p /* by value: the tile walk is filled in here */)
-{
-    typedef void (*kernel_t)(LightingParams, ur::HzbTail, HzbRide);
-    constexpr uint32_t lds = kLdsTiles + WPB * 2u * kTileBytes + kLdsCubeBytes;
-    p.timeline = ur::next_timeline_pair(ctx);
-    // MaxDynamicSharedMemorySize is a per-DEVICE attribute of the function: one flag per instantiation and device
-    static bool attr_set[2][64] = {};
-    const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : -1;
-    StreamHot& h = p.hot;
-    h.tilesX = p.W / 16u;
-    h.numTiles = h.tilesX * ((p.rows + 3u) / 4u);
-    // A deferred HZB tail (ur_defer_hzb_tail) rides along as one extra 1024-thread workgroup on a CU of its own: the
-    // lighting workgroups give up one CU (0.4 % of their throughput) and the frame saves a ~5 us single-workgroup launch.
-    ur::HzbTail tail{};
-    // UR_OPT_LIGHTING_LEAVE_CUS = n leaves n CUs to kernels of other streams (the graph's async-compute passes): the persistent
-    // workgroups otherwise fill every CU's register file and nothing runs beside them. Never below one lighting workgroup
-    // (a CPX partition reports 32 CUs), and the tail is carried only when that still leaves the lighting a CU of its own.
-    const int leave_env = ctx->opt.leave_cus;
-    const int cus = std::max(ctx->cu_count, 1);
-    const int leave_cus = std::min(leave_env, cus - 1);
-    const bool carry_tail = ctx->hzb_tail_pending && WPB == 16 && cus >= 16 && cus - leave_cus >= 2;
-    HzbRide ride{};
-    if (carry_tail) {
-        tail = ctx->pending_tail;
-        ctx->hzb_tail_pending = false;
-        if (ctx->hzb_wide_pending) { // the whole chain rides: the lighting workgroups take the wide launch's pieces along
-            ride.d = ctx->pending_wide;
-            ride.grid_x = ctx->pending_wide_grid_x;
-            ride.pieces = ctx->pending_wide_grid_x * ctx->pending_wide_grid_y;
-            ride.done = ctx->hzb_done;
-            ride.timed_out = ctx->hzb_timed_out_dev;
-            ride.spin_limit = ctx->opt.debug_hzb_ride_stall != 0 ? (1u << 9) : (1u << 22);
-            // walkers: the chain should be done within about a quarter of the shading (a piece is ~3 us of one wave's time, a
-            // tile ~1.75 us): walkers >= 7 x pieces-per-workgroup / tiles-per-wave, rounded up to a power of two
-            {
-                const int forced = ctx->opt.ride_walkers; // UR_OPT_RIDE_WALKERS
-                const uint32_t lighting_groups = std::max(1, cus - 1 - leave_cus);
-                const double per_group = (double)ride.pieces / lighting_groups, tiles_per_wave = (double)h.numTiles / (lighting_groups * WPB);
-                uint32_t wk = 1;
-                while (wk < (uint32_t)WPB && (double)wk * tiles_per_wave < 7.0 * per_group) wk *= 2;
-                if (forced >= 1) wk = (uint32_t)forced;
-                ride.walkers = wk >= 4u ? (uint32_t)WPB : 1u; // two instantiations: the last wave alone, or all of them
-            }
-            ctx->hzb_wide_pending = false;
-        }
-    } else if (ctx->hzb_wide_pending && !ctx->hzb_tail_pending && WPB == 16 && cus >= 16) {
-        // a band-sharded chain's pieces (ur_build_hzb_band) ride without a tail: the tail waits for the ranks' gather. Nothing inside
-        // the launch consumes the pieces, so no arrival is signalled (done stays null) and no CU is set aside.
-        ride.d = ctx->pending_wide;
-        ride.grid_x = ctx->pending_wide_grid_x;
-        ride.pieces = ctx->pending_wide_grid_x * ctx->pending_wide_grid_y;
-        const uint32_t lighting_groups = std::max(1, cus - leave_cus);
-        const double per_group = (double)ride.pieces / lighting_groups, tiles_per_wave = (double)h.numTiles / (lighting_groups * WPB);
-        uint32_t wk = 1;
-        while (wk < (uint32_t)WPB && (double)wk * tiles_per_wave < 7.0 * per_group) wk *= 2;
-        if (ctx->opt.ride_walkers >= 1) wk = (uint32_t)ctx->opt.ride_walkers;
-        ride.walkers = wk >= 4u ? (uint32_t)WPB : 1u;
-        ctx->hzb_wide_pending = false;
-    } else if (ctx->hzb_wide_pending) { // cannot ride (12-wave build, tiny device): the ordinary launches, in front
-        const int frc = ur::flush_hzb_tail(ctx);
-        if (frc != UR_OK) return frc;
-    }
-    const uint32_t groups = std::min<uint32_t>((uint32_t)std::max(1, cus - (carry_tail ? 1 : 0) - leave_cus), (h.numTiles + WPB - 1) / WPB);
-    h.groups = groups;
-    ride.want = groups + (ctx->opt.debug_hzb_ride_stall != 0 ? 1u : 0u);
-    // tile / tilesX by multiplication: exact while (magic * tilesX - 2^32) * tile < 2^32 (checked by the caller)
-    h.tilesXMagic = (uint32_t)((1ull << 32) / h.tilesX + 1ull);
-    // ---- the run-time part of the schedule (struct Balance): whole rounds of the static deal in front, a pool of chunks behind
-    h.staticClaims = 0xFFFFFFFFu;
-    p.bal = Balance{};
-    if (ctx->opt.balance != 0 && ctx->claim_words != nullptr && groups >= 16u && groups <= 8u * ur::kClaimWords) {
-        constexpr uint32_t cs = kChunkShift;
-        const uint32_t round = groups << cs;
-        const uint32_t want_pool = (uint32_t)((uint64_t)h.numTiles * (uint32_t)ctx->opt.balance_pool_16ths / 16u);
-        // Chunks of 16 tiles (one tile per wave of a workgroup) and nothing smaller by default: a claim blocks its wave for ~1 us, and
-        // with chunks of 4 tiles a workgroup needs one every 0.5 us - measured, that LOSES 1.5 us at 1080p and 2.2 us on a 540-row
-        // band of a 4K frame (profiles/r04_balance.txt). A launch too short for `lookahead + 2` such chunks per workgroup is dealt
-        // statically as a whole. (UR_OPT_BALANCE_CHUNK_SHIFT below 4 exists for the tests, which drive the claim path hard with it.)
-        do {
-            const uint32_t sh = (uint32_t)ctx->opt.balance_chunk_shift;
-            const uint32_t la = sh >= 4u ? 2u : (sh == 3u ? 3u : 4u); // chunks claimed ahead of use
-            const uint32_t rounds = (h.numTiles - want_pool) / round;
-            if ((rounds << cs) < 2u * (uint32_t)WPB) break; // (the two tiles of a wave's prologue are static claims)
-            const uint32_t static_tiles = rounds * round, chunks = (h.numTiles - static_tiles + (1u << sh) - 1u) >> sh;
-            if (chunks < (la + 2u) * groups) break;
-            if ((uint64_t)chunks * 8u / groups + la + 8u > kDynSlots) break; // a workgroup's slot table would not hold its word's share
-            const unsigned long long magic = (((unsigned long long)chunks << 32) + groups - 1u) / groups;
-            bool ok = true;
-            for (uint32_t q8 = 0; q8 < groups && ok; q8 += 8u) {
-                const uint32_t nq = std::min(8u, groups - q8);
-                const uint32_t P0 = (uint32_t)((q8 * magic) >> 32), P1 = (uint32_t)(((q8 + nq) * magic) >> 32);
-                ok = P1 >= P0 + la * nq && P1 <= chunks;
-            }
-            if (!ok) break;
-            h.staticClaims = rounds << cs;
-            p.bal.poolChunks = chunks; p.bal.staticTiles = static_tiles; p.bal.dynShift = sh; p.bal.lookahead = la;
-            p.bal.poolMagic = magic;
-            p.bal.words = ctx->claim_words;
-            p.bal.timedOut = ctx->claim_timed_out_dev;
-        } while (false);
-    }
-    const bool ride_all = ride.pieces != 0u && ride.walkers > 1u;
-    const kernel_t kern = ride_all ? static_cast<kernel_t>(lighting_stream_kernel<MODE, SHADOWS, IRR_LDS, WPB, true>)
-                                   : static_cast<kernel_t>(lighting_stream_kernel<MODE, SHADOWS, IRR_LDS, WPB, false>);
-    if (dev < 0 || !attr_set[ride_all][dev]) {
-        UR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0) attr_set[ride_all][dev] = true;
-    }
-    {
-        const uint32_t sched[8] = {groups, h.numTiles, p.bal.poolChunks != 0u ? p.bal.staticTiles : h.numTiles, p.bal.poolChunks, p.bal.dynShift, p.bal.lookahead,
-                                   (uint32_t)WPB, ride.pieces};
-        std::memcpy(ctx->last_schedule, sched, sizeof(sched));
-    }
-    launch_timed(ctx, kern, dim3(groups + (carry_tail ? 1u : 0u)), dim3(64 * WPB), lds, p, tail, ride);
-    return UR_OK;
-}
-
 // One persistent workgroup per CU; waves per SIMD = WPB / 4. Measured at 4K (sustained clocks), round 1: 16 -> 76.6 us, 12 -> 80.6 us,
 // 8 -> ~95 us; round 2: 16 -> 71.8 us, 12 -> 75.1 us (same box). Two workgroups of 10 waves per CU (96 VGPRs) spill.
-template <int MODE, bool SHADOWS, bool IRR_LDS>
-int launch_stream(ur_ctx* ctx, const LightingParams& p)
-{
-    if (ctx->opt.lighting_wpb == 12) /* UR_OPT_LIGHTING_WAVES_PER_WG */ return launch_stream_wpb<MODE, SHADOWS, IRR_LDS, 12>(ctx, p);
-    return launch_stream_wpb<MODE, SHADOWS, IRR_LDS, 16>(ctx, p);
-}
+typedef void (*kernel_t)(LightingParams, ur::HzbTail, HzbRide);
+#define UR_WAVES(M, S, I) lighting_stream_kernel<M, S, I, 12, true>, lighting_stream_kernel<M, S, I, 12, false>, lighting_stream_kernel<M, S, I, 16, true>, lighting_stream_kernel<M, S, I, 16, false>
+#define UR_MODE(M) UR_WAVES(M, true, true), UR_WAVES(M, true, false), UR_WAVES(M, false, true), UR_WAVES(M, false, false)
+// (listed in the order the unit has always instantiated them, which is the order of the kernels in the code object)
+const kernel_t kStreamKernels[32] = {UR_MODE(ur::UR_MODE_LIGHTING), UR_MODE(ur::UR_MODE_FUSED)}; // index bits, high to low: fused, no shadows, no irr_lds, 16 waves, not ride_all
+#undef UR_MODE
+#undef UR_WAVES
 
 } // namespace
 
-
 namespace ur {
 
-int launch_lighting(ur_ctx* ctx, const ur_scene_constants* S, const ur_sky_constants* K, const ur_half4* A, const ur_half4* B,
-                    const uint32_t* C, const float* depth, const ur_lighting_tables* T, ur_half4* hdr, uint32_t w, uint32_t h,
-                    uint32_t row0, uint32_t rows, int mode)
+int launch_lighting_stream(ur_ctx* ctx, const LightingParams& params, int mode, bool shadows, bool irr_lds)
 {
-    LightingParams p{};
-    p.W = w; p.H = h; p.row0 = row0; p.rows = rows;
-    p.invW2 = 2.0f / (float)w; p.invH2 = 2.0f / (float)h;
-    p.A = reinterpret_cast<const half4_t*>(A);
-    p.B = reinterpret_cast<const half4_t*>(B);
-    p.C = C; p.depth = depth;
-    p.hdr = reinterpret_cast<half4_t*>(hdr);
-    p.srgb = ctx->srgb_table;
-    bool shadows = false;
-    float ortho_err = 0.0f; // departure of (float3x3)ViewInverse from an orthonormal matrix
-    if (mode != UR_MODE_SKY) {
-        // the view matrix must be rigid: rows of (float3x3)ViewInverse orthonormal
-        const float* VI = S->ViewInverse;
-        for (int i = 0; i < 3; ++i)
-            for (int j = i; j < 3; ++j) {
-                const float d = VI[i * 4] * VI[j * 4] + VI[i * 4 + 1] * VI[j * 4 + 1] + VI[i * 4 + 2] * VI[j * 4 + 2];
-                ortho_err = std::fmax(ortho_err, std::fabs(d - (i == j ? 1.0f : 0.0f)));
-            }
-        // Every camera the reference builds is rigid with CameraPosition as its origin (RendererUtils.cpp: View from LookTo, its
-        // inverse, the same position). Anything else takes the per-tile kernel's literal world-space vectors.
-        float cam_err = 0.0f;
-        for (int j = 0; j < 3; ++j) {
-            p.VIt[j] = VI[12 + j]; p.camPos[j] = S->CameraPosition[j];
-            cam_err = std::fmax(cam_err, std::fabs(VI[12 + j] - S->CameraPosition[j]) / std::fmax(1.0f, std::fabs(VI[12 + j])));
-        }
-        p.general = (!(ortho_err <= 1e-3f) || !(cam_err <= 1e-5f)) ? 1u : 0u;
-        p.invP11 = 1.0f / S->Projection[0];
-        p.invP22 = 1.0f / S->Projection[5];
-        const float* V = S->View;
-        const float* LD = S->LightDirection;
-        float l[3];
-        for (int j = 0; j < 3; ++j) l[j] = (LD[0] * V[j] + LD[1] * V[4 + j]) + LD[2] * V[8 + j];
-        const float lr = 1.0f / std::sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
-        for (int j = 0; j < 3; ++j) p.L[j] = l[j] * lr;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) p.R[i * 3 + j] = VI[i * 4 + j];
-        float SM[16];
-        mat4_mul(S->ViewInverse, S->LightViewProjection, SM);
-        std::memcpy(p.SQ, SM, sizeof(p.SQ));
-        std::memcpy(p.ST, SM + 12, sizeof(p.ST));
-        for (int j = 0; j < 3; ++j) p.lightRGB[j] = S->LightIntensity * S->LightColor[j];
-        p.shadowStrength = S->ShadowStrength;
-        p.shadowBias = S->ShadowBias;
-        p.shadowW = S->ShadowMapSize[0]; p.shadowH = S->ShadowMapSize[1];
-        p.shadowWi = (int32_t)S->ShadowMapSize[0]; p.shadowHi = (int32_t)S->ShadowMapSize[1];
-        p.shadowTexelX = 1.0f / S->ShadowMapSize[0]; p.shadowTexelY = 1.0f / S->ShadowMapSize[1];
-        p.shadow = T->shadow_map;
-        shadows = p.shadowStrength > 0.0f;
-        p.shadowSmall = (shadows && (p.shadowWi < 3 || p.shadowHi < 3)) ? 1u : 0u; // per-tile kernel, every tap through the bordered PCF
-        if (shadows && (p.shadow == nullptr || p.shadowWi <= 0 || p.shadowHi <= 0)) {
-            set_error("ShadowStrength > 0 but no shadow map / ShadowMapSize");
-            return UR_EINVAL;
-        }
-        p.maxMip = std::fmax(0.0f, S->EnvMapMipCount - 1.0f);
-        p.envBase = T->env_base_size; p.envMips = T->env_mip_count;
-        if (p.envMips == 0 || p.envMips > 16 || p.envBase == 0 || T->env_cube == nullptr || T->brdf_lut_rg16 == nullptr ||
-            T->lut_width == 0 || T->lut_height == 0) {
-            set_error("bad lighting tables");
-            return UR_EINVAL;
-        }
-        if (T->env_cube_texels != (uint64_t)ur_env_cube_texels(p.envBase, p.envMips)) {
-            set_error("ur_lighting_tables.env_cube_texels = %llu, but this version's ur_stage_env_cube writes %llu texels for a %u^2 cube of %u mips: "
-                      "the buffer was sized or staged for another layout", (unsigned long long)T->env_cube_texels,
-                      (unsigned long long)ur_env_cube_texels(p.envBase, p.envMips), p.envBase, p.envMips);
-            return UR_EINVAL;
-        }
-        uint32_t off = 0;
-        for (uint32_t m = 0; m < p.envMips; ++m) {
-            p.envMipOffset[m] = off;
-            const uint32_t e = (p.envBase >> m > 1u ? p.envBase >> m : 1u) + 2u;
-            off += 6u * e * e;
-        }
-        {
-            const float l = std::fmin(std::fmax(p.maxMip, 0.0f), (float)(p.envMips - 1u));
-            const uint32_t m0 = (uint32_t)l, m1 = m0 + 1u < p.envMips ? m0 + 1u : p.envMips - 1u;
-            p.irrFrac = l - (float)m0;
-            p.irrOffset0 = p.envMipOffset[m0]; p.irrOffset1 = p.envMipOffset[m1];
-            p.irrN0 = p.envBase >> m0 > 1u ? p.envBase >> m0 : 1u;
-            p.irrN1 = p.envBase >> m1 > 1u ? p.envBase >> m1 : 1u;
-        }
-        p.env = reinterpret_cast<const half4_t*>(T->env_cube);
-        p.lut = reinterpret_cast<const uint32_t*>(T->brdf_lut_rg16);
-        p.lutW = T->lut_width; p.lutH = T->lut_height;
-    }
-    if (mode != UR_MODE_LIGHTING) {
-        for (int j = 0; j < 3; ++j)
-            for (int i = 0; i < 3; ++i) p.skyRot[j * 3 + i] = K->View[j * 4 + i];
-        p.skyInvP11 = 1.0f / K->Projection[0];
-        p.skyInvP22 = 1.0f / K->Projection[5];
-        p.skyNearOverR = K->Projection[14] / K->World[0];
-        const float* LD = K->LightDirection;
-        const float lr = 1.0f / std::sqrt((LD[0] * LD[0] + LD[1] * LD[1]) + LD[2] * LD[2]);
-        for (int j = 0; j < 3; ++j) p.sunDir[j] = LD[j] * lr;
-        const float viewHeight = std::fmax(0.0f, K->CameraPosition[1]);
-        const float rayleighDensity = std::exp(-viewHeight / 8000.0f), mieDensity = std::exp(-viewHeight / 1200.0f);
-        const float rayleighColor[3] = {0.650f, 0.570f, 0.475f};
-        const float g2 = 0.76f * 0.76f;
-        for (int j = 0; j < 3; ++j) {
-            p.skyScatterR[j] = rayleighColor[j] * rayleighDensity * (3.0f / (16.0f * 3.14159265f));
-            p.skyMie[j] = K->LightColor[j] * mieDensity * 0.8f * ((1.0f - g2) / (4.0f * 3.14159265f));
-        }
-        const float cosSunUp = p.sunDir[1];
-        p.sunAttenuation = std::fmin(std::fmax(std::exp(-std::fmax(0.0f, 1.0f - cosSunUp) * 2.0f), 0.0f), 1.0f);
-    }
-    if ((uint64_t)w * rows == 0) return UR_OK;
-    if ((uint64_t)w * rows >= (1ull << 29)) {
-        set_error("band of %u x %u pixels exceeds the 2^29-pixel limit of one launch", w, rows);
-        return UR_EUNSUPPORTED;
-    }
-    // ---- streaming kernel when the band is a whole number of 16-pixel tile columns; the per-tile kernel otherwise -----------
-    const int use_stream = ctx->opt.lighting_stream; // UR_OPT_LIGHTING_STREAM
-    bool streamed = false;
-    // (the streaming kernel addresses the staged cube's RGB row-pair section in fp32 BYTE offsets, which must stay below 2^24: base
-    // sizes up to 256; bigger cubes take the per-tile kernel)
-    uint64_t env_texels = 0;
-    if (mode != UR_MODE_SKY)
-        for (uint32_t m = 0; m < p.envMips; ++m) {
-            const uint64_t e = (uint64_t)std::max(1u, p.envBase >> m) + 2u;
-            env_texels += 6u * e * e * 8u + 6u * e * (e - 1u) * 12u;
-        }
-    const uint64_t n_tiles = (uint64_t)(w / 16u) * ((rows + 3u) / 4u);
-    const uint64_t magic_err = w >= 16u ? ((1ull << 32) / (w / 16u) + 1ull) * (w / 16u) - (1ull << 32) : 0;
-    // (the streaming kernel takes its dot products in world space: the rotation must be orthonormal to rounding; its tile DMA
-    // moves 16 bytes per lane: 16-byte-aligned band buffers)
-    const uintptr_t align_bits = reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C) |
-                                 reinterpret_cast<uintptr_t>(p.depth) | reinterpret_cast<uintptr_t>(p.hdr);
-    if (use_stream && mode != UR_MODE_SKY && (align_bits & 15u) == 0 && ortho_err <= 1e-5f && p.general == 0u && p.shadowSmall == 0u && w % 16u == 0 && w >= 32u /* the magic of one tile per row does not fit 32 bits */ && magic_err * n_tiles < (1ull << 32) && p.lutW == kLutW && p.lutH == kLutH && p.irrFrac == 0.0f && env_texels < (1ull << 24)) {
-        bool ok = true;
-        StreamHot& h = p.hot;
-        if (shadows) {
-            // orthographic light (BuildDirectionalLightViewProjection, RendererUtils.cpp:1117-1137): clip.w == 1, so
-            // su * W - 0.5, sv * H - 0.5 and depth - bias are affine in viewZ * (ra, rb, 1)
-            ok = p.SQ[3] == 0.0f && p.SQ[7] == 0.0f && p.SQ[11] == 0.0f && p.ST[3] == 1.0f;
-            const double hw = 0.5 * p.shadowW, hh = 0.5 * p.shadowH;
-            const double sc[3] = {hw, -hh, 1.0}; // clip -> (texel x, texel y, depth)
-            for (int k = 0; k < 3; ++k) {
-                // clip[k] = viewZ * (ra * SQ[k] + rb * SQ[4 + k] + SQ[8 + k]) + ST[k], ra = ndc.x / P11, rb = -ndc.y / P22
-                h.shA[k] = (float)(p.SQ[k] * sc[k] * p.invP11);
-                h.shB[k] = (float)(p.SQ[4 + k] * sc[k] * -(double)p.invP22);
-                h.shC[k] = (float)(p.SQ[8 + k] * sc[k]);
-            }
-            h.shT[0] = (float)(p.ST[0] * hw + hw - 0.5);
-            h.shT[1] = (float)(p.ST[1] * -hh + hh - 0.5);
-            h.shT[2] = p.ST[2] - p.shadowBias;
-            h.shadowXmax = p.shadowW - 0.5f;
-            h.shadowYmax = p.shadowH - 0.5f;
-            h.shadowWi = p.shadowWi; h.shadowHi = p.shadowHi;
-            h.shadowWm3 = (float)(p.shadowWi - 3); h.shadowHm3 = (float)(p.shadowHi - 3); h.shadowWf = (float)p.shadowWi;
-            h.shadowRowBytes = (uint32_t)p.shadowWi * 4u;
-            h.shadowStrength = p.shadowStrength;
-            h.shadowQuarterStrength = 0.25f * p.shadowStrength;
-            h.shadowOneMinusStrength = 1.0f - p.shadowStrength;
-            h.shadow = p.shadow;
-            ok = ok && (uint64_t)p.shadowWi * (uint64_t)p.shadowHi < (1ull << 24); // texel indices are computed in fp32 (exact below 2^24)
-        }
-        if (ok) {
-            h.W = p.W; h.rows = p.rows; h.row0 = p.row0;
-            h.invW2 = p.invW2; h.invH2 = p.invH2;
-            h.invP11 = p.invP11; h.nInvP22 = -p.invP22;
-            h.skyInvP11 = p.skyInvP11; h.nSkyInvP22 = -p.skyInvP22;
-            h.skyNearOverR2 = p.skyNearOverR * p.skyNearOverR;
-            h.maxMip = p.maxMip;
-            h.envMaxLevel = (float)(p.envMips - 1u);
-            const uint32_t iE = p.irrN0 + 2u;
-            h.irrN0 = p.irrN0; h.irrNf = (float)p.irrN0; h.irrEf = (float)iE; h.irrEEf = (float)(iE * iE);
-            if (p.irrN0 <= 2u) { h.irrEf = (float)(p.irrN0 + 1u); h.irrEEf = (float)((p.irrN0 + 1u) * (p.irrN0 + 1u)); } // LDS table of cells
-            h.irrOfff = (float)p.irrOffset0; h.irrRowBytes = iE * 8u;
-            h.env = p.env; h.hdr = p.hdr;
-            for (int k = 0; k < 9; ++k) h.R[k] = p.R[k];
-            for (int k = 0; k < 3; ++k) {
-                h.Lw[k] = (p.L[0] * p.R[k] + p.L[1] * p.R[3 + k]) + p.L[2] * p.R[6 + k]; // view-space L rotated like every other vector
-                h.WA[k] = p.invP11 * p.R[k];
-                h.WB[k] = -p.invP22 * p.R[3 + k];
-                h.WC[k] = p.R[6 + k];
-                h.lightRGB[k] = p.lightRGB[k];
-            }
-            {   // largest sphere depth of the frame: (Near/R) * |(vx, vy, 1)| at the ndc corner, with a margin of a few ulp
-                const double vx = p.skyInvP11, vy = p.skyInvP22;
-                h.skyDepthMax = (float)(p.skyNearOverR * std::sqrt(vx * vx + vy * vy + 1.0) * (1.0 + 1e-5));
-            }
-            {   // the cube's smallest mips whose RGB row-pair entries fit the workgroup's LDS copy (the shipped cube: mips 4..8)
-                uint32_t first = p.envMips;
-                uint64_t bytes = 0, bordered = 0, before = 0;
-                for (uint32_t m = p.envMips; m-- > 0;) {
-                    const uint64_t e = (uint64_t)std::max(1u, p.envBase >> m) + 2u, b = 6u * e * (e - 1u) * 12u;
-                    if (bytes + b > kLdsCubeBytes) break;
-                    bytes += b;
-                    first = m;
-                }
-                for (uint32_t m = 0; m < p.envMips; ++m) {
-                    const uint64_t e = (uint64_t)std::max(1u, p.envBase >> m) + 2u;
-                    bordered += 6u * e * e * 8u;
-                    if (m < first) before += 6u * e * (e - 1u) * 12u;
-                }
-                h.cubeLdsLevel = first < p.envMips ? (float)first : 16.0f;
-                h.cubeLdsBase = (uint32_t)(bordered + before);
-                h.cubeLdsBytes = first < p.envMips ? (uint32_t)bytes : 0u;
-            }
-            streamed = true;
-            const LightingParams& q = p;
-            const bool irr_lds = p.irrN0 <= 2u;
-            int rc;
-            if (mode == UR_MODE_LIGHTING) {
-                if (shadows) rc = irr_lds ? launch_stream<UR_MODE_LIGHTING, true, true>(ctx, q) : launch_stream<UR_MODE_LIGHTING, true, false>(ctx, q);
-                else rc = irr_lds ? launch_stream<UR_MODE_LIGHTING, false, true>(ctx, q) : launch_stream<UR_MODE_LIGHTING, false, false>(ctx, q);
-            } else {
-                if (shadows) rc = irr_lds ? launch_stream<UR_MODE_FUSED, true, true>(ctx, q) : launch_stream<UR_MODE_FUSED, true, false>(ctx, q);
-                else rc = irr_lds ? launch_stream<UR_MODE_FUSED, false, true>(ctx, q) : launch_stream<UR_MODE_FUSED, false, false>(ctx, q);
-            }
-            if (rc != UR_OK) return rc;
-        }
-    }
-    if (!streamed) {
-        // the per-tile kernel cannot carry a held-back HZB tail: it goes out on its own, in front (ur_defer_hzb_tail's contract:
-        // every Lighting launch on the context completes the chain)
+    const uint32_t wpb = ctx->opt.lighting_wpb == 12 ? 12u : 16u; // UR_OPT_LIGHTING_WAVES_PER_WG
+    const ur_ctx::Options& o = ctx->opt;
+    const StreamPlan s = plan_stream({ctx->cu_count, o.leave_cus, o.ride_walkers, o.balance, o.balance_pool_16ths, o.balance_chunk_shift, o.debug_hzb_ride_stall,
+                                      params.W, params.rows, wpb, ctx->hzb_tail_pending, ctx->hzb_wide_pending, ctx->pending_wide_grid_x,
+                                      ctx->pending_wide_grid_y, ctx->claim_words != nullptr ? kClaimWords : 0u});
+    LightingParams p = params; // the tile walk is filled in here
+    p.timeline = next_timeline_pair(ctx);
+    StreamHot& h = p.hot;
+    h.tilesX = s.tilesX; h.numTiles = s.numTiles; h.tilesXMagic = s.tilesXMagic; h.groups = s.groups; h.staticClaims = s.staticClaims;
+    p.bal = Balance{};
+    if (s.poolChunks != 0u) p.bal = Balance{s.poolChunks, s.staticTiles, s.dynShift, s.lookahead, s.poolMagic, ctx->claim_words, ctx->claim_timed_out_dev};
+    // what the plan consumes of the context's held-back HZB chain
+    HzbTail tail{};
+    HzbRide ride{};
+    if (s.carry_tail) { tail = ctx->pending_tail; ctx->hzb_tail_pending = false; }
+    if (s.rides) {
+        ride.d = ctx->pending_wide;
+        ride.grid_x = s.ride_grid_x; ride.pieces = s.ride_pieces; ride.walkers = s.ride_walkers; ride.spin_limit = s.ride_spin_limit;
+        if (s.carry_tail) { ride.done = ctx->hzb_done; ride.timed_out = ctx->hzb_timed_out_dev; }
+        ctx->hzb_wide_pending = false;
+    } else if (s.flush_first) { // cannot ride (12-wave build, tiny device): the ordinary launches, in front
         const int frc = flush_hzb_tail(ctx);
         if (frc != UR_OK) return frc;
-        switch (mode) {
-        case UR_MODE_LIGHTING:
-            if (shadows) launch_tiled<UR_MODE_LIGHTING, true>(ctx, p); else launch_tiled<UR_MODE_LIGHTING, false>(ctx, p);
-            break;
-        case UR_MODE_SKY: launch_tiled<UR_MODE_SKY, false>(ctx, p); break;
-        default:
-            if (shadows) launch_tiled<UR_MODE_FUSED, true>(ctx, p); else launch_tiled<UR_MODE_FUSED, false>(ctx, p);
-            break;
-        }
     }
-    UR_HIP_TRY(hipGetLastError());
+    ride.want = s.ride_want;
+    const bool ride_all = ride.pieces != 0u && ride.walkers > 1u;
+    const uint32_t form = (mode == UR_MODE_FUSED ? 16u : 0u) | (shadows ? 0u : 8u) | (irr_lds ? 0u : 4u) | (wpb == 16u ? 2u : 0u) | (ride_all ? 0u : 1u);
+    const kernel_t kern = kStreamKernels[form];
+    const uint32_t lds = kLdsTiles + wpb * 2u * kTileBytes + kLdsCubeBytes;
+    // MaxDynamicSharedMemorySize is a per-DEVICE attribute of the function: one flag per instantiation and device
+    static bool attr_set[32][64] = {};
+    const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : -1;
+    if (dev < 0 || !attr_set[form][dev]) {
+        UR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0) attr_set[form][dev] = true;
+    }
+    std::memcpy(ctx->last_schedule, s.reported, sizeof(ctx->last_schedule));
+    launch_timed(ctx, kern, dim3(s.groups + (s.carry_tail ? 1u : 0u)), dim3(64 * wpb), lds, p, tail, ride);
     return UR_OK;
 }
 

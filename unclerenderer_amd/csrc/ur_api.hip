@@ -1,5 +1,5 @@
 // C-ABI of include/ur_hotpath.h: argument validation, context/workspace management, setup-time staging.
-// The kernels live in hzb.hip, cull.hip and lighting.hip.
+// The kernels live in hzb.hip, cull.hip, lighting.hip and lighting_tiled.hip; Lighting's host side in lighting_host.hip and lighting_plan.cpp.
 
 #include <dlfcn.h>
 
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ur_internal.h"
+#include "lighting_plan.h"
 
 #include "../../include/ur_host.h"
 
@@ -540,30 +541,24 @@ int ur_build_hzb_tail(ur_ctx* ctx, float* hzb_base, const ur_mip_desc* mips, uin
 
 size_t ur_env_cube_texels(uint32_t base_size, uint32_t mip_count)
 {
-    if (base_size == 0 || mip_count == 0 || mip_count > 16) return 0;
-    size_t n = 0;
-    for (uint32_t m = 0; m < mip_count; ++m) {
-        const size_t e = (base_size >> m > 1u ? base_size >> m : 1u) + 2u;
-        n += 6u * e * e;        // the bordered faces
-        n += 9u * (e - 1u) * e; // the same texels once more as RGB row pairs: 6 (e - 1) e entries of 12 bytes = 9 (e - 1) e half4 units
-    }
-    return n;
+    return (size_t)ur::cube_layout(base_size, mip_count).texels; // (0: refused)
 }
 
 int ur_stage_env_cube(ur_ctx* ctx, const ur_half4* src, uint32_t base, uint32_t mip_count, ur_half4* dst_device)
 {
-    if (!ctx || !src || !dst_device || ur_env_cube_texels(base, mip_count) == 0) { set_error("ur_stage_env_cube: bad argument"); return UR_EINVAL; }
+    const ur::CubeLayout L = ur::cube_layout(base, mip_count); // csrc/lighting_plan.h: the two sections written below
+    if (!ctx || !src || !dst_device || L.texels == 0) { set_error("ur_stage_env_cube: bad argument"); return UR_EINVAL; }
     std::vector<size_t> mip_off(mip_count);
     size_t face_stride = 0;
     for (uint32_t m = 0; m < mip_count; ++m) {
         mip_off[m] = face_stride;
-        const size_t n = base >> m > 1u ? base >> m : 1u;
+        const size_t n = L.size(m);
         face_stride += n * n;
     }
-    std::vector<ur_half4> out(ur_env_cube_texels(base, mip_count));
-    size_t off = 0;
+    std::vector<ur_half4> out(L.texels);
     for (uint32_t m = 0; m < mip_count; ++m) {
-        const int N = (int)(base >> m > 1u ? base >> m : 1u), E = N + 2;
+        const int N = (int)L.size(m), E = N + 2;
+        const size_t off = L.bordered[m];
         for (int f = 0; f < 6; ++f)
             for (int j = -1; j <= N; ++j)
                 for (int i = -1; i <= N; ++i) {
@@ -571,7 +566,6 @@ int ur_stage_env_cube(ur_ctx* ctx, const ur_half4* src, uint32_t base, uint32_t 
                     resolve_border(N, f, i, j, sf, si, sj);
                     out[off + ((size_t)f * E + (j + 1)) * E + (i + 1)] = src[(size_t)sf * face_stride + mip_off[m] + (size_t)sj * N + si];
                 }
-        off += (size_t)6 * E * E;
     }
     // Second section, behind all bordered mips: every mip once more as RGB ROW PAIRS. Entry (f, j, i), j in [0, E-2], is the 12 bytes
     // {R G B of texel (i, j), R G B of texel (i, j + 1)} of the bordered face (the alpha channel is never sampled:
@@ -579,10 +573,10 @@ int ur_stage_env_cube(ur_ctx* ctx, const ur_half4* src, uint32_t base, uint32_t 
     // bytes at entry ((f (E-1) + j) E + i) - two 12-byte loads that almost always fall into ONE cache line where the bordered
     // layout's two rows are two lines and two 16-byte loads. The streaming lighting kernel gathers its prefiltered taps here.
     {
-        uint16_t* rgb = reinterpret_cast<uint16_t*>(out.data() + off);
-        size_t boff = 0, e = 0;
         for (uint32_t m = 0; m < mip_count; ++m) {
-            const size_t E = (size_t)(base >> m > 1u ? base >> m : 1u) + 2u;
+            const size_t E = L.edge[m], boff = L.bordered[m];
+            uint16_t* rgb = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(out.data()) + L.pairs[m]);
+            size_t e = 0;
             for (size_t f = 0; f < 6; ++f)
                 for (size_t j = 0; j + 1 < E; ++j)
                     for (size_t i = 0; i < E; ++i) {
@@ -591,7 +585,6 @@ int ur_stage_env_cube(ur_ctx* ctx, const ur_half4* src, uint32_t base, uint32_t 
                         rgb[e++] = t0.x; rgb[e++] = t0.y; rgb[e++] = t0.z;
                         rgb[e++] = t1.x; rgb[e++] = t1.y; rgb[e++] = t1.z;
                     }
-            boff += 6u * E * E;
         }
     }
     UR_HIP_TRY(hipMemcpy(dst_device, out.data(), out.size() * sizeof(ur_half4), hipMemcpyHostToDevice));

@@ -74,9 +74,9 @@ struct ur_ctx {
     } opt;
     // Inter-workgroup tile claims of the streaming lighting kernel (UR_OPT_LIGHTING_BALANCE): kClaimWords words, each on a 128-byte
     // line of its own, + the count of workgroups that have made their last claim. All zero between launches: the workgroup whose
-    // last claim comes last zeroes them (csrc/lighting.hip).
+    // last claim comes last zeroes them (csrc/lighting.hip; the split is planned in csrc/lighting_plan.cpp).
     uint32_t* claim_words = nullptr;
-    uint32_t last_schedule[8] = {}; // ur_debug_lighting_schedule: the tile schedule of the context's last streaming Lighting launch
+    uint32_t last_schedule[8] = {}; // ur_debug_lighting_schedule: the tile schedule of the context's last streaming Lighting launch (StreamPlan::reported)
     // host-visible (mapped, coherent) word beside hzb_timed_out: a wave of a balanced launch gave up waiting for a claim
     volatile uint32_t* claim_timed_out = nullptr;
     uint32_t* claim_timed_out_dev = nullptr;
