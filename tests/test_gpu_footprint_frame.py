@@ -1,4 +1,4 @@
-"""Footprints of GpuDebugPrint (csrc/debug_print.hip), the row all-gather and the whole frame (csrc/frame/HotPathRenderer.cpp) under the
+"""Footprints of GpuDebugPrint (csrc/debug_print.hip), the row all-gather and the whole frame (csrc/frame/) under the
 rules of tests/footprint.py: every resource a frame is given sits between guards, over two frames so that the HZB, the luminance pair
 and the TemporalAA history are live. Nothing here judges a value."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The render-graph-driven frame on the GPU (csrc/frame/HotPathRenderer.cpp through include/ur_frame.h): pass order,
+"""The render-graph-driven frame on the GPU (csrc/frame/ through include/ur_frame.h): pass order,
 pass culling, the bHZBReady hand-over between frames (DeferredRenderer.cpp:519,1210) and parity of the outputs."""
 import numpy as np
 import pytest

@@ -2,6 +2,8 @@
 reference has only the D3D12 debug layer, Source/RHI/DX12Device.cpp:82-91). CPU box only: GPU ASan is not available.
 
   * the render graph (csrc/rg/RenderGraph.cpp) compiled as host C++ together with its semantics test;
+  * the frame units (csrc/frame/*.cpp) on the render graph, driven by tests/cpp/frame_trace.cpp through its curated cases, every entry point
+    they link against a recording stand-in (tests/test_frame_trace_cpp.py): a stand-alone program, no HIP runtime, nothing loaded into Python;
   * the host-side product code (DDS/BC6H decode, scene extraction, host constant math, the Lighting launch's planner) and the oracle, driven by
     tests/cpp/sanitize_main.cpp over the shipped fixtures, random inputs and hostile inputs in exact-size heap buffers.
 Any sanitizer report aborts the binary (-fno-sanitize-recover) and fails the test."""
@@ -46,4 +48,14 @@ def test_rendergraph_under_asan_ubsan():
                  ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"])
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=ENV)
     assert r.returncode == 0 and "OK rendergraph tests passed" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or not Path("/opt/rocm/include/hip/hip_runtime.h").exists(), reason="needs g++ and the HIP headers")
+def test_frame_units_under_asan_ubsan():
+    """The frame's host code (plan, pass wiring, post chain, C face, lighting timer) instrumented, over the curated list of the frame trace."""
+    from tests.test_frame_trace_cpp import FRAME_SOURCES, HIP_FLAGS
+    exe = _build(OUT / "frame_trace_asan", [ROOT / "tests" / "cpp" / "frame_trace.cpp"] + FRAME_SOURCES, HIP_FLAGS)
+    r = subprocess.run([str(exe), "--check-curated", str(ROOT / "tests" / "golden" / "frame_traces.txt")], capture_output=True, text=True, timeout=300, env=ENV)
+    assert r.returncode == 0 and "OK frame trace: 54 curated cases" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -51,7 +51,11 @@ SOURCES = [
     ("lighting_plan.cpp", ["-x", "hip"] + EXACT),
     ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),
+    ("frame/FramePlan.cpp", ["-x", "hip"]),
     ("frame/HotPathRenderer.cpp", ["-x", "hip"]),
+    ("frame/PostPasses.cpp", ["-x", "hip"]),
+    ("frame/LightingTimer.cpp", ["-x", "hip"]),
+    ("frame/FrameApi.cpp", ["-x", "hip"]),
 ]
 
 

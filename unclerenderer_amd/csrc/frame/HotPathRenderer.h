@@ -20,6 +20,7 @@
 #include "../../../include/ur_hotpath.h"
 #include "../../../include/ur_raster.h"
 #include "../rg/RenderGraph.h"
+#include "FramePlan.h"
 
 // Device buffers owned by the caller (the renderer that rasterised the G-buffer). States mirror the variables the
 // reference keeps next to each resource (DepthBufferState, GBufferStates[], HZBState, LightingBufferState, ...).
@@ -112,41 +113,22 @@ struct FHotPathFrameConstants
     float TaaHistoryWeight = 0.9f;                                               // RendererConfig.h:34
 };
 
-struct FHotPathOptions
-{
-    bool bEnableIndirectDraw = true;  // RendererConfig IndirectDraw
-    bool bHZBEnabled = true;
-    bool bShardHZB = false;           // several ranks: build only this rank's pieces of mips 0..4 (the caller gathers and runs the tail)
-    bool bDoDepthPrepass = true;      // HZB is only built when the depth prepass ran (:996)
-    bool bRenderShadows = true;
-    bool bSkyEnabled = true;
-    bool bFuseLightingAndSky = false; // MI355X fast path: one pass, same result as Lighting followed by Sky
-    bool bTonemap = false;            // next row: Tonemap pass after Sky (TAA off)
-    bool bAutoExposure = false;       // with bTonemap: AutoExposure pass before Tonemap (bAutoExposureEnabled)
-    bool bCas = false;                // with bTonemap: CAS pass after Tonemap (bEnableCas)
-    bool bFuseTonemapCas = false;     // MI355X fast path: Tonemap + CAS in one launch (ur_tonemap_cas), CAS pass culled
-    bool bTaa = false;                // with bTonemap and a history ring: TemporalAA pass after Sky (bEnableTAA); Tonemap reads its output
-    bool bFuseTaaTonemap = false;     // with bTaa: TemporalAA + Tonemap in one launch (ur_temporal_aa_tonemap), TemporalAA pass culled
-    bool bPostExchange = false;       // row bands: with AutoExposure / CAS, end the frame with the "Post Record" pass; FinishPost runs the post passes
-    bool bTaaBand = false;            // with bTaa and bPostExchange: TemporalAA on the band too (the TAA record beside the post record); the exchange is then active without AutoExposure / CAS as well
-    bool bDebugPrint = false;         // with bTonemap, CullStats and a text buffer: reset ahead of the cull, DebugPrintEnabled, and the last pass "GpuDebugPrint" (bEnableGpuDebugPrint)
-    bool bAsyncCompute = false;       // MI355X: GPU Culling + Build HZB on the async-compute stream, overlapping Lighting
-    bool bTimeLighting = false;       // HIP event pair around the Lighting pass only (bench roofline leg), see SetLightingTimer
-    bool bGpuTiming = false;
-    bool bGraphDump = false;
-    bool bBarrierLogs = false;
-};
-
 class FHotPathRenderer
 {
 public:
     FHotPathRenderer(FHIPDevice* InDevice) : Device(InDevice) {}
 
+    // What a frame of these resources and options does (FramePlan.h), given what the renderer carries over from the last one.
+    FFramePlan PlanFrame(const FHotPathResources& Res, const FHotPathOptions& Options, int WorldSize) const;
     // Builds a fresh graph, adds the passes in the reference's order and executes it. Returns UR_OK or the first
     // error a pass reported. bHZBReady carries over between frames exactly like FDeferredRenderer::bHZBReady.
-    int RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants, const FHotPathOptions& Options);
-    // The second half of a frame rendered with bPostExchange (and AutoExposure, CAS or bTaaBand): [TemporalAA,] AutoExposure, Tonemap and
-    // CAS on the band, from the gathered records (Res.PostRecords, Res.TaaRecords), with the frame's constants and options. UR_EINVAL if
+    int RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants, const FFramePlan& FramePlan);
+    int RenderFrame(FHIPCommandContext& Cmd, FHotPathResources& Res, const FHotPathFrameConstants& Constants, const FHotPathOptions& Options)
+    {
+        return RenderFrame(Cmd, Res, Constants, PlanFrame(Res, Options, Cmd.GetWorldSize()));
+    }
+    // The second half of a frame whose plan ends at "Post Record" (bPostExchange with AutoExposure, CAS or bTaaBand): [TemporalAA,] AutoExposure,
+    // Tonemap and CAS on the band, from the gathered records (Res.PostRecords, Res.TaaRecords), with the frame's constants and plan. UR_EINVAL if
     // nothing is pending. A TemporalAA frame's history bookkeeping (EndTaaHistory) happens here, when the image has been written.
     int FinishPost(FHIPCommandContext& Cmd, FHotPathResources& Res);
     bool IsPostPending() const { return bPostPending; }
@@ -166,14 +148,18 @@ public:
     const std::vector<FRenderGraph::FPassReport>& GetLastReport() const { return LastReport; }
 
 private:
-    void AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants,
-                       const FHotPathOptions& Options, uint32 RecordRanks, FRGResourceHandle DebugStatsHandle, FRGResourceHandle DebugBufferHandle);
-    static bool IsDebugPrintActive(const FHotPathResources& Res, const FHotPathOptions& Options)
-    {
-        return Options.bDebugPrint && Options.bTonemap && Res.TonemapBand && Res.CullStats && Res.DebugPrintBuffer;
-    }
-    void EndPostHistory(bool bAutoExposure);
-    void EndTaaHistory(bool bTaaActive, uint32 WriteIndex, uint32 SlotCount);
+    struct FDebugPrintHandles { FRGResourceHandle Stats, Buffer; }; // null without GpuDebugPrint
+    // PostPasses.cpp: the post chain of the frame's plan, on the whole frame (RenderFrame) or on the band from the records (FinishPost)
+    void AddPostRecordPass(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res);
+    void AddPostPasses(FRenderGraph& Graph, FRGResourceHandle LightingHandle, FHotPathResources& Res, const FHotPathFrameConstants& Constants, FDebugPrintHandles DebugPrint);
+    void EndPostHistory();
+    void EndTaaHistory(bool bTaaWritten, uint32 SlotCount);
+    // what both halves of a frame set up alike
+    void ConfigureGraph(FRenderGraph& Graph) const;
+    FDebugPrintHandles ImportDebugPrint(FRenderGraph& Graph, FHotPathResources& Res) const;
+    FRGResourceHandle ImportTaaHistory(FRenderGraph& Graph, FHotPathResources& Res, uint32 Index) const;
+    // The frame returns the first error a pass reported; the passes behind it still run.
+    void RecordPassError(int rc) { if (rc != UR_OK && PassError == UR_OK) PassError = rc; }
 
     FHIPDevice* Device = nullptr;
     bool bHZBReady = false;
@@ -181,10 +167,10 @@ private:
     uint32 LuminanceWriteIndex = 0;
     std::vector<bool> TaaHistoryValid; // one per ring image
     uint32 TaaSampleIndex = 0;
-    struct FTaaFrame { bool bActive = false, bFuseTonemap = false; FTaaSlots Slots; } TaaFrame; // this frame's TemporalAA, for AddPostPasses
-    bool bPostPending = false;        // RenderFrame stopped at "Post Record"; FinishPost runs the rest with these
+    FFramePlan Plan;                   // of the frame being rendered; kept for FinishPost while its post passes are pending
+    FTaaSlots TaaSlots;                // that frame's TemporalAA slots (Plan.Taa != Off)
+    bool bPostPending = false;         // RenderFrame stopped at "Post Record"; FinishPost runs the rest with the plan and these
     FHotPathFrameConstants PendingConstants;
-    FHotPathOptions PendingOptions;
     int PassError = 0;
     std::vector<FRenderGraph::FPassReport> LastReport;
     std::function<void(hipStream_t, bool)> LightingTimer;

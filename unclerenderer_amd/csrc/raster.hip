@@ -546,7 +546,7 @@ int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster
 
 } // namespace
 
-// ---- what the direct calls and the frame's setters (frame/HotPathRenderer.cpp) share (ur_internal.h); `who` goes into the error text ----
+// ---- what the direct calls and the frame's setters (frame/FrameApi.cpp) share (ur_checks.h); `who` goes into the error text ----
 int ur::check_raster_draws(const char* who, const ur_raster_draws& draws, const void* target, const char* target_name, const void* stats)
 {
     if (!target) { set_error("%s: null %s", who, target_name); return UR_EINVAL; }

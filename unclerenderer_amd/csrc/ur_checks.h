@@ -1,0 +1,37 @@
+// The host-only view of the internals: what host callers outside ur_api.hip (the frame units, csrc/frame/) need of them. No device code
+// and nothing of ur_ctx's layout: a plain C++ compiler takes it. ur_internal.h includes it; the definitions stay where they were
+// (ur_api.hip, cull_views.hip, raster.hip, gbuffer_resolve.hip). Not installed.
+#pragma once
+
+#include <cstdint>
+
+#include "../../include/ur_hotpath.h"
+#include "../../include/ur_raster.h"
+
+namespace ur {
+
+void set_error(const char* fmt, ...);
+
+// ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
+int check_cull_views(const ur_cull_view* views, uint32_t view_count);
+// The raster passes: one set of checks for the direct calls and the frame's setters; `who`, the entry point called, goes into the error text.
+// Where the command slots live: the ranges' commands if ranges are set, else the draws' own
+inline const void* raster_commands(const ur_raster_draws& draws) { return draws.ranges ? draws.ranges->commands : draws.commands; }
+// (raster.hip) `target` not null; a list has both pointers; no list beside ranges; ranges whole; commands (unless command_count == 0) 16-byte, the rest 4-byte aligned
+int check_raster_draws(const char* who, const ur_raster_draws& draws, const void* target, const char* target_name, const void* stats);
+// ... behind what a direct call adds: the context, the matrices (ShadowMap passes its one twice), draws, w and h
+int check_raster_call(const char* who, const ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, const void* target, const char* target_name,
+                      uint32_t w, uint32_t h, const void* stats);
+inline int check_depth_flags(const char* who, uint32_t flags)
+{
+    if (flags & ~UR_DEPTH_QUANTIZE_D24) { set_error("%s: unknown flag bits 0x%x", who, flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
+    return UR_OK;
+}
+int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_resolve.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
+inline int check_key_triangle_bits(const char* who, uint32_t bits)
+{
+    if (bits > 31u) { set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, bits); return UR_EINVAL; }
+    return UR_OK;
+}
+
+} // namespace ur

@@ -85,9 +85,9 @@ struct ur_ctx {
     uint32_t raster_queue_cap = 0;
 };
 
-namespace ur {
+#include "ur_checks.h" // ur::set_error, ur::raster_commands and the check_* functions: what host callers outside ur_api.hip need
 
-void set_error(const char* fmt, ...);
+namespace ur {
 
 #define UR_HIP_TRY(expr)                                                                          \
     do {                                                                                          \
@@ -113,27 +113,6 @@ int launch_cull_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* b
                       const ur_mip_desc* mips, void* indirect_args, uint32_t* stats2, uint32_t* visible_idx,
                       uint32_t* visible_count, uint32_t index_base, const ur_draw_ranges* draws, const ur_cull_view* views,
                       uint32_t view_count);
-// ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
-int check_cull_views(const ur_cull_view* views, uint32_t view_count);
-// The raster passes: one set of checks for the direct calls and the frame's setters; `who`, the entry point called, goes into the error text.
-// Where the command slots live: the ranges' commands if ranges are set, else the draws' own
-inline const void* raster_commands(const ur_raster_draws& draws) { return draws.ranges ? draws.ranges->commands : draws.commands; }
-// (raster.hip) `target` not null; a list has both pointers; no list beside ranges; ranges whole; commands (unless command_count == 0) 16-byte, the rest 4-byte aligned
-int check_raster_draws(const char* who, const ur_raster_draws& draws, const void* target, const char* target_name, const void* stats);
-// ... behind what a direct call adds: the context, the matrices (ShadowMap passes its one twice), draws, w and h
-int check_raster_call(const char* who, const ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, const void* target, const char* target_name,
-                      uint32_t w, uint32_t h, const void* stats);
-inline int check_depth_flags(const char* who, uint32_t flags)
-{
-    if (flags & ~UR_DEPTH_QUANTIZE_D24) { set_error("%s: unknown flag bits 0x%x", who, flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
-    return UR_OK;
-}
-int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_resolve.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
-inline int check_key_triangle_bits(const char* who, uint32_t bits)
-{
-    if (bits > 31u) { set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, bits); return UR_EINVAL; }
-    return UR_OK;
-}
 // GBuffer's raster (UR_GBUFFER_PART_RASTER): clears the key image of the band [row0, row0 + rows) and raises it to the winning keys
 int launch_visibility_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, uint32_t* keys, uint32_t w,
                              uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats);
