@@ -3,6 +3,7 @@
 
 #include "HotPathRenderer.h"
 
+#include "../post_records.h"
 #include "../ur_checks.h"
 
 FRGResourceHandle FHotPathRenderer::ImportTaaHistory(FRenderGraph& Graph, FHotPathResources& Res, uint32 Index) const
@@ -23,11 +24,11 @@ void FHotPathRenderer::AddPostRecordPass(FRenderGraph& Graph, FRGResourceHandle 
     FRGResourceHandle TaaRecordHandle, TaaReadHandle;
     if (Plan.TaaOnBand()) {
         TaaRecordHandle = Graph.ImportTexture("TaaRecord", Res.TaaRecord, &Res.TaaRecordState,
-                                              {static_cast<uint32>(ur_taa_record_bytes(Res.Width) / 8u), 1, RG_FORMAT_R16G16B16A16_FLOAT});
+                                              {static_cast<uint32>(ur_records::taa_texels(Res.Width)), 1, RG_FORMAT_R16G16B16A16_FLOAT});
         if (Taa.bUseHistory) TaaReadHandle = ImportTaaHistory(Graph, Res, Taa.Read);
     }
     const FRGResourceHandle RecordHandle = Graph.ImportTexture("PostRecord", Res.PostRecord, &Res.PostRecordState,
-                                                               {static_cast<uint32>(ur_post_record_bytes(Res.Width) / 8u), 1, RG_FORMAT_R16G16B16A16_FLOAT});
+                                                               {static_cast<uint32>(ur_records::post_texels(Res.Width)), 1, RG_FORMAT_R16G16B16A16_FLOAT});
     Graph.AddPass<FPostRecordPassData>("Post Record", [&](FPostRecordPassData& Data, FRGPassBuilder& Builder)
     {
         Data.TaaUseHistory = Taa.bUseHistory ? 1u : 0u;
@@ -115,10 +116,15 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
     const uint32 RecordRanks = Plan.RecordRanks;
     const uint64 RecordBytes = ur_post_record_bytes(Res.Width);
     const uint8_t* Records = static_cast<const uint8_t*>(Res.PostRecords);
+    // row Row (a name of csrc/post_records.h: the layout ur_pack_post_record / ur_pack_taa_record wrote) of rank R's record, in place
+    namespace Rec = ur_records;
+    auto RecordRow = [&Res](const uint8_t* Recs, uint64 Bytes, uint32 R, uint32 Row) {
+        return reinterpret_cast<const ur_half4*>(Recs + R * Bytes + Rec::row_offset(Row, Res.Width));
+    };
     const uint32 Rank = bFromRecords ? Res.Row0 / Res.Rows : 0;
     // the neighbours' last / first HDR rows: the halo rows of CAS (none at the frame's top / bottom edge), and of TemporalAA on the band
-    const ur_half4* CurAbove = bFromRecords && Rank > 0 ? reinterpret_cast<const ur_half4*>(Records + (Rank - 1) * RecordBytes + 8ull * Res.Width) : nullptr;
-    const ur_half4* CurBelow = bFromRecords && Rank + 1 < RecordRanks ? reinterpret_cast<const ur_half4*>(Records + (Rank + 1) * RecordBytes) : nullptr;
+    const ur_half4* CurAbove = bFromRecords && Rank > 0 ? RecordRow(Records, RecordBytes, Rank - 1, Rec::kPostLastRow) : nullptr;
+    const ur_half4* CurBelow = bFromRecords && Rank + 1 < RecordRanks ? RecordRow(Records, RecordBytes, Rank + 1, Rec::kPostFirstRow) : nullptr;
     // TemporalAA on the band: behind it CAS's halo rows are the RESOLVED rows around the band, which the TemporalAA launch writes
     // from the neighbours' TAA records: above second_last_row / history_last_row, below second_row / history_first_row
     const uint64 TaaRecordBytes = ur_taa_record_bytes(Res.Width);
@@ -132,28 +138,28 @@ void FHotPathRenderer::AddPostPasses(FRenderGraph& Graph, FRGResourceHandle Ligh
         TaaRows.CurAbove = CurAbove;
         TaaRows.CurBelow = CurBelow;
         if (Plan.bTaaHaloRows && CurAbove) {
-            const uint8_t* N = TaaRecs + (Rank - 1) * TaaRecordBytes;
-            TaaRows.Above2 = reinterpret_cast<const ur_half4*>(N + 8ull * Res.Width);
-            if (TaaSlots.bUseHistory) TaaRows.HistAbove = reinterpret_cast<const ur_half4*>(N + 24ull * Res.Width);
+            TaaRows.Above2 = RecordRow(TaaRecs, TaaRecordBytes, Rank - 1, Rec::kTaaSecondLastRow);
+            if (TaaSlots.bUseHistory) TaaRows.HistAbove = RecordRow(TaaRecs, TaaRecordBytes, Rank - 1, Rec::kTaaHistLastRow);
             TaaRows.ResolvedAbove = Res.TaaHaloRows;
         }
         if (Plan.bTaaHaloRows && CurBelow) {
-            const uint8_t* N = TaaRecs + (Rank + 1) * TaaRecordBytes;
-            TaaRows.Below2 = reinterpret_cast<const ur_half4*>(N);
-            if (TaaSlots.bUseHistory) TaaRows.HistBelow = reinterpret_cast<const ur_half4*>(N + 16ull * Res.Width);
+            TaaRows.Below2 = RecordRow(TaaRecs, TaaRecordBytes, Rank + 1, Rec::kTaaSecondRow);
+            if (TaaSlots.bUseHistory) TaaRows.HistBelow = RecordRow(TaaRecs, TaaRecordBytes, Rank + 1, Rec::kTaaHistFirstRow);
             TaaRows.ResolvedBelow = Res.TaaHaloRows + Res.Width;
         }
     }
     const ur_half4* HaloAbove = Plan.CasHaloRows == ECasHaloRows::Resolved ? TaaRows.ResolvedAbove : CurAbove;
     const ur_half4* HaloBelow = Plan.CasHaloRows == ECasHaloRows::Resolved ? TaaRows.ResolvedBelow : CurBelow;
     const FRGResourceHandle TaaRecordsHandle = Plan.bTaaHaloRows
-        ? Graph.ImportTexture("TaaRecords", const_cast<void*>(Res.TaaRecords), &Res.TaaRecordsState, {static_cast<uint32>(TaaRecordBytes / 8u), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
+        ? Graph.ImportTexture("TaaRecords", const_cast<void*>(Res.TaaRecords), &Res.TaaRecordsState,
+                              {static_cast<uint32>(Rec::taa_texels(Res.Width)), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
         : FRGResourceHandle{};
     const FRGResourceHandle TaaHaloHandle = Plan.bTaaHaloRows
         ? Graph.ImportTexture("TaaHaloRows", Res.TaaHaloRows, &Res.TaaHaloRowsState, {Res.Width, 2, RG_FORMAT_R16G16B16A16_FLOAT})
         : FRGResourceHandle{};
     const FRGResourceHandle RecordsHandle = bFromRecords
-        ? Graph.ImportTexture("PostRecords", const_cast<void*>(Res.PostRecords), &Res.PostRecordsState, {static_cast<uint32>(RecordBytes / 8u), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
+        ? Graph.ImportTexture("PostRecords", const_cast<void*>(Res.PostRecords), &Res.PostRecordsState,
+                              {static_cast<uint32>(Rec::post_texels(Res.Width)), RecordRanks, RG_FORMAT_R16G16B16A16_FLOAT})
         : FRGResourceHandle{};
     FRGResourceHandle LuminanceHandles[2];
     if (Plan.AutoExposure.bExists) {

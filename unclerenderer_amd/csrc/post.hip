@@ -9,12 +9,14 @@
 // formula (not FidelityFX RCAS). The taps are exact texels: the pass samples at pixel centres with TexelDelta = (1/W, 1/H)
 // through a clamp sampler, so a tap is the neighbour texel, clamped at the image edges.
 //
-// Both CAS forms run one kernel, cas_strip_kernel below: a wave owns a 64 * PX-column strip of kRows output rows. It loads
-// the kRows + 2 input rows its taps need (rows clamped to the frame) and the texel left and right of the strip in each of
-// them in ONE load phase, converts each input row once to fp32 (R, G, B, luminance) and takes the horizontal neighbours
-// from the adjacent lanes (DPP wave shifts), the vertical ones from the rows kept in registers. No LDS, no barrier. In the
-// fused form an input row is HDR and is converted by the same tonemap_pixel as ur_tonemap (csrc/post_common.h) before
-// anything else: the bytes CAS sees are exactly ur_tonemap's, and the intermediate image is never written.
+// Every CAS form runs one body, cas_strip below (cas_strip_kernel on the full image, cas_halo_kernel on a row band with the two
+// rows around it): a wave owns a 64 * PX-column strip of kRows output rows. It loads the kRows + 2 input rows its taps need
+// (rows clamped to the frame) and the texel left and right of the strip in each of them in ONE load phase, written once for
+// every input kind and width (load_texels), converts each input row once to fp32 (R, G, B, luminance) and takes the horizontal
+// neighbours from the adjacent lanes (DPP wave shifts, csrc/ur_device.h), the vertical ones from the rows kept in registers.
+// No LDS, no barrier. Where an input row is HDR (every row of the fused form, the rows around the band of ur_cas_halo) it is
+// converted by the same tonemap_pixel as ur_tonemap (csrc/post_common.h) before anything else: the bytes CAS sees are exactly
+// ur_tonemap's, and the intermediate image is never written.
 // Bytes per output pixel: CAS 4 read + 4 written (8), fused 8 read + 4 written (12, against 8 + 4 + 4 + 4 = 20 for the two
 // launches); the two halo rows of a strip (2 / kRows more rows) are read again by the neighbouring strip's waves and,
 // in the fused form, tonemapped twice.
@@ -24,17 +26,22 @@
 #include "ur_internal.h"
 #include "ur_device.h"
 #include "post_common.h"
+#include "post_records.h"
+
+#include <type_traits>
 
 namespace {
 
 using ur_post::half4_t;
+using ur_post::u32x2_t;
+using ur_post::u32x4_t;
+using ur_post::as_half4;
 using ur_post::TonemapParams;
 using ur_post::tonemap_pixel;
 using ur_post::final_exposure;
 using ur_post::unorm8;
-
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+using namespace ur_records;
+using ur::overlaps;
 
 constexpr float kLumR = 0.2126f, kLumG = 0.7152f, kLumB = 0.0722f; // LuminanceWeights / LumCoeff of both shaders
 
@@ -116,10 +123,8 @@ __global__ __launch_bounds__(256) void auto_exposure_kernel(AeParams p)
     ae_body(p, [&](uint32_t, uint32_t x, uint32_t y) { return p.hdr[(size_t)y * p.W + x]; });
 }
 
-// ---- the post record of a row band (include/ur_hotpath.h, ur_post_record_bytes) -------------------------------------------
-// half4 slots: [0, W) the band's first row, [W, 2W) its last row, [2W, 2W + 1024) the 4 texels of each of the 256 taps (ae_tap) in
-// tap order. A tap texel is written by the band that holds its row, zero by every other band: equal bands, owner = y / (H / N).
-constexpr uint32_t kTapTexels = 1024u;
+// ---- the post record of a row band (include/ur_hotpath.h, ur_post_record_bytes; its layout: csrc/post_records.h) ----------
+// A tap texel (ae_tap) is written by the band that holds its row, zero by every other band: equal bands, owner = y / (H / N).
 
 struct PackParams {
     const half4_t* band; // rows [row0, row0 + rows) of the W x H frame
@@ -130,11 +135,13 @@ struct PackParams {
 __global__ __launch_bounds__(256) void post_record_kernel(PackParams p)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x, W = p.W;
-    if (j < 2u * W) {
-        p.record[j] = j < W ? p.band[j] : p.band[(size_t)(p.rows - 1u) * W + (j - W)];
+    if (j < kPostRows * W) { // the record's two rows
+        static_assert(kPostFirstRow == 0u && kPostLastRow == 1u && kPostRows == 2u, "the first row, then the last row");
+        const uint32_t last = kPostLastRow * W; // where the last row starts in the record
+        p.record[j] = j < last ? p.band[j] : p.band[(size_t)(p.rows - 1u) * W + (j - last)];
         return;
     }
-    const uint32_t s = j - 2u * W;
+    const uint32_t s = j - kPostRows * W;
     if (s >= kTapTexels) return;
     const uint32_t i = s >> 2, corner = s & 3u;
     const AeTap t = ae_tap(i & 15u, i >> 4, W, p.H, (float)W, (float)p.H); // InputSize == (W, H), as ur_auto_exposure requires
@@ -153,7 +160,7 @@ struct AeRecordsParams {
 // auto_exposure_kernel with every texel read from its owner's record
 __global__ __launch_bounds__(256) void ae_records_kernel(AeRecordsParams q)
 {
-    const uint32_t slot = 2u * q.ae.W + threadIdx.x * 4u;
+    const uint32_t slot = kPostRows * q.ae.W + threadIdx.x * 4u;
     ae_body(q.ae, [&](uint32_t corner, uint32_t, uint32_t y) { return q.records[(size_t)(y / q.band_rows) * q.record_texels + slot + corner]; });
 }
 
@@ -203,18 +210,17 @@ struct CasParams {
 
 constexpr int kRows = 8; // output rows per wave: kRows + 2 input rows in one load phase
 
-// DPP wave shifts (as in csrc/taa.hip): wave_shr:1 - lane l reads lane l - 1, lane 0 keeps `old`; wave_shl:1 - lane l reads
-// lane l + 1, lane 63 keeps `old`
-__device__ __forceinline__ float shr1(float old, float v)
+// a texel from the neighbouring lane (ur::wave_shr1 / wave_shl1: lane 0 / lane 63 keeps `old`, the texel beside the strip)
+__device__ __forceinline__ Px shr1(const Px& old, const Px& v)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, false));
+    auto s = [](float o, float x) { return __builtin_bit_cast(float, ur::wave_shr1(__builtin_bit_cast(uint32_t, o), __builtin_bit_cast(uint32_t, x))); };
+    return Px{s(old.r, v.r), s(old.g, v.g), s(old.b, v.b), s(old.l, v.l)};
 }
-__device__ __forceinline__ float shl1(float old, float v)
+__device__ __forceinline__ Px shl1(const Px& old, const Px& v)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
+    auto s = [](float o, float x) { return __builtin_bit_cast(float, ur::wave_shl1(__builtin_bit_cast(uint32_t, o), __builtin_bit_cast(uint32_t, x))); };
+    return Px{s(old.r, v.r), s(old.g, v.g), s(old.b, v.b), s(old.l, v.l)};
 }
-__device__ __forceinline__ Px shr1(const Px& old, const Px& v) { return Px{shr1(old.r, v.r), shr1(old.g, v.g), shr1(old.b, v.b), shr1(old.l, v.l)}; }
-__device__ __forceinline__ Px shl1(const Px& old, const Px& v) { return Px{shl1(old.r, v.r), shl1(old.g, v.g), shl1(old.b, v.b), shl1(old.l, v.l)}; }
 __device__ __forceinline__ Px readlane(const Px& v, int lane)
 {
     auto rl = [lane](float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane)); };
@@ -228,13 +234,12 @@ enum class In { Ldr, Hdr, LdrHdrHalo };
 // Where input row y (a frame row, already clamped to the frame) is. FrameRows: the full image (cas_strip_kernel). BandRows: a
 // band-local image and one row above and one below it (cas_halo_kernel), each its own pointer; a strip's rows are uniform per wave,
 // so the choice is scalar. Rows further out than the halo rows only feed output rows that are not stored: they read the halo row.
+// units<U, N>(y): the row as units U of N texels each (N = 2: W is even, so a row starts on a unit).
 struct FrameRows {
     const void* src;
     uint32_t W;
     __device__ __forceinline__ bool halo(uint32_t) const { return false; }
-    template <class T> __device__ __forceinline__ const T* row(uint32_t y) const { return static_cast<const T*>(src) + (size_t)y * W; }
-    template <class P> __device__ __forceinline__ const P* pairs(uint32_t y) const { return static_cast<const P*>(src) + (((size_t)y * W) >> 1); }
-    template <class T> __device__ __forceinline__ T texel(uint32_t y, uint32_t x) const { return static_cast<const T*>(src)[(size_t)y * W + x]; }
+    template <class U, int N> __device__ __forceinline__ const U* units(uint32_t y) const { return static_cast<const U*>(src) + ((size_t)y * W) / N; }
 };
 
 struct BandRows {
@@ -243,16 +248,46 @@ struct BandRows {
     const void* below; // row row0 + rows (null iff row0 + rows == H)
     uint32_t W, row0, rows;
     __device__ __forceinline__ bool halo(uint32_t y) const { return y < row0 || y - row0 >= rows; }
-    template <class T> __device__ __forceinline__ const T* row(uint32_t y) const
+    template <class U, int N> __device__ __forceinline__ const U* units(uint32_t y) const
     {
-        return y < row0 ? static_cast<const T*>(above) : y - row0 >= rows ? static_cast<const T*>(below) : static_cast<const T*>(band) + (size_t)(y - row0) * W;
+        return y < row0 ? static_cast<const U*>(above) : y - row0 >= rows ? static_cast<const U*>(below) : static_cast<const U*>(band) + ((size_t)(y - row0) * W) / N;
     }
-    template <class P> __device__ __forceinline__ const P* pairs(uint32_t y) const
-    {
-        return y < row0 ? static_cast<const P*>(above) : y - row0 >= rows ? static_cast<const P*>(below) : static_cast<const P*>(band) + (((size_t)(y - row0) * W) >> 1);
-    }
-    template <class T> __device__ __forceinline__ T texel(uint32_t y, uint32_t x) const { return row<T>(y)[x]; }
 };
+
+// ---- the one loader of every CAS form. N texels of an input row as loaded: N dwords of an RGBA8 row, 2N of an RGBA16F one.
+template <int DWORDS> using dwords_t = std::conditional_t<DWORDS == 1, uint32_t, std::conditional_t<DWORDS == 2, u32x2_t, u32x4_t>>;
+// ... kept as the wider of the kinds MODE can meet, RGBA8 texels in the low dwords
+template <In MODE, int N> using raw_t = dwords_t<MODE == In::Ldr ? N : 2 * N>;
+__device__ __forceinline__ u32x2_t widen(uint32_t l) { return u32x2_t{l, 0u}; }
+__device__ __forceinline__ u32x4_t widen(u32x2_t l) { return u32x4_t{l.x, l.y, 0u, 0u}; }
+__device__ __forceinline__ uint32_t dword(uint32_t v, int) { return v; }
+template <class V> __device__ __forceinline__ uint32_t dword(V v, int i) { return v[i]; }
+
+// Is input row y RGBA16F, to be tonemapped on the way in? Uniform per wave where y is.
+template <In MODE, class Rows>
+__device__ __forceinline__ bool hdr_row(const Rows& src, uint32_t y) { return MODE == In::Hdr || (MODE == In::LdrHdrHalo && src.halo(y)); }
+
+// Unit i of row y. own: a row only this strip reads, for which the source asks for a nontemporal load; a row around the band
+// (LdrHdrHalo) is a plain load whatever k. Written as a select of two loads, the request does not reach the gfx950 instructions: no
+// load of a CAS kernel carries `nt`, before this loader or with it (an open item in EXPERIMENTS.md; the form is kept as it was).
+template <In MODE, int N, class Rows>
+__device__ __forceinline__ raw_t<MODE, N> load_texels(const Rows& src, uint32_t y, size_t i, bool own)
+{
+    auto load = [](const auto* a, bool once) { return once ? __builtin_nontemporal_load(a) : *a; };
+    if constexpr (MODE == In::Ldr) return load(src.template units<dwords_t<N>, N>(y) + i, own);
+    else if (hdr_row<MODE>(src, y)) return load(src.template units<dwords_t<2 * N>, N>(y) + i, own && MODE == In::Hdr);
+    else return widen(load(src.template units<dwords_t<N>, N>(y) + i, own));
+}
+
+// Texel t of a loaded unit as the R8G8B8A8 CAS reads: an RGBA16F one through ur_tonemap's pixel
+template <In MODE, class Raw>
+__device__ __forceinline__ uint32_t rgba8(const TonemapParams& tm, float finalExposure, Raw v, bool hdr, int t)
+{
+    if constexpr (MODE != In::Ldr) {
+        if (hdr) return tonemap_pixel(tm, finalExposure, as_half4(u32x2_t{dword(v, 2 * t), dword(v, 2 * t + 1)}));
+    }
+    return dword(v, t);
+}
 
 // One strip of CAS output (see the file comment). PX: pixels per lane - 2 (even width; 16-B aligned HDR / 8-B aligned RGBA8 rows:
 // one 16- or 8-byte load and one 8-byte store per lane and row) or 1 (any width and alignment).
@@ -270,119 +305,28 @@ __device__ __forceinline__ void cas_strip(const CasParams& p, const Rows& src)
     const float finalExposure = MODE != In::Ldr ? final_exposure(p.tm) : 0.0f;
     // input row k (0 .. kRows + 1) = frame row row0 + rb0 - 1 + k, clamped (the taps' clamp at the top and bottom edges)
     auto frame_row = [&](int k) -> uint32_t { return (uint32_t)min(max((int)(p.row0 + rb0) - 1 + k, 0), maxy); };
-    auto interior = [&](int k) { return k >= 1 && k <= kRows; }; // the strip's own rows (nontemporal; its halo rows are other strips' own)
+    auto interior = [&](int k) { return k >= 1 && k <= kRows; }; // the strip's own rows (its halo rows are other strips' own): `own` of load_texels
 
     // ---- the load phase: kRows + 2 rows, and the texels left / right of the strip (lane j < kRows + 2: row j's left one,
     // lane 32 + j: its right one), all in flight before the first is used
     const uint32_t hx = lane < 32u ? (x0 == 0u ? 0u : x0 - 1u) : min(x0 + 64u * PX, maxx);
     const uint32_t hy = frame_row((int)min(lane & 31u, (uint32_t)kRows + 1u));
-    uint32_t halo;
+    const size_t unit = min(px0, maxx - (PX - 1u)) / PX; // the lane's PX texels of a row, clamped into the frame
+    const raw_t<MODE, 1> side = load_texels<MODE, 1>(src, hy, hx, false);
+    raw_t<MODE, PX> v[kRows + 2];
+#pragma unroll
+    for (int k = 0; k < kRows + 2; ++k) v[k] = load_texels<MODE, PX>(src, frame_row(k), unit, interior(k));
+    // ---- the convert phase: each texel once to RGBA8 (ur_tonemap's bytes) and on to fp32
+    const uint32_t halo = rgba8<MODE>(p.tm, finalExposure, side, hdr_row<MODE>(src, hy), 0);
     Px rowA[kRows + 2], rowB[kRows + 2]; // the lane's pixel(s) of each input row (rowB: PX == 2 only)
-    if constexpr (MODE == In::Hdr) {
-        const half4_t hh = src.template texel<half4_t>(hy, hx);
-        if constexpr (PX == 2) {
-            const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
-            u32x4_t v[kRows + 2];
 #pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const u32x4_t* a = src.template pairs<u32x4_t>(frame_row(k)) + pair;
-                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
-            }
-            halo = tonemap_pixel(p.tm, finalExposure, hh);
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                union { u32x2_t u; half4_t h; } a, b;
-                a.u = u32x2_t{v[k].x, v[k].y}; b.u = u32x2_t{v[k].z, v[k].w};
-                const uint32_t tb = tonemap_pixel(p.tm, finalExposure, b.h);
-                const uint32_t ta = beyond ? tb : tonemap_pixel(p.tm, finalExposure, a.h);
-                rowA[k] = unpack(ta); rowB[k] = unpack(tb);
-            }
-        } else {
-            const size_t x = min(px0, maxx);
-            half4_t v[kRows + 2];
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const half4_t* a = src.template row<half4_t>(frame_row(k)) + x;
-                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
-            }
-            halo = tonemap_pixel(p.tm, finalExposure, hh);
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) rowA[k] = unpack(tonemap_pixel(p.tm, finalExposure, v[k]));
-        }
-    } else if constexpr (MODE == In::Ldr) {
-        halo = src.template texel<uint32_t>(hy, hx);
-        if constexpr (PX == 2) {
-            const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
-            u32x2_t v[kRows + 2];
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const u32x2_t* a = src.template pairs<u32x2_t>(frame_row(k)) + pair;
-                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
-            }
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) { rowA[k] = unpack(beyond ? v[k].y : v[k].x); rowB[k] = unpack(v[k].y); }
-        } else {
-            const size_t x = min(px0, maxx);
-            uint32_t v[kRows + 2];
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const uint32_t* a = src.template row<uint32_t>(frame_row(k)) + x;
-                v[k] = interior(k) ? __builtin_nontemporal_load(a) : *a;
-            }
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) rowA[k] = unpack(v[k]);
-        }
-    } else { // LdrHdrHalo: per row (uniform) an RGBA8 band row or an RGBA16F halo row; the strip's side texel per lane
-        const bool hh = src.halo(hy);
-        halo = hh ? tonemap_pixel(p.tm, finalExposure, src.template texel<half4_t>(hy, hx)) : src.template texel<uint32_t>(hy, hx);
-        if constexpr (PX == 2) {
-            const size_t pair = (size_t)(min(px0, maxx - 1u) >> 1);
-            u32x4_t v[kRows + 2]; // RGBA8 rows in .xy
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const uint32_t y = frame_row(k);
-                if (src.halo(y)) {
-                    v[k] = src.template pairs<u32x4_t>(y)[pair];
-                } else {
-                    const u32x2_t* a = src.template pairs<u32x2_t>(y) + pair;
-                    const u32x2_t l = interior(k) ? __builtin_nontemporal_load(a) : *a;
-                    v[k] = u32x4_t{l.x, l.y, 0u, 0u};
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                uint32_t ta, tb;
-                if (src.halo(frame_row(k))) {
-                    union { u32x2_t u; half4_t h; } a, b;
-                    a.u = u32x2_t{v[k].x, v[k].y}; b.u = u32x2_t{v[k].z, v[k].w};
-                    tb = tonemap_pixel(p.tm, finalExposure, b.h);
-                    ta = beyond ? tb : tonemap_pixel(p.tm, finalExposure, a.h);
-                } else {
-                    tb = v[k].y;
-                    ta = beyond ? v[k].y : v[k].x;
-                }
-                rowA[k] = unpack(ta); rowB[k] = unpack(tb);
-            }
-        } else {
-            const size_t x = min(px0, maxx);
-            u32x2_t v[kRows + 2]; // an RGBA8 row in .x
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                const uint32_t y = frame_row(k);
-                if (src.halo(y)) {
-                    v[k] = src.template row<u32x2_t>(y)[x];
-                } else {
-                    const uint32_t* a = src.template row<uint32_t>(y) + x;
-                    v[k] = u32x2_t{interior(k) ? __builtin_nontemporal_load(a) : *a, 0u};
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kRows + 2; ++k) {
-                union { u32x2_t u; half4_t h; } a;
-                a.u = v[k];
-                rowA[k] = unpack(src.halo(frame_row(k)) ? tonemap_pixel(p.tm, finalExposure, a.h) : v[k].x);
-            }
-        }
+    for (int k = 0; k < kRows + 2; ++k) {
+        const bool hdr = hdr_row<MODE>(src, frame_row(k));
+        // tb: the unit's last texel (index PX - 1); ta: its first - for PX == 1 the same texel, and a lane beyond the frame repeats tb
+        const uint32_t tb = rgba8<MODE>(p.tm, finalExposure, v[k], hdr, PX - 1);
+        const uint32_t ta = (PX == 2 && beyond) ? tb : rgba8<MODE>(p.tm, finalExposure, v[k], hdr, 0);
+        rowA[k] = unpack(ta);
+        if constexpr (PX == 2) rowB[k] = unpack(tb);
     }
     const Px haloPx = unpack(halo);
 
@@ -425,28 +369,11 @@ __global__ __launch_bounds__(256) void cas_halo_kernel(CasHaloParams p)
     cas_strip<MODE, PX>(p.c, BandRows{p.c.src, p.above, p.below, p.c.W, p.c.row0, p.c.rows});
 }
 
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
-TonemapParams tonemap_params(const ur_tonemap_constants* tonemap, const float* exposure_ev)
-{
-    TonemapParams tm{}; // exactly ur_tonemap's (csrc/tonemap.hip)
-    tm.exposure_ev = exposure_ev;
-    tm.enable_tonemap = tonemap->EnableTonemap;
-    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
-    tm.exposure = tonemap->Exposure;
-    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
-    return tm;
-}
-
 // shared checks and launch of every CAS form. halo: src holds the band's rows only, above / below the RGBA16F rows around it.
 int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, In mode, bool halo, const void* src, const void* above, const void* below,
                const TonemapParams* tm, uint32_t* out, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
-    if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("%s: empty or out-of-frame band", who); return UR_EINVAL; }
+    if (rows == 0 || !ur::band_in_frame(w, h, row0, rows)) { ur::set_error("%s: empty or out-of-frame band", who); return UR_EINVAL; }
     if (halo && ((row0 > 0 && !above) || (row0 + rows < h && !below))) {
         ur::set_error("%s: hdr_above may be null only when row0 == 0, hdr_below only when row0 + rows == h", who);
         return UR_EINVAL;
@@ -473,22 +400,14 @@ int launch_cas(ur_ctx* ctx, const char* who, const ur_cas_constants* cas, In mod
     const bool pairs = (w % 2u) == 0u && aligned(src, mode == In::Hdr ? 15u : 7u) && aligned(out, 7u) && aligned(above, 15u) && aligned(below, 15u);
     const uint32_t px = pairs ? 2u : 1u;
     const dim3 grid((w + 256u * px - 1u) / (256u * px), grid_y);
-    if (halo) {
-        const CasHaloParams q{p, above, below};
-        if (mode == In::Hdr) {
-            if (pairs) hipLaunchKernelGGL((cas_halo_kernel<In::Hdr, 2>), grid, dim3(256), 0, ctx->stream, q);
-            else hipLaunchKernelGGL((cas_halo_kernel<In::Hdr, 1>), grid, dim3(256), 0, ctx->stream, q);
-        } else {
-            if (pairs) hipLaunchKernelGGL((cas_halo_kernel<In::LdrHdrHalo, 2>), grid, dim3(256), 0, ctx->stream, q);
-            else hipLaunchKernelGGL((cas_halo_kernel<In::LdrHdrHalo, 1>), grid, dim3(256), 0, ctx->stream, q);
-        }
-    } else if (mode == In::Hdr) {
-        if (pairs) hipLaunchKernelGGL((cas_strip_kernel<true, 2>), grid, dim3(256), 0, ctx->stream, p);
-        else hipLaunchKernelGGL((cas_strip_kernel<true, 1>), grid, dim3(256), 0, ctx->stream, p);
-    } else {
-        if (pairs) hipLaunchKernelGGL((cas_strip_kernel<false, 2>), grid, dim3(256), 0, ctx->stream, p);
-        else hipLaunchKernelGGL((cas_strip_kernel<false, 1>), grid, dim3(256), 0, ctx->stream, p);
-    }
+    auto launch = [&](auto* one, auto* two, const auto& q) { // the kernel of one pixel per lane, or of two
+        auto* kernel = pairs ? two : one;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, q);
+    };
+    if (halo && mode == In::Hdr) launch(cas_halo_kernel<In::Hdr, 1>, cas_halo_kernel<In::Hdr, 2>, CasHaloParams{p, above, below});
+    else if (halo) launch(cas_halo_kernel<In::LdrHdrHalo, 1>, cas_halo_kernel<In::LdrHdrHalo, 2>, CasHaloParams{p, above, below});
+    else if (mode == In::Hdr) launch(cas_strip_kernel<true, 1>, cas_strip_kernel<true, 2>, p);
+    else launch(cas_strip_kernel<false, 1>, cas_strip_kernel<false, 2>, p);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }
@@ -536,21 +455,21 @@ extern "C" int ur_tonemap_cas(ur_ctx* ctx, const ur_tonemap_constants* tonemap, 
                               const float* exposure_ev, uint32_t* out_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !tonemap || !cas || !hdr_full || !out_band) { ur::set_error("ur_tonemap_cas: null argument"); return UR_EINVAL; }
-    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    const TonemapParams tm = ur_post::tonemap_params(tonemap, exposure_ev, nullptr);
     return launch_cas(ctx, "ur_tonemap_cas", cas, In::Hdr, false, hdr_full, nullptr, nullptr, &tm, out_band, w, h, row0, rows);
 }
 
 // ---- the post exchange of row bands ---------------------------------------------------------------------------------------
 
-extern "C" uint64_t ur_post_record_bytes(uint32_t w) { return ((uint64_t)2u * w + kTapTexels) * 8u; }
+extern "C" uint64_t ur_post_record_bytes(uint32_t w) { return post_texels(w) * kTexelBytes; }
 
 extern "C" int ur_pack_post_record(ur_ctx* ctx, const ur_half4* hdr_band, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, void* record)
 {
     if (!ctx || !hdr_band || !record) { ur::set_error("ur_pack_post_record: null argument"); return UR_EINVAL; }
-    if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("ur_pack_post_record: empty or out-of-frame band"); return UR_EINVAL; }
+    if (rows == 0 || !ur::band_in_frame(w, h, row0, rows)) { ur::set_error("ur_pack_post_record: empty or out-of-frame band"); return UR_EINVAL; }
     if (overlaps(hdr_band, (size_t)w * rows * 8u, record, ur_post_record_bytes(w))) { ur::set_error("ur_pack_post_record: the record overlaps the band"); return UR_EINVAL; }
     PackParams p{reinterpret_cast<const half4_t*>(hdr_band), static_cast<half4_t*>(record), w, h, row0, rows};
-    const uint32_t n = 2u * w + kTapTexels;
+    const uint32_t n = (uint32_t)post_texels(w);
     hipLaunchKernelGGL(post_record_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
@@ -571,7 +490,7 @@ extern "C" int ur_auto_exposure_records(ur_ctx* ctx, const ur_auto_exposure_cons
     AeRecordsParams q{};
     q.ae = ae_params(constants, w, h, prev_ev, out_ev);
     q.records = static_cast<const half4_t*>(records);
-    q.record_texels = 2u * w + kTapTexels;
+    q.record_texels = (uint32_t)post_texels(w);
     q.band_rows = h / n_ranks;
     hipLaunchKernelGGL(ae_records_kernel, dim3(1), dim3(256), 0, ctx->stream, q);
     UR_HIP_TRY(hipGetLastError());
@@ -583,7 +502,7 @@ extern "C" int ur_tonemap_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tone
                                    uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !tonemap || !cas || !hdr_band || !out_band) { ur::set_error("ur_tonemap_cas_halo: null argument"); return UR_EINVAL; }
-    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    const TonemapParams tm = ur_post::tonemap_params(tonemap, exposure_ev, nullptr);
     return launch_cas(ctx, "ur_tonemap_cas_halo", cas, In::Hdr, true, hdr_band, hdr_above, hdr_below, &tm, out_band, w, h, row0, rows);
 }
 
@@ -592,6 +511,6 @@ extern "C" int ur_cas_halo(ur_ctx* ctx, const ur_tonemap_constants* tonemap, con
                            uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !tonemap || !cas || !ldr_band || !out_band) { ur::set_error("ur_cas_halo: null argument"); return UR_EINVAL; }
-    const TonemapParams tm = tonemap_params(tonemap, exposure_ev);
+    const TonemapParams tm = ur_post::tonemap_params(tonemap, exposure_ev, nullptr);
     return launch_cas(ctx, "ur_cas_halo", cas, In::LdrHdrHalo, true, ldr_band, hdr_above, hdr_below, &tm, out_band, w, h, row0, rows);
 }

@@ -1,15 +1,23 @@
-// Device functions of the post chain shared by csrc/tonemap.hip and csrc/post.hip: the Tonemap pixel (Shaders/Tonemap.hlsl)
-// and the 8-bit rounding of the back buffer. ur_tonemap_cas must produce exactly ur_tonemap's bytes before it sharpens them,
-// so there is one definition of each, compiled with the same flags (-ffp-contract=off) in both translation units. Not installed.
+// The post chain's one shared header (csrc/tonemap.hip, csrc/post.hip, csrc/taa.hip): the vector types and their bit casts, the Tonemap
+// pixel (Shaders/Tonemap.hlsl) with the 8-bit rounding of the back buffer, and the one place its constants become launch parameters.
+// ur_tonemap_cas and ur_temporal_aa_tonemap must produce exactly ur_tonemap's bytes, so there is one definition of each, compiled with
+// the same flags (-ffp-contract=off) in the three translation units. Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "../../include/ur_hotpath.h"
+
 namespace ur_post {
 
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+// two dwords as loaded are the eight bytes of an RGBA16F texel (every kernel loads and shifts dwords; only tonemap_pixel wants halves)
+__device__ __forceinline__ half4_t as_half4(u32x2_t u) { return __builtin_bit_cast(half4_t, u); }
 
 struct TonemapParams {
     const half4_t* hdr;
@@ -19,6 +27,19 @@ struct TonemapParams {
     uint32_t enable_tonemap, enable_auto_exposure;
     float exposure, inv_gamma;
 };
+
+// ur_tonemap_constants as every launch that tonemaps takes them; hdr / count stay for ur_tonemap to set
+inline TonemapParams tonemap_params(const ur_tonemap_constants* constants, const float* exposure_ev, uint32_t* out)
+{
+    TonemapParams p{};
+    p.exposure_ev = exposure_ev;
+    p.out = out;
+    p.enable_tonemap = constants->EnableTonemap;
+    p.enable_auto_exposure = constants->EnableAutoExposure;
+    p.exposure = constants->Exposure;
+    p.inv_gamma = 1.0f / (constants->Gamma > 1e-3f ? constants->Gamma : 1e-3f);
+    return p;
+}
 
 __device__ __forceinline__ float pow_pos(float x, float e) { return x > 0.0f ? __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)) : 0.0f; }
 // saturate, then R8G8B8A8_UNORM rounding (round half up of x * 255)

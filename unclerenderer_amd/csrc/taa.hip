@@ -29,10 +29,13 @@
 #include "ur_internal.h"
 #include "ur_device.h"
 #include "post_common.h"
+#include "post_records.h"
 
 namespace {
 
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+using ur_post::half4_t;
+using ur_post::u32x2_t;
+using namespace ur_records;
 
 struct TaaParams {
     const half4_t* current; // full frame
@@ -51,7 +54,6 @@ struct TaaParams {
 // lerp in fp32 as in TemporalAA.hlsl:41-49.
 constexpr int kStripRows = 8;
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 struct RowMinMax { half2_t mn0, mn1, mx0, mx1; }; // (R,G) and (B,A) pairs
 
@@ -68,9 +70,8 @@ __device__ __forceinline__ half2_t pk_max(half2_t a, half2_t b) { return __built
 // horizontal (left, centre, right) min/max of one row; (hl0, hl1) / (hr0, hr1) = the texel left of lane 0 / right of lane 63
 __device__ __forceinline__ RowMinMax row_minmax(u32x2_t c, uint32_t hl0, uint32_t hl1, uint32_t hr0, uint32_t hr1)
 {
-    // wave_shr:1 (0x138): lane l reads lane l-1, lane 0 keeps `old`; wave_shl:1 (0x130): lane l reads lane l+1, lane 63 keeps `old`
-    const uint32_t l0 = __builtin_amdgcn_update_dpp(hl0, c.x, 0x138, 0xF, 0xF, false), l1 = __builtin_amdgcn_update_dpp(hl1, c.y, 0x138, 0xF, 0xF, false);
-    const uint32_t r0 = __builtin_amdgcn_update_dpp(hr0, c.x, 0x130, 0xF, 0xF, false), r1 = __builtin_amdgcn_update_dpp(hr1, c.y, 0x130, 0xF, 0xF, false);
+    const uint32_t l0 = ur::wave_shr1(hl0, c.x), l1 = ur::wave_shr1(hl1, c.y); // the left texel: lane l - 1's, lane 0 takes hl
+    const uint32_t r0 = ur::wave_shl1(hr0, c.x), r1 = ur::wave_shl1(hr1, c.y); // the right texel: lane l + 1's, lane 63 takes hr
     RowMinMax m;
     const half2_t ql0 = quiet(l0), ql1 = quiet(l1), qr0 = quiet(r0), qr1 = quiet(r1), qc0 = quiet(c.x), qc1 = quiet(c.y);
     m.mn0 = pk_min(pk_min(ql0, qr0), qc0); m.mn1 = pk_min(pk_min(ql1, qr1), qc1);
@@ -93,9 +94,7 @@ struct TonemapPost {
     __device__ __forceinline__ float prepare() const { return ur_post::final_exposure(tm); } // uniform: one scalar load of the EV per wave
     __device__ __forceinline__ void texel(float finalExposure, size_t i, uint32_t lo, uint32_t hi) const
     {
-        union { u32x2_t u; ur_post::half4_t h; } t;
-        t.u = u32x2_t{lo, hi};
-        ur::store_once_b32(tm.out + i, ur_post::tonemap_pixel(tm, finalExposure, t.h));
+        ur::store_once_b32(tm.out + i, ur_post::tonemap_pixel(tm, finalExposure, ur_post::as_half4(u32x2_t{lo, hi})));
     }
 };
 
@@ -249,9 +248,7 @@ __global__ __launch_bounds__(256) void taa_band_kernel(TaaBandParams p, Post pos
     taa_strip(p.R, post, p.R.W, p.H, p.weight, p.use_history, p.R.row0, r0, nrows);
 }
 
-// ---- the TAA record of a row band (include/ur_hotpath.h, ur_taa_record_bytes) -----------------------------------------------
-// half4 slots: [0, W) the band's second current row, [W, 2W) its second-last, [2W, 3W) / [3W, 4W) the first / last row of the history
-// image the frame reads (zeros without history).
+// ---- the TAA record of a row band (include/ur_hotpath.h, ur_taa_record_bytes; its layout: csrc/post_records.h) ----------------
 struct TaaRecordParams {
     const u32x2_t* band;    // current rows [row0, row0 + rows)
     const u32x2_t* history; // the same rows of the history image read; null without history
@@ -262,12 +259,12 @@ struct TaaRecordParams {
 __global__ __launch_bounds__(256) void taa_record_kernel(TaaRecordParams p)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x, W = p.W;
-    if (j >= 4u * W) return;
-    const uint32_t part = j / W, x = j - part * W; // uniform per wave except across a part's edge
+    if (j >= kTaaRows * W) return;
+    const uint32_t part = j / W, x = j - part * W; // the record's row; uniform per wave except across a row's edge
     const uint32_t second = min(1u, p.rows - 1u), second_last = p.rows >= 2u ? p.rows - 2u : 0u;
     u32x2_t v = {0u, 0u};
-    if (part < 2u) v = p.band[(size_t)(part == 0u ? second : second_last) * W + x];
-    else if (p.history != nullptr) v = p.history[(size_t)(part == 2u ? 0u : p.rows - 1u) * W + x];
+    if (part < kTaaHistFirstRow) v = p.band[(size_t)(part == kTaaSecondRow ? second : second_last) * W + x];
+    else if (p.history != nullptr) v = p.history[(size_t)(part == kTaaHistFirstRow ? 0u : p.rows - 1u) * W + x];
     p.record[j] = v;
 }
 
@@ -277,7 +274,7 @@ static int fill_params(const char* who, TaaParams& p, ur_ctx* ctx, const ur_half
                        float history_weight, uint32_t use_history, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
 {
     if (!ctx || !current_frame || !output_band || (use_history && !history_band)) { ur::set_error("%s: null argument", who); return UR_EINVAL; }
-    if (w == 0 || h == 0 || (uint64_t)row0 + rows > h) { ur::set_error("%s: bad frame/band", who); return UR_EINVAL; }
+    if (!ur::band_in_frame(w, h, row0, rows)) { ur::set_error("%s: bad frame/band", who); return UR_EINVAL; } // (an empty band: nothing to do)
     p.current = reinterpret_cast<const half4_t*>(current_frame);
     p.history = reinterpret_cast<const half4_t*>(history_band);
     p.output = reinterpret_cast<half4_t*>(output_band);
@@ -311,13 +308,7 @@ extern "C" int ur_temporal_aa_tonemap(ur_ctx* ctx, const ur_tonemap_constants* t
     const int rc = fill_params("ur_temporal_aa_tonemap", p, ctx, current_frame, history_band, history_out_band, history_weight, use_history, w, h, row0, rows);
     if (rc != UR_OK) return rc;
     if (rows == 0) return UR_OK;
-    ur_post::TonemapParams tm{}; // as ur_tonemap fills it
-    tm.exposure_ev = exposure_ev;
-    tm.out = ldr_out_band;
-    tm.enable_tonemap = tonemap->EnableTonemap;
-    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
-    tm.exposure = tonemap->Exposure;
-    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
+    const ur_post::TonemapParams tm = ur_post::tonemap_params(tonemap, exposure_ev, ldr_out_band);
     const dim3 grid((w + 255u) / 256u, (rows + kStripRows - 1u) / kStripRows);
     if (ctx->opt.taa_tonemap_history_store == 0) hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<true>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<true>{tm});
     else hipLaunchKernelGGL(taa_strip_kernel<TonemapPost<false>>, grid, dim3(256), 0, ctx->stream, p, TonemapPost<false>{tm});
@@ -327,19 +318,15 @@ extern "C" int ur_temporal_aa_tonemap(ur_ctx* ctx, const ur_tonemap_constants* t
 
 // ---- row bands: the TAA record and the halo forms ---------------------------------------------------------------------------
 
-static bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
+using ur::overlaps;
 
-extern "C" uint64_t ur_taa_record_bytes(uint32_t w) { return (uint64_t)4u * w * 8u; }
+extern "C" uint64_t ur_taa_record_bytes(uint32_t w) { return taa_texels(w) * kTexelBytes; }
 
 extern "C" int ur_pack_taa_record(ur_ctx* ctx, const ur_half4* hdr_band, const ur_half4* history_read_band, uint32_t use_history, uint32_t w, uint32_t h,
                                   uint32_t row0, uint32_t rows, void* record)
 {
     if (!ctx || !hdr_band || !record || (use_history && !history_read_band)) { ur::set_error("ur_pack_taa_record: null argument"); return UR_EINVAL; }
-    if (w == 0 || h == 0 || rows == 0 || (uint64_t)row0 + rows > h) { ur::set_error("ur_pack_taa_record: empty or out-of-frame band"); return UR_EINVAL; }
+    if (rows == 0 || !ur::band_in_frame(w, h, row0, rows)) { ur::set_error("ur_pack_taa_record: empty or out-of-frame band"); return UR_EINVAL; }
     if (rows < 2u && rows != h) { ur::set_error("ur_pack_taa_record: a band that is not the whole frame needs at least 2 rows"); return UR_EUNSUPPORTED; }
     const size_t band_bytes = (size_t)w * rows * 8u;
     if (overlaps(hdr_band, band_bytes, record, ur_taa_record_bytes(w)) || (use_history && overlaps(history_read_band, band_bytes, record, ur_taa_record_bytes(w)))) {
@@ -348,7 +335,7 @@ extern "C" int ur_pack_taa_record(ur_ctx* ctx, const ur_half4* hdr_band, const u
     }
     const TaaRecordParams p{reinterpret_cast<const u32x2_t*>(hdr_band), use_history ? reinterpret_cast<const u32x2_t*>(history_read_band) : nullptr,
                             static_cast<u32x2_t*>(record), w, rows};
-    hipLaunchKernelGGL(taa_record_kernel, dim3((uint32_t)(((uint64_t)4u * w + 255u) / 256u)), dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(taa_record_kernel, dim3((uint32_t)((taa_texels(w) + 255u) / 256u)), dim3(256), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }
@@ -437,13 +424,7 @@ extern "C" int ur_temporal_aa_tonemap_halo(ur_ctx* ctx, const ur_tonemap_constan
     const int rc = fill_band_params("ur_temporal_aa_tonemap_halo", q, grid_y, ctx, current_band, cur_above, cur_below, history_band, history_out_band, above2,
                                     hist_above, below2, hist_below, resolved_above, resolved_below, history_weight, use_history, w, h, row0, rows);
     if (rc != UR_OK) return rc;
-    ur_post::TonemapParams tm{}; // as ur_tonemap fills it
-    tm.exposure_ev = exposure_ev;
-    tm.out = ldr_out_band;
-    tm.enable_tonemap = tonemap->EnableTonemap;
-    tm.enable_auto_exposure = tonemap->EnableAutoExposure;
-    tm.exposure = tonemap->Exposure;
-    tm.inv_gamma = 1.0f / (tonemap->Gamma > 1e-3f ? tonemap->Gamma : 1e-3f);
+    const ur_post::TonemapParams tm = ur_post::tonemap_params(tonemap, exposure_ev, ldr_out_band);
     hipLaunchKernelGGL(taa_band_kernel<TonemapPost<true>>, dim3((w + 255u) / 256u, grid_y), dim3(256), 0, ctx->stream, q, TonemapPost<true>{tm});
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;

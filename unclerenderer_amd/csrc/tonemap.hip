@@ -14,6 +14,9 @@
 namespace {
 
 using ur_post::half4_t;
+using ur_post::u32x2_t;
+using ur_post::u32x4_t;
+using ur_post::as_half4;
 using ur_post::TonemapParams;
 using ur_post::tonemap_pixel;
 using ur_post::final_exposure;
@@ -31,8 +34,6 @@ __global__ __launch_bounds__(256) void tonemap_kernel(TonemapParams p)
 // 2: 21.0 / 72.9, 4: 22.4 / 72.3 - short waves keep loading and converting waves mixed on a CU, long ones save launches
 // of waves once the grid is many rounds deep; a plain 2:1 streaming kernel of the 4K size takes 19.2 us
 // (tools/microbench/stream_ceiling.hip).
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 template <uint32_t kPairTrips>
 __global__ __launch_bounds__(256) void tonemap_pairs_kernel(TonemapParams p)
 {
@@ -48,9 +49,8 @@ __global__ __launch_bounds__(256) void tonemap_pairs_kernel(TonemapParams p)
     for (uint32_t k = 0; k < kPairTrips; ++k) {
         const uint32_t pr = pair0 + k * 64u;
         if (pr < npairs) {
-            union { u32x2_t u; half4_t h; } a, b;
-            a.u = u32x2_t{v[k].x, v[k].y}; b.u = u32x2_t{v[k].z, v[k].w};
-            ur::store_once_b64(reinterpret_cast<u32x2_t*>(p.out) + pr, ur::once_u32x2_t{tonemap_pixel(p, finalExposure, a.h), tonemap_pixel(p, finalExposure, b.h)});
+            const half4_t a = as_half4(u32x2_t{v[k].x, v[k].y}), b = as_half4(u32x2_t{v[k].z, v[k].w});
+            ur::store_once_b64(reinterpret_cast<u32x2_t*>(p.out) + pr, ur::once_u32x2_t{tonemap_pixel(p, finalExposure, a), tonemap_pixel(p, finalExposure, b)});
         }
     }
 }
@@ -64,15 +64,9 @@ extern "C" int ur_tonemap(ur_ctx* ctx, const ur_tonemap_constants* constants, co
     const uint64_t n = (uint64_t)w * rows;
     if (n == 0) return UR_OK;
     if (n > 0xFFFFFFFFull) { ur::set_error("ur_tonemap: band too large"); return UR_EUNSUPPORTED; }
-    TonemapParams p{};
+    TonemapParams p = ur_post::tonemap_params(constants, exposure_ev, out_rgba8);
     p.hdr = reinterpret_cast<const half4_t*>(hdr);
-    p.exposure_ev = exposure_ev;
-    p.out = out_rgba8;
     p.count = (uint32_t)n;
-    p.enable_tonemap = constants->EnableTonemap;
-    p.enable_auto_exposure = constants->EnableAutoExposure;
-    p.exposure = constants->Exposure;
-    p.inv_gamma = 1.0f / (constants->Gamma > 1e-3f ? constants->Gamma : 1e-3f);
     const bool aligned = ((reinterpret_cast<uintptr_t>(hdr) & 15u) == 0u) && ((reinterpret_cast<uintptr_t>(out_rgba8) & 7u) == 0u);
     if (aligned && n >= 2u) {
         if (n < (24u << 20)) hipLaunchKernelGGL(tonemap_pairs_kernel<1>, dim3((uint32_t)((n / 2u * 2u + 511u) / 512u)), dim3(256), 0, ctx->stream, p);

@@ -382,10 +382,9 @@ static DrawsFault check_draws(const ur_draw_ranges& d, uint32_t n, const void* i
 {
     if (!d.offsets || !d.commands || !d.counts || d.range_count == 0) return DrawsFault::member;
     if (n == ~0u || n == 0) return DrawsFault::none;
-    const uintptr_t c = reinterpret_cast<uintptr_t>(d.commands), a = reinterpret_cast<uintptr_t>(indirect_args);
-    const uintptr_t bytes = (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE;
-    if (c < a + bytes && a < c + bytes) return DrawsFault::overlap;
-    if (((c | a) & 15u) != 0) return DrawsFault::alignment;
+    const size_t bytes = (size_t)n * UR_INDIRECT_COMMAND_STRIDE;
+    if (ur::overlaps(d.commands, bytes, indirect_args, bytes)) return DrawsFault::overlap;
+    if (((reinterpret_cast<uintptr_t>(d.commands) | reinterpret_cast<uintptr_t>(indirect_args)) & 15u) != 0) return DrawsFault::alignment;
     return DrawsFault::none;
 }
 
@@ -424,11 +423,8 @@ static int check_views(const char* who, const ur_cull_view* views, uint32_t view
     if (!views || view_count == 0) return UR_OK;
     if (view_count > UR_MAX_CULL_VIEWS) { set_error("%s: %u views (at most %u)", who, view_count, (uint32_t)UR_MAX_CULL_VIEWS); return UR_EINVAL; }
     const bool known = n != ~0u;
-    const uintptr_t bytes = known ? (uintptr_t)n * UR_INDIRECT_COMMAND_STRIDE : 0u;
-    auto overlap = [&](const void* x, const void* y) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
-        return known && n != 0 && a < b + bytes && b < a + bytes;
-    };
+    const size_t bytes = known ? (size_t)n * UR_INDIRECT_COMMAND_STRIDE : 0u; // of a command buffer; 0: it cannot overlap another
+    auto overlap = [&](const void* x, const void* y) { return ur::overlaps(x, bytes, y, bytes); };
     for (uint32_t v = 0; v < view_count; ++v) {
         const ur_cull_view& V = views[v];
         if (!V.mask && !V.visible_idx && !V.visible_count && !V.draws) { set_error("%s: view %u asks for nothing (no mask, list or ranges)", who, v); return UR_EINVAL; }

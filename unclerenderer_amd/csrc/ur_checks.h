@@ -3,6 +3,7 @@
 // (ur_api.hip, cull_views.hip, raster.hip, gbuffer_resolve.hip). Not installed.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/ur_hotpath.h"
@@ -11,6 +12,16 @@
 namespace ur {
 
 void set_error(const char* fmt, ...);
+
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+inline bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+// Are rows [row0, row0 + rows) inside a w x h frame that is not empty? (rows == 0 is inside: an entry point that refuses an empty band
+// says so beside the call.) The refusal's text stays the entry point's own.
+inline bool band_in_frame(uint32_t w, uint32_t h, uint32_t row0, uint32_t rows) { return w != 0 && h != 0 && (uint64_t)row0 + rows <= h; }
 
 // ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
 int check_cull_views(const ur_cull_view* views, uint32_t view_count);

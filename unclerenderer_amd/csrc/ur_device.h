@@ -20,6 +20,11 @@ __device__ __forceinline__ void store_once_b32(void* p, uint32_t v)
     asm volatile("global_store_dword %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
 }
 
+// DPP shifts of one dword across the wave64. wave_shr1: lane l gets lane l - 1's v, lane 0 keeps `old`; wave_shl1: lane l gets
+// lane l + 1's v, lane 63 keeps `old`. A strip kernel passes as `old` the texel beside the strip.
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t old, uint32_t v) { return __builtin_amdgcn_update_dpp(old, v, 0x138, 0xF, 0xF, false); }
+__device__ __forceinline__ uint32_t wave_shl1(uint32_t old, uint32_t v) { return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xF, 0xF, false); }
+
 // Touch every 64-byte line of the kernarg segment (explicit arguments of BYTES bytes plus the hidden ones behind them)
 // with one batch of scalar loads and ONE wait. hipcc reads kernel parameters lazily, a few dwords at a time with a wait
 // after each group; at the start of a launch every new line is a scalar-cache miss, and a kernel with a dozen dependent

@@ -469,7 +469,7 @@ class Frame:
 
 def _tonemap(self, hdr, out_rgba8, w, rows, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None):
     """Tonemap pass (Tonemap.hlsl) over a band: RGBA16F -> R8G8B8A8_UNORM."""
-    k = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    k = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     _lib.check(self._L.ur_tonemap(self._ctx, C.byref(k), _ptr(hdr), _ptr(exposure_ev), _ptr(out_rgba8), w, rows), "ur_tonemap")
 
 
@@ -490,7 +490,7 @@ def _temporal_aa_tonemap(self, current_frame, history_band, history_out_band, ld
                          exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None):
     """temporal_aa() followed by tonemap() of its output band, in one launch (the same bytes in history_out_band and ldr_out_band)."""
     rows = h - row0 if rows is None else rows
-    k = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    k = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     _lib.check(self._L.ur_temporal_aa_tonemap(self._ctx, C.byref(k), _ptr(current_frame), _ptr(history_band), _ptr(history_out_band), _ptr(exposure_ev),
                                               _ptr(ldr_out_band), history_weight, int(use_history), w, h, row0, rows), "ur_temporal_aa_tonemap")
 
@@ -504,6 +504,10 @@ def _auto_exposure(self, hdr_full, out_ev, w, h, prev_ev=None, use_history=False
     Defaults: RendererConfig.h:28-32."""
     k = _lib.AutoExposureConstants((C.c_float * 2)(w, h), delta_time, speed_up, speed_down, int(use_history), key, ev_min, ev_max)
     _lib.check(self._L.ur_auto_exposure(self._ctx, C.byref(k), _ptr(hdr_full), w, h, _ptr(prev_ev), _ptr(out_ev)), "ur_auto_exposure")
+
+
+def _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma):
+    return _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)  # EnableAutoExposure: an EV texel is given
 
 
 def _cas_constants(w, h, sharpness):
@@ -521,7 +525,7 @@ def _tonemap_cas(self, hdr_full, out_band, w, h, row0=0, rows=None, exposure=1.0
                  sharpness=0.5):
     """Tonemap of the full frame then CAS of the band, in one launch (the same bytes as tonemap() followed by cas())."""
     rows = h - row0 if rows is None else rows
-    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    tk = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     ck = _cas_constants(w, h, sharpness)
     _lib.check(self._L.ur_tonemap_cas(self._ctx, C.byref(tk), C.byref(ck), _ptr(hdr_full), _ptr(exposure_ev), _ptr(out_band), w, h, row0, rows),
                "ur_tonemap_cas")
@@ -555,7 +559,7 @@ def _auto_exposure_records(self, records, n_ranks, out_ev, w, h, prev_ev=None, u
 def _tonemap_cas_halo(self, hdr_band, above, below, out_band, w, h, row0, rows, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None,
                       sharpness=0.5):
     """tonemap_cas of rows [row0,row0+rows) from the band and the HDR rows above / below it (None at the frame's edges)."""
-    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    tk = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     ck = _cas_constants(w, h, sharpness)
     _lib.check(self._L.ur_tonemap_cas_halo(self._ctx, C.byref(tk), C.byref(ck), _ptr(hdr_band), _ptr(above), _ptr(below), _ptr(exposure_ev),
                                            _ptr(out_band), w, h, row0, rows), "ur_tonemap_cas_halo")
@@ -564,7 +568,7 @@ def _tonemap_cas_halo(self, hdr_band, above, below, out_band, w, h, row0, rows, 
 def _cas_halo(self, ldr_band, above, below, out_band, w, h, row0, rows, exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None,
               sharpness=0.5):
     """cas of rows [row0,row0+rows) from tonemap()'s band output and the HDR rows above / below it, tonemapped with the same constants."""
-    tk = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    tk = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     ck = _cas_constants(w, h, sharpness)
     _lib.check(self._L.ur_cas_halo(self._ctx, C.byref(tk), C.byref(ck), _ptr(ldr_band), _ptr(above), _ptr(below), _ptr(exposure_ev),
                                    _ptr(out_band), w, h, row0, rows), "ur_cas_halo")
@@ -604,7 +608,7 @@ def _temporal_aa_tonemap_halo(self, current_band, cur_above, cur_below, history_
                               w, h, row0, rows, above2=None, hist_above=None, below2=None, hist_below=None, resolved_above=None, resolved_below=None,
                               exposure=1.0, gamma=2.2, enable_tonemap=True, exposure_ev=None):
     """temporal_aa_halo() followed by tonemap() of its output band, in one launch."""
-    k = _lib.TonemapConstants(int(enable_tonemap), int(exposure_ev is not None), exposure, gamma)
+    k = _tonemap_constants(enable_tonemap, exposure_ev, exposure, gamma)
     _lib.check(self._L.ur_temporal_aa_tonemap_halo(self._ctx, C.byref(k), _ptr(current_band), _ptr(cur_above), _ptr(cur_below), _ptr(history_band),
                                                    _ptr(history_out_band), _ptr(exposure_ev), _ptr(ldr_out_band), _ptr(above2), _ptr(hist_above),
                                                    _ptr(below2), _ptr(hist_below), _ptr(resolved_above), _ptr(resolved_below), history_weight,
