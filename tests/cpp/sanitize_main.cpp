@@ -1,11 +1,13 @@
 // Sanitizer driver (CPU build only: -fsanitize=address,undefined): runs the host-side code of the product (DDS/BC6H decode,
-// scene -> ModelBounds extraction, host constant math, the Lighting launch's planner) and the CPU oracle (test infrastructure) over the
+// scene -> ModelBounds extraction, host constant math, the Lighting launch's and the Build HZB chain's planners, the environment cube's
+// staging) and the CPU oracle (test infrastructure) over the
 // shipped fixtures, random inputs and hostile inputs (truncated files, garbage blocks, empty and ragged sizes). Any report from ASan/UBSan
 // ends the process with a non-zero status. SURVEY.md section 5, "Race detection / sanitizers": the reference has only the D3D12
 // debug layer (Source/RHI/DX12Device.cpp:82-91).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -I include \
-//       tests/cpp/sanitize_main.cpp csrc/dds.cpp csrc/scene.cpp csrc/host_math.cpp csrc/lighting_plan.cpp oracle/ur_oracle.cpp -pthread
+//       tests/cpp/sanitize_main.cpp csrc/dds.cpp csrc/scene.cpp csrc/host_math.cpp csrc/lighting_plan.cpp csrc/hzb_plan.cpp \
+//       csrc/env_cube_stage.cpp oracle/ur_oracle.cpp -pthread
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +23,7 @@
 #include "ur_hotpath.h"
 #include "ur_scene.h"
 
+#include "hzb_plan_sweep.h"
 #include "lighting_plan_sweep.h"
 
 extern "C" {
@@ -213,6 +216,53 @@ static void test_lighting_plan()
         }
 }
 
+// csrc/env_cube_stage.cpp beside the oracle's staging, on exact-size heap buffers with a distinct value in every texel: the bordered
+// section is the oracle's byte for byte (the folding rule is the specification), and every row-pair entry is the RGB of the two bordered
+// texels it is defined from
+static void test_env_cube_stage()
+{
+    const uint32_t cubes[][2] = {{1, 1}, {2, 2}, {3, 2}, {4, 3}, {16, 5}, {256, 9}};
+    for (auto& c : cubes) {
+        const uint32_t base = c[0], mips = c[1];
+        const ur::CubeLayout L = ur::cube_layout(base, mips);
+        CHECK(L.mips == mips && L.texels != 0);
+        size_t src_texels = 0;
+        for (uint32_t m = 0; m < mips; ++m) src_texels += (size_t)6 * L.size(m) * L.size(m);
+        std::vector<ur_half4> src(src_texels);
+        // positive normal halves (0x0400 ..): they survive the oracle's half -> float -> half; (x, y) alone tells any two texels apart
+        for (size_t i = 0; i < src.size(); ++i)
+            src[i] = {(uint16_t)(0x0400u + i % 30000u), (uint16_t)(0x0400u + i / 30000u), (uint16_t)(0x0400u + (i * 7u + 3u) % 30000u), (uint16_t)(0x0400u + i % 29989u)};
+        std::vector<ur_half4> got(L.texels), want(uro_env_cube_texels(base, mips));
+        CHECK(want.size() * sizeof(ur_half4) == L.pairs[0]); // the oracle stages the first section only
+        ur::stage_env_cube_host(src.data(), L, got.data());
+        uro_stage_env_cube(src.data(), base, mips, want.data());
+        CHECK(std::memcmp(got.data(), want.data(), want.size() * sizeof(ur_half4)) == 0);
+        const uint16_t* bytes16 = reinterpret_cast<const uint16_t*>(got.data());
+        size_t bad = 0;
+        for (uint32_t m = 0; m < mips; ++m) {
+            const size_t E = L.edge[m];
+            const uint16_t* rgb = bytes16 + L.pairs[m] / 2u;
+            for (size_t f = 0; f < 6; ++f)
+                for (size_t j = 0; j + 1 < E; ++j)
+                    for (size_t i = 0; i < E; ++i, rgb += 6) {
+                        const ur_half4 &t0 = got[L.bordered[m] + (f * E + j) * E + i], &t1 = got[L.bordered[m] + (f * E + j + 1) * E + i];
+                        if (rgb[0] != t0.x || rgb[1] != t0.y || rgb[2] != t0.z || rgb[3] != t1.x || rgb[4] != t1.y || rgb[5] != t1.z) ++bad;
+                    }
+            CHECK((size_t)(rgb - bytes16) * 2u == L.pairs[m + 1u]); // the entries of a mip end where the next mip's begin; the last at the buffer's end
+        }
+        CHECK(bad == 0 && L.pairs[mips] == L.bytes && L.bytes == L.texels * sizeof(ur_half4));
+    }
+}
+
+// csrc/hzb_plan.cpp: the sweep of tests/cpp/test_hzb_plan.cpp and its hostile inputs (no mips, 0 or 17 levels, a chain that does not
+// halve, a zero size), every chain in an exact-size heap buffer: each hostile one is refused and none is read past its end
+static void test_hzb_plan()
+{
+    CHECK(hzb_sweep::sweep() > 200000);
+    CHECK(hzb_sweep::hostile() > 60);
+    CHECK(hzb_sweep::g_fail == 0);
+}
+
 int main(int argc, char** argv)
 {
     const std::string assets = argc > 1 ? argv[1] : "tests/golden/assets";
@@ -220,6 +270,8 @@ int main(int argc, char** argv)
     test_scene(assets);
     test_oracle_and_host_math();
     test_lighting_plan();
+    test_env_cube_stage();
+    test_hzb_plan();
     if (g_fail) { std::printf("%d check(s) failed\n", g_fail); return 1; }
     std::printf("OK sanitized host + oracle run clean\n");
     return 0;

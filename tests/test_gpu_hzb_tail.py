@@ -200,6 +200,81 @@ def test_destroy_discards_a_held_back_tail(oracle):
     assert float(keep[last]) == -1.0
 
 
+def test_holder_transitions_at_the_smallest_chain_with_a_tail(hotpath, oracle):
+    """64 x 64: six levels, five from the wide launch and a one-level tail. Held under mode 1, switched to mode 2 (wider: nothing is
+    flushed), built again (the held tail goes out first, then the whole chain is held) and flushed, switched to mode 0: after each step the
+    HZB is the oracle's bits where the chain is complete and untouched where it is held. A context destroyed with the tail held launches nothing."""
+    import torch
+    from unclerenderer_amd.hotpath import HotPath, HzbLayout, to_device
+    w = h = 64
+    lay = HzbLayout(w, h)
+    assert lay.count == 6
+    rng = np.random.default_rng(64)
+    depth = rng.random((h, w), dtype=np.float32)
+    depth[rng.random((h, w)) < 0.1] = 0.0
+    d = to_device(depth)
+    ref = torch.from_numpy(oracle.build_hzb(depth, lay.as_list(), lay.total)).cuda()
+    levels = lay.as_list()
+    last = levels[5][0]
+
+    def complete(hzb, count=6):  # the first `count` levels are the oracle's bits
+        return all(torch.equal(hzb[off:off + mw * mh].view(torch.int32), ref[off:off + mw * mh].view(torch.int32)) for off, mw, mh in levels[:count])
+
+    def fresh():
+        return torch.full((lay.total,), -1.0, device="cuda")
+
+    try:
+        # 1. mode 1: the wide launch goes out, the tail is held
+        hzb1 = fresh()
+        hotpath.defer_hzb_tail(1)
+        hotpath.build_hzb(d, hzb1, lay)
+        torch.cuda.synchronize()
+        assert float(hzb1[last]) == -1.0 and complete(hzb1, 5), "mips 0-4 written, the tail held"
+        # 2. mode 2 is wider: nothing goes out
+        hotpath.defer_hzb_tail(2)
+        torch.cuda.synchronize()
+        assert float(hzb1[last]) == -1.0 and complete(hzb1, 5)
+        # ... another build flushes the first chain's tail and holds the second chain whole
+        hzb2 = fresh()
+        hotpath.build_hzb(d, hzb2, lay)
+        torch.cuda.synchronize()
+        assert complete(hzb1), "the first chain's tail ran before the second chain"
+        assert bool((hzb2 == -1.0).all()), "mode 2 holds the wide launch and the tail"
+        hotpath.flush()
+        torch.cuda.synchronize()
+        assert complete(hzb2)
+        # 3. mode 0 with a chain held under mode 2: both launches go out, wide first
+        hzb3 = fresh()
+        hotpath.build_hzb(d, hzb3, lay)
+        hotpath.defer_hzb_tail(0)
+        torch.cuda.synchronize()
+        assert complete(hzb3)
+        hzb4 = fresh()
+        hotpath.build_hzb(d, hzb4, lay)  # mode 0: nothing is held
+        torch.cuda.synchronize()
+        assert complete(hzb4)
+        for hz in (hzb1, hzb2, hzb3, hzb4):  # nothing outside the mips was written
+            mask = torch.ones(lay.total, dtype=torch.bool, device="cuda")
+            for off, mw, mh in levels:
+                mask[off:off + mw * mh] = False
+            assert bool((hz[mask] == -1.0).all())
+    finally:
+        hotpath.defer_hzb_tail(0)
+    # 5. ur_destroy with a tail held launches nothing (the pattern of test_destroy_discards_a_held_back_tail)
+    hp = HotPath(0)
+    hzb = fresh()
+    hp.defer_hzb_tail(1)
+    hp.build_hzb(d, hzb, lay)
+    torch.cuda.synchronize()
+    assert float(hzb[last]) == -1.0
+    keep = hzb.clone()
+    del hzb
+    torch.cuda.empty_cache()
+    hp.close()
+    torch.cuda.synchronize()
+    assert float(keep[last]) == -1.0
+
+
 def test_cull_rejects_a_chain_that_does_not_halve(hotpath):
     """ur_cull_indirect_args_ex validates EVERY level it may index (the kernel reads hzb + mips[l].offset with pitch
     mips[l].width up to HZBMipCount - 1), not only mips[0] against HZBWidth/HZBHeight."""

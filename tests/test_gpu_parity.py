@@ -23,7 +23,8 @@ def _torch():
 # BuildHZB
 # ---------------------------------------------------------------------------------------------------------------------
 HZB_SIZES = [(1, 1), (2, 2), (3, 5), (17, 9), (64, 64), (129, 67), (512, 512), (1920, 1080), (1000, 3), (5, 300), (2, 33), (4096, 16),
-             (6001, 3999), (7680, 4320)]  # the last two: mip 4 is too large for the tail's LDS (three launches)
+             (6001, 3999), (7680, 4320),  # mip 4 is too large for the tail's LDS, mip 5 fits: five levels, then the tail reads mip 4 from memory (two launches)
+             (16384, 4200)]  # mip 5 (256 x 65) is too large as well: four levels, four more from mip 3, then the tail (three launches)
 
 
 @pytest.mark.parametrize("w,h", HZB_SIZES)

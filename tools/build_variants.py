@@ -23,6 +23,16 @@ from unclerenderer_amd import build as b  # noqa: E402
 
 R02_COMMIT = "8034e2c"  # "round 2: VERDICT + ADVICE + BENCH": the last commit whose lighting.hip holds the variant switches
 BASE = None
+R02_HELD_HZB = [
+    ("        ctx->hzb_tail_pending = false;\n", ""),
+    ("            ctx->hzb_wide_pending = false;\n", ""),
+    ("ctx->pending_tail", "ctx->held_hzb.take_tail()"),
+    ("ctx->pending_wide_grid_x", "ctx->held_hzb.wide_grid_x()"),
+    ("ctx->pending_wide_grid_y", "ctx->held_hzb.wide_grid_y()"),
+    ("ctx->pending_wide;", "ctx->held_hzb.take_wide().d;"),
+    ("ctx->hzb_tail_pending", "ctx->held_hzb.has_tail()"),
+    ("ctx->hzb_wide_pending", "ctx->held_hzb.has_wide()"),
+]
 
 
 def source_for(base: str | None) -> Path:
@@ -36,6 +46,10 @@ def source_for(base: str | None) -> Path:
     text = subprocess.run(["git", "-C", str(ROOT), "show", f"{R02_COMMIT}:unclerenderer_amd/csrc/lighting.hip"], capture_output=True, text=True, check=True).stdout
     # the two context fields that changed since (the riding tail's time-out flag moved to host-visible memory)
     text = text.replace("ride.done = ctx->hzb_done;", "ride.done = ctx->hzb_done; /* [1] = the round-2 flag word, unread now */")
+    # the held-back HZB chain, loose fields of ur_ctx then, is ur::HeldHzb now (csrc/ur_internal.h): taking a step clears it
+    for old, new in R02_HELD_HZB:
+        assert old in text, old
+        text = text.replace(old, new)
     dst.write_text(text)
     return dst
 
@@ -52,7 +66,7 @@ def one(spec: str) -> Path:
     if r.returncode != 0:
         raise RuntimeError(f"{name}: {r.stderr}")
     # the round-2 file is the whole pass (ur::launch_lighting and both kernels): it replaces the three lighting units, not the planner
-    # (ur_api.hip sizes and stages the cube by it)
+    # (ur_api.hip sizes the cube by it, env_cube_stage.cpp stages it)
     replaced = {"lighting.hip"} if BASE is None else {"lighting.hip", "lighting_tiled.hip", "lighting_host.hip"}
     objs = [str(b.OUT / (s.replace("/", "_") + ".o")) for s, _ in b.SOURCES if s not in replaced] + [str(obj)]
     r = subprocess.run([b.hipcc(), f"--offload-arch={b.ARCH}", "-shared", "-fPIC", "-o", str(lib)] + objs + ["-ldl", "-lpthread"], capture_output=True, text=True)

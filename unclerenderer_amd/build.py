@@ -32,7 +32,11 @@ LIGHTING = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-atomic-optimizer-strategy=N
 # (source relative to csrc, extra flags)
 SOURCES = [
     ("ur_api.hip", []),
+    ("cull_api.hip", []),
+    ("gather.hip", []),
+    ("env_cube_stage.cpp", ["-x", "hip"]),  # (ur_api.hip's flags, which it was built with as a part of that unit)
     ("hzb.hip", EXACT),
+    ("hzb_plan.cpp", ["-x", "hip"] + EXACT),
     ("cull.hip", EXACT),
     ("cull_views.hip", EXACT),
     ("lighting.hip", LIGHTING),

@@ -281,3 +281,49 @@ int launch_debug_print_draw(ur_ctx* ctx, const ur_debug_print_constants* constan
 }
 
 } // namespace ur
+
+// ---- the entry points (include/ur_hotpath.h) ----
+
+using ur::set_error;
+
+extern "C" {
+
+uint64_t ur_debug_print_buffer_bytes(void) { return 4u + (uint64_t)UR_DEBUG_PRINT_MAX_ENTRIES * 16u; }
+
+int ur_debug_print_reset(ur_ctx* ctx, void* buffer, uint32_t* stats)
+{
+    if (!ctx || !buffer) { set_error("ur_debug_print_reset: null argument"); return UR_EINVAL; }
+    return ur::launch_debug_print_reset(ctx, buffer, stats);
+}
+
+int ur_debug_print_stats(ur_ctx* ctx, const uint32_t* stats, void* buffer)
+{
+    if (!ctx || !stats || !buffer) { set_error("ur_debug_print_stats: null argument"); return UR_EINVAL; }
+    return ur::launch_debug_print_stats(ctx, stats, buffer);
+}
+
+int ur_debug_print_text(ur_ctx* ctx, void* buffer, uint32_t x, uint32_t y, uint32_t color, const char* text, uint32_t length)
+{
+    if (!ctx || !buffer || (!text && length != 0)) { set_error("ur_debug_print_text: null argument"); return UR_EINVAL; }
+    return ur::launch_debug_print_text(ctx, buffer, x, y, color, text, length);
+}
+
+int ur_debug_print_draw(ur_ctx* ctx, const ur_debug_print_constants* constants, const ur_debug_glyph* glyphs, uint32_t glyph_count,
+                        const uint8_t* atlas_r8, uint32_t atlas_w, uint32_t atlas_h, const void* buffer, uint32_t* ldr_inout, uint32_t w,
+                        uint32_t h, uint32_t row0, uint32_t rows)
+{
+    const int rc = ur::check_band("ur_debug_print_draw", ctx, w, h, row0, rows);
+    if (rc != UR_OK) return rc;
+    if (!constants || !glyphs || !atlas_r8 || !buffer || !ldr_inout) { set_error("ur_debug_print_draw: null argument"); return UR_EINVAL; }
+    if (glyph_count == 0 || atlas_w == 0 || atlas_h == 0 || atlas_w > 16384u || atlas_h > 16384u) {
+        set_error("ur_debug_print_draw: glyph table of %u entries, atlas %u x %u (1..16384)", glyph_count, atlas_w, atlas_h);
+        return UR_EINVAL;
+    }
+    if (constants->ScreenSize[0] != (float)w || constants->ScreenSize[1] != (float)h) {
+        set_error("ur_debug_print_draw: ScreenSize (%g, %g) is not the frame's (%u, %u)", constants->ScreenSize[0], constants->ScreenSize[1], w, h);
+        return UR_EINVAL;
+    }
+    return ur::launch_debug_print_draw(ctx, constants, glyphs, glyph_count, atlas_r8, atlas_w, atlas_h, buffer, ldr_inout, w, row0, rows);
+}
+
+} // extern "C"

@@ -11,6 +11,10 @@
 //
 // Built with -ffp-contract=off; the only arithmetic is fminf, on quieted operands (hzb_min4, hzb_tail.h: HLSL min ignores a
 // NaN operand, a signalling one included).
+//
+// The host half executes a plan: which levels a launch takes, on which grid, and whether it goes out now or is held for the next
+// streaming Lighting launch is decided in csrc/hzb_plan.cpp (plain C++, tested without a GPU); here a step is bound to its buffers
+// and launched, or handed to the context's ur::HeldHzb. The Build HZB entry points of include/ur_hotpath.h are at the end.
 
 #include "ur_internal.h"
 #include "ur_device.h"
@@ -132,168 +136,226 @@ __global__ __launch_bounds__(1024) void hzb_tail_kernel(ur::HzbTail p)
 
 namespace ur {
 
-static HzbTail make_tail(float* hzb, const ur_mip_desc* mips, uint32_t mip_count, uint32_t mip);
-
-int launch_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb, const ur_mip_desc* mips,
-                     uint32_t mip_count)
+// One wide step of a plan bound to its buffers: the kernel's arguments
+static HzbDispatch bind_wide(const HzbStep& s, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb, const ur_mip_desc* mips)
 {
-    // Same grouping as the reference's while-loop (DeferredRenderer.cpp:1046-1207): <=4 mips per launch, first launch
-    // reads the depth buffer with clamped 2x2 footprints, later launches read the last mip of the previous launch —
-    // until the remaining levels fit one workgroup's LDS: those run in a single launch with the same values.
-    {
-        const int rc = flush_hzb_tail(ctx); // an earlier chain's tail must not run after this chain's levels
-        if (rc != UR_OK) return rc;
+    HzbDispatch d{};
+    if (s.from_depth) {
+        d.src = depth;
+        d.SW = src_w;
+        d.SH = src_h;
+    } else {
+        d.src = hzb + mips[s.first - 1].offset;
+        d.SW = mips[s.first - 1].width;
+        d.SH = mips[s.first - 1].height;
     }
-    uint32_t mip = 0;
-    while (mip < mip_count) {
-        if (mip > 0 && (uint64_t)mips[mip].width * mips[mip].height <= kTailTexels && mip_count - mip <= kTailMaxLevels) {
-            const HzbTail t = make_tail(hzb, mips, mip_count, mip);
-            if (ctx->defer_hzb_tail) { // the next streaming Lighting launch takes it along (lighting.hip, planned in lighting_plan.cpp); ur_flush otherwise
-                ctx->pending_tail = t;
-                ctx->hzb_tail_pending = true;
-                break;
-            }
-            hipLaunchKernelGGL(hzb_tail_kernel, dim3(1), dim3(1024), 0, ctx->stream, t);
-            UR_HIP_TRY(hipGetLastError());
-            break;
-        }
-        uint32_t n = (mip_count - mip) < 4u ? (mip_count - mip) : 4u;
-        // the first launch also produces mip 4 when a tail launch follows: the tail then starts from 1/4 of the texels
-        // (a single workgroup reads ~25 GB/s: 130 KB of mip 3 at 4K would be 5 us on its own)
-        if (mip == 0 && mip_count > 4u && (uint64_t)mips[4].width * mips[4].height <= kTailTexels) n = 5u;
-        // What has to fit the tail's LDS is ITS first level, mip 5; its parent, mip 4, is read from global memory: at 8K 130 KB
-        // through one workgroup. With 4-byte taps that was a 9-us tail (slower than a third launch); with the 16-byte loads of
-        // tail_first_level_vec it is two launches for every chain up to 8K.
-        else if (mip == 0 && mip_count > 5u && (uint64_t)mips[5].width * mips[5].height <= kTailTexels &&
-                 mip_count - 5u <= kTailMaxLevels) n = 5u;
-        HzbDispatch d{};
-        if (mip == 0) {
-            d.src = depth;
-            d.SW = src_w;
-            d.SH = src_h;
+    for (uint32_t k = 0; k < 5; ++k) {
+        if (k < s.levels) {
+            d.dst[k] = hzb + mips[s.first + k].offset;
+            d.W[k] = mips[s.first + k].width;
+            d.H[k] = mips[s.first + k].height;
         } else {
-            d.src = hzb + mips[mip - 1].offset;
-            d.SW = mips[mip - 1].width;
-            d.SH = mips[mip - 1].height;
+            d.dst[k] = nullptr;
+            d.W[k] = 0;
+            d.H[k] = 0;
         }
-        for (uint32_t k = 0; k < 5; ++k) {
-            if (k < n) {
-                d.dst[k] = hzb + mips[mip + k].offset;
-                d.W[k] = mips[mip + k].width;
-                d.H[k] = mips[mip + k].height;
-            } else {
-                d.dst[k] = nullptr;
-                d.W[k] = 0;
-                d.H[k] = 0;
-            }
-        }
-        d.mips = n;
-        d.vec4_ok = ((d.SW & 3u) == 0u && (reinterpret_cast<uintptr_t>(d.src) & 15u) == 0u) ? 1u : 0u;
-        d.pair_ok = ((d.W[0] & 1u) == 0u && (reinterpret_cast<uintptr_t>(d.dst[0]) & 7u) == 0u) ? 1u : 0u;
-        const dim3 grid((d.W[0] + 63u) / 64u, (d.H[0] + 15u) / 16u);
-        // ur_defer_hzb_tail(ctx, 2): a chain that is ONE five-level launch from the depth buffer plus the single-workgroup tail
-        // (1080p, 4K and 8K all are) is held back as a whole: the next streaming Lighting launch takes its 128x32 pieces
-        // along (lighting.hip, if lighting_plan.cpp finds that they can ride), ur_flush / a cull / another build launch it the ordinary way
-        if (mip == 0 && n == 5u && ctx->defer_hzb_tail && ctx->defer_hzb_wide && mip_count > 5u &&
-            (uint64_t)mips[5].width * mips[5].height <= kTailTexels && mip_count - 5u <= kTailMaxLevels && ctx->hzb_done != nullptr) {
-            ctx->pending_wide = d;
-            ctx->pending_wide_grid_x = grid.x;
-            ctx->pending_wide_grid_y = grid.y;
-            ctx->hzb_wide_pending = true;
-            mip += n;
-            continue;
-        }
-        hipLaunchKernelGGL(hzb_reduce4_kernel, grid, dim3(256), 0, ctx->stream, d);
-        UR_HIP_TRY(hipGetLastError());
-        mip += n;
     }
-    return UR_OK;
+    d.mips = s.levels;
+    d.vec4_ok = ((d.SW & 3u) == 0u && (reinterpret_cast<uintptr_t>(d.src) & 15u) == 0u) ? 1u : 0u;
+    d.pair_ok = ((d.W[0] & 1u) == 0u && (reinterpret_cast<uintptr_t>(d.dst[0]) & 7u) == 0u) ? 1u : 0u;
+    d.by0 = s.by0;
+    return d;
 }
 
-// ---- band-sharded chain (multi-GPU, SURVEY.md section 8e row 3's alternative): a rank builds mips 0..4 for the 128x32 source pieces
-// whose first row lies in its band - every value of those levels depends on its own piece only, so the slices are the whole-frame
-// launch's bits -, the slices are all-gathered by the host, and the single-workgroup tail (mips 5..) runs on every rank behind it.
-static bool chain_is_wide_plus_tail(const ur_mip_desc* mips, uint32_t mip_count)
-{
-    return mip_count > 5u && (uint64_t)mips[5].width * mips[5].height <= kTailTexels && mip_count - 5u <= kTailMaxLevels;
-}
-
-static HzbTail make_tail(float* hzb, const ur_mip_desc* mips, uint32_t mip_count, uint32_t mip)
+// The tail step of a plan bound to its buffers
+static HzbTail bind_tail(const HzbStep& s, float* hzb, const ur_mip_desc* mips)
 {
     HzbTail t{};
-    t.src = hzb + mips[mip - 1].offset;
-    t.SW = mips[mip - 1].width;
-    t.SH = mips[mip - 1].height;
-    t.first_mip = mip;
-    t.levels = mip_count - mip;
+    t.src = hzb + mips[s.first - 1].offset;
+    t.SW = mips[s.first - 1].width;
+    t.SH = mips[s.first - 1].height;
+    t.first_mip = s.first;
+    t.levels = s.levels;
     for (uint32_t k = 0; k < t.levels; ++k) {
-        t.dst[k] = hzb + mips[mip + k].offset;
-        t.W[k] = mips[mip + k].width;
-        t.H[k] = mips[mip + k].height;
+        t.dst[k] = hzb + mips[s.first + k].offset;
+        t.W[k] = mips[s.first + k].width;
+        t.H[k] = mips[s.first + k].height;
         t.magic[k] = t.W[k] > 1u ? (uint32_t)((1ull << 32) / t.W[k] + 1ull) : 0u; // W == 1: y = i (handled in the kernel)
     }
     return t;
 }
 
+static int launch_wide(ur_ctx* ctx, const HzbDispatch& d, uint32_t grid_x, uint32_t grid_y)
+{
+    hipLaunchKernelGGL(hzb_reduce4_kernel, dim3(grid_x, grid_y), dim3(256), 0, ctx->stream, d);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+static int launch_tail(ur_ctx* ctx, const HzbTail& t)
+{
+    hipLaunchKernelGGL(hzb_tail_kernel, dim3(1), dim3(1024), 0, ctx->stream, t);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+// Every step of a plan in order: launched, or held on the context for the next streaming Lighting launch (ur_flush otherwise)
+static int run_plan(ur_ctx* ctx, const HzbPlan& plan, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb, const ur_mip_desc* mips)
+{
+    for (uint32_t i = 0; i < plan.count; ++i) {
+        const HzbStep& s = plan.steps[i];
+        int rc = UR_OK;
+        if (s.kind == HzbStep::wide) {
+            const HzbDispatch d = bind_wide(s, depth, src_w, src_h, hzb, mips);
+            if (s.hold) ctx->held_hzb.hold_wide(d, s.grid_x, s.grid_y);
+            else rc = launch_wide(ctx, d, s.grid_x, s.grid_y);
+        } else {
+            const HzbTail t = bind_tail(s, hzb, mips);
+            if (s.hold) ctx->held_hzb.hold_tail(t);
+            else rc = launch_tail(ctx, t);
+        }
+        if (rc != UR_OK) return rc;
+    }
+    return UR_OK;
+}
+
+// The three forms below: flush what is held (an earlier chain's tail must not run after this chain's levels), plan (csrc/hzb_plan.cpp),
+// then launch or hold each step.
+int launch_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb, const ur_mip_desc* mips,
+                     uint32_t mip_count)
+{
+    const int rc = flush_hzb_tail(ctx);
+    if (rc != UR_OK) return rc;
+    const HzbPlan plan = plan_hzb_chain(src_w, src_h, mips, mip_count, ctx->held_hzb.mode(), ctx->hzb_done != nullptr);
+    if (plan.status != HzbPlan::ok) { set_error("ur_build_hzb: mip chain does not match CreateHZBResources sizing"); return UR_EINVAL; }
+    return run_plan(ctx, plan, depth, src_w, src_h, hzb, mips);
+}
+
 int launch_build_hzb_band(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb, const ur_mip_desc* mips, uint32_t mip_count,
                           uint32_t piece_row0, uint32_t piece_rows)
 {
-    {
-        const int rc = flush_hzb_tail(ctx);
-        if (rc != UR_OK) return rc;
-    }
-    if (!chain_is_wide_plus_tail(mips, mip_count)) {
+    const int rc = flush_hzb_tail(ctx);
+    if (rc != UR_OK) return rc;
+    const HzbPlan plan = plan_hzb_band(src_w, src_h, mips, mip_count, ctx->held_hzb.mode(), piece_row0, piece_rows);
+    if (plan.status == HzbPlan::not_wide_plus_tail) {
         set_error("ur_build_hzb_band: a %u x %u frame's chain is not one five-level launch plus the tail (build it whole: ur_build_hzb)", src_w, src_h);
         return UR_EUNSUPPORTED;
     }
-    HzbDispatch d{};
-    d.src = depth; d.SW = src_w; d.SH = src_h;
-    for (uint32_t k = 0; k < 5; ++k) { d.dst[k] = hzb + mips[k].offset; d.W[k] = mips[k].width; d.H[k] = mips[k].height; }
-    d.mips = 5u;
-    d.vec4_ok = ((d.SW & 3u) == 0u && (reinterpret_cast<uintptr_t>(d.src) & 15u) == 0u) ? 1u : 0u;
-    d.pair_ok = ((d.W[0] & 1u) == 0u && (reinterpret_cast<uintptr_t>(d.dst[0]) & 7u) == 0u) ? 1u : 0u;
-    d.by0 = piece_row0;
-    const dim3 grid((d.W[0] + 63u) / 64u, piece_rows);
-    if (piece_rows == 0u) return UR_OK;
-    if (ctx->defer_hzb_tail && ctx->defer_hzb_wide) { // rides the next streaming Lighting launch (no tail: it waits for the gather)
-        ctx->pending_wide = d;
-        ctx->pending_wide_grid_x = grid.x;
-        ctx->pending_wide_grid_y = grid.y;
-        ctx->hzb_wide_pending = true;
-        return UR_OK;
-    }
-    hipLaunchKernelGGL(hzb_reduce4_kernel, grid, dim3(256), 0, ctx->stream, d);
-    UR_HIP_TRY(hipGetLastError());
-    return UR_OK;
+    if (plan.status != HzbPlan::ok) { set_error("ur_build_hzb_band: mip chain does not match CreateHZBResources sizing"); return UR_EINVAL; }
+    return run_plan(ctx, plan, depth, src_w, src_h, hzb, mips);
 }
 
 int launch_build_hzb_tail(ur_ctx* ctx, float* hzb, const ur_mip_desc* mips, uint32_t mip_count)
 {
-    {
-        const int rc = flush_hzb_tail(ctx);
-        if (rc != UR_OK) return rc;
-    }
-    if (!chain_is_wide_plus_tail(mips, mip_count)) {
+    const int rc = flush_hzb_tail(ctx);
+    if (rc != UR_OK) return rc;
+    const HzbPlan plan = plan_hzb_tail(mips, mip_count);
+    if (plan.status == HzbPlan::not_wide_plus_tail) {
         set_error("ur_build_hzb_tail: the chain is not one five-level launch plus the tail");
         return UR_EUNSUPPORTED;
     }
-    hipLaunchKernelGGL(hzb_tail_kernel, dim3(1), dim3(1024), 0, ctx->stream, make_tail(hzb, mips, mip_count, 5u));
-    UR_HIP_TRY(hipGetLastError());
-    return UR_OK;
+    if (plan.status != HzbPlan::ok) { set_error("ur_build_hzb_tail: bad argument"); return UR_EINVAL; }
+    return run_plan(ctx, plan, nullptr, 0u, 0u, hzb, mips);
 }
 
 int flush_hzb_tail(ur_ctx* ctx)
 {
-    if (ctx->hzb_wide_pending) { // the held-back wide launch goes first (the tail reads what it writes)
-        ctx->hzb_wide_pending = false;
-        hipLaunchKernelGGL(hzb_reduce4_kernel, dim3(ctx->pending_wide_grid_x, ctx->pending_wide_grid_y), dim3(256), 0, ctx->stream, ctx->pending_wide);
-        UR_HIP_TRY(hipGetLastError());
+    if (ctx->held_hzb.has_wide()) { // the held-back wide launch goes first (the tail reads what it writes)
+        const HeldHzb::Wide& w = ctx->held_hzb.take_wide();
+        const int rc = launch_wide(ctx, w.d, w.grid_x, w.grid_y);
+        if (rc != UR_OK) return rc;
     }
-    if (!ctx->hzb_tail_pending) return UR_OK;
-    ctx->hzb_tail_pending = false;
-    hipLaunchKernelGGL(hzb_tail_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->pending_tail);
-    UR_HIP_TRY(hipGetLastError());
-    return UR_OK;
+    if (!ctx->held_hzb.has_tail()) return UR_OK;
+    return launch_tail(ctx, ctx->held_hzb.take_tail());
+}
+
+int check_hzb_timeout(ur_ctx* ctx, const char* who)
+{
+    if (ctx && ctx->claim_timed_out && *ctx->claim_timed_out != 0u) {
+        *ctx->claim_timed_out = 0u;
+        (void)hipMemsetAsync(ctx->claim_words, 0, (kClaimWords + 1u) * kClaimWordStride * sizeof(uint32_t), ctx->stream);
+        set_error("%s: a wave of a balanced Lighting launch gave up waiting for a tile claim of its workgroup: tiles of that launch were not shaded — "
+                  "shade the frame again (reported once; the context is usable)", who);
+        return UR_ETIMEOUT;
+    }
+    if (!ctx || !ctx->hzb_timed_out || *ctx->hzb_timed_out == 0u) return UR_OK;
+    *ctx->hzb_timed_out = 0u;
+    (void)hipMemsetAsync(ctx->hzb_done, 0, 64, ctx->stream); // stragglers may have left any count behind
+    set_error("%s: the tail of a Build HZB chain that rode a Lighting launch gave up waiting for its producers: the HZB's small levels are stale — "
+              "build it again (reported once; the context is usable)", who);
+    return UR_ETIMEOUT;
 }
 
 } // namespace ur
+
+// ---- the entry points (include/ur_hotpath.h): argument checks and error texts; the arithmetic is csrc/hzb_plan.cpp's ----
+
+using ur::set_error;
+
+extern "C" {
+
+int ur_defer_hzb_tail(ur_ctx* ctx, int enable)
+{
+    if (!ctx) { set_error("ur_defer_hzb_tail: null context"); return UR_EINVAL; }
+    if (enable < 0 || enable > 2) { set_error("ur_defer_hzb_tail: mode %d (0 off, 1 tail, 2 whole chain)", enable); return UR_EINVAL; }
+    return ctx->held_hzb.set_mode(enable) ? ur::flush_hzb_tail(ctx) : UR_OK; // (a narrower mode flushes)
+}
+
+int ur_flush(ur_ctx* ctx)
+{
+    if (!ctx) { set_error("ur_flush: null context"); return UR_EINVAL; }
+    const int trc = ur::check_hzb_timeout(ctx, "ur_flush");
+    if (trc != UR_OK) return trc;
+    return ur::flush_hzb_tail(ctx);
+}
+
+uint32_t ur_hzb_layout(uint32_t src_w, uint32_t src_h, ur_mip_desc* mips, uint32_t* mip_count)
+{
+    if (!mips || !mip_count || src_w == 0 || src_h == 0) return 0;
+    return ur::hzb_layout(src_w, src_h, mips, mip_count);
+}
+
+int ur_build_hzb(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb_base, const ur_mip_desc* mips,
+                 uint32_t mip_count)
+{
+    if (!ctx || !depth || !hzb_base || src_w == 0 || src_h == 0) { set_error("ur_build_hzb: null/zero argument"); return UR_EINVAL; }
+    if (!ur::valid_hzb_chain(src_w, src_h, mips, mip_count)) { set_error("ur_build_hzb: mip chain does not match CreateHZBResources sizing"); return UR_EINVAL; }
+    const int trc = ur::check_hzb_timeout(ctx, "ur_build_hzb");
+    if (trc != UR_OK) return trc;
+    return ur::launch_build_hzb(ctx, depth, src_w, src_h, hzb_base, mips, mip_count);
+}
+
+int ur_hzb_band_pieces(uint32_t src_h, uint32_t n_ranks, uint32_t rank, uint32_t* piece_row0, uint32_t* piece_rows)
+{
+    if (src_h == 0 || n_ranks == 0 || rank >= n_ranks || src_h % n_ranks != 0 || !piece_row0 || !piece_rows) { set_error("ur_hzb_band_pieces: bad argument"); return UR_EINVAL; }
+    ur::hzb_band_pieces(src_h, n_ranks, rank, piece_row0, piece_rows);
+    return UR_OK;
+}
+
+int ur_hzb_band_slices(const ur_mip_desc* mips, uint32_t mip_count, uint32_t piece_row0, uint32_t piece_rows, ur_hzb_slice* out5)
+{
+    if (!mips || mip_count < 5 || !out5) { set_error("ur_hzb_band_slices: bad argument"); return UR_EINVAL; }
+    ur::hzb_band_slices(mips, piece_row0, piece_rows, out5);
+    return UR_OK;
+}
+
+int ur_build_hzb_band(ur_ctx* ctx, const float* depth, uint32_t src_w, uint32_t src_h, float* hzb_base, const ur_mip_desc* mips, uint32_t mip_count,
+                      uint32_t piece_row0, uint32_t piece_rows)
+{
+    if (!ctx || !depth || !hzb_base || src_w == 0 || src_h == 0) { set_error("ur_build_hzb_band: null/zero argument"); return UR_EINVAL; }
+    if (!ur::valid_hzb_chain(src_w, src_h, mips, mip_count)) { set_error("ur_build_hzb_band: mip chain does not match CreateHZBResources sizing"); return UR_EINVAL; }
+    if ((uint64_t)piece_row0 + piece_rows > (src_h + 31u) / 32u) { set_error("ur_build_hzb_band: piece rows [%u, %u) of %u", piece_row0, piece_row0 + piece_rows, (src_h + 31u) / 32u); return UR_EINVAL; }
+    const int trc = ur::check_hzb_timeout(ctx, "ur_build_hzb_band");
+    if (trc != UR_OK) return trc;
+    return ur::launch_build_hzb_band(ctx, depth, src_w, src_h, hzb_base, mips, mip_count, piece_row0, piece_rows);
+}
+
+int ur_build_hzb_tail(ur_ctx* ctx, float* hzb_base, const ur_mip_desc* mips, uint32_t mip_count)
+{
+    if (!ctx || !hzb_base || !ur::valid_hzb_chain_below_mip0(mips, mip_count)) { set_error("ur_build_hzb_tail: bad argument"); return UR_EINVAL; }
+    const int trc = ur::check_hzb_timeout(ctx, "ur_build_hzb_tail");
+    if (trc != UR_OK) return trc;
+    return ur::launch_build_hzb_tail(ctx, hzb_base, mips, mip_count);
+}
+
+} // extern "C"

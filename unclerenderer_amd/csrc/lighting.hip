@@ -967,8 +967,8 @@ int launch_lighting_stream(ur_ctx* ctx, const LightingParams& params, int mode, 
     const uint32_t wpb = ctx->opt.lighting_wpb == 12 ? 12u : 16u; // UR_OPT_LIGHTING_WAVES_PER_WG
     const ur_ctx::Options& o = ctx->opt;
     const StreamPlan s = plan_stream({ctx->cu_count, o.leave_cus, o.ride_walkers, o.balance, o.balance_pool_16ths, o.balance_chunk_shift, o.debug_hzb_ride_stall,
-                                      params.W, params.rows, wpb, ctx->hzb_tail_pending, ctx->hzb_wide_pending, ctx->pending_wide_grid_x,
-                                      ctx->pending_wide_grid_y, ctx->claim_words != nullptr ? kClaimWords : 0u});
+                                      params.W, params.rows, wpb, ctx->held_hzb.has_tail(), ctx->held_hzb.has_wide(), ctx->held_hzb.wide_grid_x(),
+                                      ctx->held_hzb.wide_grid_y(), ctx->claim_words != nullptr ? kClaimWords : 0u});
     LightingParams p = params; // the tile walk is filled in here
     p.timeline = next_timeline_pair(ctx);
     StreamHot& h = p.hot;
@@ -978,12 +978,11 @@ int launch_lighting_stream(ur_ctx* ctx, const LightingParams& params, int mode, 
     // what the plan consumes of the context's held-back HZB chain
     HzbTail tail{};
     HzbRide ride{};
-    if (s.carry_tail) { tail = ctx->pending_tail; ctx->hzb_tail_pending = false; }
+    if (s.carry_tail) tail = ctx->held_hzb.take_tail();
     if (s.rides) {
-        ride.d = ctx->pending_wide;
+        ride.d = ctx->held_hzb.take_wide().d;
         ride.grid_x = s.ride_grid_x; ride.pieces = s.ride_pieces; ride.walkers = s.ride_walkers; ride.spin_limit = s.ride_spin_limit;
         if (s.carry_tail) { ride.done = ctx->hzb_done; ride.timed_out = ctx->hzb_timed_out_dev; }
-        ctx->hzb_wide_pending = false;
     } else if (s.flush_first) { // cannot ride (12-wave build, tiny device): the ordinary launches, in front
         const int frc = flush_hzb_tail(ctx);
         if (frc != UR_OK) return frc;

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+struct ur_half4; // include/ur_hotpath.h
+
 namespace ur {
 
 constexpr uint32_t kChunkShift = 2;       // static deal: chunks of 4 consecutive tiles (4K, round 1: chunks of 16 / 4 / 1 tiles -> 75.4 / 74.6 / 79.1 us)
@@ -27,6 +29,9 @@ struct CubeLayout {
 CubeLayout cube_layout(uint32_t base_size, uint32_t mip_count);
 // The first of the smallest mips whose row-pair entries together fit `budget` bytes (L.mips: not even the last one does)
 uint32_t cube_first_mip_within(const CubeLayout& L, uint64_t budget);
+// (env_cube_stage.cpp) Writes both sections into `out`, L.texels half4 units of host memory, from the source cube `src`: face-major, every
+// face its mips 0 .. L.mips - 1 of size(m)^2 texels one after the other. ur_stage_env_cube copies the result to the device.
+void stage_env_cube_host(const ur_half4* src, const CubeLayout& L, ur_half4* out);
 
 // ---- the schedule of one streaming launch ------------------------------------------------------------------------------------------------
 struct StreamPlanInput {

@@ -1,6 +1,6 @@
-// The host-only view of the internals: what host callers outside ur_api.hip (the frame units, csrc/frame/) need of them. No device code
+// The host-only view of the internals: what host callers outside the C-ABI units (the frame units, csrc/frame/) need of them. No device code
 // and nothing of ur_ctx's layout: a plain C++ compiler takes it. ur_internal.h includes it; the definitions stay where they were
-// (ur_api.hip, cull_views.hip, raster.hip, gbuffer_resolve.hip). Not installed.
+// (ur_api.hip, cull_api.hip, raster.hip, gbuffer_resolve.hip). Not installed.
 #pragma once
 
 #include <cstddef>
@@ -22,6 +22,15 @@ inline bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_byte
 // Are rows [row0, row0 + rows) inside a w x h frame that is not empty? (rows == 0 is inside: an entry point that refuses an empty band
 // says so beside the call.) The refusal's text stays the entry point's own.
 inline bool band_in_frame(uint32_t w, uint32_t h, uint32_t row0, uint32_t rows) { return w != 0 && h != 0 && (uint64_t)row0 + rows <= h; }
+// The Lighting, Sky and GpuDebugPrint entry points' check of the context, the frame and the band, with their text
+inline int check_band(const char* who, const ur_ctx* ctx, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows)
+{
+    if (!ctx || w == 0 || h == 0 || (uint64_t)row0 + rows > h) {
+        set_error("%s: bad frame/band (w=%u h=%u row0=%u rows=%u)", who, w, h, row0, rows);
+        return UR_EINVAL;
+    }
+    return UR_OK;
+}
 
 // ur_cull_indirect_args_views' checks of views that need no command count (ur_frame_set_cull_views)
 int check_cull_views(const ur_cull_view* views, uint32_t view_count);

@@ -9,9 +9,10 @@
 #include "../../include/ur_hotpath.h"
 #include "../../include/ur_raster.h"
 
+#include "hzb_plan.h" // ur::kTailMaxLevels, ur::kTailTexels
+
 namespace ur {
 // Arguments of the single-workgroup tail of the HZB chain (csrc/hzb_tail.h): the levels from `first_mip` on.
-constexpr uint32_t kTailMaxLevels = 12, kTailTexels = 16384;
 constexpr uint32_t kClaimWords = 32, kClaimWordStride = 32; // (stride in uint32: 128 bytes)
 struct HzbTail {
     const float* src; // mip first_mip - 1 (global memory, written by the previous launch)
@@ -22,6 +23,42 @@ struct HzbTail {
 };
 } // namespace ur
 #include "hzb_wide.h"
+
+namespace ur {
+// The held-back Build HZB chain of a context (ur_defer_hzb_tail), and the only code that touches that state. The HZB tail may ride
+// along with the next streaming Lighting launch as one extra workgroup: its single workgroup is ~5 us of latency during which the
+// other 255 CUs would idle. ur_defer_hzb_tail(ctx, 2): the wide launch in front of the tail is held back too; the Lighting launch's
+// workgroups take its 128x32 pieces along (one wave of each) and signal `hzb_done`, which the riding tail workgroup waits for.
+// Whoever launches what is held launches the wide step before the tail (the tail reads what it writes); taking a step clears it;
+// ur_destroy discards both and launches neither.
+class HeldHzb {
+public:
+    struct Wide { HzbDispatch d; uint32_t grid_x, grid_y; };
+    int mode() const { return mode_; } // ur_defer_hzb_tail's: 0 off, 1 tail, 2 whole chain
+    // true: the new mode is narrower than the old one, and what is held has to go out (flush_hzb_tail)
+    bool set_mode(int mode)
+    {
+        const bool narrower = (mode == 0) || (mode == 1 && mode_ == 2);
+        mode_ = mode;
+        return narrower;
+    }
+    void hold_tail(const HzbTail& t) { tail_ = t; has_tail_ = true; }
+    void hold_wide(const HzbDispatch& d, uint32_t grid_x, uint32_t grid_y) { wide_ = Wide{d, grid_x, grid_y}; has_wide_ = true; }
+    bool has_tail() const { return has_tail_; }
+    bool has_wide() const { return has_wide_; }
+    uint32_t wide_grid_x() const { return wide_.grid_x; } // (of the step held now or last: what plan_stream is told beside has_wide)
+    uint32_t wide_grid_y() const { return wide_.grid_y; }
+    const HzbTail& take_tail() { has_tail_ = false; return tail_; } // (valid until the next hold_tail)
+    const Wide& take_wide() { has_wide_ = false; return wide_; }
+    void discard() { has_tail_ = has_wide_ = false; }
+
+private:
+    int mode_ = 0;
+    bool has_tail_ = false, has_wide_ = false;
+    HzbTail tail_{};
+    Wide wide_{};
+};
+} // namespace ur
 
 struct ur_ctx {
     int device = 0;
@@ -41,17 +78,7 @@ struct ur_ctx {
     // 127 thresholds 2^(j / 128) (ur_host_lod_table), uploaded once: the textured GBuffer resolve's level of detail
     float* lod_table = nullptr;
     int cu_count = 256;
-    // The HZB tail may ride along with the next streaming Lighting launch as one extra workgroup (ur_defer_hzb_tail):
-    // its single workgroup is ~5 us of latency during which the other 255 CUs would idle.
-    bool defer_hzb_tail = false;
-    bool hzb_tail_pending = false;
-    ur::HzbTail pending_tail{};
-    // ur_defer_hzb_tail(ctx, 2): the wide launch in front of the tail is held back too; the Lighting launch's workgroups take its
-    // 128x32 pieces along (one wave of each) and signal `hzb_done`, which the riding tail workgroup waits for.
-    bool defer_hzb_wide = false;
-    bool hzb_wide_pending = false;
-    ur::HzbDispatch pending_wide{};
-    uint32_t pending_wide_grid_x = 0, pending_wide_grid_y = 0;
+    ur::HeldHzb held_hzb; // ur_defer_hzb_tail's mode and what it holds back of a Build HZB chain
     // ur_debug_timeline: device array of {first entry, last exit} pairs in s_memrealtime ticks (100 MHz), one pair per cull and per
     // streaming Lighting launch, in launch order (the caller initialises every pair to {~0, 0})
     unsigned long long* timeline = nullptr;
@@ -85,7 +112,7 @@ struct ur_ctx {
     uint32_t raster_queue_cap = 0;
 };
 
-#include "ur_checks.h" // ur::set_error, ur::raster_commands and the check_* functions: what host callers outside ur_api.hip need
+#include "ur_checks.h" // ur::set_error, ur::raster_commands and the check_* functions: what host callers outside the C-ABI units need
 
 namespace ur {
 
@@ -120,7 +147,7 @@ int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_c
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);
 enum { UR_MODE_LIGHTING = 0, UR_MODE_SKY = 1, UR_MODE_FUSED = 2 };
-// GpuDebugPrint (debug_print.hip); arguments checked by the C-ABI in ur_api.hip
+// GpuDebugPrint (debug_print.hip); arguments checked by the entry points beside them
 int launch_debug_print_reset(ur_ctx* ctx, void* buffer, uint32_t* stats);
 int launch_debug_print_stats(ur_ctx* ctx, const uint32_t* stats, void* buffer);
 int launch_debug_print_text(ur_ctx* ctx, void* buffer, uint32_t x, uint32_t y, uint32_t color, const char* text, uint32_t length);
