@@ -6,7 +6,9 @@
  * with a near clip, reverse-Z, into the camera's depth buffer. Its rule is DESIGN.md section 3.8, restated in tests/depth_ref.py.
  * The GBuffer pass (DeferredRenderer.cpp:720-865, Shaders/DeferredBasePass.hlsl, pipeline key 0: no texture maps, no alpha mask) and the
  * ObjectId pass (:867-980, Shaders/ObjectId.hlsl): DepthPrepass' raster writing a visibility key per texel, and a per-texel resolve of
- * the winning key into the render targets. Its rule is DESIGN.md section 3.9, restated in tests/gbuffer_ref.py.
+ * the winning key into the render targets. Its rule is DESIGN.md section 3.9, restated in tests/gbuffer_ref.py. Texture maps (pipeline
+ * keys 0-15) are section 3.10 and tests/gbuffer_tex_ref.py, the alpha-masked permutations (keys 16-31) section 3.11 and
+ * tests/gbuffer_mask_ref.py.
  */
 #ifndef UR_RASTER_H
 #define UR_RASTER_H
@@ -169,8 +171,11 @@ typedef struct ur_texture2d {
 #define UR_MATERIAL_BASE_COLOR_MAP 0x4u         /* USE_BASE_COLOR_MAP, t0 */
 #define UR_MATERIAL_EMISSIVE_MAP 0x8u           /* USE_EMISSIVE_MAP, t3 */
 
+#define UR_MATERIAL_ALPHA_MASK (0x10u)          /* USE_ALPHA_MASK: looked at by ur_gbuffer_pass_masked only, for the draws of its mask */
+
 /* What the reference binds per draw range (DeferredRenderer.cpp:800): the descriptor table t0-t3 and the pipeline key. One record per
- * command slot. Key bits 4 and above are ignored (USE_ALPHA_MASK is not drawn: the caller's ranges keep such models out). A set bit is
+ * command slot. Key bits 4 and above are ignored in ur_gbuffer_pass, _parts, _materials and _materials_parts (USE_ALPHA_MASK is not drawn
+ * by them: the caller's ranges keep such models out, or go to ur_gbuffer_pass_masked); bits 5 and above are ignored everywhere. A set bit is
  * treated as clear when its texture has a null address, an address that is not 4-byte aligned, a zero dimension, zero mips or a format
  * other than the two above. */
 typedef struct ur_material {
@@ -202,6 +207,57 @@ int ur_gbuffer_pass_materials_parts(ur_ctx* ctx, const float view[16], const flo
                                     const float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
                                     uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
                                     const ur_material* materials, uint32_t material_count);
+
+/* The alpha-masked draws of ur_gbuffer_pass_masked. */
+typedef struct ur_gbuffer_mask {
+    const ur_raster_draws* draws; /* the alpha-masked selection; same commands / command_count as the opaque one */
+    uint64_t* keys64;             /* rows x w scratch, 8-byte aligned, owned by the caller */
+    uint32_t* stats6;             /* nullable, added to: ur_depth_prepass' meanings for the masked draws */
+    uint32_t* won;                /* nullable, added to: texels whose final key is a masked fragment's */
+} ur_gbuffer_mask;
+
+/* ur_gbuffer_pass_materials with the alpha-masked permutations, pipeline keys 16-31 of DeferredBasePass.hlsl ("GBuffer" under
+ * BasePassPipelines[16..31], depth write on: DeferredRenderer.cpp:1862-1864), by the rule of DESIGN.md 3.11, restated in
+ * tests/gbuffer_mask_ref.py. `draws` are the opaque models, drawn exactly as ur_gbuffer_pass_materials draws them, against `depth` (the
+ * prepass of the opaque models only, as in the reference) into targets->keys. mask->draws are the masked models, a second selection over
+ * the same commands and command_count, so that the keys of both share one space. A masked fragment is rasterised like any other and
+ * passes iff its depth is >= depth[texel] as the call found it; when bit 4 (UR_MATERIAL_ALPHA_MASK) of its slot's pipeline_key is set it
+ * is discarded iff alpha < AlphaCutoff, alpha = BaseColorAlpha * interpolated COLOR.a (vertex byte 60), times channel A of the base-colour
+ * map (code / 255, never decoded; the resolve's sampler at the resolve's coordinates and derivatives) when bit 2 is set and the
+ * descriptor is valid. AlphaMode in the constants is not consulted; a slot >= material_count, or materials == NULL, has key 0: nothing of
+ * it is discarded. Per texel the surviving masked fragment of the greatest depth wins, the greatest key among equal depths; it replaces
+ * the opaque key iff its depth is above depth[texel], or its key above the opaque key (it passed, so its depth is not below). Where it
+ * does, depth[texel] is raised to its depth - the depth buffer the reference's "GBuffer" pass leaves for "Build HZB" - and
+ * mask->keys64[texel] keeps (depth bits << 32) | key; everywhere else in the band keys64 ends as 0. The resolve then runs over the final
+ * keys; the pixel shader behind the alpha test is that of the key without bit 4.
+ * With visible lists the ordinal of a key is the position in its own selection's list: a tie between the two selections at exactly equal
+ * depth is decided by the key's value, which is D3D's draw order only for the slot-indexed selections (every slot, ranges). The resolve
+ * then tells the selections apart by keys64.
+ * mask == NULL is ur_gbuffer_pass_materials: depth is then not written. Either selection may select nothing, and command_count may be 0.
+ * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most eight launches (clear, raster and
+ * large-triangle queue of the opaque draws, the same three of the masked draws - the queue is reused in stream order -, merge, resolve).
+ * Read: what ur_gbuffer_pass_materials reads, for both selections; materials[s] for every slot s < material_count of a masked fragment
+ * that passes the depth test; of a masked draw's textures the raster reads the base-colour chain only (4-byte texels inside its `mips`
+ * levels), the resolve what ur_gbuffer_pass_materials' reads; TEXCOORD and COLOR.a (bytes 24-31 and 60-63) of such a fragment's vertices and
+ * the constants behind ConstantBufferAddress.
+ * Written: ur_gbuffer_pass_materials' targets; all rows * w words of keys64; of depth only rows [row0, row0 + rows), and of those only
+ * the texels that `won` counts. stats6 counts the opaque draws, mask->stats6 the masked ones, mask->won is added to.
+ * UR_EINVAL, nothing launched: ur_gbuffer_pass_materials' cases for both selections; a null mask->draws; a null keys64 or one that is not
+ * 8-byte aligned; a misaligned mask->stats6 or won; mask->draws over other commands or another command_count than draws; keys64
+ * overlapping a target or depth.
+ * UR_EUNSUPPORTED, nothing launched: targets->object_id together with a mask (the reference's ObjectId pass ignores the alpha test and
+ * tests against the depth this pass writes: it needs a raster of its own). */
+int ur_gbuffer_pass_masked(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                           float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                           uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, const ur_material* materials, uint32_t material_count,
+                           const ur_gbuffer_mask* mask);
+
+/* ur_gbuffer_pass_masked in parts, as ur_gbuffer_pass_parts: UR_GBUFFER_PART_RASTER is the six raster launches and the merge (it writes
+ * keys, keys64 and depth), UR_GBUFFER_PART_RESOLVE the resolve over keys and keys64 as that part left them. */
+int ur_gbuffer_pass_masked_parts(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                                 float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                                 uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
+                                 const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
     python tools/bench_shadow.py --pass both # ShadowMap, then the DepthPrepass pass (ur_depth_prepass) over the same triangles
     python tools/bench_shadow.py --pass gbuffer # the GBuffer pass (ur_gbuffer_pass) at 3840 x 2160, its two halves timed apart
     python tools/bench_shadow.py --pass gbuffer --textured # the textured resolve (key 15) beside the untextured one and a streaming kernel
+    python tools/bench_shadow.py --pass gbuffer --masked # the alpha-masked raster (ur_gbuffer_pass_masked) beside the all-opaque one
 
 A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
   small   1 M triangles of 1/8 px to 8 px in one command;
@@ -248,6 +249,87 @@ def gbuffer_textured_leg(a, torch, hp):
     return rows
 
 
+def gbuffer_masked_leg(a, torch, hp):
+    """The rows of --pass gbuffer --masked: at 3840 x 2160 over cold buffer sets, the textured small-triangle workload cut into 8 commands
+    on one 1024 x 1024 base-colour map whose alpha is random bytes; 3 of the 8 (slots 2, 5, 7) are the masked selection on pipeline key
+    31, the others the opaque one on key 15. ur_gbuffer_pass_masked raises the depth it is given, so every timed call starts with the
+    DepthPrepass it belongs behind, and the prepasses are timed alone beside them, in the same process, batch by batch:
+      DepthPrepass of the opaque draws;              ... + the raster part with the mask (six raster launches and the merge);
+      DepthPrepass of all draws;                     ... + the raster part of ur_gbuffer_pass_materials on all draws, bit 4 cleared;
+                                                     ... + the whole ur_gbuffer_pass_materials on all draws, bit 4 cleared;
+      DepthPrepass of the opaque draws + the whole ur_gbuffer_pass_masked.
+    stats_one_call of a masked row is the masked draws' stats6; `won` the texels a masked fragment won in one call."""
+    from unclerenderer_amd import lib
+    from unclerenderer_amd.hotpath import gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, raster_draws, to_device
+    w, h = GBUFFER_W, GBUFFER_H
+    rng = np.random.default_rng(2162)
+    cb = np.zeros(152, np.float32)
+    cb[:16] = np.eye(4, dtype=np.float32).reshape(-1)
+    cb[64:68], cb[80:83], cb[104], cb[105], cb[106], cb[107] = (0.8, 0.7, 0.6, 1.0), (0.1, 0.2, 0.3), 0.25, 0.5, 1.0, 0.5
+    for at in (112, 120, 128, 136):
+        cb[at + 2], cb[at + 3], cb[at + 4] = 1.0, 1.0, 1.0
+    constants = to_device(cb)
+    pos = camera_space(triangles(rng, a.small, 0.125, 8.0, w, h))
+    v = np.zeros((pos.shape[0], 16), np.float32)
+    v[:, :3], v[:, 5] = pos, -1.0
+    v[:, 6], v[:, 7] = pos[:, 0] / pos[:, 2] * (0.5 * w / 256.0), pos[:, 1] / pos[:, 2] * (0.5 * h / 256.0 * 2.5)
+    v[:, 8], v[:, 11], v[:, 12:16] = 1.0, 1.0, 1.0
+    vb, ib = to_device(v.reshape(-1)), to_device(np.arange(pos.shape[0], dtype=np.uint32))
+    n, masked_slots = 8, (2, 5, 7)
+    cuts = (np.linspace(0, pos.shape[0] // 3, n + 1).astype(int) * 3).tolist()
+    cmds = to_device(pack_draw_commands([dict(vertices=vb, indices=ib, constants=constants, stride=64, start_index=cuts[k], index_count=cuts[k + 1] - cuts[k]) for k in range(n)]))
+    tex = pack_texture([rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)], True)
+    table = lambda masked: pack_materials([{"key": 31 if masked and k in masked_slots else 15, "base_color": tex, "emissive": tex, "metallic_roughness": tex,  # noqa: E731
+                                            "normal": tex} for k in range(n)])
+    with_mask, without = table(True), table(False)
+
+    def ranges(slots):
+        return (to_device(np.array(list(slots) + [n], np.uint32)), cmds, to_device(np.ones(len(slots), np.uint32)))
+
+    opaque, masked = ranges([k for k in range(n) if k not in masked_slots]), ranges(masked_slots)
+    mask_draws = raster_draws(None, None, None, masked, 0)
+    sets = []
+    for _ in range(a.ring):
+        ga, gb, hdr = (torch.empty((h, w, 4), dtype=torch.float16, device="cuda") for _ in range(3))
+        gc, keys = (torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(2))
+        sets.append((torch.zeros((h, w), dtype=torch.float32, device="cuda"), gbuffer_targets(ga, gb, gc, hdr, keys), torch.zeros((h, w), dtype=torch.int64, device="cuda")))
+    mstats, won = torch.zeros(6, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    RASTER = lib.UR_GBUFFER_PART_RASTER
+    hp.raster_reserve(a.reserve)
+
+    def pre(i, sel):
+        hp.depth_prepass(VIEW, PROJ, None if sel is not None else cmds, sets[i % a.ring][0], ranges=sel)
+
+    def masked_call(i, parts, st=None, wn=None):
+        pre(i, opaque)
+        d, tg, k64 = sets[i % a.ring]
+        hp.gbuffer_pass(VIEW, PROJ, None, d, tg, w, h, ranges=opaque, parts=parts, materials=with_mask, mask_draws=mask_draws, keys64=k64, mask_stats=st, won=wn)
+
+    def opaque_call(i, parts):
+        pre(i, None)
+        d, tg, _ = sets[i % a.ring]
+        hp.gbuffer_pass(VIEW, PROJ, cmds, d, tg, w, h, parts=parts, materials=without)
+
+    masked_call(0, None, mstats, won)
+    torch.cuda.synchronize()
+    seen, texels_won = mstats.cpu().numpy().view(np.uint32).tolist(), int(won.cpu().numpy().view(np.uint32)[0])
+    fns = {"DepthPrepass of the opaque draws": lambda i: pre(i, opaque),
+           "DepthPrepass of the opaque draws + raster part with the mask": lambda i: masked_call(i, RASTER),
+           "DepthPrepass of the opaque draws + whole ur_gbuffer_pass_masked": lambda i: masked_call(i, None),
+           "DepthPrepass of all draws": lambda i: pre(i, None),
+           "DepthPrepass of all draws + raster part, bit 4 cleared": lambda i: opaque_call(i, RASTER),
+           "DepthPrepass of all draws + whole ur_gbuffer_pass_materials, bit 4 cleared": lambda i: opaque_call(i, None)}
+    times = {k: [] for k in fns}
+    for f in fns.values():
+        f(0)
+    torch.cuda.synchronize()
+    for _ in range(a.batches):
+        for k, f in fns.items():
+            times[k].append(time_batch(torch, f, a.iters))
+    return [{"shape": f"{w}x{h}, gbuffer masked, small, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": seen if "mask" in k else [],
+             "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, "won": texels_won, "masked_commands": len(masked_slots), "commands": n} for k, t in times.items()]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=7)
@@ -258,6 +340,7 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer"), default="shadow")
     ap.add_argument("--textured", action="store_true", help="with --pass gbuffer: the textured resolve beside the untextured one")
+    ap.add_argument("--masked", action="store_true", help="with --pass gbuffer: the alpha-masked raster beside the all-opaque one")
     ap.add_argument("--no-probe-count", action="store_true", help="with --textured: skip the host-side mean probe count")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
@@ -312,7 +395,7 @@ def main():
                 rows.append({"shape": f"{SIZE}x{SIZE}, {label}{k}, reserve {reserve}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
                              "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
     if a.which == "gbuffer":
-        rows += gbuffer_textured_leg(a, torch, hp) if a.textured else gbuffer_leg(a, torch, hp)
+        rows += gbuffer_masked_leg(a, torch, hp) if a.masked else (gbuffer_textured_leg(a, torch, hp) if a.textured else gbuffer_leg(a, torch, hp))
     hp.raster_reserve(0)
     hp.close()
     for r in rows:

@@ -3,6 +3,7 @@
 // perspective-correct and runs the base pass' pixel shader (Shaders/DeferredBasePass.hlsl), with or without ObjectId and texture maps
 // (csrc/texture_sample.h). DESIGN.md sections 3.9 and 3.10 are its rule, tests/gbuffer_ref.py the restatement. Built with -ffp-contract=off.
 
+#include "gbuffer_interp.h"
 #include "raster_rule.h"
 #include "texture_sample.h"
 #include "ur_device.h"
@@ -31,6 +32,10 @@ struct ResolveParams {
     uint32_t material_count;
     const float* decode; // 256 entries of the sRGB decode
     const float* lod;    // 127 thresholds of the level of detail
+    // with masked draws under visible lists: a texel's key is a position in the masked list iff its word is not 0
+    const unsigned long long* keys64;
+    const uint32_t* mask_visible_idx;
+    uint32_t mask_mode, mask_index_base;
 };
 
 typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes of a vertex: 4-byte aligned
@@ -58,27 +63,7 @@ __device__ __forceinline__ uint32_t srgb_code(const float* table, float x)
     return lo;
 }
 
-// Rules 3-4 at one centre for the target-space triangle (X, Y)[0..2], already reordered: false when it is dropped, culled or does not
-// cover (sx, sy); else the exact edge values l0 = E12, l1 = E20, l2 = E01
-__device__ __forceinline__ bool cover(const float (&X)[3], const float (&Y)[3], int sx, int sy, long long& l0, long long& l1, long long& l2)
-{
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        const bool finite = fabsf(X[v]) <= kFloatMax && fabsf(Y[v]) <= kFloatMax;
-        if (!finite || fabsf(X[v]) > kDepthGuardBand || fabsf(Y[v]) > kDepthGuardBand) return false;
-    }
-    const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
-    const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
-    const long long A = (long long)(x1 - x0) * (y2 - y0) - (long long)(x2 - x0) * (y1 - y0);
-    if (A <= 0) return false;
-    const long long e01 = (long long)(x1 - x0) * (sy - y0) - (long long)(y1 - y0) * (sx - x0);
-    const long long e12 = (long long)(x2 - x1) * (sy - y1) - (long long)(y2 - y1) * (sx - x1);
-    const long long e20 = (long long)(x0 - x2) * (sy - y2) - (long long)(y0 - y2) * (sx - x2);
-    l0 = e12; l1 = e20; l2 = e01;
-    return ((e01 - edge_bias(x0, y0, x1, y1)) | (e12 - edge_bias(x1, y1, x2, y2)) | (e20 - edge_bias(x2, y2, x0, y0))) >= 0;
-}
-
-template <bool OBJECT_ID, bool MAPS = false>
+template <bool OBJECT_ID, bool MAPS = false, bool MASKED = false>
 __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams p)
 {
     __shared__ float table[256];
@@ -103,7 +88,10 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
         return;
     }
     const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
-    const uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    if constexpr (MASKED) {
+        if (p.keys64[i] != 0ull) slot = p.mask_mode == 1u ? p.mask_visible_idx[ordinal] - p.mask_index_base : ordinal;
+    }
     const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
     const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
     const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
@@ -149,68 +137,15 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
         }
     }
 
-    // ---- rule 2 again (DepthPolicy::assemble), every polygon vertex with its weight row over the original three
-    const float d0 = c[0][3] - c[0][2], d1 = c[1][3] - c[1][2], d2 = c[2][3] - c[2][2];
-    const bool o0 = d0 < 0.0f, o1 = d1 < 0.0f, o2 = d2 < 0.0f;
-    const uint32_t n_out = (o0 ? 1u : 0u) + (o1 ? 1u : 0u) + (o2 ? 1u : 0u);
-    const uint32_t rot = n_out == 1u ? (o0 ? 1u : (o1 ? 2u : 0u)) : (n_out == 2u ? (!o0 ? 0u : (!o1 ? 1u : 2u)) : 0u);
-    const uint32_t ia = rot, ib = rot == 2u ? 0u : rot + 1u, ic = rot == 0u ? 2u : rot - 1u;
-    const float ax = sel3(rot, c[0][0], c[1][0], c[2][0]), ay = sel3(rot, c[0][1], c[1][1], c[2][1]);
-    const float aw = sel3(rot, c[0][3], c[1][3], c[2][3]), ad = sel3(rot, d0, d1, d2);
-    const float bx = sel3(rot, c[1][0], c[2][0], c[0][0]), by = sel3(rot, c[1][1], c[2][1], c[0][1]);
-    const float bw = sel3(rot, c[1][3], c[2][3], c[0][3]), bd = sel3(rot, d1, d2, d0);
-    const float cx = sel3(rot, c[2][0], c[0][0], c[1][0]), cy = sel3(rot, c[2][1], c[0][1], c[1][1]);
-    const float cw = sel3(rot, c[2][3], c[0][3], c[1][3]), cd = sel3(rot, d2, d0, d1);
-    const bool one = n_out == 1u, two = n_out == 2u, whole = n_out == 0u;
-    const float ix = one ? bx : ax, iy = one ? by : ay, iw = one ? bw : aw, id = one ? bd : ad;
-    const float ox = one ? cx : bx, oy = one ? cy : by, ow = one ? cw : bw, od = one ? cd : bd;
-    const uint32_t ii = one ? ib : ia, io = one ? ic : ib;
-    const float tp = id / (id - od), tq = ad / (ad - cd);
-    const float px = ix + tp * (ox - ix), py = iy + tp * (oy - iy), pw = iw + tp * (ow - iw);
-    const float qx = ax + tq * (cx - ax), qy = ay + tq * (cy - ay), qw = aw + tq * (cw - aw);
-    float vx[4], vy[4], vw[4], B[4][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float ua = (uint32_t)j == ia ? 1.0f : 0.0f, ub = (uint32_t)j == ib ? 1.0f : 0.0f, uc = (uint32_t)j == ic ? 1.0f : 0.0f;
-        const float up = (uint32_t)j == ii ? 1.0f - tp : ((uint32_t)j == io ? tp : 0.0f);
-        const float uq = (uint32_t)j == ia ? 1.0f - tq : ((uint32_t)j == ic ? tq : 0.0f);
-        B[0][j] = ua;
-        B[1][j] = two ? up : ub;
-        B[2][j] = whole ? uc : (one ? up : uq);
-        B[3][j] = uq;
-    }
-    vx[0] = ax; vy[0] = ay; vw[0] = aw;
-    vx[1] = two ? px : bx; vy[1] = two ? py : by; vw[1] = two ? pw : bw;
-    vx[2] = whole ? cx : (one ? px : qx); vy[2] = whole ? cy : (one ? py : qy); vw[2] = whole ? cw : (one ? pw : qw);
-    vx[3] = qx; vy[3] = qy; vw[3] = qw;
-    float SX[4], SY[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        SX[k] = (vx[k] / vw[k] + 1.0f) * p.half_w;
-        SY[k] = (1.0f - vy[k] / vw[k]) * p.half_h;
-    }
-
-    // ---- the piece that covers this centre: emitted triangle 0 if rule 4 says so, else 1; reordered (r0, r1, r2) = (S0, S[2 + e], S[1 + e])
+    // ---- rule 2 again with a weight row per polygon vertex, the piece that covers this centre and its weights (gbuffer_interp.h)
+    float SX[4], SY[4], vw[4], B[4][3];
+    bool one;
+    clip_polygon(c, p.half_w, p.half_h, SX, SY, vw, B, one);
     const uint32_t row = i / p.w, column = i - row * p.w;
-    const int sx = 256 * (int)column + 128, sy = 256 * (int)(p.row0 + row) + 128;
-    long long l0 = 0, l1 = 0, l2 = 0;
-    float X[3] = {SX[0], SX[2], SX[1]}, Y[3] = {SY[0], SY[2], SY[1]};
-    bool second = false;
-    if (!cover(X, Y, sx, sy, l0, l1, l2) && one) {
-        second = true;
-        X[1] = SX[3]; Y[1] = SY[3]; X[2] = SX[2]; Y[2] = SY[2];
-        (void)cover(X, Y, sx, sy, l0, l1, l2);
-    }
-    const float cw0 = vw[0], cw1 = second ? vw[3] : vw[2], cw2 = second ? vw[2] : vw[1];
-    const float q0 = (float)l0 / cw0, q1 = (float)l1 / cw1, q2 = (float)l2 / cw2;
-    const float s = (q0 + q1) + q2;
-    const float g0 = q0 / s, g1 = q1 / s, g2 = q2 / s;
+    Piece pc;
+    covering_piece(SX, SY, vw, one, 256 * (int)column + 128, 256 * (int)(p.row0 + row) + 128, pc);
     float b[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
-        b[j] = (g0 * B[0][j] + g1 * B1) + g2 * B2;
-    }
+    piece_weights(pc, pc.l0, pc.l1, pc.l2, B, b);
     float n[3], wpos[3], colour[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -225,29 +160,9 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
         if (slot < p.material_count) bits = reinterpret_cast<const uint32_t*>(p.materials + slot)[16] & 15u;
         float base[3] = {1.0f, 1.0f, 1.0f}, mr[3] = {1.0f, 1.0f, 1.0f}, nm[3] = {0.5f, 0.5f, 1.0f}, em[3] = {1.0f, 1.0f, 1.0f};
         if (__ballot(bits != 0u) != 0ull) {
-            // the quad partners' weights: the edge functions are affine, so a step of one pixel adds the coefficient times 256
-            const int x0 = (int)rintf(X[0] * 256.0f), y0 = (int)rintf(Y[0] * 256.0f), x1 = (int)rintf(X[1] * 256.0f), y1 = (int)rintf(Y[1] * 256.0f);
-            const int x2 = (int)rintf(X[2] * 256.0f), y2 = (int)rintf(Y[2] * 256.0f);
             const bool odd_column = (column & 1u) != 0u, odd_row = ((p.row0 + row) & 1u) != 0u;
-            const long long step_x = odd_column ? -256 : 256, step_y = odd_row ? -256 : 256;
             float pu[3], pv[3]; // TEXCOORD at the centre, the horizontal and the vertical partner
-#pragma unroll
-            for (int point = 0; point < 3; ++point) {
-                long long m0 = l0, m1 = l1, m2 = l2;
-                if (point == 1) { m0 -= step_x * (y2 - y1); m1 -= step_x * (y0 - y2); m2 -= step_x * (y1 - y0); }
-                if (point == 2) { m0 += step_y * (x2 - x1); m1 += step_y * (x0 - x2); m2 += step_y * (x1 - x0); }
-                const float r0 = (float)m0 / cw0, r1 = (float)m1 / cw1, r2 = (float)m2 / cw2;
-                const float rs = (r0 + r1) + r2;
-                const float h0 = r0 / rs, h1 = r1 / rs, h2 = r2 / rs;
-                float bb[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const float B1 = second ? B[3][j] : B[2][j], B2 = second ? B[2][j] : B[1][j];
-                    bb[j] = (h0 * B[0][j] + h1 * B1) + h2 * B2;
-                }
-                pu[point] = (bb[0] * uv[0][0] + bb[1] * uv[1][0]) + bb[2] * uv[2][0];
-                pv[point] = (bb[0] * uv[0][1] + bb[1] * uv[1][1]) + bb[2] * uv[2][1];
-            }
+            quad_texcoords(pc, B, uv, odd_column, odd_row, pu, pv);
 #pragma unroll 1
             for (uint32_t map = 0u; map < 4u; ++map) { // t0 base colour, t1 metallic-roughness, t2 normal, t3 emissive
                 const uint32_t bit = map == 0u ? UR_MATERIAL_BASE_COLOR_MAP : (map == 1u ? UR_MATERIAL_METALLIC_ROUGHNESS_MAP : (map == 2u ? UR_MATERIAL_NORMAL_MAP : UR_MATERIAL_EMISSIVE_MAP));
@@ -337,7 +252,8 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
 // The checks and the launches behind the four GBuffer entry points; `who` names the caller in the error text, `who_parts` its _parts form
 int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
                   const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
-                  uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count)
+                  uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask = nullptr,
+                  float* depth_out = nullptr)
 {
     int rc = ur::check_raster_call(who, ctx, view, projection, draws, depth, "depth", w, h, stats6);
     if (rc == UR_OK) rc = ur::check_depth_flags(who, flags);
@@ -360,11 +276,20 @@ int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const flo
         return UR_EINVAL;
     }
     if (!aligned(materials, 16)) { ur::set_error("%s: a misaligned material table (16 bytes)", who); return UR_EINVAL; }
+    if (mask) {
+        rc = ur::check_gbuffer_mask(who, *draws, *mask, *targets, depth, w, h, rows);
+        if (rc != UR_OK) return rc;
+    }
     // ---- the launches: the raster over the key image (UR_GBUFFER_PART_RASTER), then the resolve (UR_GBUFFER_PART_RESOLVE)
     const uint32_t n = w * rows;
     if (parts & UR_GBUFFER_PART_RASTER) {
         rc = ur::launch_visibility_raster(ctx, view, projection, draws, depth, targets->keys, w, h, row0, rows, key_bits, (flags & UR_DEPTH_QUANTIZE_D24) != 0u, stats6);
         if (rc != UR_OK) return rc;
+        if (mask) {
+            rc = ur::launch_masked_raster(ctx, view, projection, mask->draws, depth_out, mask->keys64, targets->keys, w, h, row0, rows, key_bits,
+                                          (flags & UR_DEPTH_QUANTIZE_D24) != 0u, mask->stats6, materials, material_count, mask->won);
+            if (rc != UR_OK) return rc;
+        }
     }
     if (!(parts & UR_GBUFFER_PART_RESOLVE)) return UR_OK;
     ResolveParams r{};
@@ -380,6 +305,18 @@ int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const flo
     r.half_w = 0.5f * (float)w; r.half_h = 0.5f * (float)h;
     r.key_bits = key_bits;
     const uint32_t blocks = (n + kThreads - 1u) / kThreads;
+    if (mask && (draws->visible_idx != nullptr || mask->draws->visible_idx != nullptr)) {
+        // an ordinal is a position in its own selection's list: the resolve that looks at keys64 (no ObjectId beside a mask)
+        r.keys64 = reinterpret_cast<const unsigned long long*>(mask->keys64);
+        r.mask_mode = mask->draws->visible_idx != nullptr ? 1u : 0u;
+        r.mask_visible_idx = mask->draws->visible_idx; r.mask_index_base = mask->draws->index_base;
+        r.materials = materials; r.material_count = material_count;
+        r.decode = ctx->srgb_table; r.lod = ctx->lod_table;
+        if (materials) hipLaunchKernelGGL((gbuffer_resolve_kernel<false, true, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        else hipLaunchKernelGGL((gbuffer_resolve_kernel<false, false, true>), dim3(blocks), dim3(kThreads), 0, ctx->stream, r);
+        UR_HIP_TRY(hipGetLastError());
+        return UR_OK;
+    }
     if (materials) { // the textured resolve
         r.materials = materials; r.material_count = material_count;
         r.decode = ctx->srgb_table; r.lod = ctx->lod_table;
@@ -410,7 +347,48 @@ int ur::check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets
     return UR_OK;
 }
 
+// The checks ur_gbuffer_pass_masked adds; the opaque draws, the targets and depth have passed theirs
+int ur::check_gbuffer_mask(const char* who, const ur_raster_draws& draws, const ur_gbuffer_mask& mask, const ur_gbuffer_targets& targets, const float* depth, uint32_t w,
+                           uint32_t h, uint32_t rows)
+{
+    if (!mask.draws) { set_error("%s: a mask without draws", who); return UR_EINVAL; }
+    const int rc = check_raster_draws(who, *mask.draws, depth, "depth", mask.stats6);
+    if (rc != UR_OK) return rc;
+    if (raster_commands(*mask.draws) != raster_commands(draws) || mask.draws->command_count != draws.command_count) {
+        set_error("%s: the masked draws select from other commands, or another command_count, than the opaque draws: their keys would not share one space", who);
+        return UR_EINVAL;
+    }
+    if (!mask.keys64 || !aligned(mask.keys64, 8) || !aligned(mask.won, 4)) { set_error("%s: a null or misaligned keys64 (8 bytes) or a misaligned won (4 bytes)", who); return UR_EINVAL; }
+    const size_t n = (size_t)w * rows;
+    const struct { const void* at; size_t bytes; } others[] = {{targets.gbuf_a, n * 8u}, {targets.gbuf_b, n * 8u}, {targets.gbuf_c, n * 4u}, {targets.hdr, n * 8u},
+                                                               {targets.keys, n * 4u}, {targets.object_id, n * 4u}, {depth, (size_t)w * h * 4u}};
+    for (const auto& o : others) {
+        if (o.at && overlaps(mask.keys64, n * 8u, o.at, o.bytes)) { set_error("%s: keys64 overlaps a target or depth", who); return UR_EINVAL; }
+    }
+    if (targets.object_id) {
+        set_error("%s: object_id beside a mask: the ObjectId pass ignores the alpha test and tests against the depth this pass writes; it needs a raster of its own", who);
+        return UR_EUNSUPPORTED;
+    }
+    return UR_OK;
+}
+
 extern "C" {
+
+int ur_gbuffer_pass_masked_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, const ur_gbuffer_targets* targets,
+                                 uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
+                                 const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask)
+{
+    return gbuffer_entry("ur_gbuffer_pass_masked", "ur_gbuffer_pass_masked_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits,
+                         stats6, parts, materials, material_count, mask, depth);
+}
+
+int ur_gbuffer_pass_masked(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, const ur_gbuffer_targets* targets,
+                           uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6,
+                           const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask)
+{
+    return gbuffer_entry("ur_gbuffer_pass_masked", "ur_gbuffer_pass_masked_parts", ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits,
+                         stats6, UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, materials, material_count, mask, depth);
+}
 
 int ur_gbuffer_pass_materials_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
                                     const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,

@@ -25,8 +25,15 @@
 // against the near plane with selects on registers (no per-lane arrays): up to four vertices S0..S3 in target space, emitted triangle
 // e = (S0, S[1 + e], S[2 + e]). The wave serves emitted triangle 0 of every lane, then, when a ballot finds a lane that was cut into
 // two, runs the same code once more over emitted triangle 1.
+//
+// GBuffer's alpha-masked draws (restated in tests/gbuffer_mask_ref.py) are a third keyed policy: a fragment that
+// passes the depth test competes for a 64-bit word per texel, (depth bits << 32) | key, and runs the base pass' alpha test (alpha_discards
+// below, with the resolve's interpolation and sampler: gbuffer_interp.h, texture_sample.h) only when its word is above the texel's; a
+// merge launch then folds the words into the opaque draws' key image and raises the depth where a masked fragment won.
 
+#include "gbuffer_interp.h"
 #include "raster_rule.h"
+#include "texture_sample.h"
 #include "ur_internal.h"
 
 namespace {
@@ -66,6 +73,25 @@ struct RasterParams {
     uint32_t row0, rows, key_bits;
 };
 
+// What the masked policy's kernels take behind a RasterParams: `map` is then the band's 64-bit words
+struct MaskArgs {
+    const ur_material* materials; // null: no slot has a material (nothing is discarded)
+    uint32_t material_count;
+    const float* lod; // 127 thresholds of the level of detail
+};
+struct MaskedParams : RasterParams {
+    MaskArgs mask;
+};
+
+// What a fragment's alpha test reads: nothing in the passes without one
+struct NoAlpha {};
+struct AlphaCtx {
+    const MaskedParams* p;
+    const float* lds; // the sampler's tables (texture_sample.h): code / 255 and the level thresholds; the decode part is not filled
+};
+template <class P>
+__device__ __forceinline__ bool alpha_discards(const AlphaCtx& a, uint32_t key, int px, int py);
+
 struct Tri {
     int x0, y0, x1, y1, x2, y2; // 24.8 target space, y down
     float z0, k1, k2;
@@ -74,7 +100,7 @@ struct Tri {
 // Rules 4-6 for one pixel
 template <class P>
 __device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, uint32_t* __restrict__ map, uint32_t w, int px, int py,
-                                      const float* __restrict__ depth, uint32_t row0, uint32_t key)
+                                      const float* __restrict__ depth, uint32_t row0, uint32_t key, const typename P::Alpha& alpha)
 {
     const int sx = 256 * px + 128, sy = 256 * py + 128;
     const long long e01 = (long long)(t.x1 - t.x0) * (sy - t.y0) - (long long)(t.y1 - t.y0) * (sx - t.x0);
@@ -87,6 +113,15 @@ __device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, u
         if (z > 1.0f) z = 1.0f;
         if constexpr (P::kD24) z = (float)(__builtin_rint((double)z * 16777215.0) / 16777215.0);
         if (!(z >= depth[(size_t)py * w + (uint32_t)px])) return; // ... under GREATER_EQUAL against the prepass' maximum
+        if constexpr (P::kMasked) {
+            // section 3.11: the word's order is (depth, key); the alpha test runs only for a fragment that would raise the texel
+            unsigned long long* k64 = reinterpret_cast<unsigned long long*>(map) + (size_t)((uint32_t)py - row0) * w + (uint32_t)px;
+            const unsigned long long word = ((unsigned long long)(__float_as_uint(z) & 0x7FFFFFFFu) << 32) | key; // z += 0.0f
+            if (word <= __hip_atomic_load(k64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return; // (words only increase)
+            if (alpha_discards<P>(alpha, key, px, py)) return;
+            (void)__hip_atomic_fetch_max(k64, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
         uint32_t* k = map + (size_t)((uint32_t)py - row0) * w + (uint32_t)px;
         if (key <= __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return; // (keys only increase)
         (void)__hip_atomic_fetch_max(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -112,7 +147,7 @@ __device__ __forceinline__ void shade(const Tri& t, int b01, int b12, int b20, u
 // The whole wave stamps the pixels [px0, px1] x [py0, py1] (inside the target) of one triangle, uniform arguments
 template <class P>
 __device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ map, uint32_t w, int px0, int py0, int px1, int py1, uint32_t lane,
-                                           const float* __restrict__ depth, uint32_t row0, uint32_t key)
+                                           const float* __restrict__ depth, uint32_t row0, uint32_t key, const typename P::Alpha& alpha)
 {
     const int b01 = edge_bias(t.x0, t.y0, t.x1, t.y1), b12 = edge_bias(t.x1, t.y1, t.x2, t.y2), b20 = edge_bias(t.x2, t.y2, t.x0, t.y0);
     const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
@@ -120,7 +155,7 @@ __device__ __forceinline__ void stamp_rect(const Tri& t, uint32_t* __restrict__ 
         const int py = sy + ly;
         for (int sx = px0 & ~7; sx <= px1; sx += 8) {
             const int px = sx + lx;
-            if (px >= px0 && px <= px1 && py >= py0 && py <= py1) shade<P>(t, b01, b12, b20, map, w, px, py, depth, row0, key);
+            if (px >= px0 && px <= px1 && py >= py0 && py <= py1) shade<P>(t, b01, b12, b20, map, w, px, py, depth, row0, key, alpha);
         }
     }
 }
@@ -143,7 +178,9 @@ __device__ __forceinline__ Tri broadcast(const Tri& t, uint32_t s)
 
 // ShadowMap: orthographic, drawn iff A > 0, a per-texel minimum over a map cleared to 1.0
 struct ShadowPolicy {
-    static constexpr bool kNearest = true, kSwap12 = false, kKeyed = false;
+    using Params = RasterParams;
+    using Alpha = NoAlpha;
+    static constexpr bool kNearest = true, kSwap12 = false, kKeyed = false, kMasked = false;
     static constexpr uint32_t kEmit = 1u, kVertexBytes = 12u, kEntryDwords = ::kEntryDwords;
     static constexpr float kGuardBand = (float)UR_RASTER_MAX_TARGET;
 
@@ -176,7 +213,9 @@ struct ShadowPolicy {
 // drawn iff A > 0 as above), a per-texel maximum over a target cleared to 0.0, optionally quantised to D24
 template <bool D24>
 struct DepthPolicy {
-    static constexpr bool kNearest = false, kD24 = D24, kSwap12 = true, kKeyed = false;
+    using Params = RasterParams;
+    using Alpha = NoAlpha;
+    static constexpr bool kNearest = false, kD24 = D24, kSwap12 = true, kKeyed = false, kMasked = false;
     static constexpr uint32_t kEmit = 2u, kVertexBytes = 12u, kEntryDwords = ::kEntryDwords;
     static constexpr float kGuardBand = kDepthGuardBand;
 
@@ -251,6 +290,72 @@ struct VisPolicy : DepthPolicy<D24> {
     static constexpr uint32_t kVertexBytes = 64u, kEntryDwords = kKeyedEntryDwords;
 };
 
+// GBuffer's alpha-masked draws: VisPolicy's fragment in front of a 64-bit word per texel and the alpha test
+template <bool D24>
+struct MaskPolicy : VisPolicy<D24> {
+    using Params = MaskedParams;
+    using Alpha = AlphaCtx;
+    static constexpr bool kMasked = true;
+};
+
+// Rule 3 of section 3.11 for the fragment of the triangle `key` names at the texel (px, py): the triangle is fetched again from the key as
+// the resolve fetches it, COLOR.a and TEXCOORD interpolated with the resolve's weights, channel A of the base-colour map sampled with the
+// resolve's sampler. True iff alpha < AlphaCutoff (false for a NaN on either side).
+template <class P>
+__device__ __forceinline__ bool alpha_discards(const AlphaCtx& a, uint32_t key, int px, int py)
+{
+    const MaskedParams& p = *a.p;
+    const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
+    const uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    uint32_t bits = 0u;
+    if (p.mask.materials != nullptr && slot < p.mask.material_count) bits = reinterpret_cast<const uint32_t*>(p.mask.materials + slot)[16];
+    if ((bits & UR_MATERIAL_ALPHA_MASK) == 0u) return false;
+    const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
+    const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
+    const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
+    const uint32_t* indices = reinterpret_cast<const uint32_t*>((uint64_t)c1.x | ((uint64_t)c1.y << 32));
+    const float* cb = reinterpret_cast<const float*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
+    const uint32_t stride = c0.w;
+    const uint64_t first = (uint64_t)c3.x + 3ull * t;
+    const long long base_vertex = (int)c3.y;
+    float W[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) W[k] = cb[k];
+    float c[3][4], uv[3][2], va[3]; // clip position, TEXCOORD, COLOR.a
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
+        const float* vp = reinterpret_cast<const float*>(vertices + vi * stride);
+        P::project(vp, W, p, c[v]);
+        uv[v][0] = vp[6]; uv[v][1] = vp[7];
+        va[v] = vp[15];
+    }
+    float SX[4], SY[4], vw[4], B[4][3];
+    bool one;
+    clip_polygon(c, p.half_w, p.half_h, SX, SY, vw, B, one);
+    Piece pc;
+    covering_piece(SX, SY, vw, one, 256 * px + 128, 256 * py + 128, pc);
+    float b[3];
+    piece_weights(pc, pc.l0, pc.l1, pc.l2, B, b);
+    float alpha = cb[106] * ((b[0] * va[0] + b[1] * va[1]) + b[2] * va[2]); // BaseColorAlpha * COLOR.a
+    if (bits & UR_MATERIAL_BASE_COLOR_MAP) {
+        const u32x4_t desc = reinterpret_cast<const u32x4_t*>(p.mask.materials + slot)[0];
+        if (valid_texture(desc)) {
+            const bool odd_column = ((uint32_t)px & 1u) != 0u, odd_row = ((uint32_t)py & 1u) != 0u;
+            float pu[3], pv[3], tu[3], tv[3];
+            quad_texcoords(pc, B, uv, odd_column, odd_row, pu, pv);
+#pragma unroll
+            for (int point = 0; point < 3; ++point) texture_transform(cb, 112u, pu[point], pv[point], tu[point], tv[point]);
+            const float dxu = odd_column ? tu[0] - tu[1] : tu[1] - tu[0], dxv = odd_column ? tv[0] - tv[1] : tv[1] - tv[0];
+            const float dyu = odd_row ? tu[0] - tu[2] : tu[2] - tu[0], dyv = odd_row ? tv[0] - tv[2] : tv[2] - tv[0];
+            float sa[1];
+            sample_map<3, 1>(desc, tu[0], tv[0], dxu, dxv, dyu, dyv, a.lds, sa);
+            alpha = alpha * sa[0];
+        }
+    }
+    return alpha < cb[107]; // AlphaCutoff
+}
+
 __global__ __launch_bounds__(kThreads) void shadow_clear_kernel(float* __restrict__ map, uint32_t n, uint32_t head, uint32_t* __restrict__ queue, float value)
 {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -265,8 +370,16 @@ __global__ __launch_bounds__(kThreads) void shadow_clear_kernel(float* __restric
 }
 
 template <class P>
-__global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
+__global__ __launch_bounds__(kThreads) void raster_kernel(typename P::Params p)
 {
+    typename P::Alpha alpha{};
+    if constexpr (P::kMasked) {
+        __shared__ float sampler_tables[kLdsFloats];
+        sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
+        if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.mask.lod[min(threadIdx.x, 126u)];
+        __syncthreads();
+        alpha.p = &p; alpha.lds = sampler_tables;
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
     const uint32_t wave_count = gridDim.x * kWaves;
@@ -401,7 +514,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                 if (kind == 1u) {
                     const int b01 = edge_bias(tri.x0, tri.y0, tri.x1, tri.y1), b12 = edge_bias(tri.x1, tri.y1, tri.x2, tri.y2), b20 = edge_bias(tri.x2, tri.y2, tri.x0, tri.y0);
                     for (int py = by0; py <= by1; ++py)
-                        for (int px = bx0; px <= bx1; ++px) shade<P>(tri, b01, b12, b20, p.map, p.w, px, py, p.depth, p.row0, key);
+                        for (int px = bx0; px <= bx1; ++px) shade<P>(tri, b01, b12, b20, p.map, p.w, px, py, p.depth, p.row0, key, alpha);
                 }
                 // ---- the middle ones by the wave
                 unsigned long long todo = __ballot(kind == 2u);
@@ -409,7 +522,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                     const uint32_t s = (uint32_t)__ffsll((long long)todo) - 1u;
                     todo &= todo - 1ull;
                     const Tri u = broadcast(tri, s);
-                    stamp_rect<P>(u, p.map, p.w, rl(bx0, s), rl(by0, s), rl(bx1, s), rl(by1, s), lane, p.depth, p.row0, (uint32_t)rl((int)key, s));
+                    stamp_rect<P>(u, p.map, p.w, rl(bx0, s), rl(by0, s), rl(bx1, s), rl(by1, s), lane, p.depth, p.row0, (uint32_t)rl((int)key, s), alpha);
                 }
                 // ---- the large ones to the queue, or by the wave when there is no room
                 todo = __ballot(kind == 3u);
@@ -441,7 +554,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(RasterParams p)
                     }
                     if (!queued) {
                         ++n_unqueued;
-                        stamp_rect<P>(u, p.map, p.w, x0, y0, x1, y1, lane, p.depth, p.row0, ukey);
+                        stamp_rect<P>(u, p.map, p.w, x0, y0, x1, y1, lane, p.depth, p.row0, ukey, alpha);
                     }
                 }
             }
@@ -468,8 +581,8 @@ __device__ __forceinline__ long long edge_max(int ax, int ay, int bx, int by, in
 }
 
 template <class P>
-__global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w,
-                                                         const float* __restrict__ depth, uint32_t row0)
+__device__ __forceinline__ void large_body(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w,
+                                           const float* __restrict__ depth, uint32_t row0, const typename P::Alpha& alpha)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
@@ -490,8 +603,45 @@ __global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restr
         if (edge_max(t.x0, t.y0, t.x1, t.y1, px0, py0, px1, py1) < 0 || edge_max(t.x1, t.y1, t.x2, t.y2, px0, py0, px1, py1) < 0 ||
             edge_max(t.x2, t.y2, t.x0, t.y0, px0, py0, px1, py1) < 0)
             continue;
-        stamp_rect<P>(t, map, w, px0, py0, px1, py1, lane, depth, row0, key);
+        stamp_rect<P>(t, map, w, px0, py0, px1, py1, lane, depth, row0, key, alpha);
     }
+}
+
+template <class P>
+__global__ __launch_bounds__(kThreads) void large_kernel(const uint32_t* __restrict__ queue, uint32_t queue_cap, uint32_t* __restrict__ map, uint32_t w,
+                                                         const float* __restrict__ depth, uint32_t row0)
+{
+    large_body<P>(queue, queue_cap, map, w, depth, row0, NoAlpha{});
+}
+
+// The masked policy's: what the alpha test reads rides in the parameters, its tables in LDS
+template <class P>
+__global__ __launch_bounds__(kThreads) void large_masked_kernel(MaskedParams p)
+{
+    __shared__ float sampler_tables[kLdsFloats];
+    sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
+    if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.mask.lod[min(threadIdx.x, 126u)];
+    __syncthreads();
+    large_body<P>(p.queue, p.queue_cap, p.map, p.w, p.depth, p.row0, AlphaCtx{&p, sampler_tables});
+}
+
+// Rule 5 of section 3.11, a lane per texel of the band: the masked word against the opaque key and the depth; where the masked fragment
+// wins, the key image takes its key and the depth its depth, where it loses its word is set to 0 (a word that is left says which selection
+// the texel's key belongs to). `depth` points at the band's first row. `won` is added to once per wave.
+__global__ __launch_bounds__(kThreads) void mask_merge_kernel(unsigned long long* __restrict__ keys64, uint32_t* __restrict__ keys, uint32_t* __restrict__ depth,
+                                                              uint32_t n, uint32_t* __restrict__ won)
+{
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    bool wins = false;
+    if (i < n) {
+        const unsigned long long km = keys64[i];
+        const uint32_t hi = (uint32_t)(km >> 32), lo = (uint32_t)km;
+        wins = km != 0ull && (hi > depth[i] || lo > keys[i]);
+        if (wins) { keys[i] = lo; depth[i] = hi; }
+        else if (km != 0ull) keys64[i] = 0ull;
+    }
+    const uint32_t count = (uint32_t)__popcll(__ballot(wins));
+    if (won != nullptr && count != 0u && (threadIdx.x & 63u) == 0u) (void)__hip_atomic_fetch_add(won, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // What GBuffer's raster has beside a depth pass': the depth it tests against, its band and the key's triangle bits
@@ -504,7 +654,7 @@ struct VisArgs {
 // (vis null), GBuffer's key image of its band. m1 is null for ShadowMap.
 template <class P>
 int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, uint32_t* map, uint32_t n, uint32_t w, uint32_t h, float clear,
-                  uint32_t* stats, const VisArgs* vis)
+                  uint32_t* stats, const VisArgs* vis, const MaskArgs* mask = nullptr)
 {
     const ur_draw_ranges* rg = draws->ranges;
     const bool list = draws->visible_idx != nullptr;
@@ -515,7 +665,8 @@ int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster
     UR_HIP_TRY(hipGetLastError());
     if (draws->command_count == 0u) return UR_OK;
 
-    RasterParams p{};
+    typename P::Params p{};
+    if constexpr (P::kMasked) p.mask = *mask;
     p.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
     p.command_count = draws->command_count;
     p.mode = list ? 1u : (rg ? 2u : 0u);
@@ -538,7 +689,8 @@ int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster
     hipLaunchKernelGGL(raster_kernel<P>, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     if (queue) {
-        hipLaunchKernelGGL(large_kernel<P>, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, queue, p.queue_cap, p.map, w, p.depth, p.row0);
+        if constexpr (P::kMasked) hipLaunchKernelGGL(large_masked_kernel<P>, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, p);
+        else hipLaunchKernelGGL(large_kernel<P>, dim3((uint32_t)ctx->cu_count * 8u), dim3(kThreads), 0, ctx->stream, queue, p.queue_cap, p.map, w, p.depth, p.row0);
         UR_HIP_TRY(hipGetLastError());
     }
     return UR_OK;
@@ -579,6 +731,23 @@ int ur::launch_visibility_raster(ur_ctx* ctx, const float* view, const float* pr
     const VisArgs vis{depth, row0, rows, key_bits};
     if (d24) return launch_raster<VisPolicy<true>>(ctx, view, projection, draws, keys, w * rows, w, h, 0.0f, stats, &vis);
     return launch_raster<VisPolicy<false>>(ctx, view, projection, draws, keys, w * rows, w, h, 0.0f, stats, &vis);
+}
+
+int ur::launch_masked_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, uint64_t* keys64, uint32_t* keys,
+                             uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats, const ur_material* materials,
+                             uint32_t material_count, uint32_t* won)
+{
+    const VisArgs vis{depth, row0, rows, key_bits};
+    const MaskArgs mask{materials, material_count, ctx->lod_table};
+    uint32_t* words = reinterpret_cast<uint32_t*>(keys64);
+    const uint32_t n = w * rows;
+    const int rc = d24 ? launch_raster<MaskPolicy<true>>(ctx, view, projection, draws, words, 2u * n, w, h, 0.0f, stats, &vis, &mask)
+                       : launch_raster<MaskPolicy<false>>(ctx, view, projection, draws, words, 2u * n, w, h, 0.0f, stats, &vis, &mask);
+    if (rc != UR_OK) return rc;
+    hipLaunchKernelGGL(mask_merge_kernel, dim3((n + kThreads - 1u) / kThreads), dim3(kThreads), 0, ctx->stream, reinterpret_cast<unsigned long long*>(keys64), keys,
+                       reinterpret_cast<uint32_t*>(depth) + (size_t)row0 * w, n, won);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
 }
 
 extern "C" {

@@ -1,6 +1,7 @@
 // The static sampler of the textured GBuffer resolve (DESIGN.md section 3.10 is its rule, tests/gbuffer_tex_ref.py the restatement):
 // ApplyTextureTransform, wrap addressing, one bilinear sample, and the footprint / level of detail / trilinear probes of one map, as
-// device inline functions over tables the including kernel has put into LDS (layout below). Only csrc/gbuffer_resolve.hip includes it.
+// device inline functions over tables the including kernel has put into LDS (layout below). csrc/gbuffer_resolve.hip samples R, G and B
+// with it, the masked raster's alpha test (csrc/raster.hip) channel A: the same sampler with another output.
 #pragma once
 
 #include "raster_rule.h"
@@ -38,8 +39,9 @@ __device__ __forceinline__ void wrap_pair(float u, uint32_t size, uint32_t& i0, 
     i1 = i0 + 1u == size ? 0u : i0 + 1u;
 }
 
-// One bilinear sample of a level: R, G, B decoded through `tab` (LDS: the sRGB decode or code / 255)
-__device__ __forceinline__ void bilinear(const uint32_t* __restrict__ level, uint32_t wd, uint32_t hd, float u, float v, const float* tab, float (&out)[3])
+// One bilinear sample of a level: the channels [C0, C0 + N) decoded through `tab` (LDS: the sRGB decode or code / 255)
+template <int C0, int N>
+__device__ __forceinline__ void bilinear(const uint32_t* __restrict__ level, uint32_t wd, uint32_t hd, float u, float v, const float* tab, float (&out)[N])
 {
     uint32_t x0, x1, y0, y1;
     float fx, fy;
@@ -49,17 +51,19 @@ __device__ __forceinline__ void bilinear(const uint32_t* __restrict__ level, uin
     const uint32_t* r1 = level + (size_t)y1 * wd;
     const uint32_t t00 = r0[x0], t10 = r0[x1], t01 = r1[x0], t11 = r1[x1];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float a = tab[(t00 >> (8 * c)) & 255u], b = tab[(t10 >> (8 * c)) & 255u];
-        const float d = tab[(t01 >> (8 * c)) & 255u], e = tab[(t11 >> (8 * c)) & 255u];
+    for (int c = 0; c < N; ++c) {
+        const float a = tab[(t00 >> (8 * (C0 + c))) & 255u], b = tab[(t10 >> (8 * (C0 + c))) & 255u];
+        const float d = tab[(t01 >> (8 * (C0 + c))) & 255u], e = tab[(t11 >> (8 * (C0 + c))) & 255u];
         const float top = a + fx * (b - a), bottom = d + fx * (e - d);
         out[c] = top + fy * (bottom - top);
     }
 }
 
 // The static sampler on one map: footprint, level of detail, up to four trilinear probes. (u, v) the centre's coordinate, (dxu, dxv) and
-// (dyu, dyv) the quad's differences; `desc` a valid descriptor's four dwords; `lds` the tables
-__device__ __forceinline__ void sample_map(const u32x4_t desc, float u, float v, float dxu, float dxv, float dyu, float dyv, const float* lds, float (&out)[3])
+// (dyu, dyv) the quad's differences; `desc` a valid descriptor's four dwords; `lds` the tables. The output is the channels [C0, C0 + N):
+// R, G, B for a map of the resolve, A alone (C0 = 3: code / 255 whatever the format, and the decode table is not read) for the alpha test
+template <int C0 = 0, int N = 3>
+__device__ __forceinline__ void sample_map(const u32x4_t desc, float u, float v, float dxu, float dxv, float dyu, float dyv, const float* lds, float (&out)[N])
 {
     const uint32_t* texels = reinterpret_cast<const uint32_t*>((uint64_t)desc.x | ((uint64_t)desc.y << 32));
     const uint32_t width = desc.z & 0xFFFFu, height = desc.z >> 16, mips = desc.w & 0xFFu, format = (desc.w >> 8) & 0xFFu;
@@ -96,26 +100,26 @@ __device__ __forceinline__ void sample_map(const u32x4_t desc, float u, float v,
     const uint32_t we = max(1u, width >> min(d1, 16u)), he = max(1u, height >> min(d1, 16u));
     const uint32_t* level0 = texels + offset;
     const uint32_t* level1 = d1 == d ? level0 : level0 + (size_t)wd * hd;
-    const float* tab = lds + (format == UR_TEXTURE_R8G8B8A8_UNORM_SRGB ? kLdsDecode : kLdsUnorm);
+    const float* tab = lds + (C0 != 3 && format == UR_TEXTURE_R8G8B8A8_UNORM_SRGB ? kLdsDecode : kLdsUnorm);
     const float mu = ymajor ? dyu : dxu, mv = ymajor ? dyv : dxv;
-    float sum[3] = {0.0f, 0.0f, 0.0f};
+    float sum[N] = {};
     for (uint32_t i = 0u; i < n; ++i) {
         const float o = kProbeOffset[n * (n - 1u) / 2u + i];
         const float pu = u + mu * o, pv = v + mv * o;
-        float s[3];
-        bilinear(level0, wd, hd, pu, pv, tab, s);
+        float s[N];
+        bilinear<C0, N>(level0, wd, hd, pu, pv, tab, s);
         if (f != 0.0f) { // (lo + 0 * (hi - lo) is lo: every value here is finite and no zero is negative)
-            float t[3];
-            bilinear(level1, we, he, pu, pv, tab, t);
+            float t[N];
+            bilinear<C0, N>(level1, we, he, pu, pv, tab, t);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) s[c] = s[c] + f * (t[c] - s[c]);
+            for (int c = 0; c < N; ++c) s[c] = s[c] + f * (t[c] - s[c]);
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) sum[c] = i == 0u ? s[c] : sum[c] + s[c];
+        for (int c = 0; c < N; ++c) sum[c] = i == 0u ? s[c] : sum[c] + s[c];
     }
     const float fn = (float)n;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = sum[c] / fn;
+    for (int c = 0; c < N; ++c) out[c] = sum[c] / fn;
 }
 
 __device__ __forceinline__ bool valid_texture(const u32x4_t desc)

@@ -48,6 +48,9 @@ inline int check_depth_flags(const char* who, uint32_t flags)
     return UR_OK;
 }
 int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_resolve.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
+// (gbuffer_resolve.hip) what ur_gbuffer_pass_masked adds: the masked draws' own checks, one key space, keys64, no overlap, no ObjectId
+int check_gbuffer_mask(const char* who, const ur_raster_draws& draws, const ur_gbuffer_mask& mask, const ur_gbuffer_targets& targets, const float* depth, uint32_t w,
+                       uint32_t h, uint32_t rows);
 inline int check_key_triangle_bits(const char* who, uint32_t bits)
 {
     if (bits > 31u) { set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, bits); return UR_EINVAL; }

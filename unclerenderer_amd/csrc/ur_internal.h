@@ -143,6 +143,11 @@ int launch_cull_views(ur_ctx* ctx, const uint32_t* constants, const ur_float4* b
 // GBuffer's raster (UR_GBUFFER_PART_RASTER): clears the key image of the band [row0, row0 + rows) and raises it to the winning keys
 int launch_visibility_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, uint32_t* keys, uint32_t w,
                              uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats);
+// GBuffer's masked raster and merge, behind launch_visibility_raster over the opaque draws: clears the 64-bit words of the
+// band, raises them to the winning masked fragments, folds them into `keys` and raises `depth` in the band's rows where one won
+int launch_masked_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, uint64_t* keys64, uint32_t* keys,
+                         uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats, const ur_material* materials,
+                         uint32_t material_count, uint32_t* won);
 int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_constants* sky, const ur_half4* gbuf_a,
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);

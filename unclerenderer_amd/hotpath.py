@@ -819,11 +819,13 @@ class Materials:
 
 def pack_materials(materials) -> Materials:
     """[{"key": pipeline key, "base_color" / "metallic_roughness" / "normal" / "emissive": a Texture, a lib.Texture2D or None}, ...], one
-    per command slot, becomes the device table HotPath.gbuffer_pass(materials=) and Frame.set_gbuffer_materials take."""
+    per command slot, becomes the device table HotPath.gbuffer_pass(materials=) and Frame.set_gbuffer_materials take. A key is 0-31: bit 4
+    (UR_MATERIAL_ALPHA_MASK) is looked at for the slots of gbuffer_pass(mask_draws=) only."""
     rec = (_lib.Material * max(len(materials), 1))()
     keep = []
     for r, m in zip(rec, materials):
         r.pipeline_key = int(m.get("key", 0))
+        assert 0 <= r.pipeline_key <= 31, f"pipeline key {r.pipeline_key} (0-31)"
         for name in ("base_color", "metallic_roughness", "normal", "emissive"):
             t = m.get(name)
             if t is None:
@@ -835,20 +837,31 @@ def pack_materials(materials) -> Materials:
 
 
 def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0, rows=None, *, visible=None, ranges=None, index_base=0, stats=None,
-                  command_count=None, flags=0, key_triangle_bits=0, parts=None, materials=None):
+                  command_count=None, flags=0, key_triangle_bits=0, parts=None, materials=None, mask_draws=None, keys64=None, mask_stats=None, won=None):
     """ur_gbuffer_pass: rasterise the selected draws of `commands` (64-byte vertices, whole ur_scene_constants behind the constant address)
     into visibility keys against `depth` (the w x h result of depth_prepass, read only) and resolve the rows [row0, row0 + rows) into
     `targets` (gbuffer_targets(...)). The selections are HotPath.shadow_map's; stats: uint32[6] device tensor, added to; flags:
     UR_DEPTH_QUANTIZE_D24; key_triangle_bits: the key's triangle bits, 0 = 32 - bit_length(command_count). parts: None, or for a timing tool
     UR_GBUFFER_PART_RASTER and / or UR_GBUFFER_PART_RESOLVE through ur_gbuffer_pass_parts (the resolve part alone trusts targets.keys).
-    materials: a pack_materials(...) table, one record per command slot: the textured resolve of ur_gbuffer_pass_materials."""
+    materials: a pack_materials(...) table, one record per command slot: the textured resolve of ur_gbuffer_pass_materials.
+    mask_draws: a raster_draws(...) selection of the alpha-masked models over the same commands: ur_gbuffer_pass_masked, which applies the
+    alpha test to the slots whose key has UR_MATERIAL_ALPHA_MASK, writes `depth` where a masked fragment wins and needs keys64, an int64
+    (rows, w) device tensor of scratch; mask_stats: uint32[6] and won: uint32[1] device tensors, added to."""
     rows = h - row0 if rows is None else rows
     assert depth.dtype == torch.float32 and depth.numel() >= w * h
     v, p = _matrix16(view), _matrix16(projection)
     d = raster_draws(commands, command_count, visible, ranges, index_base)
     args = (self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), C.byref(targets), w, h, int(row0), int(rows), int(flags), int(key_triangle_bits),
             _ptr(stats))
-    if materials is not None:
+    if mask_draws is not None:
+        assert keys64 is not None and keys64.dtype == torch.int64 and keys64.is_contiguous() and keys64.numel() >= w * rows
+        mask = _lib.GBufferMask(C.pointer(mask_draws), keys64.data_ptr(), _ptr(mask_stats), _ptr(won))
+        table, count = (None, 0) if materials is None else ((materials.table, materials.count) if isinstance(materials, Materials) else materials)
+        if parts is None:
+            _lib.check(self._L.ur_gbuffer_pass_masked(*args, _ptr(table), int(count), C.byref(mask)), "ur_gbuffer_pass_masked")
+        else:
+            _lib.check(self._L.ur_gbuffer_pass_masked_parts(*args, int(parts), _ptr(table), int(count), C.byref(mask)), "ur_gbuffer_pass_masked_parts")
+    elif materials is not None:
         table, count = (materials.table, materials.count) if isinstance(materials, Materials) else materials
         if parts is None:
             _lib.check(self._L.ur_gbuffer_pass_materials(*args, _ptr(table), int(count)), "ur_gbuffer_pass_materials")

@@ -83,6 +83,12 @@ class Material(C.Structure):
 UR_TEXTURE_R8G8B8A8_UNORM = 28
 UR_TEXTURE_R8G8B8A8_UNORM_SRGB = 29
 UR_MATERIAL_NORMAL_MAP, UR_MATERIAL_METALLIC_ROUGHNESS_MAP, UR_MATERIAL_BASE_COLOR_MAP, UR_MATERIAL_EMISSIVE_MAP = 1, 2, 4, 8
+UR_MATERIAL_ALPHA_MASK = 0x10
+
+
+class GBufferMask(C.Structure):
+    """ur_gbuffer_mask (include/ur_raster.h): the alpha-masked selection of ur_gbuffer_pass_masked, its 64-bit scratch and optional counters."""
+    _fields_ = [("draws", C.POINTER(RasterDraws)), ("keys64", C.c_void_p), ("stats6", C.c_void_p), ("won", C.c_void_p)]
 
 
 class FrameGBufferPass(C.Structure):
@@ -321,6 +327,10 @@ SIGNATURES = {
     "ur_gbuffer_pass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP]),
     "ur_gbuffer_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32]),
     "ur_gbuffer_pass_materials": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _U32]),
+    "ur_gbuffer_pass_masked": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _U32,
+                                         C.POINTER(GBufferMask)]),
+    "ur_gbuffer_pass_masked_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
+                                               _VP, _U32, C.POINTER(GBufferMask)]),
     "ur_gbuffer_pass_materials_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
                                                   _VP, _U32]),
     # ur_assets.h
