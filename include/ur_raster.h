@@ -9,6 +9,8 @@
  * the winning key into the render targets. Its rule is DESIGN.md section 3.9, restated in tests/gbuffer_ref.py. Texture maps (pipeline
  * keys 0-15) are section 3.10 and tests/gbuffer_tex_ref.py, the alpha-masked permutations (keys 16-31) section 3.11 and
  * tests/gbuffer_mask_ref.py.
+ * The Forward pass (ForwardRenderer.cpp "Forward", Shaders/ForwardVS.hlsl, Shaders/ForwardPS.hlsl): the same visibility keys resolved
+ * straight to the HDR colour. Its rule is DESIGN.md section 3.12, restated in tests/forward_ref.py.
  */
 #ifndef UR_RASTER_H
 #define UR_RASTER_H
@@ -258,6 +260,55 @@ int ur_gbuffer_pass_masked_parts(ur_ctx* ctx, const float view[16], const float 
                                  float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
                                  uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
                                  const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask);
+
+/* The targets of the Forward pass: the rows [row0, row0 + rows) of the frame, w texels wide, row-major (a band's own images). */
+typedef struct ur_forward_targets {
+    ur_half4* hdr;   /* the HDR band: written where a key won, left as it is elsewhere */
+    uint32_t* keys;  /* rows x w scratch owned by the caller; holds the winning keys afterwards */
+} ur_forward_targets;
+
+/* The Forward pass (ForwardRenderer.cpp "Forward", Shaders/ForwardVS.hlsl and ForwardPS.hlsl, all 32 pipeline permutations) over the rows
+ * [row0, row0 + rows) of a w x h frame, by the rule of DESIGN.md 3.12, restated in tests/forward_ref.py. The raster is
+ * ur_gbuffer_pass_masked's, unchanged: keys, keys64, depth, won and both stats6 end exactly as that call leaves them. A second resolve over
+ * the final keys then evaluates material and lighting in one go, from fp32 values: where the key is not 0, hdr = fp16 (color.rgb, 1.0) of
+ * ForwardPS.hlsl:73-143 on the perspective-correct attributes of the key's triangle; every other texel of hdr is left untouched (the
+ * reference draws "Sky" first and "Forward" over it: call ur_sky_atmosphere on the band first). The maps are sampled with 3.10's sampler,
+ * the metallic-roughness map at the base-colour map's transform (ForwardPS.hlsl:103); the shadow map, the staged cube and the BRDF LUT are
+ * filtered as ur_deferred_lighting's definitions say (3.12 lists them).
+ * Constants. Per draw, from the 608 bytes behind each command's ConstantBufferAddress: World, BaseColor, EmissiveFactor, MetallicFactor,
+ * RoughnessFactor, BaseColorAlpha, AlphaCutoff and the BaseColor, Normal and Emissive texture transforms. Per frame, from frame_constants on
+ * the host: LightDirection, LightColor, LightIntensity, CameraPosition, LightViewProjection, ShadowStrength, ShadowBias, ShadowMapSize and
+ * EnvMapMipCount; its other fields are not read, and a command's copies of these nine are not read either. view and projection come from
+ * the host as for ur_depth_prepass.
+ * mask == NULL: the opaque raster alone (ur_gbuffer_pass_materials' keys), and depth is not written. materials == NULL: pipeline key 0 for
+ * every slot.
+ * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most eight launches (ur_gbuffer_pass_masked's
+ * seven raster and merge launches, and the forward resolve).
+ * Read: what ur_gbuffer_pass_masked reads (the resolve reads the keys, keys64 under visible lists, the named vertices' 64 bytes, the constants
+ * and the valid maps of the winning slots); of tables->shadow_map, when ShadowStrength > 0, floats inside its ShadowMapSize.x * ShadowMapSize.y;
+ * of tables->env_cube the bordered faces (the first section of what ur_stage_env_cube wrote); of tables->brdf_lut_rg16 its lut_width *
+ * lut_height texels. None of these is written.
+ * Written: all rows * w keys; of hdr only the texels whose final key is not 0; with a mask, keys64 and depth as ur_gbuffer_pass_masked writes
+ * them. stats6, mask->stats6 and mask->won are added to.
+ * UR_EINVAL, nothing launched: ur_gbuffer_pass_masked's cases (with hdr and keys for the targets: null targets, a null or misaligned hdr
+ * (8 bytes) or keys (4)); null tables or frame_constants; ShadowStrength > 0 with a null shadow_map or a ShadowMapSize outside 1..16384; a
+ * null or misaligned env_cube or brdf_lut_rg16; env_base_size, env_mip_count, lut_width or lut_height 0, or more than 16 mips; an
+ * env_cube_texels that is not ur_env_cube_texels(env_base_size, env_mip_count); hdr or keys overlapping each other, depth, the commands, the
+ * material table, the shadow map, the staged cube, the LUT or keys64.
+ * UR_EUNSUPPORTED, nothing launched: key_triangle_bits == 0 with command_count >= 2^24. */
+int ur_forward_pass(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                    float* depth, const ur_forward_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                    uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, const ur_material* materials, uint32_t material_count,
+                    const ur_gbuffer_mask* mask, const ur_scene_constants* frame_constants, const ur_lighting_tables* tables);
+
+/* ur_forward_pass in parts, as ur_gbuffer_pass_masked_parts: UR_GBUFFER_PART_RASTER is the raster launches and the merge (hdr is not
+ * touched), UR_GBUFFER_PART_RESOLVE the forward resolve over keys and keys64 as that part left them (tools/bench_shadow.py --pass forward).
+ * Arguments, checks and return values are ur_forward_pass', all of them in either part; parts == 0 or an unknown bit is UR_EINVAL. */
+int ur_forward_pass_parts(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                          float* depth, const ur_forward_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                          uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
+                          const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask,
+                          const ur_scene_constants* frame_constants, const ur_lighting_tables* tables);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@
     python tools/bench_shadow.py --pass gbuffer # the GBuffer pass (ur_gbuffer_pass) at 3840 x 2160, its two halves timed apart
     python tools/bench_shadow.py --pass gbuffer --textured # the textured resolve (key 15) beside the untextured one and a streaming kernel
     python tools/bench_shadow.py --pass gbuffer --masked # the alpha-masked raster (ur_gbuffer_pass_masked) beside the all-opaque one
+    python tools/bench_shadow.py --pass forward [--textured] [--masked] # the forward resolve beside the GBuffer resolve + ur_deferred_lighting
 
 A 2048 x 2048 map over three workloads, each with and without a large-triangle queue (ur_raster_reserve):
   small   1 M triangles of 1/8 px to 8 px in one command;
@@ -330,6 +331,95 @@ def gbuffer_masked_leg(a, torch, hp):
              "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, "won": texels_won, "masked_commands": len(masked_slots), "commands": n} for k, t in times.items()]
 
 
+def forward_leg(a, torch, hp):
+    """The rows of --pass forward: at 3840 x 2160 over cold target sets, the small-triangle workload cut into 8 commands as the masked leg
+    cuts it (--textured: pipeline key 15 on one 1024 x 1024 chain of random bytes; --masked: slots 2, 5 and 7 are the masked selection, key
+    bit 4 set), rasterised once per set by the raster part of ur_forward_pass behind its DepthPrepass. Then, batch by batch in the same
+    process over the same keys (and keys64): the forward resolve alone (ur_forward_pass_parts), the GBuffer resolve alone, ur_deferred_lighting
+    alone over the G-buffer that resolve left, and the last two back to back: what the deferred path spends between the keys and the lit HDR.
+    The tables are the shipped shapes with procedural content: a 2048 x 2048 shadow map, a 256-texel 9-mip cube, the 128 x 32 LUT."""
+    from unclerenderer_amd import lib, synth
+    from unclerenderer_amd.hotpath import forward_targets, gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, raster_draws, to_device
+    w, h = GBUFFER_W, GBUFFER_H
+    rng = np.random.default_rng(2163)
+    cb = np.zeros(152, np.float32)
+    cb[:16] = np.eye(4, dtype=np.float32).reshape(-1)
+    cb[64:68], cb[80:83], cb[104], cb[105], cb[106], cb[107] = (0.8, 0.7, 0.6, 1.0), (0.1, 0.2, 0.3), 0.25, 0.5, 1.0, 0.5
+    for at in (112, 120, 128, 136):
+        cb[at + 2], cb[at + 3], cb[at + 4] = 1.0, 1.0, 1.0
+    constants = to_device(cb)
+    pos = camera_space(triangles(rng, a.small, 0.125, 8.0, w, h))
+    v = np.zeros((pos.shape[0], 16), np.float32)
+    v[:, :3], v[:, 5] = pos, -1.0
+    v[:, 6], v[:, 7] = pos[:, 0] / pos[:, 2] * (0.5 * w / 256.0), pos[:, 1] / pos[:, 2] * (0.5 * h / 256.0 * 2.5)
+    v[:, 8], v[:, 11], v[:, 12:16] = 1.0, 1.0, 1.0
+    vb, ib = to_device(v.reshape(-1)), to_device(np.arange(pos.shape[0], dtype=np.uint32))
+    n, masked_slots = 8, ((2, 5, 7) if a.masked else ())
+    cuts = (np.linspace(0, pos.shape[0] // 3, n + 1).astype(int) * 3).tolist()
+    cmds = to_device(pack_draw_commands([dict(vertices=vb, indices=ib, constants=constants, stride=64, start_index=cuts[k], index_count=cuts[k + 1] - cuts[k]) for k in range(n)]))
+    materials = None
+    if a.textured or a.masked:
+        tex = pack_texture([rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)], True)
+        maps = {"base_color": tex, "emissive": tex, "metallic_roughness": tex, "normal": tex} if a.textured else {}
+        materials = pack_materials([{"key": (15 if a.textured else 0) | (16 if k in masked_slots else 0), **maps} for k in range(n)])
+
+    def ranges(slots):
+        return (to_device(np.array(list(slots) + [n], np.uint32)), cmds, to_device(np.ones(len(slots), np.uint32)))
+
+    opaque = ranges([k for k in range(n) if k not in masked_slots])
+    mask_draws = raster_draws(None, None, None, ranges(masked_slots), 0) if a.masked else None
+    scene = lib.SceneConstants()
+    for name in ("World", "View", "ViewInverse"):
+        getattr(scene, name)[:] = VIEW.tolist()
+    scene.Projection[:] = PROJ.tolist()
+    scene.LightDirection[:], scene.LightColor[:], scene.LightIntensity = (0.3, 0.8, -0.5), (1.0, 0.95, 0.85), 3.0
+    scene.LightViewProjection[:] = [0.4, 0, 0, 0, 0, 0.4, 0, 0, 0, 0, 0.3, 0, 0, 0, 0.1, 1]
+    scene.ShadowStrength, scene.ShadowBias, scene.EnvMapMipCount = 0.8, 0.002, 9.0
+    scene.ShadowMapSize[:] = (2048.0, 2048.0)
+    tables = hp.make_tables(to_device(synth.shadow_map_noise(2048, 1)), hp.stage_env_cube(synth.env_cube_procedural(256, 9), 256, 9), 256, 9,
+                            to_device(synth.brdf_lut_procedural(128, 32)))
+    sets = []
+    for _ in range(a.ring):
+        ga, gb, hdr, lit = (torch.zeros((h, w, 4), dtype=torch.float16, device="cuda") for _ in range(4))
+        gc, keys = (torch.zeros((h, w), dtype=torch.int32, device="cuda") for _ in range(2))
+        sets.append(dict(depth=torch.zeros((h, w), dtype=torch.float32, device="cuda"), gbuffer=gbuffer_targets(ga, gb, gc, hdr, keys), forward=forward_targets(lit, keys),
+                         keys64=torch.zeros((h, w), dtype=torch.int64, device="cuda"), a=ga, b=gb, c=gc, hdr=hdr))
+    RASTER, RESOLVE = lib.UR_GBUFFER_PART_RASTER, lib.UR_GBUFFER_PART_RESOLVE
+    hp.raster_reserve(a.reserve)
+
+    def forward(i, parts):
+        s = sets[i % a.ring]
+        mask = dict(mask_draws=mask_draws, keys64=s["keys64"]) if a.masked else {}
+        hp.forward_pass(VIEW, PROJ, None, s["depth"], s["forward"], w, h, scene=scene, tables=tables, ranges=opaque, parts=parts, materials=materials, **mask)
+
+    def resolve(i):
+        s = sets[i % a.ring]
+        mask = dict(mask_draws=mask_draws, keys64=s["keys64"]) if a.masked else {}
+        hp.gbuffer_pass(VIEW, PROJ, None, s["depth"], s["gbuffer"], w, h, ranges=opaque, parts=RESOLVE, materials=materials, **mask)
+
+    def lighting(i):
+        s = sets[i % a.ring]
+        hp.deferred_lighting(scene, s["a"], s["b"], s["c"], tables, s["hdr"], w, h)
+
+    for i in range(a.ring):
+        hp.depth_prepass(VIEW, PROJ, None, sets[i]["depth"], ranges=opaque)
+        forward(i, RASTER)
+    torch.cuda.synchronize()
+    drawn = int((sets[0]["forward"]._keep[1] != 0).sum())
+    fns = {"forward resolve": lambda i: forward(i, RESOLVE), "GBuffer resolve": resolve, "ur_deferred_lighting": lighting,
+           "GBuffer resolve + ur_deferred_lighting": lambda i: (resolve(i), lighting(i))}
+    times = {k: [] for k in fns}
+    for f in fns.values():
+        f(0)
+    torch.cuda.synchronize()
+    for _ in range(a.batches):
+        for k, f in fns.items():
+            times[k].append(time_batch(torch, f, a.iters))
+    kind = f"{'textured' if a.textured else 'untextured'}{', masked' if a.masked else ''}"
+    return [{"shape": f"{w}x{h}, forward, small, {kind}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": [], "batches": len(t),
+             "calls_per_batch": a.iters, "maps": a.ring, "texels_drawn": drawn} for k, t in times.items()]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=7)
@@ -338,9 +428,9 @@ def main():
     ap.add_argument("--small", type=int, default=1_000_000)
     ap.add_argument("--reserve", type=int, default=1 << 19)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer"), default="shadow")
-    ap.add_argument("--textured", action="store_true", help="with --pass gbuffer: the textured resolve beside the untextured one")
-    ap.add_argument("--masked", action="store_true", help="with --pass gbuffer: the alpha-masked raster beside the all-opaque one")
+    ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer", "forward"), default="shadow")
+    ap.add_argument("--textured", action="store_true", help="with --pass gbuffer: the textured resolve beside the untextured one; with --pass forward: key 15")
+    ap.add_argument("--masked", action="store_true", help="with --pass gbuffer: the alpha-masked raster beside the all-opaque one; with --pass forward: a masked selection")
     ap.add_argument("--no-probe-count", action="store_true", help="with --textured: skip the host-side mean probe count")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
@@ -396,10 +486,12 @@ def main():
                              "stats_one_call": seen[k], "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring})
     if a.which == "gbuffer":
         rows += gbuffer_masked_leg(a, torch, hp) if a.masked else (gbuffer_textured_leg(a, torch, hp) if a.textured else gbuffer_leg(a, torch, hp))
+    if a.which == "forward":
+        rows += forward_leg(a, torch, hp)
     hp.raster_reserve(0)
     hp.close()
     for r in rows:
-        print(f"{r['shape']:{96 if a.which == 'gbuffer' else 64}s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
+        print(f"{r['shape']:{96 if a.which in ('gbuffer', 'forward') else 64}s} median {r['median_us']:10.2f} us  min {r['min_us']:10.2f} us  stats {r['stats_one_call']}")
     if a.json:
         with open(a.json, "a") as f:
             for r in rows:

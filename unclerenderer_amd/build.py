@@ -48,6 +48,7 @@ SOURCES = [
     ("debug_print.hip", EXACT),
     ("raster.hip", EXACT),
     ("gbuffer_resolve.hip", EXACT),
+    ("forward_resolve.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),

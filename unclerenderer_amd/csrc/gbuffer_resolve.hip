@@ -2,9 +2,14 @@
 // targets: it fetches the key's triangle again, restates the near clip with a weight row per polygon vertex, interpolates the attributes
 // perspective-correct and runs the base pass' pixel shader (Shaders/DeferredBasePass.hlsl), with or without ObjectId and texture maps
 // (csrc/texture_sample.h). DESIGN.md sections 3.9 and 3.10 are its rule, tests/gbuffer_ref.py the restatement. Built with -ffp-contract=off.
+// The entry points of the Forward pass sit here too: they share gbuffer_entry's checks and raster launches, and
+// their resolve is csrc/forward_resolve.hip's.
 
+#include "forward_resolve.h"
 #include "gbuffer_interp.h"
+#include "lighting_plan.h"
 #include "raster_rule.h"
+#include "resolve_pack.h"
 #include "texture_sample.h"
 #include "ur_device.h"
 #include "ur_internal.h"
@@ -37,18 +42,6 @@ struct ResolveParams {
     const uint32_t* mask_visible_idx;
     uint32_t mask_mode, mask_index_base;
 };
-
-typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes of a vertex: 4-byte aligned
-
-__device__ __forceinline__ uint32_t half_bits(float v)
-{
-    const _Float16 h = (_Float16)v; // round to nearest even
-    return (uint32_t)__builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ ur::once_u32x2_t pack_half4(float x, float y, float z, float w)
-{
-    return ur::once_u32x2_t{half_bits(x) | (half_bits(y) << 16), half_bits(z) | (half_bits(w) << 16)};
-}
 
 // the number of thresholds with x >= entry (ascending entries: a binary search; every compare is false for a NaN: 0)
 __device__ __forceinline__ uint32_t srgb_code(const float* table, float x)
@@ -249,15 +242,63 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
     if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
 }
 
-// The checks and the launches behind the four GBuffer entry points; `who` names the caller in the error text, `who_parts` its _parts form
+// What ur_forward_pass adds to a GBuffer call: its targets are hdr and keys alone, and the resolve shades (csrc/forward_resolve.hip)
+struct ForwardCall {
+    const ur_scene_constants* frame;
+    const ur_lighting_tables* tables;
+};
+
+// ur_forward_pass' own checks (the draws, depth and the matrices have passed theirs); fills in the staged cube's layout
+int check_forward_call(const char* who, const ForwardCall& f, const ur_gbuffer_targets* targets, const ur_raster_draws& draws, const float* depth,
+                       const ur_material* materials, uint32_t material_count, uint32_t w, uint32_t h, uint32_t rows, ur::CubeLayout& cube)
+{
+    if (!targets || !targets->hdr || !targets->keys) { ur::set_error("%s: null targets, hdr or keys", who); return UR_EINVAL; }
+    if (!aligned(targets->hdr, 8) || !aligned(targets->keys, 4)) { ur::set_error("%s: a misaligned target (hdr 8 bytes, keys 4)", who); return UR_EINVAL; }
+    if (!f.frame || !f.tables) { ur::set_error("%s: null frame_constants or tables", who); return UR_EINVAL; }
+    const ur_lighting_tables& t = *f.tables;
+    const float sw = f.frame->ShadowMapSize[0], sh = f.frame->ShadowMapSize[1];
+    const bool shadows = f.frame->ShadowStrength > 0.0f;
+    if (shadows && (!t.shadow_map || !(sw >= 1.0f && sw <= (float)UR_RASTER_MAX_TARGET) || !(sh >= 1.0f && sh <= (float)UR_RASTER_MAX_TARGET))) {
+        ur::set_error("%s: ShadowStrength > 0 without a shadow map, or a ShadowMapSize outside 1..%u", who, UR_RASTER_MAX_TARGET);
+        return UR_EINVAL;
+    }
+    if (!t.env_cube || t.env_base_size == 0u || t.env_mip_count == 0u || t.env_mip_count > 16u || !t.brdf_lut_rg16 || t.lut_width == 0u || t.lut_height == 0u ||
+        !aligned(t.env_cube, 8) || !aligned(t.brdf_lut_rg16, 4) || !aligned(t.shadow_map, 4)) {
+        ur::set_error("%s: bad lighting tables (a null or misaligned cube or LUT, a zero size, no mip or more than 16)", who);
+        return UR_EINVAL;
+    }
+    cube = ur::cube_layout(t.env_base_size, t.env_mip_count);
+    if (cube.mips == 0u || t.env_cube_texels != cube.texels) {
+        ur::set_error("%s: ur_lighting_tables.env_cube_texels = %llu, but ur_stage_env_cube writes %llu texels for a %u^2 cube of %u mips", who,
+                      (unsigned long long)t.env_cube_texels, (unsigned long long)cube.texels, t.env_base_size, t.env_mip_count);
+        return UR_EINVAL;
+    }
+    const size_t n = (size_t)w * rows;
+    const struct { const void* at; size_t bytes; } inputs[] = {
+        {depth, (size_t)w * h * 4u}, {ur::raster_commands(draws), (size_t)draws.command_count * UR_INDIRECT_COMMAND_STRIDE},
+        {materials, (size_t)material_count * sizeof(ur_material)}, {shadows ? t.shadow_map : nullptr, (size_t)sw * (size_t)sh * 4u},
+        {t.env_cube, (size_t)cube.texels * 8u}, {t.brdf_lut_rg16, (size_t)t.lut_width * t.lut_height * 4u}};
+    for (const auto& in : inputs) {
+        if (in.at && in.bytes && (ur::overlaps(targets->hdr, n * 8u, in.at, in.bytes) || ur::overlaps(targets->keys, n * 4u, in.at, in.bytes))) {
+            ur::set_error("%s: hdr or keys overlaps an input (depth, the commands, the materials or a lighting table)", who);
+            return UR_EINVAL;
+        }
+    }
+    if (ur::overlaps(targets->hdr, n * 8u, targets->keys, n * 4u)) { ur::set_error("%s: hdr overlaps keys", who); return UR_EINVAL; }
+    return UR_OK;
+}
+
+// The checks and the launches behind the GBuffer and the Forward entry points; `who` names the caller in the error text, `who_parts` its
+// _parts form; `forward`: ur_forward_pass (targets then holds hdr and keys alone)
 int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth,
                   const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits,
                   uint32_t* stats6, uint32_t parts, const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask = nullptr,
-                  float* depth_out = nullptr)
+                  float* depth_out = nullptr, const ForwardCall* forward = nullptr)
 {
+    ur::CubeLayout cube{};
     int rc = ur::check_raster_call(who, ctx, view, projection, draws, depth, "depth", w, h, stats6);
     if (rc == UR_OK) rc = ur::check_depth_flags(who, flags);
-    if (rc == UR_OK) rc = ur::check_gbuffer_targets(who, targets);
+    if (rc == UR_OK && !forward) rc = ur::check_gbuffer_targets(who, targets);
     if (rc == UR_OK) rc = ur::check_key_triangle_bits(who, key_triangle_bits);
     if (rc != UR_OK) return rc;
     if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("%s: rows [%u, %u + %u) of a target %u high", who, row0, row0, rows, h); return UR_EINVAL; }
@@ -276,6 +317,10 @@ int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const flo
         return UR_EINVAL;
     }
     if (!aligned(materials, 16)) { ur::set_error("%s: a misaligned material table (16 bytes)", who); return UR_EINVAL; }
+    if (forward) {
+        rc = check_forward_call(who, *forward, targets, *draws, depth, materials, material_count, w, h, rows, cube);
+        if (rc != UR_OK) return rc;
+    }
     if (mask) {
         rc = ur::check_gbuffer_mask(who, *draws, *mask, *targets, depth, w, h, rows);
         if (rc != UR_OK) return rc;
@@ -292,6 +337,41 @@ int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const flo
         }
     }
     if (!(parts & UR_GBUFFER_PART_RESOLVE)) return UR_OK;
+    if (forward) {
+        ur::ForwardParams f{};
+        f.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
+        f.mode = draws->visible_idx != nullptr ? 1u : 0u;
+        f.visible_idx = draws->visible_idx; f.index_base = draws->index_base;
+        for (int k = 0; k < 16; ++k) { f.V[k] = view[k]; f.Pr[k] = projection[k]; f.lvp[k] = forward->frame->LightViewProjection[k]; }
+        f.keys = targets->keys; f.hdr = reinterpret_cast<uint2*>(targets->hdr);
+        f.w = w; f.row0 = row0; f.n = n;
+        f.half_w = 0.5f * (float)w; f.half_h = 0.5f * (float)h;
+        f.key_bits = key_bits;
+        f.materials = materials; f.material_count = material_count;
+        f.decode = ctx->srgb_table; f.lod = ctx->lod_table;
+        const bool lists = mask && (draws->visible_idx != nullptr || mask->draws->visible_idx != nullptr);
+        if (lists) {
+            f.keys64 = reinterpret_cast<const unsigned long long*>(mask->keys64);
+            f.mask_mode = mask->draws->visible_idx != nullptr ? 1u : 0u;
+            f.mask_visible_idx = mask->draws->visible_idx; f.mask_index_base = mask->draws->index_base;
+        }
+        const ur_scene_constants& S = *forward->frame;
+        const ur_lighting_tables& T = *forward->tables;
+        for (int k = 0; k < 3; ++k) { f.camera[k] = S.CameraPosition[k]; f.light_direction[k] = S.LightDirection[k]; f.light_color[k] = S.LightColor[k]; }
+        f.light_intensity = S.LightIntensity;
+        f.shadow_strength = S.ShadowStrength; f.shadow_bias = S.ShadowBias;
+        f.shadow_size[0] = S.ShadowMapSize[0]; f.shadow_size[1] = S.ShadowMapSize[1];
+        const float above = S.EnvMapMipCount - 1.0f;
+        f.max_mip = above > 0.0f ? above : 0.0f;
+        f.shadow = T.shadow_map;
+        f.shadow_w = S.ShadowStrength > 0.0f ? (int)S.ShadowMapSize[0] : 0; f.shadow_h = S.ShadowStrength > 0.0f ? (int)S.ShadowMapSize[1] : 0;
+        f.env = reinterpret_cast<const uint2*>(T.env_cube);
+        f.env_base = T.env_base_size; f.env_mips = T.env_mip_count;
+        for (uint32_t m = 0; m < 16u; ++m) f.env_offset[m] = m < T.env_mip_count ? (uint32_t)cube.bordered[m] : 0u;
+        f.lut = reinterpret_cast<const uint32_t*>(T.brdf_lut_rg16);
+        f.lut_w = T.lut_width; f.lut_h = T.lut_height;
+        return ur::launch_forward_resolve(ctx, f, materials != nullptr, lists);
+    }
     ResolveParams r{};
     r.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
     r.mode = draws->visible_idx != nullptr ? 1u : 0u;
@@ -373,6 +453,26 @@ int ur::check_gbuffer_mask(const char* who, const ur_raster_draws& draws, const 
 }
 
 extern "C" {
+
+int ur_forward_pass_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, const ur_forward_targets* targets,
+                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
+                          const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask, const ur_scene_constants* frame_constants,
+                          const ur_lighting_tables* tables)
+{
+    ur_gbuffer_targets t{};
+    if (targets) { t.hdr = targets->hdr; t.keys = targets->keys; }
+    const ForwardCall forward{frame_constants, tables};
+    return gbuffer_entry("ur_forward_pass", "ur_forward_pass_parts", ctx, view, projection, draws, depth, targets ? &t : nullptr, w, h, row0, rows, flags,
+                         key_triangle_bits, stats6, parts, materials, material_count, mask, depth, &forward);
+}
+
+int ur_forward_pass(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, const ur_forward_targets* targets, uint32_t w,
+                    uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, const ur_material* materials,
+                    uint32_t material_count, const ur_gbuffer_mask* mask, const ur_scene_constants* frame_constants, const ur_lighting_tables* tables)
+{
+    return ur_forward_pass_parts(ctx, view, projection, draws, depth, targets, w, h, row0, rows, flags, key_triangle_bits, stats6,
+                                 UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE, materials, material_count, mask, frame_constants, tables);
+}
 
 int ur_gbuffer_pass_masked_parts(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, const ur_gbuffer_targets* targets,
                                  uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,

@@ -873,7 +873,42 @@ def _gbuffer_pass(self, view, projection, commands, depth, targets, w, h, row0=0
         _lib.check(self._L.ur_gbuffer_pass_parts(*args, int(parts)), "ur_gbuffer_pass_parts")
 
 
+def forward_targets(hdr, keys) -> _lib.ForwardTargets:
+    """ur_forward_targets over device tensors of the band (rows x w): hdr float16 (..., 4), keys int32. Keeps them alive."""
+    assert hdr.dtype == torch.float16 and hdr.is_contiguous() and keys.dtype == torch.int32 and keys.is_contiguous()
+    tg = _lib.ForwardTargets(hdr.data_ptr(), keys.data_ptr())
+    tg._keep = (hdr, keys)
+    return tg
+
+
+def _forward_pass(self, view, projection, commands, depth, targets, w, h, row0=0, rows=None, *, scene, tables, visible=None, ranges=None, index_base=0,
+                  stats=None, command_count=None, flags=0, key_triangle_bits=0, parts=None, materials=None, mask_draws=None, keys64=None, mask_stats=None,
+                  won=None):
+    """ur_forward_pass: HotPath.gbuffer_pass' raster (with mask_draws, the masked raster and the merge that raises `depth`), then the forward
+    resolve of the rows [row0, row0 + rows) into targets.hdr (forward_targets(...)) where a key won; the other texels keep what sky_atmosphere
+    drew before. scene: a lib.SceneConstants whose per-frame fields are read (light, camera, LightViewProjection, the shadow fields,
+    EnvMapMipCount; the per-draw ones come from each command's own block); tables: make_tables(...). The other arguments are
+    HotPath.gbuffer_pass'; parts: None, or UR_GBUFFER_PART_RASTER and / or UR_GBUFFER_PART_RESOLVE through ur_forward_pass_parts."""
+    rows = h - row0 if rows is None else rows
+    assert depth.dtype == torch.float32 and depth.numel() >= w * h
+    v, p = _matrix16(view), _matrix16(projection)
+    d = raster_draws(commands, command_count, visible, ranges, index_base)
+    mask = None
+    if mask_draws is not None:
+        assert keys64 is not None and keys64.dtype == torch.int64 and keys64.is_contiguous() and keys64.numel() >= w * rows
+        mask = C.byref(_lib.GBufferMask(C.pointer(mask_draws), keys64.data_ptr(), _ptr(mask_stats), _ptr(won)))
+    table, count = (None, 0) if materials is None else ((materials.table, materials.count) if isinstance(materials, Materials) else materials)
+    head = (self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), C.byref(targets), w, h, int(row0), int(rows), int(flags), int(key_triangle_bits),
+            _ptr(stats))
+    tail = (_ptr(table), int(count), mask, C.byref(scene), C.byref(tables))
+    if parts is None:
+        _lib.check(self._L.ur_forward_pass(*head, *tail), "ur_forward_pass")
+    else:
+        _lib.check(self._L.ur_forward_pass_parts(*head, int(parts), *tail), "ur_forward_pass_parts")
+
+
 HotPath.gbuffer_pass = _gbuffer_pass
+HotPath.forward_pass = _forward_pass
 HotPath.shadow_map = _shadow_map
 HotPath.raster_reserve = _raster_reserve
 HotPath.depth_prepass = _depth_prepass

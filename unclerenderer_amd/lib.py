@@ -91,6 +91,11 @@ class GBufferMask(C.Structure):
     _fields_ = [("draws", C.POINTER(RasterDraws)), ("keys64", C.c_void_p), ("stats6", C.c_void_p), ("won", C.c_void_p)]
 
 
+class ForwardTargets(C.Structure):
+    """ur_forward_targets (include/ur_raster.h): the band's HDR image and the key scratch of ur_forward_pass."""
+    _fields_ = [("hdr", C.c_void_p), ("keys", C.c_void_p)]
+
+
 class FrameGBufferPass(C.Structure):
     """ur_frame_gbuffer_pass (include/ur_frame.h): the draws, targets, optional counters, ur_gbuffer_pass flags and key bits of UR_FRAME_GBUFFER_PASS."""
     _fields_ = [("draws", RasterDraws), ("targets", GBufferTargets), ("stats6", C.c_void_p), ("flags", C.c_uint32), ("key_triangle_bits", C.c_uint32)]
@@ -333,6 +338,10 @@ SIGNATURES = {
                                                _VP, _U32, C.POINTER(GBufferMask)]),
     "ur_gbuffer_pass_materials_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(GBufferTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
                                                   _VP, _U32]),
+    "ur_forward_pass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(ForwardTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _U32,
+                                  C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
+    "ur_forward_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(ForwardTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
+                                        _VP, _U32, C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
