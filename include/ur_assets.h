@@ -33,6 +33,13 @@ typedef struct ur_dds_info {
 } ur_dds_info;
 
 int ur_dds_parse(const void* file, size_t size, ur_dds_info* out);
+/* A material texture for the sampler of the raster passes (ur_texture2d in ur_raster.h): a 2D DDS - no cube, no array, no volume - of
+ * DXGI format 28, 29 (R8G8B8A8_UNORM[_SRGB]), 71, 72 (BC1), 77, 78 (BC3) or 83 (BC5_UNORM), in a DX10 header or as the legacy FourCCs
+ * "DXT1" (71), "DXT5" (77), "ATI2" and "BC5U" (83). Fills `out` (slices 1, is_cube 0; block_dim 4 and 8 or 16 bytes per block for BC,
+ * 1 and 4 for RGBA8). The mip chain behind header_size is in ur_texture2d's order and pitch: the payload is the device buffer.
+ * UR_ASSET_EUNSUPPORTED for any other format or shape, UR_ASSET_EFORMAT for a file that is not DDS, a dimension above 65535, more than
+ * 255 mips or a payload shorter than the chain. */
+int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out);
 /* texels of the whole chain (all slices, all mips) */
 size_t ur_dds_texel_count(const ur_dds_info* info);
 /* BC6H / RGBA16F file -> RGBA16F texels, slice-major, mips inner, rows top-down. reserved_blocks (nullable) counts BC6H

@@ -73,6 +73,16 @@ void ur_host_srgb_decode_table(float out[256]);
  * 128 e + (the number of entries with m >= entry) = floor(256 log2 rho): the device reads these very bytes. */
 void ur_host_lod_table(float out[127]);
 
+/* The block-compressed formats of the material sampler (UR_TEXTURE_BC*), on the host: these two run csrc/bc_decode.h,
+ * the very functions the kernels decode with.
+ * Bytes of a chain of `mips` levels of a width x height texture as ur_texture2d lays it out; 0 for a format that is not one of the five
+ * BC codes, a zero dimension, a dimension above 65535, or mips outside 1..255. */
+uint64_t ur_host_bc_chain_bytes(uint32_t format, uint32_t width, uint32_t height, uint32_t mips);
+/* One level of ((level_width + 3) >> 2) x ((level_height + 3) >> 2) blocks, row-major -> level_width x level_height RGBA8 code words,
+ * row-major, R in byte 0 (the _SRGB formats give the same codes as their UNORM twins: the decode to linear comes behind the code word).
+ * UR_EINVAL for a null pointer, a format that is not one of the five BC codes or a zero dimension. */
+int ur_host_bc_decode_level(uint32_t format, const void* blocks, uint32_t level_width, uint32_t level_height, uint8_t* rgba8_out);
+
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own
  * design for codes 32..95 in 8 x 8 cells of a 64 x 64 R8 atlas; glyph quad = the cell, Size (8, 8), Offset (0, -7), Advance 8

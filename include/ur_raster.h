@@ -157,10 +157,25 @@ int ur_gbuffer_pass_parts(ur_ctx* ctx, const float view[16], const float project
 #define UR_TEXTURE_R8G8B8A8_UNORM 28u      /* DXGI_FORMAT_R8G8B8A8_UNORM */
 #define UR_TEXTURE_R8G8B8A8_UNORM_SRGB 29u /* DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: R, G and B decode through ur_host_srgb_decode_table, alpha never */
 
+/* The block-compressed formats: a texel is the RGBA8 code word that the integer rule of 3.13 decodes from its 4 x 4
+ * block, and everything behind the code word is the RGBA8 formats'. BC2, BC4, BC6H, BC7 and the SNORM forms are not sampled. (The values
+ * stand in parentheses as UR_MATERIAL_ALPHA_MASK's does: tests/test_gbuffer_tex_abi.py pins the list of bare ones.) */
+#define UR_TEXTURE_BC1_UNORM (71u)    /* DXGI_FORMAT_BC1_UNORM: 8-byte blocks; index 3 of a block with c0 <= c1 is (0, 0, 0, 0) */
+#define UR_TEXTURE_BC1_UNORM_SRGB (72u) /* DXGI_FORMAT_BC1_UNORM_SRGB */
+#define UR_TEXTURE_BC3_UNORM (77u)    /* DXGI_FORMAT_BC3_UNORM: 16-byte blocks, an alpha block in front of a four-colour block */
+#define UR_TEXTURE_BC3_UNORM_SRGB (78u) /* DXGI_FORMAT_BC3_UNORM_SRGB */
+#define UR_TEXTURE_BC5_UNORM (83u)    /* DXGI_FORMAT_BC5_UNORM: 16-byte blocks, R and G; B = 0, A = 255 */
+
 /* A texture of the textured GBuffer resolve: `mips` levels packed tightly one behind the other from `texels` (device, 4-byte aligned),
  * level k = max(1, width >> k) x max(1, height >> k) texels of 4 bytes, row-major, R in the low byte. Any size 1..65535, powers of two
  * or not. `mips` may be anything 1..255: levels past the end of the chain (every level from 16 on) are 1 x 1 texels packed one behind
- * the other like any level. */
+ * the other like any level.
+ * A BC format: level k has the same wk = max(1, width >> min(k, 16)) by hk = max(1, height >> min(k, 16)) texels, stored as
+ * ((wk + 3) >> 2) x ((hk + 3) >> 2) blocks, row-major, 8 bytes a block for BC1 and 16 for BC3 and BC5; the levels follow each other with
+ * no padding - the order and pitch of a DDS file's mip chain, so a file's payload is the device buffer - and every level from 16 on is
+ * one block. Texel (x, y) lies in block (x >> 2, y >> 2) at index 4 * (y & 3) + (x & 3). Wrap addressing stays in texels over wk, hk: the
+ * padding texels of an edge block are never selected. `texels` is then aligned to the block size, 8 or 16 bytes
+ * (ur_host_bc_chain_bytes gives the chain's size). */
 typedef struct ur_texture2d {
     uint64_t texels;
     uint16_t width, height;
@@ -178,8 +193,8 @@ typedef struct ur_texture2d {
 /* What the reference binds per draw range (DeferredRenderer.cpp:800): the descriptor table t0-t3 and the pipeline key. One record per
  * command slot. Key bits 4 and above are ignored in ur_gbuffer_pass, _parts, _materials and _materials_parts (USE_ALPHA_MASK is not drawn
  * by them: the caller's ranges keep such models out, or go to ur_gbuffer_pass_masked); bits 5 and above are ignored everywhere. A set bit is
- * treated as clear when its texture has a null address, an address that is not 4-byte aligned, a zero dimension, zero mips or a format
- * other than the two above. */
+ * treated as clear when its texture has a null address, an address that is not aligned to 4 bytes (RGBA8), 8 (BC1) or 16 (BC3, BC5), a zero
+ * dimension, zero mips or a format other than the seven above. */
 typedef struct ur_material {
     ur_texture2d base_color, metallic_roughness, normal, emissive; /* t0, t1, t2, t3 */
     uint32_t pipeline_key;
@@ -196,8 +211,8 @@ typedef struct ur_material {
  * materials: device, 16-byte aligned, material_count records; NULL is ur_gbuffer_pass (material_count is then not looked at). A slot
  * >= material_count resolves as key 0.
  * Read: what ur_gbuffer_pass reads; materials[s] (80 bytes) for every slot s < material_count that a winning key names; of a texture
- * whose bit is set and whose descriptor is valid, 4-byte texels inside its `mips` levels (width, height and mips as the record gives
- * them) and nothing around them. None of these is written.
+ * whose bit is set and whose descriptor is valid, 4-byte texels - of a BC format whole 8- or 16-byte blocks - inside the bytes of its
+ * `mips` levels (width, height, mips and format as the record gives them) and nothing around them. None of these is written.
  * Written, launches, stats6: ur_gbuffer_pass'.
  * UR_EINVAL, nothing launched: ur_gbuffer_pass' cases; materials not 16-byte aligned. */
 int ur_gbuffer_pass_materials(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
@@ -239,8 +254,8 @@ typedef struct ur_gbuffer_mask {
  * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most eight launches (clear, raster and
  * large-triangle queue of the opaque draws, the same three of the masked draws - the queue is reused in stream order -, merge, resolve).
  * Read: what ur_gbuffer_pass_materials reads, for both selections; materials[s] for every slot s < material_count of a masked fragment
- * that passes the depth test; of a masked draw's textures the raster reads the base-colour chain only (4-byte texels inside its `mips`
- * levels), the resolve what ur_gbuffer_pass_materials' reads; TEXCOORD and COLOR.a (bytes 24-31 and 60-63) of such a fragment's vertices and
+ * that passes the depth test; of a masked draw's textures the raster reads the base-colour chain only (4-byte texels, or whole BC blocks,
+ * inside the bytes of its `mips` levels; nothing of a BC5 chain), the resolve what ur_gbuffer_pass_materials' reads; TEXCOORD and COLOR.a (bytes 24-31 and 60-63) of such a fragment's vertices and
  * the constants behind ConstantBufferAddress.
  * Written: ur_gbuffer_pass_materials' targets; all rows * w words of keys64; of depth only rows [row0, row0 + rows), and of those only
  * the texels that `won` counts. stats6 counts the opaque draws, mask->stats6 the masked ones, mask->won is added to.
@@ -285,7 +300,7 @@ typedef struct ur_forward_targets {
  * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most eight launches (ur_gbuffer_pass_masked's
  * seven raster and merge launches, and the forward resolve).
  * Read: what ur_gbuffer_pass_masked reads (the resolve reads the keys, keys64 under visible lists, the named vertices' 64 bytes, the constants
- * and the valid maps of the winning slots); of tables->shadow_map, when ShadowStrength > 0, floats inside its ShadowMapSize.x * ShadowMapSize.y;
+ * and the valid maps of the winning slots: 4-byte texels, or whole BC blocks, inside the bytes of their chains); of tables->shadow_map, when ShadowStrength > 0, floats inside its ShadowMapSize.x * ShadowMapSize.y;
  * of tables->env_cube the bordered faces (the first section of what ur_stage_env_cube wrote); of tables->brdf_lut_rg16 its lut_width *
  * lut_height texels. None of these is written.
  * Written: all rows * w keys; of hdr only the texels whose final key is not 0; with a mask, keys64 and depth as ur_gbuffer_pass_masked writes

@@ -6,6 +6,7 @@
     python tools/bench_shadow.py --pass both # ShadowMap, then the DepthPrepass pass (ur_depth_prepass) over the same triangles
     python tools/bench_shadow.py --pass gbuffer # the GBuffer pass (ur_gbuffer_pass) at 3840 x 2160, its two halves timed apart
     python tools/bench_shadow.py --pass gbuffer --textured # the textured resolve (key 15) beside the untextured one and a streaming kernel
+    python tools/bench_shadow.py --pass gbuffer --textured --bc 1 # the same with the four maps as BC1 blocks (--bc 3, --bc 5; --pass forward too)
     python tools/bench_shadow.py --pass gbuffer --masked # the alpha-masked raster (ur_gbuffer_pass_masked) beside the all-opaque one
     python tools/bench_shadow.py --pass forward [--textured] [--masked] # the forward resolve beside the GBuffer resolve + ur_deferred_lighting
 
@@ -156,6 +157,23 @@ def gbuffer_leg(a, torch, hp):
     return rows
 
 
+BC_FORMATS = {1: (71, 72), 3: (77, 78), 5: (83, 83)}  # --bc N: (UR_TEXTURE_BCN_UNORM, its _SRGB form; BC5 has none)
+
+
+def bc_chain_1024(rng, bc: int, srgb: bool):
+    """A full 1024 x 1024 chain of random blocks (every bit pattern is a valid block): (blocks, format, the decoded levels for the host-side
+    probe count, by ur_host_bc_decode_level)."""
+    from unclerenderer_amd import hostmath
+    fmt = BC_FORMATS[bc][1 if srgb else 0]
+    data = rng.integers(0, 256, hostmath.bc_chain_bytes(fmt, 1024, 1024, 11), dtype=np.uint8)
+    levels, at = [], 0
+    for k in range(11):
+        size = max(1, 1024 >> k)
+        levels.append(hostmath.bc_decode_level(fmt, data[at:], size, size))
+        at += hostmath.bc_chain_bytes(fmt, size, size, 1)
+    return data, fmt, levels
+
+
 def gbuffer_textured_leg(a, torch, hp):
     """The rows of --pass gbuffer --textured: at 3840 x 2160 over cold buffer sets, the resolve part alone (ur_gbuffer_pass_materials_parts)
     with the one command on pipeline key 15 - two 1024 x 1024 sRGB (base colour, emissive) and two UNORM (metallic-roughness, normal)
@@ -164,9 +182,10 @@ def gbuffer_textured_leg(a, torch, hp):
     that in v: about 4 x 10 texels per pixel, so the nominal footprint is N = 3 probes between levels 2 and 3 (the perspective of each
     triangle moves it a little; the mean probe count of a row is computed on the host by the numpy restatement over every 64th texel of the
     keys the device rasterised). Only the targets are ringed: the four 5.6 MB texture chains are shared by every set of the ring, so
-    they stay warm in the L2 and the Infinity Cache, as a frame's textures would between passes but not as a streamed scene's would."""
+    they stay warm in the L2 and the Infinity Cache, as a frame's textures would between passes but not as a streamed scene's would.
+    --bc N: the same four chains as random BC1 / BC3 / BC5 blocks (1.4 MB each in BC3 and BC5, half that in BC1), sRGB forms where RGBA8's are."""
     from unclerenderer_amd import lib
-    from unclerenderer_amd.hotpath import gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, to_device
+    from unclerenderer_amd.hotpath import gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, pack_texture_bc, to_device
     w, h = GBUFFER_W, GBUFFER_H
     rng = np.random.default_rng(2161)
     cb = np.zeros(152, np.float32)
@@ -186,8 +205,15 @@ def gbuffer_textured_leg(a, torch, hp):
         return dict(vertices=to_device(v.reshape(-1)), indices=to_device(np.arange(pos.shape[0], dtype=np.uint32)), constants=constants, stride=64)
 
     chain = lambda: [rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)]  # noqa: E731
-    chains = {"base_color": (chain(), True), "emissive": (chain(), True), "metallic_roughness": (chain(), False), "normal": (chain(), False)}
-    materials = pack_materials([{"key": 15, **{k: pack_texture(*v) for k, v in chains.items()}}])
+    srgb_of = {"base_color": True, "emissive": True, "metallic_roughness": False, "normal": False}
+    if a.bc:
+        blocks = {k: bc_chain_1024(rng, a.bc, srgb) for k, srgb in srgb_of.items()}
+        chains = {k: (levels, fmt in (72, 78)) for k, (_, fmt, levels) in blocks.items()}  # the decoded twins, for mean_probes
+        materials = pack_materials([{"key": 15, **{k: pack_texture_bc(data, 1024, 1024, 11, fmt) for k, (data, fmt, _) in blocks.items()}}])
+    else:
+        chains = {k: (chain(), srgb) for k, srgb in srgb_of.items()}
+        materials = pack_materials([{"key": 15, **{k: pack_texture(*v) for k, v in chains.items()}}])
+    maps_label = f"four 1024 x 1024 BC{a.bc} maps" if a.bc else "four 1024 x 1024 maps"
     host_vertices = {}
 
     def mesh_kept(name, pos):
@@ -234,7 +260,7 @@ def gbuffer_textured_leg(a, torch, hp):
         drawn = int((sets[0][1]._keep[4] != 0).sum())
         probes, level, sampled = mean_probes(name, sets[0][1]._keep[4].cpu().numpy().view(np.uint32)) if not a.no_probe_count else (None, None, 0)
         fns = {"streaming kernel of the resolve's 32 B per texel": lambda i: hp.stream_ceiling(*ring[i % a.ring]),
-               "resolve, untextured": lambda i: gb(i, RESOLVE), "resolve, key 15 (four 1024 x 1024 maps)": lambda i: gb(i, RESOLVE, materials)}
+               "resolve, untextured": lambda i: gb(i, RESOLVE), f"resolve, key 15 ({maps_label})": lambda i: gb(i, RESOLVE, materials)}
         times = {k: [] for k in fns}
         for f in fns.values():
             f(0)
@@ -244,7 +270,7 @@ def gbuffer_textured_leg(a, torch, hp):
                 times[k].append(time_batch(torch, f, a.iters))
         base = float(np.median(times["resolve, untextured"]))
         for k, t in times.items():
-            rows.append({"shape": f"{w}x{h}, gbuffer textured, {name}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": [],
+            rows.append({"shape": f"{w}x{h}, gbuffer textured, {name}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "max_us": float(np.max(t)), "stats_one_call": [],
                          "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, "texels_drawn": drawn, "ratio_to_untextured": float(np.median(t)) / base,
                          "mean_probes_per_map": probes, "mean_level": level, "texels_sampled_for_probes": sampled})
     return rows
@@ -339,7 +365,7 @@ def forward_leg(a, torch, hp):
     alone over the G-buffer that resolve left, and the last two back to back: what the deferred path spends between the keys and the lit HDR.
     The tables are the shipped shapes with procedural content: a 2048 x 2048 shadow map, a 256-texel 9-mip cube, the 128 x 32 LUT."""
     from unclerenderer_amd import lib, synth
-    from unclerenderer_amd.hotpath import forward_targets, gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, raster_draws, to_device
+    from unclerenderer_amd.hotpath import forward_targets, gbuffer_targets, pack_draw_commands, pack_materials, pack_texture, pack_texture_bc, raster_draws, to_device
     w, h = GBUFFER_W, GBUFFER_H
     rng = np.random.default_rng(2163)
     cb = np.zeros(152, np.float32)
@@ -359,7 +385,11 @@ def forward_leg(a, torch, hp):
     cmds = to_device(pack_draw_commands([dict(vertices=vb, indices=ib, constants=constants, stride=64, start_index=cuts[k], index_count=cuts[k + 1] - cuts[k]) for k in range(n)]))
     materials = None
     if a.textured or a.masked:
-        tex = pack_texture([rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)], True)
+        if a.bc:  # the one chain as random blocks
+            data, fmt, _ = bc_chain_1024(rng, a.bc, True)
+            tex = pack_texture_bc(data, 1024, 1024, 11, fmt)
+        else:
+            tex = pack_texture([rng.integers(0, 256, (max(1, 1024 >> k), max(1, 1024 >> k), 4), dtype=np.uint8) for k in range(11)], True)
         maps = {"base_color": tex, "emissive": tex, "metallic_roughness": tex, "normal": tex} if a.textured else {}
         materials = pack_materials([{"key": (15 if a.textured else 0) | (16 if k in masked_slots else 0), **maps} for k in range(n)])
 
@@ -415,8 +445,8 @@ def forward_leg(a, torch, hp):
     for _ in range(a.batches):
         for k, f in fns.items():
             times[k].append(time_batch(torch, f, a.iters))
-    kind = f"{'textured' if a.textured else 'untextured'}{', masked' if a.masked else ''}"
-    return [{"shape": f"{w}x{h}, forward, small, {kind}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": [], "batches": len(t),
+    kind = f"{'textured' if a.textured else 'untextured'}{f' BC{a.bc}' if a.bc else ''}{', masked' if a.masked else ''}"
+    return [{"shape": f"{w}x{h}, forward, small, {kind}, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "max_us": float(np.max(t)), "stats_one_call": [], "batches": len(t),
              "calls_per_batch": a.iters, "maps": a.ring, "texels_drawn": drawn} for k, t in times.items()]
 
 
@@ -431,9 +461,12 @@ def main():
     ap.add_argument("--pass", dest="which", choices=("shadow", "depth", "both", "gbuffer", "forward"), default="shadow")
     ap.add_argument("--textured", action="store_true", help="with --pass gbuffer: the textured resolve beside the untextured one; with --pass forward: key 15")
     ap.add_argument("--masked", action="store_true", help="with --pass gbuffer: the alpha-masked raster beside the all-opaque one; with --pass forward: a masked selection")
+    ap.add_argument("--bc", type=int, choices=(1, 3, 5), default=0, help="with --textured: the maps as random BC1 / BC3 / BC5 blocks instead of RGBA8 texels")
     ap.add_argument("--no-probe-count", action="store_true", help="with --textured: skip the host-side mean probe count")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
+    if a.bc and not (a.textured and a.which in ("gbuffer", "forward")):
+        ap.error("--bc goes with --pass gbuffer --textured or --pass forward --textured")
     if a.quick:
         a.batches, a.iters, a.ring = 1, 2, 2
     import torch

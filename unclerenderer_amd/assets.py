@@ -1,5 +1,6 @@
-"""IBL asset loading: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables.
-All decoding happens in libur_hotpath.so (csrc/dds.cpp); this module only reads the file and marshals."""
+"""Asset loading. IBL: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables. Material textures: DDS
+(RGBA8, BC1, BC3, BC5) -> what hotpath.pack_texture / pack_texture_bc take; BC blocks stay compressed, the sampler decodes them.
+All parsing and decoding happens in libur_hotpath.so (csrc/dds.cpp); this module only reads the file and marshals."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,3 +43,38 @@ def load_brdf_lut_dds(path) -> np.ndarray:
     if rc != 0:
         raise ValueError(f"ur_dds_copy_rg16 failed ({rc})")
     return out
+
+
+# MakeSRGBFormat (Source/Render/TextureLoader.cpp) for the formats the sampler takes; BC5 has no sRGB form
+_SRGB_FORM = {_lib.UR_TEXTURE_R8G8B8A8_UNORM: _lib.UR_TEXTURE_R8G8B8A8_UNORM_SRGB, _lib.UR_TEXTURE_BC1_UNORM: _lib.UR_TEXTURE_BC1_UNORM_SRGB,
+              _lib.UR_TEXTURE_BC3_UNORM: _lib.UR_TEXTURE_BC3_UNORM_SRGB}
+
+
+def parse_texture_dds(data: bytes) -> _lib.DdsInfo:
+    info = _lib.DdsInfo()
+    rc = _lib.load().ur_dds_parse_texture2d(data, len(data), C.byref(info))
+    if rc != 0:
+        raise ValueError(f"ur_dds_parse_texture2d failed ({rc}): not a 2D DDS of RGBA8, BC1, BC3 or BC5 with its whole mip chain")
+    return info
+
+
+def load_texture_dds(path_or_bytes, srgb: bool = False):
+    """A material texture from a DDS file (a path, or the file's bytes). `srgb` applies the reference's MakeSRGBFormat: 28 -> 29, 71 -> 72,
+    77 -> 78, every other format as it is. Returns the arguments of the packer that takes it:
+      a BC format: (payload bytes, width, height, mips, format) for hotpath.pack_texture_bc(*...);
+      RGBA8:       (levels, srgb) for hotpath.pack_texture(*...), levels a list of (h, w, 4) uint8 arrays."""
+    data = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else Path(path_or_bytes).read_bytes()
+    info = parse_texture_dds(data)
+    fmt = int(info.dxgi_format)
+    if srgb:
+        fmt = _SRGB_FORM.get(fmt, fmt)
+    w, h, mips = int(info.width), int(info.height), int(info.mip_count)
+    sizes = [(max(1, w >> min(k, 16)), max(1, h >> min(k, 16))) for k in range(mips)]
+    if info.block_dim == 4:
+        size = sum(((wk + 3) >> 2) * ((hk + 3) >> 2) for wk, hk in sizes) * int(info.bytes_per_block)
+        return data[info.header_size:info.header_size + size], w, h, mips, fmt
+    levels, at = [], int(info.header_size)
+    for wk, hk in sizes:
+        levels.append(np.frombuffer(data, np.uint8, wk * hk * 4, at).reshape(hk, wk, 4).copy())
+        at += wk * hk * 4
+    return levels, fmt == _lib.UR_TEXTURE_R8G8B8A8_UNORM_SRGB

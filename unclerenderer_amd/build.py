@@ -53,6 +53,7 @@ SOURCES = [
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),
     ("host_math.cpp", ["-x", "hip"] + EXACT),
+    ("bc_host.cpp", ["-x", "hip"]),  # host code only, over csrc/bc_decode.h: integer arithmetic, so no flag changes its results
     ("lighting_plan.cpp", ["-x", "hip"] + EXACT),
     ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),

@@ -322,6 +322,49 @@ int ur_dds_parse(const void* file, size_t size, ur_dds_info* out)
     return UR_ASSET_OK;
 }
 
+// A material texture: what the sampler of the raster passes takes (include/ur_raster.h), in the container forms the reference's loader
+// meets (Source/Render/TextureLoader.cpp:42-63, 178-315). The payload behind the header is the device buffer as it lies.
+int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out)
+{
+    if (!file || !out || size < 128) return UR_ASSET_EINVAL;
+    const uint8_t* p = static_cast<const uint8_t*>(file);
+    if (rd32(p) != kMagic || rd32(p + 4) != 124) return UR_ASSET_EFORMAT;
+    ur_dds_info d{};
+    d.height = rd32(p + 12);
+    d.width = rd32(p + 16);
+    d.mip_count = rd32(p + 28) ? rd32(p + 28) : 1u;
+    const uint32_t pf_flags = rd32(p + 80), fourcc = rd32(p + 84), caps2 = rd32(p + 112);
+    d.header_size = 128;
+    d.slices = 1;
+    if (caps2 & (DDSCAPS2_CUBEMAP | 0x200000u)) return UR_ASSET_EUNSUPPORTED; // a cube or a volume
+    if (!(pf_flags & DDPF_FOURCC)) return UR_ASSET_EUNSUPPORTED;
+    if (fourcc == kFourCC_DX10) {
+        if (size < 148) return UR_ASSET_EFORMAT;
+        d.header_size = 148;
+        d.dxgi_format = rd32(p + 128);
+        const uint32_t dimension = rd32(p + 132), misc = rd32(p + 136), array_size = rd32(p + 140);
+        if (dimension != 3u || (misc & 0x4u) || array_size > 1u) return UR_ASSET_EUNSUPPORTED; // not TEXTURE2D, a cube, an array
+    } else if (fourcc == 0x31545844u) d.dxgi_format = 71u; // "DXT1"
+    else if (fourcc == 0x35545844u) d.dxgi_format = 77u;   // "DXT5"
+    else if (fourcc == 0x32495441u || fourcc == 0x55354342u) d.dxgi_format = 83u; // "ATI2", "BC5U"
+    else return UR_ASSET_EUNSUPPORTED;
+    switch (d.dxgi_format) {
+    case 28u: case 29u: d.block_dim = 1; d.bytes_per_block = 4; break;
+    case 71u: case 72u: d.block_dim = 4; d.bytes_per_block = 8; break;
+    case 77u: case 78u: case 83u: d.block_dim = 4; d.bytes_per_block = 16; break;
+    default: return UR_ASSET_EUNSUPPORTED;
+    }
+    if (d.width == 0 || d.height == 0 || d.width > 65535u || d.height > 65535u || d.mip_count > 255u) return UR_ASSET_EFORMAT;
+    size_t need = d.header_size;
+    for (uint32_t m = 0; m < d.mip_count; ++m) {
+        const size_t bw = (mip_dim(d.width, m < 16u ? m : 16u) + d.block_dim - 1) / d.block_dim, bh = (mip_dim(d.height, m < 16u ? m : 16u) + d.block_dim - 1) / d.block_dim;
+        need += bw * bh * d.bytes_per_block;
+    }
+    if (need > size) return UR_ASSET_EFORMAT;
+    *out = d;
+    return UR_ASSET_OK;
+}
+
 size_t ur_dds_texel_count(const ur_dds_info* d)
 {
     if (!d) return 0;

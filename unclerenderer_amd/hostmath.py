@@ -83,6 +83,27 @@ def srgb_decode_table() -> np.ndarray:
     return out
 
 
+def bc_chain_bytes(format: int, width: int, height: int, mips: int) -> int:
+    """ur_host_bc_chain_bytes: the bytes of a chain of `mips` BC1 / BC3 / BC5 levels as ur_texture2d lays them out (0 for anything it does not
+    describe: another format, a dimension outside 1..65535, mips outside 1..255)."""
+    return int(_lib.load().ur_host_bc_chain_bytes(int(format), int(width), int(height), int(mips)))
+
+
+def bc_decode_level(format: int, blocks, level_width: int, level_height: int) -> np.ndarray:
+    """ur_host_bc_decode_level: one level of ((w + 3) >> 2) x ((h + 3) >> 2) blocks (bytes or a uint8 array) -> its (h, w, 4) uint8 RGBA8 code
+    words, by the functions the kernels decode with (csrc/bc_decode.h)."""
+    data = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8).reshape(-1)
+    per = 8 if format in (_lib.UR_TEXTURE_BC1_UNORM, _lib.UR_TEXTURE_BC1_UNORM_SRGB) else 16
+    need = ((level_width + 3) >> 2) * ((level_height + 3) >> 2) * per
+    if level_width < 1 or level_height < 1 or data.size < need:
+        raise ValueError(f"a {level_width} x {level_height} level of format {format} needs {need} bytes of blocks, got {data.size}")
+    out = np.zeros((level_height, level_width, 4), np.uint8)
+    rc = _lib.load().ur_host_bc_decode_level(int(format), data.ctypes.data_as(C.c_void_p), int(level_width), int(level_height), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"ur_host_bc_decode_level failed ({rc}): format {format}")
+    return out
+
+
 def lod_table() -> np.ndarray:
     """ur_host_lod_table: the 127 ascending fp32 thresholds 2^(j / 128), j = 1..127, of the textured GBuffer resolve's level of detail."""
     out = np.zeros(127, np.float32)

@@ -810,6 +810,21 @@ def pack_texture(levels, srgb: bool) -> Texture:
     return Texture(buffer, desc)
 
 
+def pack_texture_bc(payload, width: int, height: int, mips: int, format: int) -> Texture:
+    """A chain of BC1 / BC3 / BC5 blocks (bytes or a uint8 array: a DDS file's payload as it lies, level 0 first, no padding) becomes one device
+    buffer and its descriptor. `format` is one of lib.UR_TEXTURE_BC*; the length must be what hostmath.bc_chain_bytes gives for the chain."""
+    from . import hostmath
+    data = np.frombuffer(bytes(payload), np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, np.uint8).reshape(-1)
+    need = hostmath.bc_chain_bytes(format, width, height, mips)
+    if need == 0:
+        raise ValueError(f"no BC chain: format {format}, {width} x {height}, {mips} mips (UR_TEXTURE_BC*, sizes 1..65535, mips 1..255)")
+    if data.size != need:
+        raise ValueError(f"a {width} x {height} chain of {mips} mips in format {format} is {need} bytes, the payload has {data.size}")
+    buffer = to_device(data.copy())  # (torch allocations are aligned far beyond a block's 16 bytes)
+    assert buffer.data_ptr() % 16 == 0
+    return Texture(buffer, _lib.Texture2D(buffer.data_ptr(), width, height, mips, int(format), 0))
+
+
 class Materials:
     """A ur_material table on the device: `table` (int32 tensor, 20 dwords per record), `count`, and the textures it points to."""
 
