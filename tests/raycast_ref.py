@@ -39,6 +39,16 @@ them per scene and target with record_property and asserts each is at most 1). T
   shadow             3.69 %, 1.31 %                  0.0278, 0.0379   -                -
 A's 0.125 is the half ulp of fp16 rounding over the 4-ulp bound, C's 0.5 one code where the spread's ends encode alike; ObjectId, B, HDR
 and covered-or-clear agree exactly everywhere. No disagreement was found, so no rule changed.
+
+The textured, the alpha-masked and the forward pass are held by tests/raycast_tex.py, which takes hits() - every
+hit of every ray with the whole 64-byte vertex - and winners() from here and adds the pixel shaders' material, the alpha test and the
+level of detail. Its scenes against the section 3.10 bounds (128 fp16 ulps, 4 codes), the same way; its docstring has every output:
+  scene              left out (64 x 64, 257 x 130)   A                C          B.yz             hdr (emissive)
+  textured           1.86 %, 0.28 %                  0.0255, 0.0253   0.2, 0.2   0.0041, 0.0041   0.0041, 0.0040
+  textured strip     1.15 %, 0.55 %                  0.0163, 0.0249   0.2, 0.2   0.0045, 0.0047   0.0042, 0.0049
+  levels             3.70 %, 2.74 %                  0.0093, 0.0165   0.2, 0.2   0.4476, 0.4525   0.4436, 0.4526  (the level read back: 0.4734, 0.4746)
+  masked             1.27 %, 0.28 %                  0.0225, 0.0238   0.2, 0.2   0.0041, 0.0041   0.0040, 0.0040  (depth behind the pass: 0.0242, 0.0247)
+  forward            4.39 %, 0.99 % (textured), 2.69 %, 0.65 % (masked); hdr within 0.2383, 0.2456 and 0.2368, 0.2436 of 2 fp16 ulps + spread
 """
 from __future__ import annotations
 
@@ -63,9 +73,10 @@ _ROUNDING = 1e-9  # float64 rounding of the ray caster itself, relative: lets tw
 # ---- the draws as triangles -----------------------------------------------------------------------------------------------------------
 
 def _mesh(d):
-    """(positions (n, 3, 3), normals (n, 3, 3), colours (n, 3, 3)) of a draw's triangles in float64, object space."""
+    """Every attribute of a draw's triangles in float64, object space: (positions (n, 3, 3), normals (n, 3, 3), colours (n, 3, 4) with
+    COLOR.a, texcoords (n, 3, 2), tangents (n, 3, 4) with TANGENT.w). A vertex shorter than 64 bytes has position alone."""
     if d.instance_count == 0:
-        return (np.zeros((0, 3, 3)),) * 3
+        return np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3, 4)), np.zeros((0, 3, 2)), np.zeros((0, 3, 4))
     raw = np.ascontiguousarray(d.vertices).reshape(-1).view(np.uint8)
     floats = raw[:raw.size // d.stride * d.stride].reshape(-1, d.stride)
     idx = np.ascontiguousarray(d.indices).reshape(-1).view(np.uint32).astype(np.int64)
@@ -73,8 +84,8 @@ def _mesh(d):
     tri = idx[d.start_index:d.start_index + 3 * n].reshape(n, 3) + d.base_vertex
     v = floats[tri.reshape(-1)].copy().view(np.float32).astype(np.float64).reshape(n, 3, -1)
     if v.shape[2] >= 16:
-        return v[:, :, 0:3], v[:, :, 3:6], v[:, :, 12:15]
-    return v[:, :, 0:3], np.zeros((n, 3, 3)), np.ones((n, 3, 3))
+        return v[:, :, 0:3], v[:, :, 3:6], v[:, :, 12:16], v[:, :, 6:8], v[:, :, 8:12]
+    return v[:, :, 0:3], np.zeros((n, 3, 3)), np.ones((n, 3, 4)), np.zeros((n, 3, 2)), np.zeros((n, 3, 4))
 
 
 def _m4(m):
@@ -107,6 +118,16 @@ def cast(draws, w: int, h: int, view=None, proj=None, lvp=None, tile: int = 16):
     (.., 3) - NaN on a miss -, and, for classify(), "gtri" (the triangle counted over all draws), "altitude" (per such triangle: its
     smallest screen-space altitude in px) and "plane_spread" ((h, w): the sheet test's prediction). tile: see below; any value gives
     the same result."""
+    H = hits(draws, w, h, view, proj, lvp, tile)
+    order = np.lexsort((H["z"] if H["light"] else -H["z"], H["ray"]))  # per ray, the winner first
+    first = order[np.r_[True, H["ray"][order][1:] != H["ray"][order][:-1]]] if order.size else order
+    return winners(H, first)
+
+
+def hits(draws, w: int, h: int, view=None, proj=None, lvp=None, tile: int = 16):
+    """Every hit of every ray, not only the nearest: a dict of the rays (o, d (9 h w, 3)), the triangles in world space (P, and per
+    vertex N, C (rgba), UV, TAN: the tangent through World's 3 x 3, normalised per vertex as the vertex shaders do, with w passed
+    through; owner, local), and per hit its ray, triangle (counted over all draws), world-space barycentrics, point and depth z / w."""
     light = lvp is not None
     V = None if light else _m4(view)
     VP = _m4(lvp) if light else V @ _m4(proj)
@@ -116,17 +137,21 @@ def cast(draws, w: int, h: int, view=None, proj=None, lvp=None, tile: int = 16):
     o, d = _rays(px[None] + 0.5 + OFFSETS[:, 0, None, None], py[None] + 0.5 + OFFSETS[:, 1, None, None], w, h, inv_vp, light)
     R = o.shape[0]
 
-    P, N, C, owner, local, base = [], [], [], [], [], []
+    P, N, C, UV, TAN, owner, local, base = [], [], [], [], [], [], [], []
     for k, dr in enumerate(draws):
-        p, n, c = _mesh(dr)
+        p, n, c, uv, tan = _mesh(dr)
         W = _m4(dr.world)
         P.append(p @ W[:3, :3] + W[3, :3])
         N.append(n @ W[:3, :3])  # the shader's mul(N, (float3x3)World)
         C.append(c)
+        UV.append(uv)
+        with np.errstate(all="ignore"):
+            t = tan[:, :, :3] @ W[:3, :3]
+            TAN.append(np.concatenate([t / np.linalg.norm(t, axis=2, keepdims=True), tan[:, :, 3:4]], axis=2))
         owner.append(np.full(p.shape[0], k))
         local.append(np.arange(p.shape[0]))
         base.append(np.asarray(getattr(dr, "base_color", np.ones(3)), np.float64))
-    P, N, C, owner, local = (np.concatenate(a) for a in (P, N, C, owner, local))
+    P, N, C, UV, TAN, owner, local = (np.concatenate(a) for a in (P, N, C, UV, TAN, owner, local))
     T = P.shape[0]
 
     # Pluecker side products: for the edge v_i -> v_j, u = d . (v_i x v_j) + (v_j - v_i) . (o x d) = d . ((v_i - o) x (v_j - o)). The three
@@ -163,13 +188,18 @@ def cast(draws, w: int, h: int, view=None, proj=None, lvp=None, tile: int = 16):
     with np.errstate(all="ignore"):
         z = clip[:, 2] / clip[:, 3]
     ok = ((z >= 0) & (z <= 1)) if light else ((clip[:, 3] > 0) & (clip[:, 2] <= clip[:, 3]))
-    hr, ht, hb, point, z = hr[ok], ht[ok], hb[ok], point[ok], z[ok]
-    order = np.lexsort((z if light else -z, hr))  # per ray, the winner first
-    first = order[np.r_[True, hr[order][1:] != hr[order][:-1]]] if order.size else order
-    hr, ht, hb, point, z = hr[first], ht[first], hb[first], point[first], z[first]
+    return {"w": w, "h": h, "light": light, "V": V, "VP": VP, "along": along, "o": o, "d": d, "P": P, "N": N, "C": C, "UV": UV, "TAN": TAN, "owner": owner,
+            "local": local, "base": np.stack(base) if base else np.zeros((0, 3)), "ray": hr[ok], "tri": ht[ok], "bary": hb[ok], "point": point[ok], "z": z[ok]}
 
+
+def winners(H, chosen):
+    """cast()'s dict from hits() and the indices of the hit each ray keeps (at most one per ray)."""
+    w, h, light, V, VP, along, o, d, P, N, C, owner, local = (H[k] for k in ("w", "h", "light", "V", "VP", "along", "o", "d", "P", "N", "C", "owner", "local"))
+    hr, ht, hb, point, z = (H[k][chosen] for k in ("ray", "tri", "bary", "point", "z"))
+    R = o.shape[0]
     out = {"hit": np.zeros(R, bool), "draw": np.full(R, -1), "tri": np.full(R, -1), "gtri": np.full(R, -1), "depth": np.full(R, np.nan),
-           "view_depth": np.full(R, np.nan), "normal": np.full((R, 3), np.nan), "albedo": np.full((R, 3), np.nan)}
+           "view_depth": np.full(R, np.nan), "normal": np.full((R, 3), np.nan), "albedo": np.full((R, 3), np.nan), "index": np.full(R, -1)}
+    out["index"][hr] = chosen  # (the kept hit's place in hits()' arrays)
     out["hit"][hr], out["draw"][hr], out["tri"][hr], out["gtri"][hr], out["depth"][hr] = True, owner[ht], local[ht], ht, z
     out["view_depth"][hr] = -(point @ along[:3] + along[3])
     with np.errstate(all="ignore"):
@@ -177,7 +207,7 @@ def cast(draws, w: int, h: int, view=None, proj=None, lvp=None, tile: int = 16):
         n = n / np.linalg.norm(n, axis=1, keepdims=True)
         m = n @ (np.eye(3) if light else V[:3, :3])
         out["normal"][hr] = m / np.linalg.norm(m, axis=1, keepdims=True)
-    out["albedo"][hr] = np.stack(base)[owner[ht]] * np.einsum("nk,nkc->nc", hb, C[ht])
+    out["albedo"][hr] = H["base"][owner[ht]] * np.einsum("nk,nkc->nc", hb, C[ht][:, :, :3])
     out = {k: v.reshape((9, h, w) + v.shape[1:]) for k, v in out.items()}
 
     # the sheet test's prediction: the view depths at which the 9 rays meet the plane of the centre ray's triangle
