@@ -8,7 +8,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from tests.test_taa_abi import LLVM, _code_objects, _kernel_metadata
+from tests.code_objects import LLVM, code_objects, kernel_metadata
 
 ROOT = Path(__file__).resolve().parent.parent
 NEW = ("ur_debug_print_buffer_bytes", "ur_debug_print_reset", "ur_debug_print_stats", "ur_debug_print_text", "ur_debug_print_draw",
@@ -149,8 +149,8 @@ def test_kernels_use_no_scratch(urlib, tmp_path, record_property):
     if not (LLVM / "llvm-readelf").exists():
         pytest.skip("llvm tools not found")
     meta = {}
-    for co in _code_objects(lib.library_path(), tmp_path):
-        meta.update({k: v for k, v in _kernel_metadata(co).items() if "debug_print_" in k})
+    for co in code_objects(lib.library_path(), tmp_path):
+        meta.update({k: v for k, v in kernel_metadata(co).items() if "debug_print_" in k})
     for want in ("debug_print_stats_kernel", "debug_print_text_kernel", "debug_print_draw_kernel"):
         hits = [k for k in meta if want in k]
         assert len(hits) == 1, (want, sorted(meta))

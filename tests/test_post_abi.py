@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 from tests import post_ref
+from tests.code_objects import LLVM, library_kernels
 
 ROOT = Path(__file__).resolve().parent.parent
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 F = np.float32
 
 
@@ -93,45 +93,11 @@ def test_frame_flags_do_not_collide():
     assert len(set(defined.values())) == len(defined)
 
 
-def _kernel_metadata(co: Path) -> dict:
-    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s*(.*)$", line)
-        if not m:
-            continue
-        k, v = m.group(1), m.group(2).strip().strip("'\"")
-        if k == "name" and v.startswith("_Z") and not v.endswith(".kd"):
-            cur = kernels.setdefault(v, {})
-        elif cur is not None and k in ("private_segment_fixed_size", "vgpr_spill_count", "vgpr_count") and v.isdigit():
-            cur[k] = int(v)
-    return kernels
-
-
 def test_post_kernels_use_no_scratch(urlib, tmp_path):
     """The gfx950 code of the AutoExposure and CAS kernels (all four strip forms) has no scratch and no spills."""
-    import struct
-    from unclerenderer_amd import lib
     if not (LLVM / "llvm-readelf").exists():
         pytest.skip("llvm tools not found")
-    fat = tmp_path / "fat.bin"
-    subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib.library_path()), str(tmp_path / "x.so")], check=True)
-    data = fat.read_bytes()
-    magic, meta, pos, n_co = b"__CLANG_OFFLOAD_BUNDLE__", {}, 0, 0
-    while (i := data.find(magic, pos)) >= 0:
-        (n,) = struct.unpack_from("<Q", data, i + 24)
-        o = i + 32
-        for _ in range(n):
-            off, size, tl = struct.unpack_from("<QQQ", data, o)
-            o += 24
-            triple = data[o:o + tl].decode()
-            o += tl
-            if "gfx950" in triple and size:
-                co = tmp_path / f"co_{n_co}.elf"
-                co.write_bytes(data[i + off:i + off + size])
-                n_co += 1
-                meta.update(_kernel_metadata(co))
-        pos = i + len(magic)
+    meta = library_kernels(tmp_path)
     post = {k: v for k, v in meta.items() if "cas_strip_kernel" in k or "auto_exposure_kernel" in k}
     assert len(post) == 5, sorted(post)
     for name, m in post.items():

@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import re
 import socket
-import struct
 import subprocess
 from pathlib import Path
 
@@ -15,8 +14,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.code_objects import LLVM, library_kernels
+
 ROOT = Path(__file__).resolve().parent.parent
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 F = np.float32
 NEW = ("ur_post_record_bytes", "ur_pack_post_record", "ur_auto_exposure_records", "ur_tonemap_cas_halo", "ur_cas_halo",
        "ur_frame_set_post_records", "ur_frame_finish_post")
@@ -95,36 +95,12 @@ def test_null_and_bad_arguments_are_rejected(urlib):
         assert fn(ctx, C.byref(tm), C.byref(bad), p, None, None, None, q, 16, 16, 0, 16) == lib.UR_EUNSUPPORTED
 
 
-def _fatbin_kernels(tmp_path) -> dict:
-    from tests.test_post_abi import _kernel_metadata
-    from unclerenderer_amd import lib
-    fat = tmp_path / "fat.bin"
-    subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib.library_path()), str(tmp_path / "x.so")], check=True)
-    data = fat.read_bytes()
-    magic, meta, pos, n_co = b"__CLANG_OFFLOAD_BUNDLE__", {}, 0, 0
-    while (i := data.find(magic, pos)) >= 0:
-        (n,) = struct.unpack_from("<Q", data, i + 24)
-        o = i + 32
-        for _ in range(n):
-            off, size, tl = struct.unpack_from("<QQQ", data, o)
-            o += 24
-            triple = data[o:o + tl].decode()
-            o += tl
-            if "gfx950" in triple and size:
-                co = tmp_path / f"co_{n_co}.elf"
-                co.write_bytes(data[i + off:i + off + size])
-                n_co += 1
-                meta.update(_kernel_metadata(co))
-        pos = i + len(magic)
-    return meta
-
-
 def test_new_kernels_use_no_scratch(urlib, tmp_path):
     """post_record_kernel, ae_records_kernel and the four cas_halo_kernel forms: no scratch, no spills; and the names the existing
     count of cas_strip_kernel / auto_exposure_kernel forms relies on are not reused."""
     if not (LLVM / "llvm-readelf").exists():
         pytest.skip("llvm tools not found")
-    meta = _fatbin_kernels(tmp_path)
+    meta = library_kernels(tmp_path)
     new = {k: v for k, v in meta.items() if any(n in k for n in ("post_record_kernel", "ae_records_kernel", "cas_halo_kernel"))}
     assert len(new) == 6, sorted(new)
     assert sum("cas_halo_kernel" in k for k in new) == 4

@@ -2,14 +2,14 @@
 ur_frame_set_taa / reset_taa / taa_next, UR_FRAME_TAA / FUSE_TAA_TONEMAP), and the gfx950 code of the strip kernel's three forms."""
 import ctypes as C
 import re
-import struct
 import subprocess
 from pathlib import Path
 
 import pytest
 
+from tests.code_objects import LLVM, code_objects, kernel_metadata
+
 ROOT = Path(__file__).resolve().parent.parent
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 NEW = ("ur_temporal_aa_tonemap", "ur_frame_set_taa", "ur_frame_reset_taa", "ur_frame_taa_next", "ur_host_taa_jitter", "ur_host_apply_taa_jitter")
 
 
@@ -155,41 +155,6 @@ def test_frame_ring_argument_checks(urlib):
             urlib.ur_frame_destroy(f)
 
 
-def _code_objects(lib_path: Path, tmp_path: Path) -> list[Path]:
-    fat = tmp_path / "fat.bin"
-    subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib_path), str(tmp_path / "discard.so")], check=True)
-    data, magic, out, pos = fat.read_bytes(), b"__CLANG_OFFLOAD_BUNDLE__", [], 0
-    while (i := data.find(magic, pos)) >= 0:
-        (n,) = struct.unpack_from("<Q", data, i + 24)
-        o = i + 32
-        for _ in range(n):
-            off, size, tl = struct.unpack_from("<QQQ", data, o)
-            o += 24
-            triple = data[o:o + tl].decode()
-            o += tl
-            if "gfx950" in triple and size:
-                p = tmp_path / f"co_{len(out)}.elf"
-                p.write_bytes(data[i + off:i + off + size])
-                out.append(p)
-        pos = i + len(magic)
-    return out
-
-
-def _kernel_metadata(co: Path) -> dict:
-    notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-    kernels, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*\.(\w+):\s*(.*)$", line)
-        if not m:
-            continue
-        k, v = m.group(1), m.group(2).strip().strip("'\"")
-        if k == "name" and v.startswith("_Z") and not v.endswith(".kd"):
-            cur = kernels.setdefault(v, {})
-        elif cur is not None and k in ("private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "vgpr_count", "sgpr_count") and v.isdigit():
-            cur[k] = int(v)
-    return kernels
-
-
 def test_strip_kernels_use_no_scratch(urlib, tmp_path, record_property):
     """The gfx950 code of taa_strip_kernel: the plain form (ur_temporal_aa) and the two Tonemap forms (ur_temporal_aa_tonemap with
     either history-store hint) have no scratch and spill neither VGPRs nor SGPRs. The register counts are recorded, not asserted."""
@@ -197,8 +162,8 @@ def test_strip_kernels_use_no_scratch(urlib, tmp_path, record_property):
     if not (LLVM / "llvm-readelf").exists():
         pytest.skip("llvm tools not found")
     meta = {}
-    for co in _code_objects(lib.library_path(), tmp_path):
-        meta.update({k: v for k, v in _kernel_metadata(co).items() if "taa_strip_kernel" in k})
+    for co in code_objects(lib.library_path(), tmp_path):
+        meta.update({k: v for k, v in kernel_metadata(co).items() if "taa_strip_kernel" in k})
     assert len(meta) == 3, sorted(meta)
     assert sum("TonemapPost" in k for k in meta) == 2 and sum("NoPost" in k for k in meta) == 1, sorted(meta)
     for name, m in meta.items():

@@ -201,13 +201,13 @@ def test_new_kernels_use_no_scratch(urlib, tmp_path):
     """taa_band_kernel (plain and Tonemap forms) and taa_record_kernel: no scratch, no VGPR or SGPR spills, and within the register
     budget of the strip kernel they share their body with (8 waves per SIMD: at most 64 VGPRs). Their names contain none of the
     substrings by which the existing tests count kernels."""
-    from tests.test_taa_abi import _code_objects, _kernel_metadata
+    from tests.code_objects import code_objects, kernel_metadata
     from unclerenderer_amd import lib
     if not (LLVM / "llvm-readelf").exists():
         pytest.skip("llvm tools not found")
     meta = {}
-    for co in _code_objects(lib.library_path(), tmp_path):
-        meta.update(_kernel_metadata(co))
+    for co in code_objects(lib.library_path(), tmp_path):
+        meta.update(kernel_metadata(co))
     new = {k: v for k, v in meta.items() if "taa_band_kernel" in k or "taa_record_kernel" in k}
     assert len(new) == 3, sorted(new)
     assert sum("taa_band_kernel" in k and "NoPost" in k for k in new) == 1 and sum("taa_band_kernel" in k and "TonemapPost" in k for k in new) == 1

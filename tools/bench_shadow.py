@@ -124,7 +124,7 @@ def gbuffer_leg(a, torch, hp):
     rows = []
 
     def row(shape, t, seen=None, **more):
-        rows.append({"shape": f"{w}x{h}, gbuffer, {shape}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": seen or [],
+        rows.append({"shape": f"{w}x{h}, gbuffer, {shape}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "max_us": float(np.max(t)), "stats_one_call": seen or [],
                      "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, **more})
 
     for oid in (False, True):
@@ -353,7 +353,7 @@ def gbuffer_masked_leg(a, torch, hp):
     for _ in range(a.batches):
         for k, f in fns.items():
             times[k].append(time_batch(torch, f, a.iters))
-    return [{"shape": f"{w}x{h}, gbuffer masked, small, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "stats_one_call": seen if "mask" in k else [],
+    return [{"shape": f"{w}x{h}, gbuffer masked, small, {k}", "median_us": float(np.median(t)), "min_us": float(np.min(t)), "max_us": float(np.max(t)), "stats_one_call": seen if "mask" in k else [],
              "batches": len(t), "calls_per_batch": a.iters, "maps": a.ring, "won": texels_won, "masked_commands": len(masked_slots), "commands": n} for k, t in times.items()]
 
 

@@ -48,6 +48,7 @@ SOURCES = [
     ("debug_print.hip", EXACT),
     ("raster.hip", EXACT),
     ("gbuffer_resolve.hip", EXACT),
+    ("gbuffer_api.hip", EXACT),  # host code only: the entry points of the GBuffer and the Forward pass
     ("forward_resolve.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),

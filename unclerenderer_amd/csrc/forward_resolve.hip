@@ -5,11 +5,9 @@
 // is its rule, tests/forward_ref.py the restatement. Built with -ffp-contract=off; every divide and square root is IEEE.
 
 #include "forward_resolve.h"
-#include "gbuffer_interp.h"
-#include "raster_rule.h"
 #include "resolve_pack.h"
-#include "texture_sample.h"
 #include "ur_device.h"
+#include "visibility_key.h"
 
 namespace {
 
@@ -229,40 +227,27 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
     __shared__ uint32_t mip_offset[kLdsMips];
     __shared__ float sampler_tables[MAPS ? kLdsFloats : 1u];
     if (threadIdx.x < kLdsMips) mip_offset[threadIdx.x] = p.env_offset[threadIdx.x];
-    if constexpr (MAPS) {
-        sampler_tables[kLdsDecode + threadIdx.x] = p.decode[threadIdx.x];
-        sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
-        if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.lod[min(threadIdx.x, 126u)];
-    }
+    if constexpr (MAPS) fill_sampler_tables<true>(sampler_tables, p.decode, p.lod);
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     const uint32_t key = i < p.n ? p.keys[i] : 0u;
     __syncthreads();
     if (__ballot(key != 0u) == 0ull) return; // nothing of this wave's 64 texels is covered
     if (key == 0u) return;                   // hdr keeps what the caller drew before (the sky)
-    const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
-    uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
-    if constexpr (MASKED) {
-        if (p.keys64[i] != 0ull) slot = p.mask_mode == 1u ? p.mask_visible_idx[ordinal] - p.mask_index_base : ordinal;
-    }
-    const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
-    const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
-    const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
-    const uint32_t* indices = reinterpret_cast<const uint32_t*>((uint64_t)c1.x | ((uint64_t)c1.y << 32));
-    const float* cb = reinterpret_cast<const float*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
-    const uint32_t stride = c0.w;
-    const uint64_t first = (uint64_t)c3.x + 3ull * t;
-    const long long base_vertex = (int)c3.y;
-    float W[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) W[k] = cb[k];
+    uint32_t t;
+    const uint32_t slot = key_slot<MASKED>(p, key, i, t);
+    const KeyDraw d = key_draw(p.commands, slot, t);
+    const float* cb = d.cb;
+    const float (&W)[16] = d.W;
 
-    // ---- ForwardVS.hlsl on the three vertices: clip position (rule 1), WorldPos, Normal * (float3x3)World, the normalised tangent, Color
+    // ---- ForwardVS.hlsl on the three vertices: clip position (rule 1), WorldPos, Normal * (float3x3)World, the normalised tangent, Color.
+    // (One text with the vertex stage of GBuffer's resolve, csrc/gbuffer_resolve.hip, and not one function: in every form tried the
+    // textured kernel here spills two or three registers to scratch at its three-wave bound. DESIGN.md 3.14 has the table)
     float c[3][4], wp[3][3], wn[3][3], col[3][3];
     [[maybe_unused]] float uv[3][2], tg[3][4];
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
-        const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
-        const f32x4u_t* vp = reinterpret_cast<const f32x4u_t*>(vertices + vi * stride);
+        const uint64_t vi = (uint64_t)(d.base_vertex + (long long)d.indices[d.first + (uint32_t)v]);
+        const f32x4u_t* vp = reinterpret_cast<const f32x4u_t*>(d.vertices + vi * d.stride);
         const f32x4u_t v0 = vp[0], v1 = vp[1], v3 = vp[3];
         const float x = v0.x, y = v0.y, z = v0.z, nx = v0.w, ny = v1.x, nz = v1.y;
         float wv[4], vv[4];
@@ -326,52 +311,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
             const bool odd_column = (column & 1u) != 0u, odd_row = ((p.row0 + row) & 1u) != 0u;
             float pu[3], pv[3]; // TEXCOORD at the centre, the horizontal and the vertical partner
             quad_texcoords(pc, B, uv, odd_column, odd_row, pu, pv);
-#pragma unroll 1
-            for (uint32_t map = 0u; map < 4u; ++map) { // t0 base colour, t1 metallic-roughness, t2 normal, t3 emissive
-                const uint32_t bit = map == 0u ? UR_MATERIAL_BASE_COLOR_MAP : (map == 1u ? UR_MATERIAL_METALLIC_ROUGHNESS_MAP : (map == 2u ? UR_MATERIAL_NORMAL_MAP : UR_MATERIAL_EMISSIVE_MAP));
-                if (__ballot((bits & bit) != 0u) == 0ull) continue;
-                if ((bits & bit) == 0u) continue;
-                const u32x4_t desc = reinterpret_cast<const u32x4_t*>(p.materials + slot)[map];
-                if (!valid_texture(desc)) { bits &= ~bit; continue; }
-                // the map's OffsetScale and Rotation in ur_scene_constants; the metallic-roughness map is sampled at baseUV (ForwardPS.hlsl:103)
-                const uint32_t at = map == 1u ? 112u : 112u + 8u * map;
-                float tu[3], tv[3];
-#pragma unroll
-                for (int point = 0; point < 3; ++point) texture_transform(cb, at, pu[point], pv[point], tu[point], tv[point]);
-                const float dxu = odd_column ? tu[0] - tu[1] : tu[1] - tu[0], dxv = odd_column ? tv[0] - tv[1] : tv[1] - tv[0];
-                const float dyu = odd_row ? tu[0] - tu[2] : tu[2] - tu[0], dyv = odd_row ? tv[0] - tv[2] : tv[2] - tv[0];
-                float smp[3];
-                sample_map<0, 3, false>(desc, tu[0], tv[0], dxu, dxv, dyu, dyv, sampler_tables, smp); // (no SPLIT: 168 registers do not hold both forms)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (map == 0u) base[k] = smp[k];
-                    if (map == 1u) mr[k] = smp[k];
-                    if (map == 2u) nm[k] = smp[k];
-                    if (map == 3u) em[k] = smp[k];
-                }
-            }
+            // (no SPLIT: 168 registers do not hold both forms of the gather)
+            sample_maps<false, true>(p.materials + slot, bits, cb, pu, pv, odd_column, odd_row, sampler_tables, base, mr, nm, em);
         }
         if (bits & UR_MATERIAL_NORMAL_MAP) {
-            float tan4[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) tan4[k] = (b[0] * tg[0][k] + b[1] * tg[1][k]) + b[2] * tg[2][k];
-            const float dt = (vn[0] * tan4[0] + vn[1] * tan4[1]) + vn[2] * tan4[2];
-            const float u0 = tan4[0] - vn[0] * dt, u1 = tan4[1] - vn[1] * dt, u2 = tan4[2] - vn[2] * dt;
-            const float ul = sqrtf((u0 * u0 + u1 * u1) + u2 * u2);
-            const float t0 = u0 / ul, t1 = u1 / ul, t2 = u2 / ul;
-            const float x0 = vn[1] * t2 - vn[2] * t1, x1 = vn[2] * t0 - vn[0] * t2, x2 = vn[0] * t1 - vn[1] * t0;
-            const float xl = sqrtf((x0 * x0 + x1 * x1) + x2 * x2);
-            const float bt0 = (x0 / xl) * tan4[3], bt1 = (x1 / xl) * tan4[3], bt2 = (x2 / xl) * tan4[3];
+            float tn[3], bt[3];
+            tangent_frame(vn, b, tg, tn, bt);
+            // the tangent-space vector: the map's three channels (ForwardPS.hlsl takes the blue as it is; GBuffer's shader reconstructs it)
             const float nr = nm[0] * 2.0f - 1.0f, ng = nm[1] * 2.0f - 1.0f, nb = nm[2] * 2.0f - 1.0f;
             const bool flat = sqrtf((nr * nr + ng * ng) + nb * nb) < 1e-5f;
-            const float e0 = flat ? 0.0f : nr, e1 = flat ? 0.0f : ng, e2 = flat ? 1.0f : nb;
-            const float w0 = (e0 * t0 + e1 * bt0) + e2 * vn[0], w1 = (e0 * t1 + e1 * bt1) + e2 * vn[1], w2 = (e0 * t2 + e1 * bt2) + e2 * vn[2];
-            const float wl = sqrtf((w0 * w0 + w1 * w1) + w2 * w2);
-            s.n[0] = w0 / wl; s.n[1] = w1 / wl; s.n[2] = w2 / wl;
+            const float e[3] = {flat ? 0.0f : nr, flat ? 0.0f : ng, flat ? 1.0f : nb};
+            tangent_to_world(e, tn, bt, vn, s.n);
         }
-        if (bits & UR_MATERIAL_BASE_COLOR_MAP) { s.albedo[0] = s.albedo[0] * base[0]; s.albedo[1] = s.albedo[1] * base[1]; s.albedo[2] = s.albedo[2] * base[2]; }
-        if (bits & UR_MATERIAL_METALLIC_ROUGHNESS_MAP) { s.metallic = s.metallic * mr[2]; s.roughness = s.roughness * mr[1]; }
-        if (bits & UR_MATERIAL_EMISSIVE_MAP) { s.emissive[0] = s.emissive[0] * em[0]; s.emissive[1] = s.emissive[1] * em[1]; s.emissive[2] = s.emissive[2] * em[2]; }
+        apply_map_factors(bits, base, mr, em, s.albedo, s.metallic, s.roughness, s.emissive);
     }
 
     // ---- phase 2: the shading, and the store

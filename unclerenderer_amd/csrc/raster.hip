@@ -28,13 +28,12 @@
 //
 // GBuffer's alpha-masked draws (restated in tests/gbuffer_mask_ref.py) are a third keyed policy: a fragment that
 // passes the depth test competes for a 64-bit word per texel, (depth bits << 32) | key, and runs the base pass' alpha test (alpha_discards
-// below, with the resolve's interpolation and sampler: gbuffer_interp.h, texture_sample.h) only when its word is above the texel's; a
+// below, with the resolves' front end: visibility_key.h, gbuffer_interp.h, texture_sample.h) only when its word is above the texel's; a
 // merge launch then folds the words into the opaque draws' key image and raises the depth where a masked fragment won.
 
-#include "gbuffer_interp.h"
 #include "raster_rule.h"
-#include "texture_sample.h"
 #include "ur_internal.h"
+#include "visibility_key.h"
 
 namespace {
 
@@ -305,27 +304,19 @@ template <class P>
 __device__ __forceinline__ bool alpha_discards(const AlphaCtx& a, uint32_t key, int px, int py)
 {
     const MaskedParams& p = *a.p;
-    const uint32_t ordinal = (key >> p.key_bits) - 1u, t = key & ((1u << p.key_bits) - 1u);
-    const uint32_t slot = p.mode == 1u ? p.visible_idx[ordinal] - p.index_base : ordinal;
+    uint32_t t;
+    const uint32_t slot = key_slot<false>(p, key, 0u, t); // (the masked draws' own selection: no detour)
     uint32_t bits = 0u;
     if (p.mask.materials != nullptr && slot < p.mask.material_count) bits = reinterpret_cast<const uint32_t*>(p.mask.materials + slot)[16];
     if ((bits & UR_MATERIAL_ALPHA_MASK) == 0u) return false;
-    const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
-    const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
-    const uint8_t* vertices = reinterpret_cast<const uint8_t*>((uint64_t)c0.x | ((uint64_t)c0.y << 32));
-    const uint32_t* indices = reinterpret_cast<const uint32_t*>((uint64_t)c1.x | ((uint64_t)c1.y << 32));
-    const float* cb = reinterpret_cast<const float*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
-    const uint32_t stride = c0.w;
-    const uint64_t first = (uint64_t)c3.x + 3ull * t;
-    const long long base_vertex = (int)c3.y;
-    float W[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) W[k] = cb[k];
+    const KeyDraw d = key_draw(p.commands, slot, t);
+    const float* cb = d.cb;
+    const float (&W)[16] = d.W;
     float c[3][4], uv[3][2], va[3]; // clip position, TEXCOORD, COLOR.a
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
-        const uint64_t vi = (uint64_t)(base_vertex + (long long)indices[first + (uint32_t)v]);
-        const float* vp = reinterpret_cast<const float*>(vertices + vi * stride);
+        const uint64_t vi = (uint64_t)(d.base_vertex + (long long)d.indices[d.first + (uint32_t)v]);
+        const float* vp = reinterpret_cast<const float*>(d.vertices + vi * d.stride);
         P::project(vp, W, p, c[v]);
         uv[v][0] = vp[6]; uv[v][1] = vp[7];
         va[v] = vp[15];
@@ -346,9 +337,8 @@ __device__ __forceinline__ bool alpha_discards(const AlphaCtx& a, uint32_t key, 
             quad_texcoords(pc, B, uv, odd_column, odd_row, pu, pv);
 #pragma unroll
             for (int point = 0; point < 3; ++point) texture_transform(cb, 112u, pu[point], pv[point], tu[point], tv[point]);
-            const float dxu = odd_column ? tu[0] - tu[1] : tu[1] - tu[0], dxv = odd_column ? tv[0] - tv[1] : tv[1] - tv[0];
-            const float dyu = odd_row ? tu[0] - tu[2] : tu[2] - tu[0], dyv = odd_row ? tv[0] - tv[2] : tv[2] - tv[0];
-            float sa[1];
+            float dxu, dxv, dyu, dyv, sa[1];
+            quad_differences(tu, tv, odd_column, odd_row, dxu, dxv, dyu, dyv);
             sample_map<3, 1>(desc, tu[0], tv[0], dxu, dxv, dyu, dyv, a.lds, sa);
             alpha = alpha * sa[0];
         }
@@ -375,8 +365,7 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(typename P::Params p)
     typename P::Alpha alpha{};
     if constexpr (P::kMasked) {
         __shared__ float sampler_tables[kLdsFloats];
-        sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
-        if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.mask.lod[min(threadIdx.x, 126u)];
+        fill_sampler_tables<false>(sampler_tables, nullptr, p.mask.lod);
         __syncthreads();
         alpha.p = &p; alpha.lds = sampler_tables;
     }
@@ -619,8 +608,7 @@ template <class P>
 __global__ __launch_bounds__(kThreads) void large_masked_kernel(MaskedParams p)
 {
     __shared__ float sampler_tables[kLdsFloats];
-    sampler_tables[kLdsUnorm + threadIdx.x] = (float)threadIdx.x / 255.0f;
-    if (threadIdx.x < 128u) sampler_tables[kLdsLod + threadIdx.x] = p.mask.lod[min(threadIdx.x, 126u)];
+    fill_sampler_tables<false>(sampler_tables, nullptr, p.mask.lod);
     __syncthreads();
     large_body<P>(p.queue, p.queue_cap, p.map, p.w, p.depth, p.row0, AlphaCtx{&p, sampler_tables});
 }

@@ -1,4 +1,4 @@
-// What the two resolves over the visibility keys (csrc/gbuffer_resolve.hip, csrc/forward_resolve.hip) share beside gbuffer_interp.h: the
+// What the two resolves over the visibility keys (csrc/gbuffer_resolve.hip, csrc/forward_resolve.hip) share beside visibility_key.h and gbuffer_interp.h: the
 // 4-byte aligned load of 16 bytes of a vertex and the RGBA16F store's packing. Device inline functions only.
 #pragma once
 

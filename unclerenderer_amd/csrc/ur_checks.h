@@ -1,6 +1,6 @@
 // The host-only view of the internals: what host callers outside the C-ABI units (the frame units, csrc/frame/) need of them. No device code
 // and nothing of ur_ctx's layout: a plain C++ compiler takes it. ur_internal.h includes it; the definitions stay where they were
-// (ur_api.hip, cull_api.hip, raster.hip, gbuffer_resolve.hip). Not installed.
+// (ur_api.hip, cull_api.hip, raster.hip, gbuffer_api.hip). Not installed.
 #pragma once
 
 #include <cstddef>
@@ -47,8 +47,8 @@ inline int check_depth_flags(const char* who, uint32_t flags)
     if (flags & ~UR_DEPTH_QUANTIZE_D24) { set_error("%s: unknown flag bits 0x%x", who, flags & ~UR_DEPTH_QUANTIZE_D24); return UR_EINVAL; }
     return UR_OK;
 }
-int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_resolve.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
-// (gbuffer_resolve.hip) what ur_gbuffer_pass_masked adds: the masked draws' own checks, one key space, keys64, no overlap, no ObjectId
+int check_gbuffer_targets(const char* who, const ur_gbuffer_targets* targets); // (gbuffer_api.hip) none null but object_id; gbuf_a, gbuf_b, hdr 8-byte aligned, the others 4
+// (gbuffer_api.hip) what ur_gbuffer_pass_masked adds: the masked draws' own checks, one key space, keys64, no overlap, no ObjectId
 int check_gbuffer_mask(const char* who, const ur_raster_draws& draws, const ur_gbuffer_mask& mask, const ur_gbuffer_targets& targets, const float* depth, uint32_t w,
                        uint32_t h, uint32_t rows);
 inline int check_key_triangle_bits(const char* who, uint32_t bits)
