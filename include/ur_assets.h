@@ -40,6 +40,11 @@ int ur_dds_parse(const void* file, size_t size, ur_dds_info* out);
  * UR_ASSET_EUNSUPPORTED for any other format or shape, UR_ASSET_EFORMAT for a file that is not DDS, a dimension above 65535, more than
  * 255 mips or a payload shorter than the chain. */
 int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out);
+/* A source of ur_texture_transcode (include/ur_raster.h): everything ur_dds_parse_texture2d accepts, plus DXGI 74, 75 (BC2), 80
+ * (BC4_UNORM), 98 and 99 (BC7), in a DX10 header or as the legacy FourCCs "DXT3" (74), "ATI1" and "BC4U" (80); 8 bytes a block for BC4,
+ * 16 for BC2 and BC7. The payload behind header_size is the source chain as it lies. The SNORM forms, BC6H, cubes, arrays and volumes
+ * stay UR_ASSET_EUNSUPPORTED; the other refusals are ur_dds_parse_texture2d's. */
+int ur_dds_parse_texture2d_source(const void* file, size_t size, ur_dds_info* out);
 /* texels of the whole chain (all slices, all mips) */
 size_t ur_dds_texel_count(const ur_dds_info* info);
 /* BC6H / RGBA16F file -> RGBA16F texels, slice-major, mips inner, rows top-down. reserved_blocks (nullable) counts BC6H

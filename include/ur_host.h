@@ -83,6 +83,15 @@ uint64_t ur_host_bc_chain_bytes(uint32_t format, uint32_t width, uint32_t height
  * UR_EINVAL for a null pointer, a format that is not one of the five BC codes or a zero dimension. */
 int ur_host_bc_decode_level(uint32_t format, const void* blocks, uint32_t level_width, uint32_t level_height, uint8_t* rgba8_out);
 
+/* The same two over the ten source formats of ur_texture_transcode (include/ur_raster.h): 71, 72, 77, 78, 83 and
+ * UR_TEXTURE_SOURCE_* 74, 75, 80, 98, 99. They run csrc/bc_wide_decode.h, the very functions the transcode kernel decodes with.
+ * Bytes of the source chain: 8 bytes a block for BC1 and BC4, 16 for the rest, in the layout above; 0 for any other format, a zero
+ * dimension, a dimension above 65535, or mips outside 1..255. */
+uint64_t ur_host_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t height, uint32_t mips);
+/* One level of blocks -> level_width x level_height RGBA8 code words, as ur_host_bc_decode_level. UR_EINVAL for a null pointer, a format
+ * outside the ten or a zero dimension. */
+int ur_host_texture_decode_level(uint32_t format, const void* blocks, uint32_t level_width, uint32_t level_height, uint8_t* rgba8_out);
+
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own
  * design for codes 32..95 in 8 x 8 cells of a 64 x 64 R8 atlas; glyph quad = the cell, Size (8, 8), Offset (0, -7), Advance 8

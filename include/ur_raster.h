@@ -183,6 +183,31 @@ typedef struct ur_texture2d {
     uint16_t reserved;
 } ur_texture2d; /* 16 bytes */
 
+/* Transcode at load time: a chain of block-compressed levels becomes the RGBA8 chain the sampler is fastest on, on the
+ * device. The sources are the five BC codes above and the five below - ten in all. The five below are transcode sources only, never
+ * ur_texture2d.format values: a descriptor that carries one is invalid as before. (Values in parentheses, as above.) */
+#define UR_TEXTURE_SOURCE_BC2_UNORM (74u)      /* DXGI_FORMAT_BC2_UNORM: 16 four-bit alphas (A = a * 17) in front of a four-colour block */
+#define UR_TEXTURE_SOURCE_BC2_UNORM_SRGB (75u) /* DXGI_FORMAT_BC2_UNORM_SRGB */
+#define UR_TEXTURE_SOURCE_BC4_UNORM (80u)      /* DXGI_FORMAT_BC4_UNORM: 8-byte blocks, R; G = B = 0, A = 255 */
+#define UR_TEXTURE_SOURCE_BC7_UNORM (98u)      /* DXGI_FORMAT_BC7_UNORM: 16-byte blocks, the BPTC rule; the reserved mode is (0, 0, 0, 0) */
+#define UR_TEXTURE_SOURCE_BC7_UNORM_SRGB (99u) /* DXGI_FORMAT_BC7_UNORM_SRGB */
+
+/* Bytes of the RGBA8 chain of a width x height texture with `mips` levels: 4 bytes a texel, level k = max(1, width >> min(k, 16)) by
+ * max(1, height >> min(k, 16)), tightly packed. Host only. 0 for a zero dimension, a dimension above 65535, or mips outside 1..255. */
+uint64_t ur_texture_transcode_bytes(uint32_t width, uint32_t height, uint32_t mips);
+/* Decode the chain at `blocks` (device; the BC layout above, 8 bytes a block for BC1 and BC4 and 16 for the rest;
+ * ur_host_texture_chain_bytes gives its size) into the RGBA8 chain at `rgba8` (device, ur_texture_transcode_bytes bytes): every texel
+ * becomes its RGBA8 code word, R in the low byte, the _SRGB forms giving their UNORM twins' code words. One launch on the context's
+ * stream, asynchronous: the host neither reads device memory nor synchronises. Reads exactly the source chain's bytes and writes
+ * exactly the destination chain's; the padding texels of edge blocks are never written.
+ * out_descriptor (host, nullable) is filled with {rgba8, width, height, mips, UR_TEXTURE_R8G8B8A8_UNORM_SRGB for the sources 72, 75,
+ * 78 and 99, else UR_TEXTURE_R8G8B8A8_UNORM}: what ur_material takes.
+ * UR_EINVAL, nothing launched: a null context, blocks or rgba8; a source_format outside the ten; blocks not aligned to the block size
+ * (8 or 16 bytes); rgba8 not 4-byte aligned; a zero dimension, a dimension above 65535, mips outside 1..255; source and destination
+ * sharing a byte. */
+int ur_texture_transcode(ur_ctx* ctx, uint32_t source_format, const void* blocks, uint32_t width, uint32_t height, uint32_t mips, void* rgba8,
+                         ur_texture2d* out_descriptor);
+
 #define UR_MATERIAL_NORMAL_MAP 0x1u             /* BuildPipelineKey (DeferredRenderer.cpp:28-36): USE_NORMAL_MAP, texture t2 */
 #define UR_MATERIAL_METALLIC_ROUGHNESS_MAP 0x2u /* USE_METALLIC_ROUGHNESS_MAP, t1 */
 #define UR_MATERIAL_BASE_COLOR_MAP 0x4u         /* USE_BASE_COLOR_MAP, t0 */

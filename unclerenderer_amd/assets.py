@@ -1,5 +1,6 @@
 """Asset loading. IBL: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables. Material textures: DDS
 (RGBA8, BC1, BC3, BC5) -> what hotpath.pack_texture / pack_texture_bc take; BC blocks stay compressed, the sampler decodes them.
+BC2, BC4 and BC7 too (load_texture_dds_source) -> what HotPath.transcode_texture takes: decoded to RGBA8 once, on the device.
 All parsing and decoding happens in libur_hotpath.so (csrc/dds.cpp); this module only reads the file and marshals."""
 from __future__ import annotations
 
@@ -56,6 +57,35 @@ def parse_texture_dds(data: bytes) -> _lib.DdsInfo:
     if rc != 0:
         raise ValueError(f"ur_dds_parse_texture2d failed ({rc}): not a 2D DDS of RGBA8, BC1, BC3 or BC5 with its whole mip chain")
     return info
+
+
+# ... and for the formats that only the transcode takes; BC4 has no sRGB form
+_SRGB_SOURCE_FORM = {**_SRGB_FORM, _lib.UR_TEXTURE_SOURCE_BC2_UNORM: _lib.UR_TEXTURE_SOURCE_BC2_UNORM_SRGB,
+                     _lib.UR_TEXTURE_SOURCE_BC7_UNORM: _lib.UR_TEXTURE_SOURCE_BC7_UNORM_SRGB}
+
+
+def parse_texture_dds_source(data: bytes) -> _lib.DdsInfo:
+    info = _lib.DdsInfo()
+    rc = _lib.load().ur_dds_parse_texture2d_source(data, len(data), C.byref(info))
+    if rc != 0:
+        raise ValueError(f"ur_dds_parse_texture2d_source failed ({rc}): not a 2D DDS of RGBA8, BC1, BC2, BC3, BC4, BC5 or BC7 with its whole mip chain")
+    return info
+
+
+def load_texture_dds_source(path_or_bytes, srgb: bool = False):
+    """A block-compressed source of HotPath.transcode_texture from a DDS file (a path, or the file's bytes): BC1, BC2, BC3, BC4_UNORM, BC5_UNORM
+    or BC7. `srgb` applies the reference's MakeSRGBFormat: 71 -> 72, 74 -> 75, 77 -> 78, 98 -> 99. Returns (payload bytes, width, height,
+    mips, format): transcode_texture's arguments. An RGBA8 file has nothing to transcode: ValueError (load_texture_dds takes it)."""
+    data = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else Path(path_or_bytes).read_bytes()
+    info = parse_texture_dds_source(data)
+    if info.block_dim != 4:
+        raise ValueError(f"format {int(info.dxgi_format)} is not block-compressed: load_texture_dds takes it")
+    fmt = int(info.dxgi_format)
+    if srgb:
+        fmt = _SRGB_SOURCE_FORM.get(fmt, fmt)
+    w, h, mips = int(info.width), int(info.height), int(info.mip_count)
+    size = sum(((max(1, w >> min(k, 16)) + 3) >> 2) * ((max(1, h >> min(k, 16)) + 3) >> 2) for k in range(mips)) * int(info.bytes_per_block)
+    return data[info.header_size:info.header_size + size], w, h, mips, fmt
 
 
 def load_texture_dds(path_or_bytes, srgb: bool = False):

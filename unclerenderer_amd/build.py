@@ -50,6 +50,7 @@ SOURCES = [
     ("gbuffer_resolve.hip", EXACT),
     ("gbuffer_api.hip", EXACT),  # host code only: the entry points of the GBuffer and the Forward pass
     ("forward_resolve.hip", EXACT),
+    ("texture_transcode.hip", []),  # integer arithmetic alone: no flag changes its results
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),

@@ -324,7 +324,8 @@ int ur_dds_parse(const void* file, size_t size, ur_dds_info* out)
 
 // A material texture: what the sampler of the raster passes takes (include/ur_raster.h), in the container forms the reference's loader
 // meets (Source/Render/TextureLoader.cpp:42-63, 178-315). The payload behind the header is the device buffer as it lies.
-int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out)
+// `source`: the formats that only ur_texture_transcode takes (BC2, BC4_UNORM, BC7) pass too.
+static int parse_texture2d(const void* file, size_t size, ur_dds_info* out, bool source)
 {
     if (!file || !out || size < 128) return UR_ASSET_EINVAL;
     const uint8_t* p = static_cast<const uint8_t*>(file);
@@ -347,11 +348,15 @@ int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out)
     } else if (fourcc == 0x31545844u) d.dxgi_format = 71u; // "DXT1"
     else if (fourcc == 0x35545844u) d.dxgi_format = 77u;   // "DXT5"
     else if (fourcc == 0x32495441u || fourcc == 0x55354342u) d.dxgi_format = 83u; // "ATI2", "BC5U"
+    else if (source && fourcc == 0x33545844u) d.dxgi_format = 74u;                // "DXT3"
+    else if (source && (fourcc == 0x31495441u || fourcc == 0x55344342u)) d.dxgi_format = 80u; // "ATI1", "BC4U"
     else return UR_ASSET_EUNSUPPORTED;
     switch (d.dxgi_format) {
     case 28u: case 29u: d.block_dim = 1; d.bytes_per_block = 4; break;
     case 71u: case 72u: d.block_dim = 4; d.bytes_per_block = 8; break;
     case 77u: case 78u: case 83u: d.block_dim = 4; d.bytes_per_block = 16; break;
+    case 80u: if (!source) return UR_ASSET_EUNSUPPORTED; d.block_dim = 4; d.bytes_per_block = 8; break;
+    case 74u: case 75u: case 98u: case 99u: if (!source) return UR_ASSET_EUNSUPPORTED; d.block_dim = 4; d.bytes_per_block = 16; break;
     default: return UR_ASSET_EUNSUPPORTED;
     }
     if (d.width == 0 || d.height == 0 || d.width > 65535u || d.height > 65535u || d.mip_count > 255u) return UR_ASSET_EFORMAT;
@@ -364,6 +369,9 @@ int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out)
     *out = d;
     return UR_ASSET_OK;
 }
+
+int ur_dds_parse_texture2d(const void* file, size_t size, ur_dds_info* out) { return parse_texture2d(file, size, out, false); }
+int ur_dds_parse_texture2d_source(const void* file, size_t size, ur_dds_info* out) { return parse_texture2d(file, size, out, true); }
 
 size_t ur_dds_texel_count(const ur_dds_info* d)
 {

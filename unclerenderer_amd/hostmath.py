@@ -104,6 +104,26 @@ def bc_decode_level(format: int, blocks, level_width: int, level_height: int) ->
     return out
 
 
+def texture_chain_bytes(format: int, width: int, height: int, mips: int) -> int:
+    """ur_host_texture_chain_bytes: the bytes of a source chain of ur_texture_transcode, over its ten formats (71, 72, 74, 75, 77, 78, 80, 83,
+    98, 99); 0 for anything else, as bc_chain_bytes."""
+    return int(_lib.load().ur_host_texture_chain_bytes(int(format), int(width), int(height), int(mips)))
+
+
+def texture_decode_level(format: int, blocks, level_width: int, level_height: int) -> np.ndarray:
+    """ur_host_texture_decode_level: bc_decode_level over the ten source formats, by the functions the transcode kernel decodes with
+    (csrc/bc_wide_decode.h)."""
+    data = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8).reshape(-1)
+    need = texture_chain_bytes(format, max(level_width, 1), max(level_height, 1), 1)
+    if level_width < 1 or level_height < 1 or need == 0 or data.size < need:
+        raise ValueError(f"a {level_width} x {level_height} level of format {format} needs {need} bytes of blocks, got {data.size}")
+    out = np.zeros((level_height, level_width, 4), np.uint8)
+    rc = _lib.load().ur_host_texture_decode_level(int(format), data.ctypes.data_as(C.c_void_p), int(level_width), int(level_height), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"ur_host_texture_decode_level failed ({rc}): format {format}")
+    return out
+
+
 def lod_table() -> np.ndarray:
     """ur_host_lod_table: the 127 ascending fp32 thresholds 2^(j / 128), j = 1..127, of the textured GBuffer resolve's level of detail."""
     out = np.zeros(127, np.float32)

@@ -922,6 +922,33 @@ def _forward_pass(self, view, projection, commands, depth, targets, w, h, row0=0
         _lib.check(self._L.ur_forward_pass_parts(*head, int(parts), *tail), "ur_forward_pass_parts")
 
 
+def _transcode_texture(self, data_or_tensor, width: int, height: int, mips: int, format: int):
+    """ur_texture_transcode: a chain of BC1 / BC2 / BC3 / BC4 / BC5 / BC7 blocks (bytes or a uint8 array: a DDS file's payload as it lies,
+    uploaded here; or a uint8 device tensor that already holds it) is decoded on the device, once, into the RGBA8 chain the sampler is
+    fastest on. `format` is one of the ten source codes (lib.UR_TEXTURE_BC*, lib.UR_TEXTURE_SOURCE_*). Returns (the chain as an int32
+    device tensor, its lib.Texture2D - UR_TEXTURE_R8G8B8A8_UNORM_SRGB for the _SRGB sources), ready for pack_materials. One launch on the
+    context's stream; nothing is synchronised."""
+    from . import hostmath
+    need = hostmath.texture_chain_bytes(format, width, height, mips)
+    if need == 0:
+        raise ValueError(f"no source chain: format {format}, {width} x {height}, {mips} mips (71, 72, 74, 75, 77, 78, 80, 83, 98, 99; sizes 1..65535, mips 1..255)")
+    blocks = data_or_tensor
+    if not isinstance(blocks, torch.Tensor):
+        blocks = np.frombuffer(bytes(blocks), np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blocks, np.uint8).reshape(-1)
+    have = blocks.numel() if isinstance(blocks, torch.Tensor) else blocks.size
+    if have != need:  # (refused before any upload)
+        raise ValueError(f"a {width} x {height} chain of {mips} mips in format {format} is {need} bytes, the payload has {have}")
+    if not isinstance(blocks, torch.Tensor):
+        blocks = to_device(blocks.copy())
+    assert blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.is_cuda
+    out = torch.empty(self._L.ur_texture_transcode_bytes(int(width), int(height), int(mips)) // 4, dtype=torch.int32, device=blocks.device)
+    desc = _lib.Texture2D()
+    _lib.check(self._L.ur_texture_transcode(self._ctx, int(format), blocks.data_ptr(), int(width), int(height), int(mips), out.data_ptr(), C.byref(desc)),
+               "ur_texture_transcode")
+    return out, desc
+
+
+HotPath.transcode_texture = _transcode_texture
 HotPath.gbuffer_pass = _gbuffer_pass
 HotPath.forward_pass = _forward_pass
 HotPath.shadow_map = _shadow_map

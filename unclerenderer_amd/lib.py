@@ -83,6 +83,9 @@ class Material(C.Structure):
 UR_TEXTURE_R8G8B8A8_UNORM = 28
 UR_TEXTURE_R8G8B8A8_UNORM_SRGB = 29
 UR_TEXTURE_BC1_UNORM, UR_TEXTURE_BC1_UNORM_SRGB, UR_TEXTURE_BC3_UNORM, UR_TEXTURE_BC3_UNORM_SRGB, UR_TEXTURE_BC5_UNORM = 71, 72, 77, 78, 83
+# sources of ur_texture_transcode only, never Texture2D.format values
+UR_TEXTURE_SOURCE_BC2_UNORM, UR_TEXTURE_SOURCE_BC2_UNORM_SRGB, UR_TEXTURE_SOURCE_BC4_UNORM = 74, 75, 80
+UR_TEXTURE_SOURCE_BC7_UNORM, UR_TEXTURE_SOURCE_BC7_UNORM_SRGB = 98, 99
 UR_MATERIAL_NORMAL_MAP, UR_MATERIAL_METALLIC_ROUGHNESS_MAP, UR_MATERIAL_BASE_COLOR_MAP, UR_MATERIAL_EMISSIVE_MAP = 1, 2, 4, 8
 UR_MATERIAL_ALPHA_MASK = 0x10
 
@@ -343,9 +346,12 @@ SIGNATURES = {
                                   C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
     "ur_forward_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(ForwardTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
                                         _VP, _U32, C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
+    "ur_texture_transcode_bytes": (C.c_uint64, [_U32, _U32, _U32]),
+    "ur_texture_transcode": (C.c_int, [_VP, _U32, _VP, _U32, _U32, _U32, _VP, C.POINTER(Texture2D)]),
     # ur_assets.h
     "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
+    "ur_dds_parse_texture2d_source": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
     "ur_dds_decode_rgba16f": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo), _VP, C.POINTER(_U32)]),
     "ur_dds_copy_rg16": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo), _VP]),
@@ -401,6 +407,8 @@ SIGNATURES = {
     "ur_host_lod_table": (None, [_FP]),
     "ur_host_bc_chain_bytes": (C.c_uint64, [_U32, _U32, _U32, _U32]),
     "ur_host_bc_decode_level": (C.c_int, [_U32, _VP, _U32, _U32, _VP]),
+    "ur_host_texture_chain_bytes": (C.c_uint64, [_U32, _U32, _U32, _U32]),
+    "ur_host_texture_decode_level": (C.c_int, [_U32, _VP, _U32, _U32, _VP]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
