@@ -11,6 +11,8 @@
  * tests/gbuffer_mask_ref.py.
  * The Forward pass (ForwardRenderer.cpp "Forward", Shaders/ForwardVS.hlsl, Shaders/ForwardPS.hlsl): the same visibility keys resolved
  * straight to the HDR colour. Its rule is DESIGN.md section 3.12, restated in tests/forward_ref.py.
+ * The ObjectId pass of both renderers as a call of its own over any draws and any depth, and the pick of up to 64 texels without an
+ * image: DESIGN.md section 3.16, restated in tests/object_id_ref.py.
  */
 #ifndef UR_RASTER_H
 #define UR_RASTER_H
@@ -288,7 +290,7 @@ typedef struct ur_gbuffer_mask {
  * 8-byte aligned; a misaligned mask->stats6 or won; mask->draws over other commands or another command_count than draws; keys64
  * overlapping a target or depth.
  * UR_EUNSUPPORTED, nothing launched: targets->object_id together with a mask (the reference's ObjectId pass ignores the alpha test and
- * tests against the depth this pass writes: it needs a raster of its own). */
+ * tests against the depth this pass writes: it needs a raster of its own - ur_object_id_pass below, over the depth this call leaves). */
 int ur_gbuffer_pass_masked(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
                            float* depth, const ur_gbuffer_targets* targets, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
                            uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, const ur_material* materials, uint32_t material_count,
@@ -349,6 +351,60 @@ int ur_forward_pass_parts(ur_ctx* ctx, const float view[16], const float project
                           uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6, uint32_t parts,
                           const ur_material* materials, uint32_t material_count, const ur_gbuffer_mask* mask,
                           const ur_scene_constants* frame_constants, const ur_lighting_tables* tables);
+
+/* The ObjectId pass of either renderer (DeferredRenderer.cpp:867-980, ForwardRenderer.cpp:782-890, Shaders/ObjectId.hlsl, pipeline at
+ * RendererUtils.cpp:692-760) as a call of its own, over any draws and any depth: DESIGN.md 3.16, restated in tests/object_id_ref.py. The
+ * rule is ur_gbuffer_pass' (3.9) and nothing in it is new: every selected draw - opaque and alpha-masked models in ONE selection, as the
+ * reference loops over all its models - is rasterised exactly as ur_depth_prepass rasterises it; there is no alpha test; a fragment passes
+ * iff its value is >= depth[texel] (GREATER_EQUAL, depth is never written); a texel of `keys` ends as the maximum key over its passing
+ * fragments, 0 = nothing - under the slot-indexed selections (every slot, ranges) the draw D3D draws last -; object_id[texel] is ObjectId
+ * (dword 148) of the winning command's constants, 0 for key 0.
+ * With the depth ur_gbuffer_pass_masked or ur_forward_pass left behind (or ur_depth_prepass' for opaque models) this is the reference's
+ * ObjectId picture, its quirk included: a masked fragment that the base pass discarded in front of the visible surface still passes
+ * GREATER_EQUAL here, so a pick through a hole of a masked model that is drawn later than the surface seen through it returns the masked
+ * model, not that surface.
+ * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; at most four launches (clear of the keys,
+ * raster, the large-triangle queue when ur_raster_reserve gave one, resolve).
+ * Read: what ur_depth_prepass reads, with all 64 bytes of a named vertex's stride checked as ur_gbuffer_pass checks them and dword 148
+ * behind the ConstantBufferAddress of a winning command; rows [row0, row0 + rows) of depth. None of these is written.
+ * Written: all rows * w words of keys and of object_id, every one of them, and nothing around them; keys ends as ur_gbuffer_pass leaves it.
+ * stats6 is added to, with ur_gbuffer_pass' meanings.
+ * UR_EINVAL, nothing launched: ur_gbuffer_pass' cases (the targets being object_id and keys: either null or not 4-byte aligned);
+ * object_id or keys overlapping depth, the commands or each other.
+ * UR_EUNSUPPORTED, nothing launched: key_triangle_bits == 0 with command_count >= 2^24. */
+int ur_object_id_pass(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                      const float* depth, uint32_t* object_id, uint32_t* keys,
+                      uint32_t w, uint32_t h, uint32_t row0, uint32_t rows,
+                      uint32_t flags, uint32_t key_triangle_bits, uint32_t* stats6);
+
+#define UR_PICK_MAX_POINTS 64u /* the most points of one ur_object_id_pick */
+
+/* What ur_object_id_pick answers for one point. */
+typedef struct ur_pick_result {
+    uint32_t object_id;  /* ur_object_id_pass' object_id at the texel */
+    uint32_t key;        /* ... and its key; 0 = nothing */
+    uint32_t slot;       /* the command slot the key names; 0xFFFFFFFF for key 0 */
+    uint32_t depth_bits; /* the bits of the winning fragment's depth (the value the depth test compared, after D24); 0 for key 0 */
+} ur_pick_result; /* 16 bytes */
+
+/* The pick: ur_object_id_pass' answer at up to UR_PICK_MAX_POINTS texels of the whole w x h frame, from the triangles alone - no key
+ * image, no clear of one and no fragments other than the points' (DESIGN.md 3.16). Point i is (min(x, w - 1), min(y, h - 1)) of
+ * points_xy[2 i], points_xy[2 i + 1] (the reference's clamp, DeferredRenderer.cpp:945-946); results[i] is exactly what ur_object_id_pass
+ * over the same draws, matrices, depth, flags and key_triangle_bits gives at that texel, with the slot and the depth of the fragment that
+ * won (the greatest among the winning key's fragments there). Equal points get equal records.
+ * points_xy: host, read before the call returns. results: device, 16-byte aligned, point_count records.
+ * Asynchronous on the context's stream; the host neither reads device memory nor synchronises; three stream operations (a clear of the
+ * records, the pick, a one-wave finish), none when point_count == 0 (UR_OK; points_xy and results may then be NULL). The cost does not
+ * depend on w * h.
+ * Read: what ur_object_id_pass reads of the draws; of depth the floats at the clamped points only. Written: the point_count records,
+ * nothing else; stats6 is added to as ur_object_id_pass adds to it, except [3], which is never touched (there is no queue).
+ * UR_EINVAL, nothing launched: ur_gbuffer_pass' cases for the context, matrices, draws, depth, w, h, flags and key_triangle_bits;
+ * point_count > UR_PICK_MAX_POINTS; with point_count != 0 a null points_xy, a null results or one not 16-byte aligned, results
+ * overlapping depth or the commands.
+ * UR_EUNSUPPORTED, nothing launched: key_triangle_bits == 0 with command_count >= 2^24. */
+int ur_object_id_pick(ur_ctx* ctx, const float view[16], const float projection[16], const ur_raster_draws* draws,
+                      const float* depth, uint32_t w, uint32_t h, uint32_t flags, uint32_t key_triangle_bits,
+                      const uint32_t* points_xy, uint32_t point_count, ur_pick_result* results, uint32_t* stats6);
 
 #ifdef __cplusplus
 }

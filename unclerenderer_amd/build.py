@@ -49,6 +49,7 @@ SOURCES = [
     ("raster.hip", EXACT),
     ("gbuffer_resolve.hip", EXACT),
     ("gbuffer_api.hip", EXACT),  # host code only: the entry points of the GBuffer and the Forward pass
+    ("object_id_api.hip", EXACT),  # host code only: the entry points of the ObjectId pass and the pick
     ("forward_resolve.hip", EXACT),
     ("texture_transcode.hip", []),  # integer arithmetic alone: no flag changes its results
     ("stream_ceiling.hip", []),

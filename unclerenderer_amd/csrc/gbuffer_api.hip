@@ -95,19 +95,9 @@ int gbuffer_entry(const char* who, const char* who_parts, ur_ctx* ctx, const flo
     if (rc != UR_OK) return rc;
     if (rows == 0u || (uint64_t)row0 + rows > h) { ur::set_error("%s: rows [%u, %u + %u) of a target %u high", who, row0, row0, rows, h); return UR_EINVAL; }
     if (parts == 0u || (parts & ~(UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE))) { ur::set_error("%s: parts 0x%x (UR_GBUFFER_PART_RASTER | UR_GBUFFER_PART_RESOLVE)", who_parts, parts); return UR_EINVAL; }
-    uint32_t key_bits = key_triangle_bits;
-    if (key_bits == 0u) {
-        if (draws->command_count >= (1u << 24)) {
-            ur::set_error("%s: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", who, draws->command_count);
-            return UR_EUNSUPPORTED;
-        }
-        uint32_t length = 0u;
-        while ((draws->command_count >> length) != 0u) ++length;
-        key_bits = min(32u - length, 31u);
-    } else if ((uint64_t)draws->command_count >= (1ull << (32u - key_bits))) {
-        ur::set_error("%s: %u command slots do not fit the %u key bits beside key_triangle_bits %u", who, draws->command_count, 32u - key_bits, key_bits);
-        return UR_EINVAL;
-    }
+    uint32_t key_bits = 0u;
+    rc = ur::split_key_bits(who, draws->command_count, key_triangle_bits, key_bits);
+    if (rc != UR_OK) return rc;
     if (!aligned(materials, 16)) { ur::set_error("%s: a misaligned material table (16 bytes)", who); return UR_EINVAL; }
     if (forward) {
         rc = check_forward_call(who, *forward, targets, *draws, depth, materials, material_count, w, h, rows, cube);

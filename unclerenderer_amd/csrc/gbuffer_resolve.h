@@ -37,4 +37,17 @@ struct ResolveParams : KeyParams {
 // a masked key's slot through keys64 (never beside object_id: check_gbuffer_mask refuses the pair)
 int launch_gbuffer_resolve(ur_ctx* ctx, const ResolveParams& p, bool object_id, bool maps, bool masked);
 
+// The ObjectId pass' resolve: what of a KeyParams takes a key to its command, and the one target
+struct ObjectIdParams {
+    const uint8_t* commands;
+    uint32_t mode; // as KeyParams'
+    const uint32_t* visible_idx;
+    uint32_t index_base;
+    const uint32_t* keys;
+    uint32_t n, key_bits;
+    uint32_t* object_id;
+};
+
+int launch_object_id_resolve(ur_ctx* ctx, const ObjectIdParams& p);
+
 } // namespace ur

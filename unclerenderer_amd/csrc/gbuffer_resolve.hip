@@ -153,6 +153,23 @@ __global__ __launch_bounds__(kThreads) void gbuffer_resolve_kernel(ResolveParams
     if constexpr (OBJECT_ID) ur::store_once_b32(p.object_id + i, reinterpret_cast<const uint32_t*>(cb)[148]);
 }
 
+// The ObjectId pass' resolve, a lane per texel of the band: key -> ordinal -> slot -> command -> dword 148 of its
+// constants, 0 for key 0. No vertex is loaded and no LDS used
+__global__ __launch_bounds__(kThreads) void object_id_resolve_kernel(ur::ObjectIdParams p)
+{
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const uint32_t key = p.keys[i];
+    uint32_t id = 0u;
+    if (key != 0u) {
+        uint32_t t;
+        const uint32_t slot = key_slot<false>(p, key, i, t);
+        const u32x4_t c2 = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE)[2];
+        id = reinterpret_cast<const uint32_t*>((uint64_t)c2.x | ((uint64_t)c2.y << 32))[148];
+    }
+    ur::store_once_b32(p.object_id + i, id);
+}
+
 template <bool OBJECT_ID, bool MAPS, bool MASKED>
 void launch(ur_ctx* ctx, const ResolveParams& p)
 {
@@ -169,6 +186,13 @@ int ur::launch_gbuffer_resolve(ur_ctx* ctx, const ResolveParams& p, bool object_
     else if (object_id) launch<true, false, false>(ctx, p);
     else if (maps) launch<false, true, false>(ctx, p);
     else launch<false, false, false>(ctx, p);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+int ur::launch_object_id_resolve(ur_ctx* ctx, const ObjectIdParams& p)
+{
+    hipLaunchKernelGGL(object_id_resolve_kernel, dim3((p.n + kThreads - 1u) / kThreads), dim3(kThreads), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }

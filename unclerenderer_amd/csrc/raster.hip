@@ -30,6 +30,10 @@
 // passes the depth test competes for a 64-bit word per texel, (depth bits << 32) | key, and runs the base pass' alpha test (alpha_discards
 // below, with the resolves' front end: visibility_key.h, gbuffer_interp.h, texture_sample.h) only when its word is above the texel's; a
 // merge launch then folds the words into the opaque draws' key image and raises the depth where a masked fragment won.
+//
+// The ObjectId pick (restated in tests/object_id_ref.py) is the keyed raster at up to 64 given texels: pick_kernel
+// runs raster_kernel's front half and tests the points against each surviving triangle instead of serving its fragments; a word per point
+// takes (key << 32) | depth bits, and a one-wave finish turns the words into records.
 
 #include "raster_rule.h"
 #include "ur_internal.h"
@@ -80,6 +84,14 @@ struct MaskArgs {
 };
 struct MaskedParams : RasterParams {
     MaskArgs mask;
+};
+
+// What the pick kernels take behind a RasterParams: `map`, the band and the queue are not used. The points ride in the
+// kernel arguments, 256 bytes for the most there can be
+struct PickParams : RasterParams {
+    uint32_t point_count;
+    uint32_t points[UR_PICK_MAX_POINTS]; // x | y << 16, clamped to the target
+    unsigned long long* results;         // 16-byte records: the first 8 bytes of record i take (key << 32) | depth bits
 };
 
 // What a fragment's alpha test reads: nothing in the passes without one
@@ -561,6 +573,190 @@ __global__ __launch_bounds__(kThreads) void raster_kernel(typename P::Params p)
     }
 }
 
+// ---- the pick: the key raster's answer at up to 64 texels, from the triangles alone ---------------------------------
+
+// Rules 4-5 and the depth test of `shade` for one triangle at one point, whose depth rides in `point_depth`: a passing fragment raises
+// the point's word to (key << 32) | depth bits, so the greatest key wins and carries its own depth
+template <class P>
+__device__ __forceinline__ void pick_fragment(const Tri& t, int b01, int b12, int b20, int px, int py, float point_depth, uint32_t key,
+                                              unsigned long long* __restrict__ word_at)
+{
+    const int sx = 256 * px + 128, sy = 256 * py + 128;
+    const long long e01 = (long long)(t.x1 - t.x0) * (sy - t.y0) - (long long)(t.y1 - t.y0) * (sx - t.x0);
+    const long long e12 = (long long)(t.x2 - t.x1) * (sy - t.y1) - (long long)(t.y2 - t.y1) * (sx - t.x1);
+    const long long e20 = (long long)(t.x0 - t.x2) * (sy - t.y2) - (long long)(t.y0 - t.y2) * (sx - t.x2);
+    if (((e01 - b01) | (e12 - b12) | (e20 - b20)) < 0) return;
+    float z = t.z0 + ((float)e20 * t.k1 + (float)e01 * t.k2);
+    if (!(z >= 0.0f)) return;
+    if (z > 1.0f) z = 1.0f;
+    if constexpr (P::kD24) z = (float)(__builtin_rint((double)z * 16777215.0) / 16777215.0);
+    if (!(z >= point_depth)) return;
+    const unsigned long long word = ((unsigned long long)key << 32) | (__float_as_uint(z) & 0x7FFFFFFFu); // z += 0.0f
+    if (word <= __hip_atomic_load(word_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return; // (words only increase)
+    (void)__hip_atomic_fetch_max(word_at, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// raster_kernel's work distribution and per-triangle front half (selection, command, rules 1-3, the near clip, the guard band, the
+// snap), written out again and not shared as a function, so that raster_kernel's registers stay what they were; behind it a surviving
+// lane tests the points against its triangle's box instead of serving fragments. Lane j of every wave holds point j's depth
+template <class P>
+__global__ __launch_bounds__(kThreads) void pick_kernel(PickParams p)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    const uint32_t wave_count = gridDim.x * kWaves;
+    uint32_t n_drawn = 0, n_unsupported = 0, n_dropped = 0, n_cut = 0, n_behind = 0; // uniform; added to stats once per wave
+    float point_depth = 0.0f;
+    if (lane < p.point_count) {
+        const uint32_t xy = p.points[lane];
+        point_depth = p.depth[(size_t)(xy >> 16) * p.w + (xy & 0xFFFFu)];
+    }
+
+    for (uint32_t item = wave; item < p.items; item += wave_count) {
+        const uint32_t cand = item / p.segments, seg = item - cand * p.segments;
+        // ---- selection: the candidate's slot, or none
+        uint32_t slot = cand;
+        if (p.mode == 1u) {
+            if (cand >= *p.visible_count) continue;
+            slot = p.visible_idx[cand] - p.index_base;
+        } else if (p.mode == 2u) {
+            uint32_t lo = 0u, hi = p.range_count + 1u; // first k with offsets[k] > cand
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (p.offsets[mid] > cand) hi = mid; else lo = mid + 1u;
+            }
+            if (lo == 0u || lo > p.range_count) continue;
+            const uint32_t r = lo - 1u;
+            if (cand - p.offsets[r] >= p.counts[r]) continue;
+        }
+        slot = __builtin_amdgcn_readfirstlane(slot);
+        if (slot >= p.command_count) continue;
+        // ---- the command (uniform)
+        const u32x4_t* cmd = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE);
+        const u32x4_t c0 = cmd[0], c1 = cmd[1], c2 = cmd[2], c3 = cmd[3];
+        if (c2.w == 0u) continue; // InstanceCount
+        const uint64_t vb = (uint64_t)c0.x | ((uint64_t)c0.y << 32), ib = (uint64_t)c1.x | ((uint64_t)c1.y << 32), cb = (uint64_t)c2.x | ((uint64_t)c2.y << 32);
+        const uint32_t vb_size = c0.z, stride = c0.w, ib_size = c1.z, format = c1.w;
+        const uint32_t tri_count = c2.z / 3u, start_index = c3.x;
+        const long long base_vertex = (int)c3.y;
+        if (tri_count > (1u << p.key_bits) || format != UR_RASTER_INDEX_FORMAT_R32_UINT || stride < P::kVertexBytes || (stride & 3u) != 0u || vb == 0u || (vb & 3u) != 0u ||
+            ib == 0u || (ib & 3u) != 0u || cb == 0u || (cb & 3u) != 0u) {
+            if (seg == 0u) n_unsupported += tri_count;
+            continue;
+        }
+        const uint32_t chunks = (tri_count + 63u) / 64u;
+        if (seg >= chunks) continue;
+        float W[16];
+        {
+            const float* wp = reinterpret_cast<const float*>(cb);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) W[k] = wp[k];
+        }
+        const uint32_t* indices = reinterpret_cast<const uint32_t*>(ib);
+        const uint8_t* vertices = reinterpret_cast<const uint8_t*>(vb);
+        const uint64_t index_slots = ib_size / 4u;
+
+        for (uint32_t chunk = seg; chunk < chunks; chunk += p.segments) {
+            const uint32_t t = chunk * 64u + lane;
+            const uint32_t key = ((cand + 1u) << p.key_bits) | t;
+            // ---- a lane per triangle: rules 1-2 and the near clip, up to four target-space vertices
+            float SX[4] = {}, SY[4] = {}, SZ[4] = {};
+            uint32_t emit = 0u;
+            bool unsupported = false, cut = false, behind = false;
+            if (t < tri_count) {
+                const uint64_t first = (uint64_t)start_index + 3ull * t;
+                float clip[3][4] = {};
+                if (first + 2u >= index_slots) unsupported = true;
+                if (!unsupported) {
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const long long vi = base_vertex + (long long)indices[first + (uint32_t)v];
+                        if (vi < 0 || (uint64_t)vi * stride + P::kVertexBytes > (uint64_t)vb_size) { unsupported = true; continue; }
+                        P::project(reinterpret_cast<const float*>(vertices + (uint64_t)vi * stride), W, p, clip[v]);
+                    }
+                }
+                if (!unsupported) emit = P::assemble(clip, p, SX, SY, SZ, unsupported, cut, behind);
+            }
+            n_unsupported += (uint32_t)__popcll(__ballot(unsupported));
+            n_cut += (uint32_t)__popcll(__ballot(cut));
+            n_behind += (uint32_t)__popcll(__ballot(behind));
+            const uint32_t passes = __ballot(emit > 1u) != 0ull ? 2u : 1u;
+
+            for (uint32_t e = 0u; e < passes; ++e) {
+                // ---- emitted triangle e of the lane: the guard band, rule 3 and the box of the centres it can cover
+                Tri tri = {};
+                int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
+                bool drawn = false, dropped = false;
+                if (e < emit) {
+                    float X[3], Y[3], Z[3];
+                    const bool second = e != 0u;
+                    X[0] = SX[0]; Y[0] = SY[0]; Z[0] = SZ[0]; // (u0, u2, u1)
+                    X[2] = second ? SX[2] : SX[1]; Y[2] = second ? SY[2] : SY[1]; Z[2] = second ? SZ[2] : SZ[1];
+                    X[1] = second ? SX[3] : SX[2]; Y[1] = second ? SY[3] : SY[2]; Z[1] = second ? SZ[3] : SZ[2];
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) {
+                        const bool finite = fabsf(X[v]) <= kFloatMax && fabsf(Y[v]) <= kFloatMax && fabsf(Z[v]) <= kFloatMax; // (false for NaN)
+                        if (!finite || fabsf(X[v]) > P::kGuardBand || fabsf(Y[v]) > P::kGuardBand) dropped = true;
+                    }
+                    if (!dropped) {
+                        tri.x0 = (int)rintf(X[0] * 256.0f); tri.y0 = (int)rintf(Y[0] * 256.0f);
+                        tri.x1 = (int)rintf(X[1] * 256.0f); tri.y1 = (int)rintf(Y[1] * 256.0f);
+                        tri.x2 = (int)rintf(X[2] * 256.0f); tri.y2 = (int)rintf(Y[2] * 256.0f);
+                        const long long A = (long long)(tri.x1 - tri.x0) * (tri.y2 - tri.y0) - (long long)(tri.x2 - tri.x0) * (tri.y1 - tri.y0); // rule 3
+                        if (A > 0) {
+                            drawn = true;
+                            const float inv = 1.0f / (float)A; // rule 5
+                            tri.z0 = Z[0];
+                            tri.k1 = (Z[1] - Z[0]) * inv;
+                            tri.k2 = (Z[2] - Z[0]) * inv;
+                            const int minx = min(tri.x0, min(tri.x1, tri.x2)), maxx = max(tri.x0, max(tri.x1, tri.x2));
+                            const int miny = min(tri.y0, min(tri.y1, tri.y2)), maxy = max(tri.y0, max(tri.y1, tri.y2));
+                            bx0 = (minx + 127) >> 8; bx1 = (maxx - 128) >> 8; // (a point lies inside the target: no clamp)
+                            by0 = (miny + 127) >> 8; by1 = (maxy - 128) >> 8;
+                        }
+                    }
+                }
+                n_drawn += (uint32_t)__popcll(__ballot(drawn));
+                n_dropped += (uint32_t)__popcll(__ballot(dropped));
+                if (__ballot(drawn && bx0 <= bx1 && by0 <= by1) == 0ull) continue;
+                // ---- the points against the lane's triangle: a uniform loop, the point and its depth in scalar registers
+                const int b01 = edge_bias(tri.x0, tri.y0, tri.x1, tri.y1), b12 = edge_bias(tri.x1, tri.y1, tri.x2, tri.y2), b20 = edge_bias(tri.x2, tri.y2, tri.x0, tri.y0);
+                for (uint32_t j = 0u; j < p.point_count; ++j) {
+                    const uint32_t xy = p.points[j];
+                    const int px = (int)(xy & 0xFFFFu), py = (int)(xy >> 16);
+                    const float d = rlf(point_depth, j);
+                    if (drawn && px >= bx0 && px <= bx1 && py >= by0 && py <= by1) pick_fragment<P>(tri, b01, b12, b20, px, py, d, key, p.results + 2u * j);
+                }
+            }
+        }
+    }
+    if (p.stats != nullptr && lane == 0u) {
+        if (n_drawn) (void)__hip_atomic_fetch_add(p.stats + 0, n_drawn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_unsupported) (void)__hip_atomic_fetch_add(p.stats + 1, n_unsupported, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_dropped) (void)__hip_atomic_fetch_add(p.stats + 2, n_dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_cut) (void)__hip_atomic_fetch_add(p.stats + 4, n_cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n_behind) (void)__hip_atomic_fetch_add(p.stats + 5, n_behind, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One wave behind pick_kernel: lane i turns record i's word into {ObjectId, key, slot, depth bits}; a word of 0 is {0, 0, ~0, 0}
+__global__ __launch_bounds__(64) void pick_finish_kernel(PickParams p)
+{
+    const uint32_t i = threadIdx.x;
+    if (i >= p.point_count) return;
+    const unsigned long long word = p.results[2u * i];
+    const uint32_t key = (uint32_t)(word >> 32), zbits = (uint32_t)word;
+    u32x4_t record = {0u, 0u, 0xFFFFFFFFu, 0u};
+    if (key != 0u) {
+        uint32_t t;
+        const uint32_t slot = key_slot<false>(p, key, 0u, t);
+        const u32x4_t c2 = reinterpret_cast<const u32x4_t*>(p.commands + (size_t)slot * UR_INDIRECT_COMMAND_STRIDE)[2];
+        const uint32_t* cb = reinterpret_cast<const uint32_t*>((uint64_t)c2.x | ((uint64_t)c2.y << 32));
+        record = u32x4_t{cb[148], key, slot, zbits};
+    }
+    reinterpret_cast<u32x4_t*>(p.results)[i] = record;
+}
+
 // The largest value of the edge function a->b over the centres of the pixels [px0, px1] x [py0, py1]: below zero, no centre passes
 __device__ __forceinline__ long long edge_max(int ax, int ay, int bx, int by, int px0, int py0, int px1, int py1)
 {
@@ -638,14 +834,37 @@ struct VisArgs {
     uint32_t row0, rows, key_bits;
 };
 
+// What the raster and the pick launch alike: the selection, the matrices, the target's size, the counters, GBuffer's depth, band and key
+// bits, and the split of the work into (candidate, segment) items - enough waves to fill the device whatever the command count, since
+// index counts live on the device. Returns the blocks of the launch. command_count is not 0.
+uint32_t fill_raster_params(RasterParams& p, const ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, uint32_t w, uint32_t h, uint32_t* stats,
+                            const VisArgs* vis)
+{
+    const ur_draw_ranges* rg = draws->ranges;
+    p.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
+    p.command_count = draws->command_count;
+    p.mode = draws->visible_idx != nullptr ? 1u : (rg ? 2u : 0u);
+    p.visible_idx = draws->visible_idx; p.visible_count = draws->visible_count; p.index_base = draws->index_base;
+    if (rg) { p.range_count = rg->range_count; p.offsets = rg->offsets; p.counts = rg->counts; }
+    for (int k = 0; k < 16; ++k) { p.L[k] = m0[k]; p.Pr[k] = m1 ? m1[k] : 0.0f; }
+    p.w = w; p.h = h;
+    p.half_w = 0.5f * (float)w; p.half_h = 0.5f * (float)h;
+    p.stats = stats;
+    if (vis) { p.depth = vis->depth; p.row0 = vis->row0; p.rows = vis->rows; p.key_bits = vis->key_bits; }
+    const uint32_t want_waves = (uint32_t)ctx->cu_count * 16u;
+    p.segments = max(1u, min(1024u, want_waves / p.command_count));
+    const uint64_t items = (uint64_t)p.command_count * p.segments;
+    p.items = (uint32_t)items;
+    if (items > 0xFFFFFFFFull) { p.segments = 1u; p.items = p.command_count; }
+    return min((p.items + kWaves - 1u) / kWaves, (uint32_t)ctx->cu_count * 32u);
+}
+
 // clear, raster, large: the launches every pass shares. `map` holds n = w * (rows of the map) dwords: the whole target of a depth pass
 // (vis null), GBuffer's key image of its band. m1 is null for ShadowMap.
 template <class P>
 int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster_draws* draws, uint32_t* map, uint32_t n, uint32_t w, uint32_t h, float clear,
                   uint32_t* stats, const VisArgs* vis, const MaskArgs* mask = nullptr)
 {
-    const ur_draw_ranges* rg = draws->ranges;
-    const bool list = draws->visible_idx != nullptr;
     const uint32_t head = min((uint32_t)((16u - (reinterpret_cast<uintptr_t>(map) & 15u)) & 15u) / 4u, n);
     uint32_t* queue = ctx->raster_queue_cap != 0u ? ctx->raster_queue : nullptr;
     const uint32_t clear_blocks = min((n / 4u + kThreads - 1u) / kThreads + 1u, (uint32_t)ctx->cu_count * 16u);
@@ -655,25 +874,9 @@ int launch_raster(ur_ctx* ctx, const float* m0, const float* m1, const ur_raster
 
     typename P::Params p{};
     if constexpr (P::kMasked) p.mask = *mask;
-    p.commands = static_cast<const uint8_t*>(ur::raster_commands(*draws));
-    p.command_count = draws->command_count;
-    p.mode = list ? 1u : (rg ? 2u : 0u);
-    p.visible_idx = draws->visible_idx; p.visible_count = draws->visible_count; p.index_base = draws->index_base;
-    if (rg) { p.range_count = rg->range_count; p.offsets = rg->offsets; p.counts = rg->counts; }
-    for (int k = 0; k < 16; ++k) { p.L[k] = m0[k]; p.Pr[k] = m1 ? m1[k] : 0.0f; }
     p.map = map;
-    p.w = w; p.h = h;
-    p.half_w = 0.5f * (float)w; p.half_h = 0.5f * (float)h;
-    p.stats = stats;
     p.queue = queue; p.queue_cap = queue ? ctx->raster_queue_cap : 0u;
-    if (vis) { p.depth = vis->depth; p.row0 = vis->row0; p.rows = vis->rows; p.key_bits = vis->key_bits; }
-    // enough (candidate, segment) waves to fill the device whatever the command count: index counts live on the device
-    const uint32_t want_waves = (uint32_t)ctx->cu_count * 16u;
-    p.segments = max(1u, min(1024u, want_waves / p.command_count));
-    const uint64_t items = (uint64_t)p.command_count * p.segments;
-    p.items = (uint32_t)items;
-    if (items > 0xFFFFFFFFull) { p.segments = 1u; p.items = p.command_count; }
-    const uint32_t blocks = min((p.items + kWaves - 1u) / kWaves, (uint32_t)ctx->cu_count * 32u);
+    const uint32_t blocks = fill_raster_params(p, ctx, m0, m1, draws, w, h, stats, vis);
     hipLaunchKernelGGL(raster_kernel<P>, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
     UR_HIP_TRY(hipGetLastError());
     if (queue) {
@@ -734,6 +937,27 @@ int ur::launch_masked_raster(ur_ctx* ctx, const float* view, const float* projec
     if (rc != UR_OK) return rc;
     hipLaunchKernelGGL(mask_merge_kernel, dim3((n + kThreads - 1u) / kThreads), dim3(kThreads), 0, ctx->stream, reinterpret_cast<unsigned long long*>(keys64), keys,
                        reinterpret_cast<uint32_t*>(depth) + (size_t)row0 * w, n, won);
+    UR_HIP_TRY(hipGetLastError());
+    return UR_OK;
+}
+
+int ur::launch_object_id_pick(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, uint32_t w, uint32_t h,
+                              uint32_t key_bits, bool d24, const uint32_t* points, uint32_t point_count, ur_pick_result* results, uint32_t* stats)
+{
+    static_assert(sizeof(ur_pick_result) == 16, "a pick record is 16 bytes");
+    UR_HIP_TRY(hipMemsetAsync(results, 0, (size_t)point_count * sizeof(ur_pick_result), ctx->stream));
+    PickParams p{};
+    p.point_count = point_count;
+    for (uint32_t i = 0; i < point_count; ++i) p.points[i] = points[i];
+    p.results = reinterpret_cast<unsigned long long*>(results);
+    if (draws->command_count != 0u) {
+        const VisArgs vis{depth, 0u, h, key_bits};
+        const uint32_t blocks = fill_raster_params(p, ctx, view, projection, draws, w, h, stats, &vis);
+        if (d24) hipLaunchKernelGGL(pick_kernel<VisPolicy<true>>, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
+        else hipLaunchKernelGGL(pick_kernel<VisPolicy<false>>, dim3(blocks), dim3(kThreads), 0, ctx->stream, p);
+        UR_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pick_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, p); // (every word is 0 without commands)
     UR_HIP_TRY(hipGetLastError());
     return UR_OK;
 }

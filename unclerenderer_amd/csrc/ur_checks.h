@@ -56,5 +56,24 @@ inline int check_key_triangle_bits(const char* who, uint32_t bits)
     if (bits > 31u) { set_error("%s: key_triangle_bits %u (0 = automatic, 1..31)", who, bits); return UR_EINVAL; }
     return UR_OK;
 }
+// T, the key's triangle bits, of a call over command_count slots: key_triangle_bits (checked above), or 32 - bit_length(command_count) when
+// that is 0. UR_EUNSUPPORTED when the automatic split leaves fewer than 8 bits, UR_EINVAL when the slots do not fit beside the bits asked for
+inline int split_key_bits(const char* who, uint32_t command_count, uint32_t key_triangle_bits, uint32_t& key_bits)
+{
+    key_bits = key_triangle_bits;
+    if (key_bits == 0u) {
+        if (command_count >= (1u << 24)) {
+            set_error("%s: %u command slots leave fewer than 8 key bits for the triangle: pass key_triangle_bits", who, command_count);
+            return UR_EUNSUPPORTED;
+        }
+        uint32_t length = 0u;
+        while ((command_count >> length) != 0u) ++length;
+        key_bits = 32u - length < 31u ? 32u - length : 31u;
+    } else if ((uint64_t)command_count >= (1ull << (32u - key_bits))) {
+        set_error("%s: %u command slots do not fit the %u key bits beside key_triangle_bits %u", who, command_count, 32u - key_bits, key_bits);
+        return UR_EINVAL;
+    }
+    return UR_OK;
+}
 
 } // namespace ur

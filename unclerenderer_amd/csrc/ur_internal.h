@@ -148,6 +148,10 @@ int launch_visibility_raster(ur_ctx* ctx, const float* view, const float* projec
 int launch_masked_raster(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, float* depth, uint64_t* keys64, uint32_t* keys,
                          uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, uint32_t key_bits, bool d24, uint32_t* stats, const ur_material* materials,
                          uint32_t material_count, uint32_t* won);
+// The pick: zeroes point_count records, raises their first 8 bytes to the winning (key, depth bits) of the selected
+// draws at the points (host, x | y << 16, inside the w x h target) and finishes them into ur_pick_result records
+int launch_object_id_pick(ur_ctx* ctx, const float* view, const float* projection, const ur_raster_draws* draws, const float* depth, uint32_t w, uint32_t h,
+                          uint32_t key_bits, bool d24, const uint32_t* points, uint32_t point_count, ur_pick_result* results, uint32_t* stats);
 int launch_lighting(ur_ctx* ctx, const ur_scene_constants* scene, const ur_sky_constants* sky, const ur_half4* gbuf_a,
                     const ur_half4* gbuf_b, const uint32_t* gbuf_c, const float* depth, const ur_lighting_tables* tables,
                     ur_half4* hdr, uint32_t w, uint32_t h, uint32_t row0, uint32_t rows, int mode);

@@ -922,6 +922,40 @@ def _forward_pass(self, view, projection, commands, depth, targets, w, h, row0=0
         _lib.check(self._L.ur_forward_pass_parts(*head, int(parts), *tail), "ur_forward_pass_parts")
 
 
+def _object_id_pass(self, draws, view, projection, depth, w, h, *, object_id=None, keys=None, row0=0, rows=None, flags=0, key_triangle_bits=0, stats=None):
+    """ur_object_id_pass: the ObjectId pass of either renderer over the rows [row0, row0 + rows). draws: a raster_draws(...) selection - the
+    opaque and the alpha-masked models together - or the commands tensor (every slot); depth: the w x h depth gbuffer_pass(mask_draws=) or
+    forward_pass left (depth_prepass' for opaque models), read only. object_id, keys: (rows, w) int32 device tensors, made here when None.
+    There is no alpha test: a masked model drawn later than the surface seen through its holes wins there. Returns (object_id, keys)."""
+    rows = h - row0 if rows is None else rows
+    assert depth.dtype == torch.float32 and depth.numel() >= w * h
+    d = draws if isinstance(draws, _lib.RasterDraws) else raster_draws(draws)
+    object_id = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if object_id is None else object_id
+    keys = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if keys is None else keys
+    for t in (object_id, keys):
+        assert t.dtype == torch.int32 and t.numel() >= w * rows
+    v, p = _matrix16(view), _matrix16(projection)
+    _lib.check(self._L.ur_object_id_pass(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), _ptr(object_id), _ptr(keys), w, h, int(row0), int(rows),
+                                         int(flags), int(key_triangle_bits), _ptr(stats)), "ur_object_id_pass")
+    return object_id, keys
+
+
+def _object_id_pick(self, draws, view, projection, depth, w, h, points, *, results=None, flags=0, key_triangle_bits=0, stats=None):
+    """ur_object_id_pick: what object_id_pass gives at up to lib.UR_PICK_MAX_POINTS texels, from the triangles alone. points: (n, 2) host
+    integers (x, y), clamped to the frame by the call. Returns the records as an (n, 4) int32 device tensor - object_id, key, slot (-1 =
+    nothing), depth bits per row, lib.PickResult's fields - (`results` when given: 16-byte aligned); nothing is synchronised."""
+    pts = np.ascontiguousarray(np.asarray(points, np.int64).reshape(-1, 2).astype(np.uint32))
+    n = int(pts.shape[0])
+    assert depth.dtype == torch.float32 and depth.numel() >= w * h
+    d = draws if isinstance(draws, _lib.RasterDraws) else raster_draws(draws)
+    results = torch.empty((n, 4), dtype=torch.int32, device=depth.device) if results is None else results
+    assert results.dtype == torch.int32 and results.numel() >= 4 * n
+    v, p = _matrix16(view), _matrix16(projection)
+    _lib.check(self._L.ur_object_id_pick(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), w, h, int(flags), int(key_triangle_bits),
+                                         pts.ctypes.data_as(C.POINTER(C.c_uint32)), n, _ptr(results), _ptr(stats)), "ur_object_id_pick")
+    return results
+
+
 def _transcode_texture(self, data_or_tensor, width: int, height: int, mips: int, format: int):
     """ur_texture_transcode: a chain of BC1 / BC2 / BC3 / BC4 / BC5 / BC7 blocks (bytes or a uint8 array: a DDS file's payload as it lies,
     uploaded here; or a uint8 device tensor that already holds it) is decoded on the device, once, into the RGBA8 chain the sampler is
@@ -951,6 +985,8 @@ def _transcode_texture(self, data_or_tensor, width: int, height: int, mips: int,
 HotPath.transcode_texture = _transcode_texture
 HotPath.gbuffer_pass = _gbuffer_pass
 HotPath.forward_pass = _forward_pass
+HotPath.object_id_pass = _object_id_pass
+HotPath.object_id_pick = _object_id_pick
 HotPath.shadow_map = _shadow_map
 HotPath.raster_reserve = _raster_reserve
 HotPath.depth_prepass = _depth_prepass

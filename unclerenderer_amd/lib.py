@@ -100,6 +100,14 @@ class ForwardTargets(C.Structure):
     _fields_ = [("hdr", C.c_void_p), ("keys", C.c_void_p)]
 
 
+class PickResult(C.Structure):
+    """ur_pick_result (include/ur_raster.h): what ur_object_id_pick answers for one point, 16 bytes."""
+    _fields_ = [("object_id", C.c_uint32), ("key", C.c_uint32), ("slot", C.c_uint32), ("depth_bits", C.c_uint32)]
+
+
+UR_PICK_MAX_POINTS = 64
+
+
 class FrameGBufferPass(C.Structure):
     """ur_frame_gbuffer_pass (include/ur_frame.h): the draws, targets, optional counters, ur_gbuffer_pass flags and key bits of UR_FRAME_GBUFFER_PASS."""
     _fields_ = [("draws", RasterDraws), ("targets", GBufferTargets), ("stats6", C.c_void_p), ("flags", C.c_uint32), ("key_triangle_bits", C.c_uint32)]
@@ -346,6 +354,8 @@ SIGNATURES = {
                                   C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
     "ur_forward_pass_parts": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, C.POINTER(ForwardTargets), _U32, _U32, _U32, _U32, _U32, _U32, _VP, _U32,
                                         _VP, _U32, C.POINTER(GBufferMask), C.POINTER(SceneConstants), C.POINTER(LightingTables)]),
+    "ur_object_id_pass": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _VP, _VP, _U32, _U32, _U32, _U32, _U32, _U32, _VP]),
+    "ur_object_id_pick": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _U32, _U32, C.POINTER(_U32), _U32, _VP, _VP]),
     "ur_texture_transcode_bytes": (C.c_uint64, [_U32, _U32, _U32]),
     "ur_texture_transcode": (C.c_int, [_VP, _U32, _VP, _U32, _U32, _U32, _VP, C.POINTER(Texture2D)]),
     # ur_assets.h
