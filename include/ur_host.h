@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "ur_hotpath.h"
+#include "ur_mesh.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -91,6 +92,13 @@ uint64_t ur_host_texture_chain_bytes(uint32_t format, uint32_t width, uint32_t h
 /* One level of blocks -> level_width x level_height RGBA8 code words, as ur_host_bc_decode_level. UR_EINVAL for a null pointer, a format
  * outside the ten or a zero dimension. */
 int ur_host_texture_decode_level(uint32_t format, const void* blocks, uint32_t level_width, uint32_t level_height, uint8_t* rgba8_out);
+
+/* ur_mesh_build (include/ur_mesh.h) on the host, serial, in the reference's order: the CPU fallback and the time baseline.
+ * It runs csrc/mesh_rule.h, the very per-triangle and per-vertex functions the kernels run, and gives the device build's bytes. All
+ * pointers are host memory; `buffer` may lie at any address. vertices_out takes 64 * V bytes, indices_out I words (ur_mesh_layout_of);
+ * sections_out n entries, or NULL. UR_EINVAL for a null pointer and for everything ur_mesh_layout_of refuses. */
+int ur_host_mesh_build(const void* buffer, uint64_t buffer_size, const ur_mesh_primitive* primitives, uint32_t n, void* vertices_out, uint32_t* indices_out,
+                       ur_mesh_section* sections_out, ur_mesh_info* info_out);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

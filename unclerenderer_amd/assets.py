@@ -108,3 +108,73 @@ def load_texture_dds(path_or_bytes, srgb: bool = False):
         levels.append(np.frombuffer(data, np.uint8, wk * hk * 4, at).reshape(hk, wk, 4).copy())
         at += wk * hk * 4
     return levels, fmt == _lib.UR_TEXTURE_R8G8B8A8_UNORM_SRGB
+
+
+def gltf_mesh_primitives(gltf: dict, mesh_index: int):
+    """The hostmath.mesh_primitive records of meshes[mesh_index] of a parsed .gltf, and each primitive's material index (-1: none), as the
+    reference's loader reads them (GltfLoader.cpp:732-801): a stream's offset is the accessor's byteOffset plus the view's, its stride the
+    view's byteStride or the packed size, the mode 4 and the index component type 5125 by default. ValueError for a primitive without
+    POSITION or indices, a sparse accessor or an attribute that is not fp32."""
+    from . import hostmath
+    accessors, views = gltf.get("accessors", []), gltf.get("bufferViews", [])
+
+    def stream(index):
+        a = accessors[index]
+        if "sparse" in a or a.get("componentType", 5126) != 5126 or "bufferView" not in a:
+            raise ValueError(f"accessor {index}: only plain fp32 attribute accessors are built (no sparse, normalised-integer or view-less ones)")
+        view = views[a["bufferView"]]
+        if view.get("buffer", 0) != 0:
+            raise ValueError(f"accessor {index}: only buffers[0] is read")
+        return (a.get("byteOffset", 0) + view.get("byteOffset", 0), view.get("byteStride", 0))
+
+    primitives, materials = [], []
+    for k, primitive in enumerate(gltf["meshes"][mesh_index]["primitives"]):
+        attributes = primitive.get("attributes", {})
+        if "POSITION" not in attributes or "indices" not in primitive:
+            raise ValueError(f"mesh {mesh_index}, primitive {k}: POSITION and indices are required")
+        streams = {name: stream(attributes[key]) for key, name in (("NORMAL", "normal"), ("TEXCOORD_0", "texcoord"), ("TANGENT", "tangent"), ("COLOR_0", "color"))
+                   if key in attributes}
+        components = 4 if "COLOR_0" in attributes and accessors[attributes["COLOR_0"]].get("type") == "VEC4" else 3
+        a = accessors[primitive["indices"]]
+        if "sparse" in a or "bufferView" not in a or views[a["bufferView"]].get("buffer", 0) != 0:
+            raise ValueError(f"mesh {mesh_index}, primitive {k}: the index accessor needs a plain view of buffers[0]")
+        indices = (a.get("byteOffset", 0) + views[a["bufferView"]].get("byteOffset", 0), a.get("count", 0), a.get("componentType", 5125))
+        primitives.append(hostmath.mesh_primitive(accessors[attributes["POSITION"]].get("count", 0), stream(attributes["POSITION"]), indices,
+                                                  color_components=components, mode=primitive.get("mode", 4), **streams))
+        materials.append(int(primitive.get("material", -1)))
+    return primitives, materials
+
+
+def read_gltf(path):
+    """(the parsed .gltf, the bytes of its external buffer). The buffer is the file buffers[0].uri names, beside the .gltf; a GLB file and
+    an embedded (data:) buffer are refused."""
+    import json
+    path = Path(path)
+    head = path.read_bytes()[:4]
+    if head == b"glTF":
+        raise ValueError(f"{path}: a binary glTF (GLB) is not read; export the .gltf with an external .bin")
+    gltf = json.loads(path.read_text())
+    buffers = gltf.get("buffers", [])
+    uri = buffers[0].get("uri") if buffers else None
+    if not uri:
+        raise ValueError(f"{path}: buffers[0] has no uri (a GLB-stored buffer is not read)")
+    if uri.startswith("data:"):
+        raise ValueError(f"{path}: an embedded (data:) buffer is not read; export the .gltf with an external .bin")
+    from urllib.parse import unquote
+    return gltf, (path.parent / unquote(uri)).read_bytes()
+
+
+def load_gltf_meshes(path, hp):
+    """Every mesh of a .gltf built on the device: the external .bin is uploaded once and HotPath.build_mesh runs per glTF mesh, on the
+    context's stream, nothing read back. Returns the hotpath.Mesh objects in the file's mesh order, each with `materials` (per primitive,
+    the glTF material index). Which model draws which mesh, and the pipeline keys, stay ur_scene_extract's."""
+    from . import hotpath
+    gltf, data = read_gltf(path)
+    buffer = hotpath.to_device(np.frombuffer(data, np.uint8).copy())
+    meshes = []
+    for index in range(len(gltf.get("meshes", []))):
+        primitives, materials = gltf_mesh_primitives(gltf, index)
+        mesh = hp.build_mesh(buffer, primitives)
+        mesh.materials = materials
+        meshes.append(mesh)
+    return meshes

@@ -273,3 +273,49 @@ def build_frame_constants(preset: ScenePreset | str, width: int, height: int, *,
     L.ur_host_fill_sky_constants(_lib.fptr(view), _lib.fptr(proj), _lib.fptr(pos), sky_radius, _lib.fptr(light_dir),
                                  _lib.fptr(_f(*preset.light_color)), C.byref(sky))
     return FrameConstants(width, height, view, proj, pos, light_dir, scene, sky, center, scene_radius, sky_radius, near)
+
+
+def mesh_primitive(vertex_count: int, position, indices, *, normal=None, texcoord=None, tangent=None, color=None, color_components: int = 3, mode: int = 4):
+    """A ur_mesh_primitive (include/ur_mesh.h). A stream is (byte offset, stride) or None for an absent one; a stride of None or 0 is the
+    packed default (12, 12, 8, 16 and 4 * color_components bytes). indices is (byte offset, count, component type 5121 / 5123 / 5125)."""
+    p = _lib.MeshPrimitive()
+    packed = {"position": 12, "normal": 12, "texcoord": 8, "tangent": 16, "color": 4 * int(color_components)}
+    for name, stream in (("position", position), ("normal", normal), ("texcoord", texcoord), ("tangent", tangent), ("color", color)):
+        if stream is not None:
+            offset, stride = stream
+            setattr(p, name, _lib.MeshStream(int(offset), int(stride) if stride else packed[name], 1))
+    p.index_offset, p.index_count, p.index_component_type = int(indices[0]), int(indices[1]), int(indices[2])
+    p.mode, p.vertex_count, p.color_components = int(mode), int(vertex_count), int(color_components)
+    return p
+
+
+def mesh_primitive_array(primitives):
+    """A ctypes array of ur_mesh_primitive from MeshPrimitive records (copied)."""
+    primitives = list(primitives)
+    return (_lib.MeshPrimitive * max(len(primitives), 1))(*primitives)
+
+
+def mesh_layout(primitives, buffer_size: int):
+    """ur_mesh_layout_of: (lib.MeshLayout, [(vertex_offset, index_start, index_count) per primitive]); ValueError with the library's text
+    for anything it refuses."""
+    primitives = list(primitives)
+    layout, sections = _lib.MeshLayout(), (_lib.MeshSection * max(len(primitives), 1))()
+    rc = _lib.load().ur_mesh_layout_of(mesh_primitive_array(primitives), len(primitives), int(buffer_size), C.byref(layout), sections)
+    if rc != 0:
+        raise ValueError(_lib.load().ur_last_error().decode(errors="replace"))
+    return layout, [(s.vertex_offset, s.index_start, s.index_count) for s in sections[:len(primitives)]]
+
+
+def mesh_build(buffer, primitives):
+    """ur_host_mesh_build: the mesh rule on the host, serial, by the functions the kernels run (csrc/mesh_rule.h). `buffer`:
+    the .bin's bytes. Returns (vertices uint32[V, 16], indices uint32[I], sections, lib.MeshInfo): the bytes HotPath.build_mesh leaves on
+    the device."""
+    primitives = list(primitives)
+    data = np.ascontiguousarray(np.frombuffer(bytes(buffer), np.uint8) if isinstance(buffer, (bytes, bytearray, memoryview)) else buffer, np.uint8).reshape(-1)
+    layout, sections = mesh_layout(primitives, data.size)
+    vertices, indices, info = np.zeros((layout.vertex_count, 16), np.uint32), np.zeros(layout.index_count, np.uint32), _lib.MeshInfo()
+    rc = _lib.load().ur_host_mesh_build(data.ctypes.data_as(C.c_void_p), data.size, mesh_primitive_array(primitives), len(primitives),
+                                        vertices.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p), None, C.byref(info))
+    if rc != 0:
+        raise ValueError(f"ur_host_mesh_build failed ({rc})")
+    return vertices, indices, sections, info

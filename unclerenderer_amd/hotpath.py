@@ -982,6 +982,58 @@ def _transcode_texture(self, data_or_tensor, width: int, height: int, mips: int,
     return out, desc
 
 
+class Mesh:
+    """A built mesh on the device: `vertices` (int32 [V, 16]: 64-byte vertices), `indices` (int32 [I]), `sections` (per primitive
+    (vertex_offset, index_start, index_count)), `info` (int32 [14]: a lib.MeshInfo record, read with mesh_info once the stream is done) and
+    `materials` (per primitive the glTF material index, -1 for none; filled by assets.load_gltf_meshes)."""
+
+    def __init__(self, vertices, indices, sections, info, materials=None):
+        self.vertices, self.indices, self.sections, self.info, self.materials = vertices, indices, sections, info, materials
+
+    def mesh_info(self):
+        """The lib.MeshInfo record (synchronises: a device-to-host copy)."""
+        return _lib.MeshInfo.from_buffer_copy(self.info.cpu().numpy().tobytes())
+
+
+def _build_mesh(self, buffer, primitives, scratch=None):
+    """ur_mesh_build: `buffer` (the glTF .bin as a uint8 device tensor, or bytes / a uint8 array uploaded here) and hostmath.mesh_primitive
+    records of one glTF mesh become a Mesh on the device, by the reference's assembly, index expansion and normal / tangent rules
+    (DESIGN.md 3.17). Asynchronous on the context's stream; nothing is read back. scratch: a uint8 device tensor of at least the
+    layout's scratch_bytes to reuse, else one is allocated."""
+    from . import hostmath
+    primitives = list(primitives)
+    if not isinstance(buffer, torch.Tensor):
+        data = np.frombuffer(bytes(buffer), np.uint8) if isinstance(buffer, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buffer, np.uint8).reshape(-1)
+        size = data.size
+    else:
+        assert buffer.dtype == torch.uint8 and buffer.is_contiguous()
+        size = buffer.numel()
+    layout, sections = hostmath.mesh_layout(primitives, size)  # refuses before anything is uploaded
+    if not isinstance(buffer, torch.Tensor):
+        buffer = to_device(data.copy())
+    assert buffer.is_cuda
+    vertices = torch.empty((layout.vertex_count, 16), dtype=torch.int32, device=buffer.device)
+    indices = torch.empty(layout.index_count, dtype=torch.int32, device=buffer.device)
+    info = torch.empty(C.sizeof(_lib.MeshInfo) // 4, dtype=torch.int32, device=buffer.device)
+    if scratch is None:
+        scratch = torch.empty(int(layout.scratch_bytes), dtype=torch.uint8, device=buffer.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= layout.scratch_bytes
+    _lib.check(self._L.ur_mesh_build(self._ctx, buffer.data_ptr(), size, hostmath.mesh_primitive_array(primitives), len(primitives), vertices.data_ptr(),
+                                     indices.data_ptr(), scratch.data_ptr(), scratch.numel(), info.data_ptr()), "ur_mesh_build")
+    mesh = Mesh(vertices, indices, sections, info)
+    mesh._keep = (buffer, scratch)  # (the launches are still in flight)
+    return mesh
+
+
+def mesh_draws(mesh, constants, constants_offset: int = 0, constants_stride: int = 0):
+    """pack_draw_commands' dicts for a Mesh: one command per primitive with start_index / index_count from its section, base_vertex 0 (the
+    indices already carry the primitive's vertex offset) and stride 64. constants: the device tensor of the draws' constants, primitive k at
+    constants_offset + k * constants_stride bytes."""
+    return [{"vertices": mesh.vertices, "stride": 64, "indices": mesh.indices, "constants": constants, "constants_offset": constants_offset + k * constants_stride,
+             "start_index": start, "index_count": count, "base_vertex": 0} for k, (_, start, count) in enumerate(mesh.sections)]
+
+
+HotPath.build_mesh = _build_mesh
 HotPath.transcode_texture = _transcode_texture
 HotPath.gbuffer_pass = _gbuffer_pass
 HotPath.forward_pass = _forward_pass

@@ -164,6 +164,39 @@ class LightingTables(C.Structure):
     ]
 
 
+class MeshStream(C.Structure):
+    """ur_mesh_stream (include/ur_mesh.h): one fp32 attribute stream of a glTF buffer."""
+    _fields_ = [("offset", C.c_uint64), ("stride", C.c_uint32), ("present", C.c_uint32)]
+
+
+class MeshPrimitive(C.Structure):
+    """ur_mesh_primitive (include/ur_mesh.h), 112 bytes."""
+    _fields_ = [("position", MeshStream), ("normal", MeshStream), ("texcoord", MeshStream), ("tangent", MeshStream), ("color", MeshStream),
+                ("index_offset", C.c_uint64), ("index_count", C.c_uint32), ("index_component_type", C.c_uint32), ("mode", C.c_uint32),
+                ("vertex_count", C.c_uint32), ("color_components", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MeshSection(C.Structure):
+    """ur_mesh_section (include/ur_mesh.h)."""
+    _fields_ = [("vertex_offset", C.c_uint32), ("index_start", C.c_uint32), ("index_count", C.c_uint32)]
+
+
+class MeshLayout(C.Structure):
+    """ur_mesh_layout (include/ur_mesh.h)."""
+    _fields_ = [("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+
+class MeshInfo(C.Structure):
+    """ur_mesh_info (include/ur_mesh.h), 56 bytes."""
+    _fields_ = [("min", C.c_float * 3), ("max", C.c_float * 3), ("center", C.c_float * 3), ("radius", C.c_float), ("normals_regenerated", C.c_uint32),
+                ("tangents_regenerated", C.c_uint32), ("skipped_determinant_triangles", C.c_uint32), ("out_of_range_triangles", C.c_uint32)]
+
+
+UR_MESH_MODE_TRIANGLES, UR_MESH_MODE_TRIANGLE_STRIP, UR_MESH_MODE_TRIANGLE_FAN = 4, 5, 6
+UR_MESH_INDEX_U8, UR_MESH_INDEX_U16, UR_MESH_INDEX_U32 = 5121, 5123, 5125
+UR_MESH_BUILD_MAX_STREAM_OPS = 14
+
+
 class DdsInfo(C.Structure):
     """ur_dds_info (include/ur_assets.h)."""
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "mip_count", "slices", "is_cube", "dxgi_format", "header_size", "block_dim", "bytes_per_block")]
@@ -358,8 +391,11 @@ SIGNATURES = {
     "ur_object_id_pick": (C.c_int, [_VP, _FP, _FP, C.POINTER(RasterDraws), _VP, _U32, _U32, _U32, _U32, C.POINTER(_U32), _U32, _VP, _VP]),
     "ur_texture_transcode_bytes": (C.c_uint64, [_U32, _U32, _U32]),
     "ur_texture_transcode": (C.c_int, [_VP, _U32, _VP, _U32, _U32, _U32, _VP, C.POINTER(Texture2D)]),
+    # ur_mesh.h
+    "ur_mesh_layout_of": (C.c_int, [C.POINTER(MeshPrimitive), _U32, C.c_uint64, C.POINTER(MeshLayout), C.POINTER(MeshSection)]),
+    "ur_mesh_build": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(MeshPrimitive), _U32, _VP, _VP, _VP, C.c_uint64, _VP]),
     # ur_assets.h
-    "ur_dds_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
+    "ur_dds_parse":(C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d_source": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_texel_count": (C.c_size_t, [C.POINTER(DdsInfo)]),
@@ -419,6 +455,7 @@ SIGNATURES = {
     "ur_host_bc_decode_level": (C.c_int, [_U32, _VP, _U32, _U32, _VP]),
     "ur_host_texture_chain_bytes": (C.c_uint64, [_U32, _U32, _U32, _U32]),
     "ur_host_texture_decode_level": (C.c_int, [_U32, _VP, _U32, _U32, _VP]),
+    "ur_host_mesh_build": (C.c_int, [_VP, C.c_uint64, C.POINTER(MeshPrimitive), _U32, _VP, _VP, C.POINTER(MeshSection), C.POINTER(MeshInfo)]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
