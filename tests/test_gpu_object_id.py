@@ -307,6 +307,67 @@ def test_pick_on_the_strip_through_the_near_plane(hotpath, w, h):
         same_pick(run_pick(hotpath, sel, sc.view, sc.proj, depth, w, h, points), want, points, w, h, f"strip {w}x{h}, points {seed}")
 
 
+# ---- the walk both kernels share -------------------------------------------------------------------------------------------------------------
+
+def _walk_commands(w, h):
+    """Eight commands of at most 70 triangles on a w x h target under hand_camera, one per refusal or skip of the walk over the draws, and
+    two good ones: 0 a stride of 32, 1 an R16 index format, 2 an index range of 6 triangles over an index buffer of 3, 3 two triangles with
+    a vertex past the vertex buffer, 4 InstanceCount 0, 5 seventy triangles (more than 1 << 6), 6 sixty-five (a second chunk), 7 sixty.
+    Seeded triangles of both windings with edges up to half the target, at view depths 1, 2 and 4, some cut by the near plane or behind it."""
+    rng = np.random.default_rng(16)
+
+    def triangles(n):
+        corner = rng.uniform(-2.0, w + 2.0, (n, 1, 2))
+        xy = corner + rng.uniform(-0.5 * w, 0.5 * w, (n, 3, 2)) * rng.uniform(0.05, 1.0, (n, 1, 1))
+        z = rng.choice([1.0, 2.0, 4.0], (n, 3))
+        z[(rng.uniform(size=(n, 3)) < 0.1) | (rng.uniform(size=(n, 1)) < 0.05)] = 0.5 * D.NEAR  # behind the near plane: a vertex, or all three
+        return np.array([D.at(x, y, zz, w, h) for (x, y), zz in zip(xy.reshape(-1, 2), z.reshape(-1))], np.float32)
+
+    def draw(n, oid, **kw):
+        return G.GDraw(G.vertex_buffer(triangles(n)), np.arange(3 * n, dtype=np.uint32), object_id=oid, **kw)
+
+    short = G.GDraw(D.S.vertex_buffer(triangles(4), stride=32), np.arange(12, dtype=np.uint32), stride=32, object_id=10)
+    past_vb = draw(6, 13)
+    past_vb.indices[4], past_vb.indices[15] = 18, 0x7FFFFFF0  # triangles 1 and 5: one vertex behind the last, one far behind
+    return [short, draw(4, 11, index_format=57), draw(3, 12, index_count=18), past_vb, draw(5, 14, instance_count=0), draw(70, 15), draw(65, 16), draw(60, 17)]
+
+
+@pytest.mark.parametrize("bits,refused", [(7, 4 + 4 + 3 + 2), (6, 4 + 4 + 3 + 2 + 70 + 65)])
+def test_refusals_of_the_shared_walk_from_both_kernels(hotpath, bits, refused):
+    """ur_object_id_pass and ur_object_id_pick (four calls of 64 points: every texel of 16 x 16) over _walk_commands under every slot, a
+    list and ranges give the restatement's records and counters. With 7 triangle bits the commands of 70 and 65 triangles are drawn, the
+    latter through a second chunk; with 6 both are refused as a whole, so stats[1] is worked by hand for both."""
+    from unclerenderer_amd.hotpath import raster_draws, to_device
+    w = h = 16
+    draws = _walk_commands(w, h)
+    assert len(draws) == 8 and max(d.count() // 3 for d in draws) == 70
+    view, proj = D.hand_camera(w, h)
+    rng = np.random.default_rng(3)
+    depth = np.where(rng.uniform(size=(h, w)) < 0.3, np.float32(D.NEAR / 1.5), np.float32(0.0)).astype(np.float32)  # (behind it: view depths 2 and 4)
+    dd = device_draws(draws)
+    base = 1000
+    idx = np.array([base + k for k in (7, 5, 0, 6, 2, 1, 3, 4)], np.uint32)
+    offsets, counts = np.array([0, 3, 3, 8], np.uint32), np.array([3, 0, 5], np.uint32)
+    compacted = to_device(dd.host_commands.view(np.int32).copy())
+    selections = [("every slot", None, raster_draws(dd.commands)),
+                  ("list", G.selection(8, visible=(idx, 8), index_base=base), raster_draws(dd.commands, None, (to_device(idx), to_device(np.array([8], np.uint32))), None, base)),
+                  ("ranges", G.selection(8, ranges=(offsets, counts)), raster_draws(None, None, None, (to_device(offsets), compacted, to_device(counts))))]
+    assert [s for _, s in selections[1][1]] == [7, 5, 0, 6, 2, 1, 3, 4] and [s for _, s in selections[2][1]] == list(range(8))
+    calls = O.every_texel(w, h)
+    assert len(calls) == 4
+    for name, select, sel in selections:
+        want = O.image(draws, view, proj, depth, w, h, select=select, key_triangle_bits=bits)
+        ids = set(want["object_id"].reshape(-1).tolist())
+        assert want["stats"][1] == refused and want["stats"][0] > 0 and want["stats"][4] > 0 and want["stats"][5] > 0 and 17 in ids and (16 in ids) == (bits == 7) and not ids & {10, 11, 14}, (name, want["stats"].tolist(), ids)
+        same_image(run_image(hotpath, sel, view, proj, depth, w, h, key_triangle_bits=bits), want, f"{name}, {bits} bits")
+        total = np.zeros(6, np.int64)
+        for k, points in enumerate(calls):
+            got = run_pick(hotpath, sel, view, proj, depth, w, h, points, key_triangle_bits=bits)
+            same_pick(got, want, points, w, h, f"{name}, {bits} bits, call {k}")
+            total += got[1]
+        assert total[3] == 0 and total[COUNTED].tolist() == (4 * want["stats"][COUNTED].astype(np.int64)).tolist()
+
+
 # ---- held independently by the ray casters ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("w,h", R.TARGETS)

@@ -69,8 +69,8 @@ def test_struct_layout_matches_a_compiled_probe(tmp_path):
 
 def test_new_kernels_use_no_scratch_and_the_keyed_raster_keeps_its_registers(urlib, tmp_path):
     """The code objects' metadata notes: pick_kernel in both forms, pick_finish_kernel and object_id_resolve_kernel have no
-    scratch and spill no VGPR, the pick within the raster's own occupancy step; raster_kernel<VisPolicy<...>>, beside which pick_kernel was
-    written out instead of sharing its front half, stays without scratch inside its four-wave step (3.16 records the counts)."""
+    scratch and spill no VGPR, the pick within the raster's own occupancy step; raster_kernel<VisPolicy<...>>, whose walk and per-triangle
+    front half pick_kernel shares (csrc/raster_front.h), stays without scratch inside its four-wave step (3.16 records the counts)."""
     from tests.code_objects import library_kernels
     kernels = library_kernels(tmp_path)
     find = lambda pattern: {k: m for k, m in kernels.items() if re.search(pattern, k)}  # noqa: E731
@@ -86,6 +86,33 @@ def test_new_kernels_use_no_scratch_and_the_keyed_raster_keeps_its_registers(url
     for name, m in rasters.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["vgpr_count"] <= 128, (name, m)
     assert all(m["vgpr_count"] <= 128 for m in picks.values()), picks  # four waves per SIMD, as the raster
+
+
+# The VGPR count up to which a kernel keeps the waves per SIMD it had before it shared csrc/raster_front.h (512 / waves, in granules of 8)
+OCCUPANCY_STEP = {
+    r"\d+raster_kernelINS_12ShadowPolicyEE": 96,          # 5 waves (it had 87)
+    r"\d+raster_kernelINS_11DepthPolicyILb[01]EE": 128,   # 4 waves (104 and 110)
+    r"\d+raster_kernelINS_9VisPolicyILb[01]EE": 128,      # 4 waves (114 and 120)
+    r"\d+raster_kernelINS_10MaskPolicyILb[01]EE": 256,    # 2 waves (220)
+    r"\d+pick_kernelINS_9VisPolicyILb[01]EE": 80,         # 6 waves (79)
+}
+
+
+def test_the_kernels_over_the_shared_front_half_keep_their_occupancy_step(urlib, tmp_path):
+    """raster_kernel in its seven forms and pick_kernel in both are one walk and one per-triangle front half (csrc/raster_front.h) plus
+    their own back halves: none has scratch or spills a VGPR, and each stays at or below the VGPR count of the occupancy step it had when
+    pick_kernel carried its own copy (DESIGN.md 3.16 has the counts). Metadata notes only; spilled SGPRs move with any change and are not held."""
+    from tests.code_objects import library_kernels
+    kernels = library_kernels(tmp_path)
+    seen = 0
+    for pattern, bound in OCCUPANCY_STEP.items():
+        found = {k: m for k, m in kernels.items() if re.search(pattern, k)}
+        assert len(found) == (1 if "Shadow" in pattern else 2), (pattern, sorted(found))
+        for name, m in found.items():
+            print(name, m)
+            assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["vgpr_count"] <= bound, (name, m, bound)
+        seen += len(found)
+    assert seen == 9
 
 
 def test_argument_checks(urlib):

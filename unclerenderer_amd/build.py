@@ -47,6 +47,8 @@ SOURCES = [
     ("post.hip", EXACT),
     ("debug_print.hip", EXACT),
     ("raster.hip", EXACT),
+    ("raster_mask.hip", EXACT),
+    ("raster_pick.hip", EXACT),
     ("gbuffer_resolve.hip", EXACT),
     ("gbuffer_api.hip", EXACT),  # host code only: the entry points of the GBuffer and the Forward pass
     ("object_id_api.hip", EXACT),  # host code only: the entry points of the ObjectId pass and the pick

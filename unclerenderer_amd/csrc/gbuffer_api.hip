@@ -1,5 +1,5 @@
 // The C ABI of the GBuffer and the Forward pass (include/ur_raster.h; DESIGN.md sections 3.9 to 3.12), host code only: the entry points,
-// their argument checks, the raster launches (csrc/raster.hip) and the arguments of the two resolves (csrc/gbuffer_resolve.hip,
+// their argument checks, the raster launches (csrc/raster.hip, csrc/raster_mask.hip) and the arguments of the two resolves (csrc/gbuffer_resolve.hip,
 // csrc/forward_resolve.hip). The Forward pass' entry points share gbuffer_entry's checks and raster launches. Built with the kernels' flags.
 
 #include "forward_resolve.h"

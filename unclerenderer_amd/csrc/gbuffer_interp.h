@@ -1,5 +1,5 @@
 // From a visibility key's triangle to a texel's attribute weights — what the two resolves (csrc/gbuffer_resolve.hip,
-// csrc/forward_resolve.hip) and the alpha test of the masked raster (csrc/raster.hip) must compute alike, operation for operation: the near
+// csrc/forward_resolve.hip) and the alpha test of the masked raster (csrc/raster_mask.hip) must compute alike, operation for operation: the near
 // clip restated with a weight row per polygon vertex, the piece of the triangle that covers a centre with its
 // exact edge values, the perspective-correct weights over the original three vertices, and TEXCOORD at the texel's quad partners
 // (section 3.10). Device inline functions only; csrc/visibility_key.h has what comes before and after them.

@@ -1,5 +1,5 @@
 // The C ABI of the ObjectId pass and the pick (include/ur_raster.h), host code only: the entry points, their
-// argument checks, the raster launches (csrc/raster.hip) and the arguments of the ObjectId resolve (csrc/gbuffer_resolve.hip). Built with
+// argument checks, the raster launches (csrc/raster.hip, csrc/raster_pick.hip) and the arguments of the ObjectId resolve (csrc/gbuffer_resolve.hip). Built with
 // the kernels' flags.
 
 #include "gbuffer_resolve.h"

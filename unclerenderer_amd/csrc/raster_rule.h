@@ -1,4 +1,4 @@
-// What the raster (csrc/raster.hip) and GBuffer's resolve (csrc/gbuffer_resolve.hip) must compute alike to decide a texel alike - not
+// What the raster (csrc/raster_front.h, csrc/raster_kernels.h) and GBuffer's resolve (csrc/gbuffer_resolve.hip) must compute alike to decide a texel alike - not
 // constants only: the launch shape, the finite test's bound, the depth passes' guard band, and as device functions rule 4's tie-break
 //  and the near clip's select (section 3.8). The host checks' alignment test rides along. Nothing else belongs here.
 #pragma once

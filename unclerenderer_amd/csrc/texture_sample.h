@@ -2,7 +2,7 @@
 // ApplyTextureTransform, wrap addressing, one bilinear sample, and the footprint / level of detail / trilinear probes of one map, as
 // device inline functions over tables the including kernel has put into LDS (layout below). A texel is an RGBA8 code word: read as it
 // lies, or decoded from its BC1 / BC3 / BC5 block by csrc/bc_decode.h. csrc/gbuffer_resolve.hip samples R, G and B
-// with it, the masked raster's alpha test (csrc/raster.hip) channel A: the same sampler with another output.
+// with it, the masked raster's alpha test (csrc/raster_mask.hip) channel A: the same sampler with another output.
 #pragma once
 
 #include "bc_decode.h"

@@ -107,7 +107,7 @@ struct ur_ctx {
     // host-visible (mapped, coherent) word beside hzb_timed_out: a wave of a balanced launch gave up waiting for a claim
     volatile uint32_t* claim_timed_out = nullptr;
     uint32_t* claim_timed_out_dev = nullptr;
-    // ur_raster_reserve: the large-triangle queue of the raster passes (csrc/raster.hip): a 64-byte header (the count) + entries
+    // ur_raster_reserve: the large-triangle queue of the raster passes (csrc/raster_params.h has its layout, csrc/raster_kernels.h its kernels): a 64-byte header (the count) + entries
     uint32_t* raster_queue = nullptr;
     uint32_t raster_queue_cap = 0;
 };

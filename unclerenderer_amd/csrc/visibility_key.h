@@ -1,5 +1,5 @@
 // What every consumer of a visibility key does alike, operation for operation (DESIGN.md sections 3.9 to 3.12): GBuffer's resolve
-// (csrc/gbuffer_resolve.hip), the Forward pass' resolve (csrc/forward_resolve.hip) and the alpha test of the masked raster (csrc/raster.hip).
+// (csrc/gbuffer_resolve.hip), the Forward pass' resolve (csrc/forward_resolve.hip) and the alpha test of the masked raster (csrc/raster_mask.hip).
 // The key's way back to its draw, the fill of the sampler's tables, the quad's differences, and the two resolves' loop over the four maps,
 // tangent frame and material factors; from the triangle to the texel's weights it is gbuffer_interp.h, the sampler texture_sample.h.
 // Device inline functions only. The two resolves' vertex stage is not here: DESIGN.md section 3.14 says why.
