@@ -1,13 +1,13 @@
 // Sanitizer driver (CPU build only: -fsanitize=address,undefined): runs the host-side code of the product (DDS/BC6H decode,
-// scene -> ModelBounds extraction, host constant math, the Lighting launch's and the Build HZB chain's planners, the environment cube's
-// staging) and the CPU oracle (test infrastructure) over the
+// scene -> ModelBounds extraction, host constant math, the Lighting launch's, the Build HZB chain's and the cull's planners, the
+// environment cube's staging) and the CPU oracle (test infrastructure) over the
 // shipped fixtures, random inputs and hostile inputs (truncated files, garbage blocks, empty and ragged sizes). Any report from ASan/UBSan
 // ends the process with a non-zero status. SURVEY.md section 5, "Race detection / sanitizers": the reference has only the D3D12
 // debug layer (Source/RHI/DX12Device.cpp:82-91).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -I include \
 //       tests/cpp/sanitize_main.cpp csrc/dds.cpp csrc/scene.cpp csrc/host_math.cpp csrc/lighting_plan.cpp csrc/hzb_plan.cpp \
-//       csrc/env_cube_stage.cpp oracle/ur_oracle.cpp -pthread
+//       csrc/cull_plan.cpp csrc/env_cube_stage.cpp oracle/ur_oracle.cpp -pthread
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +23,7 @@
 #include "ur_hotpath.h"
 #include "ur_scene.h"
 
+#include "cull_plan_sweep.h"
 #include "hzb_plan_sweep.h"
 #include "lighting_plan_sweep.h"
 
@@ -263,6 +264,22 @@ static void test_hzb_plan()
     CHECK(hzb_sweep::g_fail == 0);
 }
 
+// csrc/cull_plan.cpp: the sweep of tests/cpp/test_cull_plan.cpp (the full cross product of the recorded calls' values), and counts no
+// call can have (more views than there are, the largest n and range count): the plan's per-view arrays are not written past their end
+static void test_cull_plan()
+{
+    CHECK(cull_sweep::sweep() > 50000);
+    CHECK(cull_sweep::g_fail == 0);
+    for (uint32_t n : {0u, 257u, 0xFFFFFF00u, 0xFFFFFFFFu})
+        for (uint32_t views : {0u, 4u, 5u, 0xFFFFFFFFu}) {
+            ur::CullPlanInput in{};
+            in.n = n; in.view_count = views; in.most_ranges = 0xFFFFFFFFu; in.store_flavour = 4; in.camera_ranges = true;
+            for (bool& c : in.view_compacted) c = true;
+            const ur::CullPlan p = ur::plan_cull(in);
+            CHECK(p.compact_grid_y <= 1u + UR_MAX_CULL_VIEWS && (n != 0 || p.zero_grid == 0x1000000u));
+        }
+}
+
 int main(int argc, char** argv)
 {
     const std::string assets = argc > 1 ? argv[1] : "tests/golden/assets";
@@ -272,6 +289,7 @@ int main(int argc, char** argv)
     test_lighting_plan();
     test_env_cube_stage();
     test_hzb_plan();
+    test_cull_plan();
     if (g_fail) { std::printf("%d check(s) failed\n", g_fail); return 1; }
     std::printf("OK sanitized host + oracle run clean\n");
     return 0;

@@ -315,6 +315,45 @@ def test_instance_range_sharding(hotpath, oracle, ranks):
         assert np.array_equal(np.concatenate(lists[k]), _u(v.vis)[:int(_u(v.cnt)[0])])
 
 
+def test_a_workspace_with_no_slack(hotpath, oracle):
+    """The workspace grown inside the call, so that it has no slack: a view's slice that overran its neighbour would land in the next
+    slice, not in spare room. ur_create reserves 1 << 20 instances, so the sizes lie just above that, on a context of its own:
+    n = (1 << 20) + 1 makes the call itself reserve 4097 * 256 instances: 4097 blocks in a stride of 4097, every slice exactly full, 65
+    compaction workgroups per row; the same call again on the same command buffer meets a valid record (flavour 4) on that exact
+    workspace; n = (1 << 20) + 16385 grows it again inside the call (4161 blocks, stride 4161) and drops the record; and that call again.
+    Four views, all compacted, two with lists and two with ranges; the camera with a list and ranges; UR_OPT_CULL_STORE = 4. Every call's
+    words, lists, counts and range commands are the oracle's (one oracle run at the larger n: an instance's result does not depend on n)."""
+    from unclerenderer_amd import hostmath, lib
+    from unclerenderer_amd.hotpath import HotPath, to_device
+    n_max = (1 << 20) + 16385
+    fc, lay, hzb, all_bounds = _setup(oracle, n_max, seed=901, box=400.0, w=960, h=540)
+    all_cmds = _commands(n_max, seed=902)
+    consts_of = lambda n: hostmath.pack_culling_constants(fc.view, fc.proj, n, True, lay.count, lay.width, lay.height, True)
+    all_args, _, all_vis, _ = oracle.cull_indirect_args(consts_of(n_max), all_bounds, hzb, lay.as_list(), all_cmds)
+    planes = _view_planes(fc, consts_of(n_max))
+    d_bounds, d_hzb = to_device(all_bounds), to_device(hzb)
+    own = HotPath(0)
+    try:
+        own.set_option(lib.UR_OPT_CULL_STORE, 4)
+        for n in ((1 << 20) + 1, n_max):
+            consts, bounds, cmds = consts_of(n), all_bounds[:n], all_cmds[:n]
+            ref_args, ref_vis = all_args[:n], all_vis[all_vis < n]
+            d_args = to_device(cmds)
+            o = np.linspace(0, n, 9).astype(np.uint32)
+            want_cmds, want_counts = _expected(ref_args[:, 11], cmds, o)
+            for call in (1, 2):  # (the first grows the workspace inside the call; the second meets the record the first left)
+                vs = [_View(planes[0], n), _View(planes[1], n, lst=False, offsets=o), _View(planes[2], n),
+                      _View(planes[3], n, lst=False, offsets=np.array([0, n // 3, n], np.uint32))]
+                got = _camera_call(own, consts, d_bounds[:n], d_hzb, lay, cmds, [v.arg for v in vs], offsets=o, d_args=d_args)
+                assert np.array_equal(got[0], ref_args), (n, call, "words")
+                assert got[3] == ref_vis.size and np.array_equal(got[2][:got[3]], ref_vis) and (got[2][got[3]:] == SENT).all(), (n, call, "list")
+                assert np.array_equal(got[5], want_counts) and np.array_equal(got[4].reshape(-1, 16)[:n], want_cmds), (n, call, "ranges")
+                for v in vs:
+                    v.check(oracle, bounds, cmds)
+    finally:
+        own.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The frame
 # ---------------------------------------------------------------------------------------------------------------------

@@ -4,8 +4,8 @@ reference has only the D3D12 debug layer, Source/RHI/DX12Device.cpp:82-91). CPU 
   * the render graph (csrc/rg/RenderGraph.cpp) compiled as host C++ together with its semantics test;
   * the frame units (csrc/frame/*.cpp) on the render graph, driven by tests/cpp/frame_trace.cpp through its curated cases, every entry point
     they link against a recording stand-in (tests/test_frame_trace_cpp.py): a stand-alone program, no HIP runtime, nothing loaded into Python;
-  * the host-side product code (DDS/BC6H decode, scene extraction, host constant math, the Lighting launch's and the Build HZB chain's planners, the environment
-    cube's staging) and the oracle, driven by
+  * the host-side product code (DDS/BC6H decode, scene extraction, host constant math, the Lighting launch's, the Build HZB chain's and the cull's planners, the
+    environment cube's staging) and the oracle, driven by
     tests/cpp/sanitize_main.cpp over the shipped fixtures, random inputs and hostile inputs in exact-size heap buffers.
 Any sanitizer report aborts the binary (-fno-sanitize-recover) and fails the test."""
 import shutil
@@ -35,7 +35,7 @@ def _build(exe: Path, sources: list[Path], extra: list[str]) -> Path:
 def test_host_code_and_oracle_under_asan_ubsan():
     csrc = ROOT / "unclerenderer_amd" / "csrc"
     exe = _build(OUT / "sanitize_main", [ROOT / "tests" / "cpp" / "sanitize_main.cpp", csrc / "dds.cpp", csrc / "scene.cpp", csrc / "host_math.cpp",
-                                         csrc / "lighting_plan.cpp", csrc / "hzb_plan.cpp", csrc / "env_cube_stage.cpp", ROOT / "oracle" / "ur_oracle.cpp"], [])
+                                         csrc / "lighting_plan.cpp", csrc / "hzb_plan.cpp", csrc / "cull_plan.cpp", csrc / "env_cube_stage.cpp", ROOT / "oracle" / "ur_oracle.cpp"], [])
     r = subprocess.run([str(exe), str(ROOT / "tests" / "golden" / "assets")], capture_output=True, text=True, timeout=300, env=ENV)
     assert r.returncode == 0 and "OK sanitized host + oracle run clean" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -125,7 +125,8 @@ def main():
     rows = []
     for key, t in times.items():
         rows.append({"shape": f"C5 {n} instances, {visible} visible, list on, {key}", "median_us": float(np.median(t)),
-                     "min_us": float(np.min(t)), "batches": len(t), "calls_per_batch": a.iters, "inputs": f"{a.ring} buffer sets cycled (cold)"})
+                     "min_us": float(np.min(t)), "max_us": float(np.max(t)), "batches": len(t), "calls_per_batch": a.iters,
+                     "inputs": f"{a.ring} buffer sets cycled (cold)"})
     del sets, calls, dev_layouts
     torch.cuda.empty_cache()
 
@@ -159,7 +160,7 @@ def main():
                 ts[key].append(time_batch(torch, f, a.iters * 4))
         for key, t in ts.items():
             rows.append({"shape": f"{name} {m} commands, list on, {key}", "median_us": float(np.median(t)), "min_us": float(np.min(t)),
-                         "batches": len(t), "calls_per_batch": a.iters * 4, "inputs": "one buffer set"})
+                         "max_us": float(np.max(t)), "batches": len(t), "calls_per_batch": a.iters * 4, "inputs": "one buffer set"})
     hp.close()
     for r in rows:
         print(f"{r['shape']:80s} median {r['median_us']:8.2f} us  min {r['min_us']:8.2f} us")

@@ -39,6 +39,7 @@ SOURCES = [
     ("hzb_plan.cpp", ["-x", "hip"] + EXACT),
     ("cull.hip", EXACT),
     ("cull_views.hip", EXACT),
+    ("cull_plan.cpp", ["-x", "hip"] + EXACT),
     ("lighting.hip", LIGHTING),
     ("lighting_tiled.hip", LIGHTING),
     ("lighting_host.hip", LIGHTING),  # host code only; the kernels' bits depend on its arithmetic, so it keeps their flags

@@ -24,10 +24,12 @@
 // (one more launch row per view, its masks in its own slice of the context's scratch). The VIEWS template parameter: the
 // instantiations without it are, again, the kernels as they were.
 //
-// The kernels and their launch path (cull_launches) are in cull_kernels.h. This file instantiates the camera-only kernels, cull_views.hip
-// those with views: each module holds one set, so the camera-only kernels compile exactly as they did before the views existed.
+// The kernels are in cull_kernels.h (with cull_params.h, cull_tests.h, cull_compact.h), their launch path (cull_launches) in cull_launch.h,
+// its decisions in cull_plan.cpp. This file instantiates the camera-only kernels, cull_views.hip those with views: each module holds one
+// set, so the camera-only kernels compile exactly as they did before the views existed.
 
 #include "cull_kernels.h"
+#include "cull_launch.h"
 
 namespace ur {
 

@@ -1,7 +1,8 @@
 // CullIndirectArgs with extra views (ur_cull_indirect_args_views): cull_launches<true> instantiates cull_kernel / compact_kernel with VIEWS
-// (cull_kernels.h). A translation unit of its own, so that the camera-only kernels in cull.hip compile exactly as they did without views.
+// (cull_kernels.h, launched by cull_launch.h). A translation unit of its own, so that the camera-only kernels in cull.hip compile exactly as they did without views.
 
 #include "cull_kernels.h"
+#include "cull_launch.h"
 
 namespace ur {
 
