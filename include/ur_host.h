@@ -10,6 +10,7 @@
 
 #include "ur_hotpath.h"
 #include "ur_mesh.h"
+#include "ur_scene_build.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -99,6 +100,14 @@ int ur_host_texture_decode_level(uint32_t format, const void* blocks, uint32_t l
  * sections_out n entries, or NULL. UR_EINVAL for a null pointer and for everything ur_mesh_layout_of refuses. */
 int ur_host_mesh_build(const void* buffer, uint64_t buffer_size, const ur_mesh_primitive* primitives, uint32_t n, void* vertices_out, uint32_t* indices_out,
                        ur_mesh_section* sections_out, ur_mesh_info* info_out);
+
+/* ur_scene_build (include/ur_scene_build.h) on the host, serial, draw by draw in command order: the CPU fallback and the time
+ * baseline. It runs csrc/scene_rule.h, the very functions the kernels run, and gives the device build's bytes. All pointers are host
+ * memory at any alignment; no scratch. A command's ConstantBufferAddress is constants_address + slot * constants_stride: the caller
+ * gives the address the records will have where the commands are read. UR_EINVAL for a null pointer (centers may be null),
+ * draw_count == 0 or >= 2^24, an empty table, slot_count == 0, a stride below 608 or no multiple of 16, unknown flag bits. */
+int ur_host_scene_build(const ur_scene_build_tables* tables, const ur_scene_constants* frame, const ur_scene_build_outputs* outputs,
+                        uint64_t constants_address, uint32_t flags);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

@@ -178,3 +178,54 @@ def load_gltf_meshes(path, hp):
         mesh.materials = materials
         meshes.append(mesh)
     return meshes
+
+
+def gltf_material_factors(gltf: dict) -> np.ndarray:
+    """The lib.SceneMaterialFactors records of a parsed .gltf's materials (a structured array of len(materials) + 1 records), as the
+    reference's loader and model set-up read them (GltfLoader.cpp:1040-1100, RendererUtils.cpp:34-44): baseColorFactor, metallicFactor,
+    roughnessFactor (1), emissiveFactor (0), alphaMode MASK with alphaCutoff (0.5), and per texture the KHR_texture_transform offset,
+    scale and rotation as (offset.xy, scale.xy) and (cos, sin, 0, 0), in fp32. The last record is the default material: what a primitive
+    without a material gets (index -1), and every primitive of a file without materials, textures or images (the reference reads the
+    materials only when all three are there)."""
+    record = np.dtype(_lib.SceneMaterialFactors)
+    materials = gltf.get("materials") or []
+    out = np.zeros(len(materials) + 1, record)
+    out["BaseColor"], out["BaseColorAlpha"], out["MetallicFactor"], out["RoughnessFactor"], out["AlphaCutoff"] = 1.0, 1.0, 1.0, 1.0, 0.5
+    out["transforms"][:, 0::2] = (0.0, 0.0, 1.0, 1.0)
+    out["transforms"][:, 1::2] = (1.0, 0.0, 0.0, 0.0)
+    if not (materials and gltf.get("textures") and gltf.get("images")):
+        return out
+
+    def number(array, index, default):
+        return array[index] if isinstance(array, list) and index < len(array) and isinstance(array[index], (int, float)) else default
+
+    def transform(info):
+        offset, scale, rotation = [0.0, 0.0], [1.0, 1.0], 0.0
+        if isinstance(info, dict):
+            source = (info.get("extensions") or {}).get("KHR_texture_transform") or info
+            offset = [number(source.get("offset"), k, offset[k]) for k in range(2)]
+            scale = [number(source.get("scale"), k, scale[k]) for k in range(2)]
+            rotation = source.get("rotation", rotation)
+        r = np.float32(rotation)
+        return (offset[0], offset[1], scale[0], scale[1]), (np.cos(r), np.sin(r), 0.0, 0.0)
+
+    for k, material in enumerate(materials):
+        m = out[k]
+        pbr = material.get("pbrMetallicRoughness")
+        pairs = [transform(None)] * 4
+        if isinstance(pbr, dict):
+            factor = pbr.get("baseColorFactor")
+            if isinstance(factor, list):
+                m["BaseColor"] = [number(factor, c, 1.0) for c in range(3)]
+                m["BaseColorAlpha"] = number(factor, 3, 1.0)
+            m["MetallicFactor"], m["RoughnessFactor"] = pbr.get("metallicFactor", 1.0), pbr.get("roughnessFactor", 1.0)
+            pairs[0], pairs[1] = transform(pbr.get("baseColorTexture")), transform(pbr.get("metallicRoughnessTexture"))
+        pairs[2], pairs[3] = transform(material.get("normalTexture")), transform(material.get("emissiveTexture"))
+        emissive = material.get("emissiveFactor")
+        if isinstance(emissive, list):
+            m["EmissiveFactor"] = [number(emissive, c, 0.0) for c in range(3)]
+        if material.get("alphaMode") == "MASK":
+            m["AlphaMode"], m["AlphaCutoff"] = 1, material.get("alphaCutoff", 0.5)
+        for t, (offset_scale, rotation) in enumerate(pairs):
+            m["transforms"][2 * t], m["transforms"][2 * t + 1] = offset_scale, rotation
+    return out

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/ur_scene.h"
+#include "scene_rule.h"
 
 namespace {
 
@@ -198,21 +199,11 @@ void walk(const JValue& nodes, int64_t index, const M4& parent, size_t mesh_coun
         for (const JValue& c : ch->arr) walk(nodes, (int64_t)c.num, world, mesh_count, out, depth + 1);
 }
 
-// Row-vector product used from here on (DirectXMath side): XMFLOAT4X4.m[r][c] = M[r*4+c] of the column-major array.
-struct RM { float m[4][4]; };
-RM rm_mul(const RM& A, const RM& B)
-{
-    RM R{};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) R.m[i][j] = ((A.m[i][0] * B.m[0][j] + A.m[i][1] * B.m[1][j]) + A.m[i][2] * B.m[2][j]) + A.m[i][3] * B.m[3][j];
-    return R;
-}
-void transform_coord(const RM& M, const float p[3], float out[3])
-{
-    float r[4];
-    for (int j = 0; j < 4; ++j) r[j] = ((p[0] * M.m[0][j] + p[1] * M.m[1][j]) + p[2] * M.m[2][j]) + M.m[3][j];
-    for (int j = 0; j < 3; ++j) out[j] = r[j] / r[3];
-}
+// Row-vector products from here on (DirectXMath side): XMFLOAT4X4.m[r][c] = M[r*4+c] of the column-major array. The products and the
+// divide are csrc/scene_rule.h's, the file the device build of the same rule (csrc/scene_build.hip) runs.
+using ur_scene::RM;
+using ur_scene::rm_mul;
+using ur_scene::transform_coord;
 RM rotation_roll_pitch_yaw(float pitch, float yaw, float roll) // XMMatrixRotationRollPitchYaw
 {
     const float cp = std::cos(pitch), sp = std::sin(pitch), cy = std::cos(yaw), sy = std::sin(yaw), cr = std::cos(roll), sr = std::sin(roll);
@@ -241,41 +232,21 @@ uint32_t pipeline_key(const JValue* materials, int material) // BuildPipelineKey
     return normal | (mr << 1) | (base << 2) | (emissive << 3) | (mask << 4);
 }
 
-} // namespace
+// One draw as the walk creates it: the model record of ur_scene_extract, its node record and its place in creation order
+struct Entry { ur_scene_model M; uint32_t node, creation; };
 
-extern "C" {
-
-int ur_scene_model_count(const char* scene_json)
-{
-    JValue root;
-    if (!parse_json(scene_json, root)) return -1;
-    const JValue* models = root.find("models");
-    return (models && models->type == JValue::Array) ? (int)models->arr.size() : 0;
-}
-
-int ur_scene_model_path(const char* scene_json, uint32_t index, char* buf, uint32_t cap)
-{
-    JValue root;
-    if (!parse_json(scene_json, root) || !buf || cap == 0) return -1;
-    const JValue* models = root.find("models");
-    const JValue* m = models ? models->at(index) : nullptr;
-    const JValue* path = m ? m->find("path") : nullptr;
-    if (!path || path->type != JValue::String) return -1;
-    std::snprintf(buf, cap, "%s", path->str.c_str());
-    return (int)path->str.size();
-}
-
-int ur_scene_extract(const char* scene_json, const char* const* gltf_json, uint32_t gltf_count, ur_scene_model* out, uint32_t capacity,
-                     ur_scene_summary* summary)
+// The walk ur_scene_extract and ur_scene_plan share: the draws in command order, the node records in creation order (when asked for)
+// and the scene box.
+int walk_scene(const char* scene_json, const char* const* gltf_json, uint32_t gltf_count, std::vector<Entry>& all, std::vector<ur_scene_node>* node_records, float smin[3],
+               float smax[3])
 {
     JValue scene;
     if (!parse_json(scene_json, scene)) return UR_SCENE_EJSON;
     const JValue* models = scene.find("models");
     if (!models || models->type != JValue::Array || models->arr.empty()) return UR_SCENE_EEMPTY;
     if (gltf_count != models->arr.size()) return UR_SCENE_EINVAL;
-
-    std::vector<ur_scene_model> all;
-    float smin[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f}, smax[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+    uint32_t node_total = 0u;
+    for (int a = 0; a < 3; ++a) { smin[a] = 3.402823466e38f; smax[a] = -3.402823466e38f; }
     for (size_t mi = 0; mi < models->arr.size(); ++mi) {
         const JValue& model = models->arr[mi];
         float position[3] = {0, 0, 0}, euler[3] = {0, 0, 0}, scale[3] = {1, 1, 1};
@@ -353,6 +324,16 @@ int ur_scene_extract(const char* scene_json, const char* const* gltf_json, uint3
             float center[3];
             transform_coord(World, B.center, center);
             const float radius = B.radius * max_scale * node_scale;
+            if (node_records) {
+                ur_scene_node record{};
+                for (int r = 0; r < 4; ++r)
+                    for (int c = 0; c < 4; ++c) record.node_world[r * 4 + c] = NW.m[r][c];
+                for (int a = 0; a < 3; ++a) { record.scale[a] = scale[a]; record.translate[a] = position[a]; }
+                record.max_scale = max_scale;
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) record.rotation[r * 3 + c] = R.m[r][c];
+                node_records->push_back(record);
+            }
             const size_t sections = std::max<size_t>(1, B.materials.size());
             for (size_t s = 0; s < sections; ++s) {
                 ur_scene_model M{};
@@ -362,15 +343,49 @@ int ur_scene_extract(const char* scene_json, const char* const* gltf_json, uint3
                 M.pipeline_key = pipeline_key(materials, s < B.materials.size() ? B.materials[s] : -1);
                 M.model_index = (uint32_t)mi; M.node_order = (uint32_t)ni; M.mesh_index = (uint32_t)nd.mesh; M.primitive_index = (uint32_t)s;
                 for (int a = 0; a < 3; ++a) { smin[a] = std::min(smin[a], center[a] - radius); smax[a] = std::max(smax[a], center[a] + radius); }
-                all.push_back(M);
+                all.push_back(Entry{M, node_total, (uint32_t)all.size()});
             }
+            ++node_total;
         }
     }
     if (all.empty()) return UR_SCENE_EEMPTY;
-    std::stable_sort(all.begin(), all.end(), [](const ur_scene_model& a, const ur_scene_model& b) {
-        if (a.pipeline_key != b.pipeline_key) return a.pipeline_key < b.pipeline_key;
-        return a.material_index < b.material_index;
+    std::stable_sort(all.begin(), all.end(), [](const Entry& a, const Entry& b) {
+        if (a.M.pipeline_key != b.M.pipeline_key) return a.M.pipeline_key < b.M.pipeline_key;
+        return a.M.material_index < b.M.material_index;
     });
+    return UR_SCENE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ur_scene_model_count(const char* scene_json)
+{
+    JValue root;
+    if (!parse_json(scene_json, root)) return -1;
+    const JValue* models = root.find("models");
+    return (models && models->type == JValue::Array) ? (int)models->arr.size() : 0;
+}
+
+int ur_scene_model_path(const char* scene_json, uint32_t index, char* buf, uint32_t cap)
+{
+    JValue root;
+    if (!parse_json(scene_json, root) || !buf || cap == 0) return -1;
+    const JValue* models = root.find("models");
+    const JValue* m = models ? models->at(index) : nullptr;
+    const JValue* path = m ? m->find("path") : nullptr;
+    if (!path || path->type != JValue::String) return -1;
+    std::snprintf(buf, cap, "%s", path->str.c_str());
+    return (int)path->str.size();
+}
+
+int ur_scene_extract(const char* scene_json, const char* const* gltf_json, uint32_t gltf_count, ur_scene_model* out, uint32_t capacity,
+                     ur_scene_summary* summary)
+{
+    std::vector<Entry> all;
+    float smin[3], smax[3];
+    if (const int rc = walk_scene(scene_json, gltf_json, gltf_count, all, nullptr, smin, smax)) return rc;
     if (summary) {
         summary->model_count = (uint32_t)all.size();
         float e2 = 0.0f;
@@ -379,7 +394,32 @@ int ur_scene_extract(const char* scene_json, const char* const* gltf_json, uint3
     }
     if (out) {
         if (capacity < all.size()) return UR_SCENE_ECAPACITY;
-        std::memcpy(out, all.data(), all.size() * sizeof(ur_scene_model));
+        for (size_t i = 0; i < all.size(); ++i) out[i] = all[i].M;
+    }
+    return UR_SCENE_OK;
+}
+
+int ur_scene_plan(const char* scene_json, const char* const* gltf_json, uint32_t gltf_count, const uint32_t* mesh_base, ur_scene_node* nodes,
+                  uint32_t node_capacity, uint32_t* node_count, ur_scene_plan_draw* draws, uint32_t draw_capacity, uint32_t* draw_count)
+{
+    if (!mesh_base || !node_count || !draw_count) return UR_SCENE_EINVAL;
+    std::vector<Entry> all;
+    std::vector<ur_scene_node> records;
+    float smin[3], smax[3];
+    if (const int rc = walk_scene(scene_json, gltf_json, gltf_count, all, &records, smin, smax)) return rc;
+    *node_count = (uint32_t)records.size();
+    *draw_count = (uint32_t)all.size();
+    if (nodes) {
+        if (node_capacity < records.size()) return UR_SCENE_ECAPACITY;
+        std::memcpy(nodes, records.data(), records.size() * sizeof(ur_scene_node));
+    }
+    if (draws) {
+        if (draw_capacity < all.size()) return UR_SCENE_ECAPACITY;
+        for (size_t i = 0; i < all.size(); ++i) {
+            const Entry& e = all[i];
+            draws[i] = ur_scene_plan_draw{e.node, mesh_base[e.M.model_index] + e.M.mesh_index, e.M.primitive_index, e.M.material_index, e.M.pipeline_key,
+                                          e.M.model_index, e.creation, e.creation + 1u};
+        }
     }
     return UR_SCENE_OK;
 }

@@ -319,3 +319,29 @@ def mesh_build(buffer, primitives):
     if rc != 0:
         raise ValueError(f"ur_host_mesh_build failed ({rc})")
     return vertices, indices, sections, info
+
+
+def scene_build(nodes, meshes, mesh_infos, materials, draws, frame, slot_count: int, constants_stride: int = 608, constants_address: int = 0, *,
+                transforms_only: bool = False, out=None, library=None):
+    """ur_host_scene_build: the scene rule on the host, serial, by the functions the kernels run (csrc/scene_rule.h). The
+    tables are numpy arrays of the records' bytes (any dtype); `frame` a lib.SceneConstants. Returns a dict of numpy arrays: bounds float32
+    [D, 2, 4], commands uint32 [D, 16], constants uint8 [slot_count, constants_stride], centers float32 [D, 4], summary uint8 [48] (a
+    lib.SceneBuildSummary) - the bytes HotPath.build_scene leaves on the device when its constants lie at constants_address. out: such a
+    dict to write into (what a build leaves alone keeps its bytes), else zeroed arrays."""
+    L = library if library is not None else _lib.load()
+    tables = [np.ascontiguousarray(t).view(np.uint8).reshape(-1) for t in (nodes, meshes, mesh_infos, materials, draws)]
+    counts = [t.size // C.sizeof(r) for t, r in zip(tables, (_lib.SceneNode, _lib.SceneMesh, _lib.MeshInfo, _lib.SceneMaterialFactors, _lib.SceneDraw))]
+    if counts[1] != counts[2]:
+        raise ValueError(f"{counts[1]} mesh records and {counts[2]} info records")
+    D = counts[4]
+    if out is None:
+        out = {"bounds": np.zeros((D, 2, 4), np.float32), "commands": np.zeros((D, 16), np.uint32), "constants": np.zeros((slot_count, constants_stride), np.uint8),
+               "centers": np.zeros((D, 4), np.float32), "summary": np.zeros(48, np.uint8)}
+    at = lambda a: a.ctypes.data  # noqa: E731
+    record = _lib.SceneBuildTables(at(tables[0]), at(tables[1]), at(tables[2]), at(tables[3]), at(tables[4]), counts[0], counts[1], counts[3], D)
+    outputs = _lib.SceneBuildOutputs(at(out["bounds"]), at(out["commands"]), at(out["constants"]), at(out["centers"]) if out.get("centers") is not None else None,
+                                     at(out["summary"]), constants_stride, slot_count)
+    rc = L.ur_host_scene_build(C.byref(record), C.byref(frame), C.byref(outputs), C.c_uint64(constants_address), C.c_uint32(1 if transforms_only else 0))
+    if rc != 0:
+        raise ValueError(f"ur_host_scene_build failed ({rc})")
+    return out

@@ -1033,6 +1033,82 @@ def mesh_draws(mesh, constants, constants_offset: int = 0, constants_stride: int
              "start_index": start, "index_count": count, "base_vertex": 0} for k, (_, start, count) in enumerate(mesh.sections)]
 
 
+def mesh_infos(meshes) -> torch.Tensor:
+    """The info records of built meshes, stacked on the device as int32 [len(meshes), 14]: ur_scene_build's mesh_infos table. A device copy
+    on the current stream; nothing is read back."""
+    return torch.stack([m.info for m in meshes]).contiguous()
+
+
+class SceneTables:
+    """The tables of ur_scene_build on the device (include/ur_scene_build.h): `nodes`, `meshes`, `mesh_infos`, `materials` and `draws` as
+    device tensors of the records' bytes (any dtype), the counts taken from their sizes; `slot_count` constants records of
+    `constants_stride` bytes. The caller keeps them and may patch them between builds (a node's transform, say)."""
+
+    def __init__(self, nodes, meshes, mesh_infos, materials, draws, slot_count=None, constants_stride=608, keep=None):
+        def device(t):
+            if not isinstance(t, torch.Tensor):
+                a = np.ascontiguousarray(t)
+                t = to_device(a.view(np.uint8).reshape(-1))
+            assert t.is_cuda and t.is_contiguous(), "device tensors must be contiguous CUDA/HIP tensors"
+            return t
+        self.nodes, self.meshes, self.mesh_infos, self.materials, self.draws = (device(t) for t in (nodes, meshes, mesh_infos, materials, draws))
+        size = lambda t, record: t.numel() * t.element_size() // C.sizeof(record)  # noqa: E731
+        self.node_count, self.mesh_count = size(self.nodes, _lib.SceneNode), size(self.meshes, _lib.SceneMesh)
+        self.material_count, self.draw_count = size(self.materials, _lib.SceneMaterialFactors), size(self.draws, _lib.SceneDraw)
+        if size(self.mesh_infos, _lib.MeshInfo) != self.mesh_count:
+            raise ValueError(f"{self.mesh_count} mesh records and {size(self.mesh_infos, _lib.MeshInfo)} info records")
+        self.slot_count = self.draw_count if slot_count is None else int(slot_count)
+        self.constants_stride = int(constants_stride)
+        self._keep = keep  # (what the mesh records point at)
+
+    def record(self) -> _lib.SceneBuildTables:
+        return _lib.SceneBuildTables(self.nodes.data_ptr(), self.meshes.data_ptr(), self.mesh_infos.data_ptr(), self.materials.data_ptr(), self.draws.data_ptr(),
+                                     self.node_count, self.mesh_count, self.material_count, self.draw_count)
+
+
+class BuiltScene:
+    """What ur_scene_build leaves on the device: `bounds` (float32 [D, 2, 4], Frame.resources' bounds and the cull's), `commands` (int32
+    [D, 16], what pack_draw_commands + to_device give), `constants` (uint8 [slots, stride]), `centers` (float32 [D, 4]: centre, radius) and
+    `summary` (int32 [12]: a lib.SceneBuildSummary, read with scene_summary once the stream is done)."""
+
+    def __init__(self, bounds, commands, constants, centers, summary, scratch):
+        self.bounds, self.commands, self.constants, self.centers, self.summary, self.scratch = bounds, commands, constants, centers, summary, scratch
+
+    def scene_summary(self) -> _lib.SceneBuildSummary:
+        """The lib.SceneBuildSummary record (synchronises: a device-to-host copy). hostmath.light_view_projection takes its scene_center and
+        scene_radius, once at load time, as the reference does."""
+        return _lib.SceneBuildSummary.from_buffer_copy(self.summary.cpu().numpy().tobytes())
+
+
+def _build_scene(self, tables: SceneTables, frame, *, transforms_only: bool = False, out: "BuiltScene | None" = None) -> BuiltScene:
+    """ur_scene_build: the tables and the constants template `frame` (a lib.SceneConstants: view, projection, light and shadow fields as
+    hostmath fills them) become a BuiltScene: bounds, commands, one constants record per draw, centres and the scene summary, on the
+    device. Asynchronous on the context's stream; nothing is read back. out: the BuiltScene to write into (a moving scene's per-frame call),
+    else one is allocated. transforms_only: only bounds, centres, World of each draw's record and the summary are rewritten (needs out)."""
+    D = tables.draw_count
+    if transforms_only and out is None:
+        raise ValueError("build_scene: transforms_only rewrites an earlier build: pass it as out")
+    if out is None:
+        dev = tables.draws.device
+        need = int(self._L.ur_scene_build_scratch_bytes(D))
+        if need == 0:
+            raise ValueError(f"build_scene: {D} draws (1 .. 2^24 - 1)")
+        out = BuiltScene(torch.empty((D, 2, 4), dtype=torch.float32, device=dev), torch.empty((D, 16), dtype=torch.int32, device=dev),
+                         torch.zeros((tables.slot_count, tables.constants_stride), dtype=torch.uint8, device=dev),
+                         torch.empty((D, 4), dtype=torch.float32, device=dev), torch.empty(12, dtype=torch.int32, device=dev),
+                         torch.empty(need, dtype=torch.uint8, device=dev))
+    assert out.constants.numel() * out.constants.element_size() >= tables.slot_count * tables.constants_stride and out.bounds.numel() * out.bounds.element_size() >= 32 * D
+    assert out.commands.numel() * out.commands.element_size() >= 64 * D and (out.centers is None or out.centers.numel() * out.centers.element_size() >= 16 * D)
+    outputs = _lib.SceneBuildOutputs(out.bounds.data_ptr(), out.commands.data_ptr(), out.constants.data_ptr(), out.centers.data_ptr() if out.centers is not None else None,
+                                     out.summary.data_ptr(), tables.constants_stride, tables.slot_count)
+    record = tables.record()
+    _lib.check(self._L.ur_scene_build(self._ctx, C.byref(record), C.byref(frame), C.byref(outputs), out.scratch.data_ptr(), out.scratch.numel(),
+                                      _lib.UR_SCENE_BUILD_TRANSFORMS_ONLY if transforms_only else 0), "ur_scene_build")
+    out._keep = tables  # (the launches are still in flight, and the commands point into the meshes)
+    return out
+
+
+HotPath.build_scene = _build_scene
 HotPath.build_mesh = _build_mesh
 HotPath.transcode_texture = _transcode_texture
 HotPath.gbuffer_pass = _gbuffer_pass

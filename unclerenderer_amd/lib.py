@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_host.h).
+"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_host.h).
 
 The shared library is the product; there is no Python or CPU fallback. If it is missing, importing the compute
 entry points raises — build it with `python -m unclerenderer_amd.build` (hipcc, gfx950).
@@ -197,6 +197,52 @@ UR_MESH_INDEX_U8, UR_MESH_INDEX_U16, UR_MESH_INDEX_U32 = 5121, 5123, 5125
 UR_MESH_BUILD_MAX_STREAM_OPS = 14
 
 
+class SceneNode(C.Structure):
+    """ur_scene_node (include/ur_scene_build.h), 144 bytes."""
+    _fields_ = [("node_world", C.c_float * 16), ("scale", C.c_float * 3), ("max_scale", C.c_float), ("rotation", C.c_float * 9), ("translate", C.c_float * 3),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class SceneMesh(C.Structure):
+    """ur_scene_mesh (include/ur_scene_build.h), 32 bytes."""
+    _fields_ = [("vertices", C.c_uint64), ("indices", C.c_uint64), ("vertex_bytes", C.c_uint32), ("index_bytes", C.c_uint32), ("stride", C.c_uint32),
+                ("index_format", C.c_uint32)]
+
+
+class SceneMaterialFactors(C.Structure):
+    """ur_scene_material_factors (include/ur_scene_build.h), 176 bytes."""
+    _fields_ = [("BaseColor", C.c_float * 3), ("BaseColorAlpha", C.c_float), ("EmissiveFactor", C.c_float * 3), ("MetallicFactor", C.c_float),
+                ("RoughnessFactor", C.c_float), ("AlphaCutoff", C.c_float), ("AlphaMode", C.c_uint32), ("Padding", C.c_uint32), ("transforms", (C.c_float * 4) * 8)]
+
+
+class SceneDraw(C.Structure):
+    """ur_scene_draw (include/ur_scene_build.h), 32 bytes."""
+    _fields_ = [(n, C.c_uint32) for n in ("node", "mesh", "material", "constants_slot", "object_id", "index_start", "index_count", "reserved")]
+
+
+class SceneBuildSummary(C.Structure):
+    """ur_scene_build_summary (include/ur_scene_build.h), 48 bytes."""
+    _fields_ = [("scene_min", C.c_float * 3), ("scene_max", C.c_float * 3), ("scene_center", C.c_float * 3), ("scene_radius", C.c_float),
+                ("draw_count", C.c_uint32), ("skipped_draws", C.c_uint32)]
+
+
+class SceneBuildTables(C.Structure):
+    """ur_scene_build_tables (include/ur_scene_build.h): the addresses and counts of the five tables."""
+    _fields_ = [("nodes", C.c_void_p), ("meshes", C.c_void_p), ("mesh_infos", C.c_void_p), ("materials", C.c_void_p), ("draws", C.c_void_p),
+                ("node_count", C.c_uint32), ("mesh_count", C.c_uint32), ("material_count", C.c_uint32), ("draw_count", C.c_uint32)]
+
+
+class SceneBuildOutputs(C.Structure):
+    """ur_scene_build_outputs (include/ur_scene_build.h): the addresses of the five outputs, the constants stride and the slot count."""
+    _fields_ = [("bounds", C.c_void_p), ("commands", C.c_void_p), ("constants", C.c_void_p), ("centers", C.c_void_p), ("summary", C.c_void_p),
+                ("constants_stride", C.c_uint32), ("slot_count", C.c_uint32)]
+
+
+UR_SCENE_BUILD_MAX_STREAM_OPS = 3
+UR_SCENE_BUILD_TRANSFORMS_ONLY = 0x1
+UR_SCENE_BUILD_MAX_DRAWS = 1 << 24
+
+
 class DdsInfo(C.Structure):
     """ur_dds_info (include/ur_assets.h)."""
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "mip_count", "slices", "is_cube", "dxgi_format", "header_size", "block_dim", "bytes_per_block")]
@@ -211,6 +257,11 @@ class SceneModel(C.Structure):
 
 class SceneSummary(C.Structure):
     _fields_ = [("model_count", C.c_uint32), ("scene_center", C.c_float * 3), ("scene_radius", C.c_float)]
+
+
+class ScenePlanDraw(C.Structure):
+    """ur_scene_plan_draw (include/ur_scene.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("node", "mesh", "primitive", "material_index", "pipeline_key", "model_index", "constants_slot", "object_id")]
 
 
 class TonemapConstants(C.Structure):
@@ -394,6 +445,9 @@ SIGNATURES = {
     # ur_mesh.h
     "ur_mesh_layout_of": (C.c_int, [C.POINTER(MeshPrimitive), _U32, C.c_uint64, C.POINTER(MeshLayout), C.POINTER(MeshSection)]),
     "ur_mesh_build": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(MeshPrimitive), _U32, _VP, _VP, _VP, C.c_uint64, _VP]),
+    # ur_scene_build.h
+    "ur_scene_build_scratch_bytes": (C.c_uint64, [_U32]),
+    "ur_scene_build": (C.c_int, [_VP, C.POINTER(SceneBuildTables), C.POINTER(SceneConstants), C.POINTER(SceneBuildOutputs), _VP, C.c_uint64, _U32]),
     # ur_assets.h
     "ur_dds_parse":(C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
@@ -407,6 +461,8 @@ SIGNATURES = {
     "ur_scene_model_count": (C.c_int, [C.c_char_p]),
     "ur_scene_model_path": (C.c_int, [C.c_char_p, _U32, C.c_char_p, _U32]),
     "ur_scene_extract": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _U32, C.POINTER(SceneModel), _U32, C.POINTER(SceneSummary)]),
+    "ur_scene_plan": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _U32, C.POINTER(_U32), C.POINTER(SceneNode), _U32, C.POINTER(_U32),
+                                C.POINTER(ScenePlanDraw), _U32, C.POINTER(_U32)]),
     # ur_frame.h
     "ur_frame_create": (_VP, [_VP, _VP, _U32, C.c_int, C.c_int]),
     "ur_frame_destroy": (None, [_VP]),
@@ -456,6 +512,7 @@ SIGNATURES = {
     "ur_host_texture_chain_bytes": (C.c_uint64, [_U32, _U32, _U32, _U32]),
     "ur_host_texture_decode_level": (C.c_int, [_U32, _VP, _U32, _U32, _VP]),
     "ur_host_mesh_build": (C.c_int, [_VP, C.c_uint64, C.POINTER(MeshPrimitive), _U32, _VP, _VP, C.POINTER(MeshSection), C.POINTER(MeshInfo)]),
+    "ur_host_scene_build": (C.c_int, [C.POINTER(SceneBuildTables), C.POINTER(SceneConstants), C.POINTER(SceneBuildOutputs), C.c_uint64, _U32]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),

@@ -59,6 +59,87 @@ def load_scene_bounds(scene_json_path, assets_root=None) -> SceneBounds:
                        np.array(list(summary.scene_center), np.float32), float(summary.scene_radius))
 
 
+def _scene_texts(scene_json_path, assets_root):
+    """(the scene JSON's bytes, the models' .gltf paths) of a scene file."""
+    scene_json_path = Path(scene_json_path)
+    assets_root = Path(assets_root) if assets_root is not None else scene_json_path.parent.parent  # RendererUtils.cpp:326-329
+    L = _lib.load()
+    text = scene_json_path.read_bytes()
+    n = L.ur_scene_model_count(text)
+    if n <= 0:
+        raise ValueError(f"{scene_json_path}: no models")
+    paths = []
+    buf = C.create_string_buffer(1024)
+    for i in range(n):
+        if L.ur_scene_model_path(text, i, buf, 1024) < 0:
+            raise ValueError(f"model {i} has no path")
+        paths.append(assets_root / buf.value.decode())
+    return text, paths
+
+
+def plan_scene(scene_text: bytes, gltf_texts, mesh_base):
+    """ur_scene_plan: (node records, draws) of a scene as structured arrays of lib.SceneNode and lib.ScenePlanDraw, the draws in
+    ur_scene_extract's command order. mesh_base: per model, the number of meshes of the models in front."""
+    L = _lib.load()
+    n = len(gltf_texts)
+    arr = (C.c_char_p * n)(*gltf_texts)
+    base = (C.c_uint32 * n)(*[int(b) for b in mesh_base])
+    node_count, draw_count = C.c_uint32(0), C.c_uint32(0)
+    rc = L.ur_scene_plan(scene_text, arr, n, base, None, 0, C.byref(node_count), None, 0, C.byref(draw_count))
+    if rc != 0:
+        raise ValueError(f"ur_scene_plan failed ({rc})")
+    nodes, draws = (_lib.SceneNode * node_count.value)(), (_lib.ScenePlanDraw * draw_count.value)()
+    rc = L.ur_scene_plan(scene_text, arr, n, base, nodes, node_count.value, C.byref(node_count), draws, draw_count.value, C.byref(draw_count))
+    if rc != 0:
+        raise ValueError(f"ur_scene_plan failed ({rc})")
+    return np.frombuffer(nodes, np.dtype(_lib.SceneNode)).copy(), np.frombuffer(draws, np.dtype(_lib.ScenePlanDraw)).copy()
+
+
+def scene_draw_table(plan_draws, sections, material_base, material_counts) -> np.ndarray:
+    """The lib.SceneDraw records of a plan: a draw's section (index_start, index_count) is sections[mesh][primitive] (Mesh.sections of the
+    mesh among all models' meshes); its material record is material_base[model] + the glTF material index, or the model's default
+    record (the last of its material_counts[model]) when the primitive names none or one out of range."""
+    out = np.zeros(len(plan_draws), np.dtype(_lib.SceneDraw))
+    for d, p in zip(out, plan_draws):
+        model, material = int(p["model_index"]), int(p["material_index"])
+        default = material_counts[model] - 1
+        _, start, count = sections[int(p["mesh"])][int(p["primitive"])]
+        d["node"], d["mesh"], d["constants_slot"], d["object_id"] = p["node"], p["mesh"], p["constants_slot"], p["object_id"]
+        d["material"] = material_base[model] + (material if material < default else default)
+        d["index_start"], d["index_count"] = start, count
+    return out
+
+
+def load_scene_tables(scene_json_path, assets_root=None, meshes=None, constants_stride: int = 608):
+    """The four host tables of ur_scene_build composed from a scene file, and the mesh infos stacked on the device, as a
+    hotpath.SceneTables ready for HotPath.build_scene. meshes: per model the hotpath.Mesh objects assets.load_gltf_meshes built from its
+    file (device memory the commands will point into; kept alive by the result). The result also carries `plan` (the lib.ScenePlanDraw
+    records: pipeline keys, glTF material indices, model indices, in command order) and `pipeline_keys`."""
+    import json
+
+    from . import assets, hotpath
+    text, paths = _scene_texts(scene_json_path, assets_root)
+    if meshes is None or len(meshes) != len(paths):
+        raise ValueError(f"load_scene_tables: {len(paths)} models need their built meshes (assets.load_gltf_meshes per model)")
+    gltf_texts = [p.read_bytes() for p in paths]
+    mesh_base = np.concatenate([[0], np.cumsum([len(m) for m in meshes])]).astype(np.int64)
+    nodes, plan = plan_scene(text, gltf_texts, mesh_base[:-1])
+    factors = [assets.gltf_material_factors(json.loads(t)) for t in gltf_texts]
+    material_counts = [len(f) for f in factors]
+    material_base = np.concatenate([[0], np.cumsum(material_counts)])
+    flat = [mesh for model in meshes for mesh in model]
+    mesh_table = np.zeros(len(flat), np.dtype(_lib.SceneMesh))
+    for record, mesh in zip(mesh_table, flat):
+        record["vertices"], record["indices"] = mesh.vertices.data_ptr(), mesh.indices.data_ptr()
+        record["vertex_bytes"], record["index_bytes"] = mesh.vertices.numel() * mesh.vertices.element_size(), mesh.indices.numel() * mesh.indices.element_size()
+        record["stride"], record["index_format"] = 64, _lib.UR_RASTER_INDEX_FORMAT_R32_UINT
+    draws = scene_draw_table(plan, [mesh.sections for mesh in flat], material_base, material_counts)
+    tables = hotpath.SceneTables(nodes, mesh_table, hotpath.mesh_infos(flat), np.concatenate(factors), draws, slot_count=len(draws),
+                                 constants_stride=constants_stride, keep=flat)
+    tables.plan, tables.pipeline_keys = plan, plan["pipeline_key"].copy()
+    return tables
+
+
 def draw_offsets(keys) -> np.ndarray:
     """Draw-range offsets (ur_draw_ranges.offsets) over commands in command order: a new range starts wherever the key changes.
     uint32[R + 1] with offsets[0] = 0 and offsets[R] = len(keys). The reference's FIndirectDrawRanges break on every texture-handle
