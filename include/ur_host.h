@@ -8,6 +8,7 @@
 
 #include <stdint.h>
 
+#include "ur_env_cube.h"
 #include "ur_hotpath.h"
 #include "ur_mesh.h"
 #include "ur_scene_build.h"
@@ -108,6 +109,15 @@ int ur_host_mesh_build(const void* buffer, uint64_t buffer_size, const ur_mesh_p
  * draw_count == 0 or >= 2^24, an empty table, slot_count == 0, a stride below 608 or no multiple of 16, unknown flag bits. */
 int ur_host_scene_build(const ur_scene_build_tables* tables, const ur_scene_constants* frame, const ur_scene_build_outputs* outputs,
                         uint64_t constants_address, uint32_t flags);
+
+/* ur_env_cube_build (include/ur_env_cube.h) on the host, serial: the CPU fallback and the byte reference. It decodes with
+ * csrc/bc6h_decode.h, the very functions the kernels decode with, and stages with the function ur_stage_env_cube runs; it gives the device
+ * build's bytes, and in *reserved_blocks (or NULL) the device build's info word. All pointers are host memory; no GPU is needed. The same
+ * refusals as ur_env_cube_build but for the context: UR_EINVAL for a null source or destination, an unknown format, a cube
+ * ur_env_cube_texels refuses or a base size above UR_ENV_CUBE_MAX_BASE_SIZE, src_bytes or dst_texels that are not the cube's, a source or
+ * destination that is not 16-byte aligned, and source, destination and reserved_blocks overlapping. */
+int ur_host_env_cube_build(const void* src_host, size_t src_bytes, uint32_t format, uint32_t base_size, uint32_t mip_count, ur_half4* dst_host,
+                           size_t dst_texels, uint32_t* reserved_blocks);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

@@ -1,4 +1,5 @@
-"""Asset loading. IBL: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables. Material textures: DDS
+"""Asset loading. IBL: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables; or the cube's payload as it
+lies (load_env_cube_dds_source) -> what HotPath.build_env_cube decodes and stages on the device. Material textures: DDS
 (RGBA8, BC1, BC3, BC5) -> what hotpath.pack_texture / pack_texture_bc take; BC blocks stay compressed, the sampler decodes them.
 BC2, BC4 and BC7 too (load_texture_dds_source) -> what HotPath.transcode_texture takes: decoded to RGBA8 once, on the device.
 All parsing and decoding happens in libur_hotpath.so (csrc/dds.cpp); this module only reads the file and marshals."""
@@ -33,6 +34,22 @@ def load_env_cube_dds(path) -> tuple[np.ndarray, int, int, int]:
     if rc != 0:
         raise ValueError(f"ur_dds_decode_rgba16f failed ({rc})")
     return out, int(info.width), int(info.mip_count), int(bad.value)
+
+
+def load_env_cube_dds_source(path_or_bytes) -> tuple[np.ndarray, int, int, int]:
+    """The source of HotPath.build_env_cube from a DDS file (a path, or the file's bytes): the payload behind the header as a uint8 array -
+    BC6H blocks or RGBA16F texels, six faces, face-major with mips inner - with (format, base size, mip count): lib.UR_ENV_SOURCE_*.
+    Nothing is decoded here. ValueError for what load_env_cube_dds refuses (no cube, an array of cubes, faces that are not square) and for
+    a cube of any other format."""
+    data = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else Path(path_or_bytes).read_bytes()
+    info = parse_dds(data)
+    if not info.is_cube or info.slices != 6 or info.width != info.height:
+        raise ValueError("not a single cube map")
+    fmt, base, mips = int(info.dxgi_format), int(info.width), int(info.mip_count)
+    size = int(_lib.load().ur_env_cube_source_bytes(fmt, base, mips))
+    if size == 0:
+        raise ValueError(f"a cube of format {fmt} with {mips} mips is no source of the environment cube build (10, 95, 96; up to 16 mips)")
+    return np.frombuffer(data, np.uint8, size, int(info.header_size)).copy(), fmt, base, mips
 
 
 def load_brdf_lut_dds(path) -> np.ndarray:

@@ -345,3 +345,29 @@ def scene_build(nodes, meshes, mesh_infos, materials, draws, frame, slot_count: 
     if rc != 0:
         raise ValueError(f"ur_host_scene_build failed ({rc})")
     return out
+
+
+def _aligned16(nbytes: int) -> np.ndarray:
+    """nbytes uint8 at a 16-byte aligned address (a view into a larger array)."""
+    raw = np.zeros(nbytes + 16, np.uint8)
+    start = (-raw.ctypes.data) % 16
+    return raw[start:start + nbytes]
+
+
+def env_cube_build(payload, format: int, base: int, mips: int, *, library=None):
+    """ur_host_env_cube_build: the environment cube build on the host, serial, by the decoder the kernels run
+    (csrc/bc6h_decode.h) and the staging ur_stage_env_cube runs. payload: the DDS cube's payload (bytes or a uint8 array;
+    assets.load_env_cube_dds_source). Returns (the staged cube as uint16 [texels, 4] - the bytes HotPath.build_env_cube leaves on the
+    device - and the number of reserved-mode blocks)."""
+    L = library if library is not None else _lib.load()
+    data = np.frombuffer(bytes(payload), np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, np.uint8).reshape(-1)
+    texels = int(_lib.load().ur_env_cube_texels(int(base), int(mips)))
+    src = _aligned16(data.size)
+    src[:] = data
+    dst = _aligned16(8 * texels)
+    bad = C.c_uint32(0)
+    rc = L.ur_host_env_cube_build(C.c_void_p(src.ctypes.data), C.c_size_t(data.size), C.c_uint32(int(format)), C.c_uint32(int(base)), C.c_uint32(int(mips)),
+                                  C.c_void_p(dst.ctypes.data), C.c_size_t(texels), C.byref(bad))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_cube_build failed ({rc}): format {format}, base size {base}, {mips} mips, {data.size} payload bytes")
+    return dst.view(np.uint16).reshape(texels, 4), int(bad.value)

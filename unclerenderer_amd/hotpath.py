@@ -1108,6 +1108,33 @@ def _build_scene(self, tables: SceneTables, frame, *, transforms_only: bool = Fa
     return out
 
 
+def _build_env_cube(self, payload, format: int, base: int, mips: int, info=None, *, out=None) -> torch.Tensor:
+    """ur_env_cube_build: a DDS cube's payload (assets.load_env_cube_dds_source: a uint8 device tensor that holds it, or a uint8 array or
+    bytes, uploaded here) is decoded and staged on the device - what stage_env_cube gives for the same cube, to the byte. `format` is
+    lib.UR_ENV_SOURCE_*. info: an int32 device tensor whose first word receives the number of reserved-mode BC6H blocks, or None. out: a
+    device tensor of ur_env_cube_texels(base, mips) * 8 bytes to build into (an environment that changes while frames run), else one is
+    allocated. Returns the staged cube, ready for make_tables. Three launches on the context's stream; nothing is synchronised or read back."""
+    need = int(self._L.ur_env_cube_source_bytes(int(format), int(base), int(mips)))
+    texels = int(self._L.ur_env_cube_texels(int(base), int(mips)))
+    if need == 0 or texels == 0:
+        raise ValueError(f"no cube source: format {format}, base size {base}, {mips} mips (10, 95, 96; mips 1..16)")
+    src = payload
+    if not isinstance(src, torch.Tensor):
+        src = np.frombuffer(bytes(src), np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src, np.uint8).reshape(-1)
+    have = src.numel() * src.element_size() if isinstance(src, torch.Tensor) else src.size
+    if have != need:  # (refused before any upload)
+        raise ValueError(f"a cube of base size {base} with {mips} mips in format {format} is {need} bytes, the payload has {have}")
+    if not isinstance(src, torch.Tensor):
+        src = to_device(src.copy(), self.device)
+    dst = out if out is not None else torch.empty((texels, 4), dtype=torch.int16, device=src.device)
+    if dst.numel() * dst.element_size() != 8 * texels:
+        raise ValueError(f"a staged cube of base size {base} with {mips} mips is {8 * texels} bytes, out has {dst.numel() * dst.element_size()}")
+    _lib.check(self._L.ur_env_cube_build(self._ctx, _ptr(src), need, int(format), int(base), int(mips), _ptr(dst), texels, _ptr(info)), "ur_env_cube_build")
+    dst._keep = (src, info)  # (the launches are still in flight)
+    return dst
+
+
+HotPath.build_env_cube = _build_env_cube
 HotPath.build_scene = _build_scene
 HotPath.build_mesh = _build_mesh
 HotPath.transcode_texture = _transcode_texture
