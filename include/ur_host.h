@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "ur_env_cube.h"
+#include "ur_env_prefilter.h"
 #include "ur_hotpath.h"
 #include "ur_mesh.h"
 #include "ur_scene_build.h"
@@ -118,6 +119,21 @@ int ur_host_scene_build(const ur_scene_build_tables* tables, const ur_scene_cons
  * destination that is not 16-byte aligned, and source, destination and reserved_blocks overlapping. */
 int ur_host_env_cube_build(const void* src_host, size_t src_bytes, uint32_t format, uint32_t base_size, uint32_t mip_count, ur_half4* dst_host,
                            size_t dst_texels, uint32_t* reserved_blocks);
+
+/* The sample table of the environment prefilter (include/ur_env_prefilter.h): for every level k = 1 .. L - 1 of a cube of
+ * edge base_size, alpha = (k / (L - 1))^2, the sample_count Hammersley points' GGX half vectors give (with V = N) the tangent-space light
+ * vector l = (2 hz hx, 2 hz hy, 2 hz^2 - 1) and the source level clamp(0.5 log2(Omega_s / Omega_p), 0, L - 1) with
+ * Omega_s = 4 / (sample_count D(hz)), Omega_p = 4 pi / (6 base_size^2), all in double, each
+ * rounded to fp32; samples with l.z <= 0 are dropped (sixteen zero bytes). L headers of 16 bytes come first: {fp32 1 / sum of the kept
+ * l.z, uint32 samples kept, 0, 0}, level 0's {1, 0, 0, 0}; then 16 bytes a sample a level. The device reads these very bytes. Writes
+ * ur_env_prefilter_table_bytes(base_size, sample_count) bytes; UR_EINVAL for a null out, numbers that function refuses or fewer out_bytes. */
+int ur_host_env_prefilter_table(uint32_t base_size, uint32_t sample_count, void* out, size_t out_bytes);
+
+/* ur_env_prefilter (include/ur_env_prefilter.h) on the host, serial: the CPU fallback and the byte reference, over csrc/env_prefilter_rule.h,
+ * the very functions the kernels run - the pyramid, its bordered faces and the sums in the device's order. It allocates its own scratch.
+ * All pointers are host memory; no GPU is needed. The same refusals as ur_env_prefilter but for the context and the scratch. */
+int ur_host_env_prefilter(const void* src_host, size_t src_bytes, uint32_t base_size, uint32_t sample_count, const void* table_host, size_t table_bytes,
+                          void* dst_host, size_t dst_bytes);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

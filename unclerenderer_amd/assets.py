@@ -36,6 +36,14 @@ def load_env_cube_dds(path) -> tuple[np.ndarray, int, int, int]:
     return out, int(info.width), int(info.mip_count), int(bad.value)
 
 
+def load_env_cube_top_level(path) -> tuple[np.ndarray, int]:
+    """Level 0 of any cube DDS load_env_cube_dds reads, as six RGBA16F faces: (texels uint16 [6, base, base, 4], base size) - the source
+    of HotPath.prefilter_env_cube and hostmath.env_prefilter when base is a power of two."""
+    texels, base, mips, _ = load_env_cube_dds(path)
+    per_face = sum(max(1, base >> m) ** 2 for m in range(mips))
+    return np.ascontiguousarray(texels.reshape(6, per_face, 4)[:, :base * base]).reshape(6, base, base, 4), base
+
+
 def load_env_cube_dds_source(path_or_bytes) -> tuple[np.ndarray, int, int, int]:
     """The source of HotPath.build_env_cube from a DDS file (a path, or the file's bytes): the payload behind the header as a uint8 array -
     BC6H blocks or RGBA16F texels, six faces, face-major with mips inner - with (format, base size, mip count): lib.UR_ENV_SOURCE_*.

@@ -60,6 +60,16 @@ __global__ __launch_bounds__(kThreads) void env_cube_pairs_kernel(ur_envc::Plan 
 uint32_t groups(uint32_t items) { return (items + kThreads - 1u) / kThreads; }
 
 } // namespace
+
+// The decode and border launches over an RGBA16F payload, no info word: the bordered section alone (the environment prefilter stages
+// its source pyramid with them, csrc/env_prefilter.hip). The caller has checked the arguments and looks at hipGetLastError.
+void launch_env_cube_bordered(hipStream_t stream, const ur_envc::Plan& p, const void* src, uint64_t* dst)
+{
+    const dim3 threads(kThreads);
+    hipLaunchKernelGGL(env_cube_decode_kernel<ur_envc::kRGBA16F>, dim3(groups(6u * p.decode_face)), threads, 0, stream, p, src, dst, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(env_cube_border_kernel, dim3(groups(6u * p.border_face)), threads, 0, stream, p, src, dst, (uint32_t*)nullptr);
+}
+
 } // namespace ur
 
 extern "C" int ur_env_cube_build(ur_ctx* ctx, const void* src_device, size_t src_bytes, uint32_t format, uint32_t base_size, uint32_t mip_count,

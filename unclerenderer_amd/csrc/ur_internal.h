@@ -11,6 +11,8 @@
 
 #include "hzb_plan.h" // ur::kTailMaxLevels, ur::kTailTexels
 
+namespace ur_envc { struct Plan; } // csrc/env_cube_rule.h
+
 namespace ur {
 // Arguments of the single-workgroup tail of the HZB chain (csrc/hzb_tail.h): the levels from `first_mip` on.
 constexpr uint32_t kClaimWords = 32, kClaimWordStride = 32; // (stride in uint32: 128 bytes)
@@ -163,6 +165,8 @@ int launch_debug_print_text(ur_ctx* ctx, void* buffer, uint32_t x, uint32_t y, u
 int launch_debug_print_draw(ur_ctx* ctx, const ur_debug_print_constants* constants, const ur_debug_glyph* glyphs, uint32_t glyph_count,
                             const uint8_t* atlas_r8, uint32_t atlas_w, uint32_t atlas_h, const void* buffer, uint32_t* ldr_inout, uint32_t w,
                             uint32_t row0, uint32_t rows);
+// (env_cube_build.hip) the bordered section of the staged cube from an RGBA16F payload: ur_env_cube_build's decode and border launches
+void launch_env_cube_bordered(hipStream_t stream, const ur_envc::Plan& p, const void* src, uint64_t* dst);
 // the next {entry, exit} pair of the debug timeline (nullptr when it is off)
 inline unsigned long long* next_timeline_pair(ur_ctx* ctx)
 {

@@ -371,3 +371,41 @@ def env_cube_build(payload, format: int, base: int, mips: int, *, library=None):
     if rc != 0:
         raise ValueError(f"ur_host_env_cube_build failed ({rc}): format {format}, base size {base}, {mips} mips, {data.size} payload bytes")
     return dst.view(np.uint16).reshape(texels, 4), int(bad.value)
+
+
+def env_prefilter_table(base: int, sample_count: int, *, library=None) -> np.ndarray:
+    """ur_host_env_prefilter_table: the sample table of the environment prefilter for a cube of edge `base` and
+    `sample_count` samples a texel, as uint8 at a 16-byte aligned address - the bytes HotPath.prefilter_env_cube uploads. ValueError for a
+    base that is no power of two up to 2048 or a sample count that is no power of two in 16..4096."""
+    L = library if library is not None else _lib.load()
+    need = int(_lib.load().ur_env_prefilter_table_bytes(int(base), int(sample_count)))
+    if need == 0:
+        raise ValueError(f"no prefilter table: base size {base}, {sample_count} samples (powers of two, 1..2048 and 16..4096)")
+    out = _aligned16(need)
+    rc = L.ur_host_env_prefilter_table(C.c_uint32(int(base)), C.c_uint32(int(sample_count)), C.c_void_p(out.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_prefilter_table failed ({rc})")
+    return out
+
+
+def env_prefilter(src, base: int, sample_count: int = 1024, *, table=None, library=None) -> np.ndarray:
+    """ur_host_env_prefilter: the environment prefilter on the host, serial, by the functions the kernels run
+    (csrc/env_prefilter_rule.h). src: the cube's top level, six RGBA16F faces (6 * base * base * 8 bytes, any dtype or bytes;
+    assets.load_env_cube_top_level). Returns the prefiltered chain as uint16 [texels, 4] in DDS order - the bytes
+    HotPath.prefilter_env_cube leaves on the device, the UR_ENV_SOURCE_RGBA16F payload of env_cube_build with log2(base) + 1 mips."""
+    L = library if library is not None else _lib.load()
+    data = np.frombuffer(bytes(src), np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+    if table is None:
+        table = env_prefilter_table(base, sample_count, library=library)
+    mips = int(base).bit_length()
+    need = int(_lib.load().ur_env_cube_source_bytes(_lib.UR_ENV_SOURCE_RGBA16F, int(base), mips))
+    source = _aligned16(data.size)
+    source[:] = data
+    tab = _aligned16(table.size)
+    tab[:] = np.ascontiguousarray(table).view(np.uint8).reshape(-1)
+    dst = _aligned16(need)
+    rc = L.ur_host_env_prefilter(C.c_void_p(source.ctypes.data), C.c_size_t(data.size), C.c_uint32(int(base)), C.c_uint32(int(sample_count)),
+                                 C.c_void_p(tab.ctypes.data), C.c_size_t(tab.size), C.c_void_p(dst.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_prefilter failed ({rc}): base size {base}, {sample_count} samples, {data.size} source bytes, {tab.size} table bytes")
+    return dst.view(np.uint16).reshape(-1, 4)

@@ -1135,6 +1135,46 @@ def _build_env_cube(self, payload, format: int, base: int, mips: int, info=None,
 
 
 HotPath.build_env_cube = _build_env_cube
+def _prefilter_env_cube(self, src, base_size: int, sample_count: int = 1024, *, table=None, out=None, scratch=None) -> torch.Tensor:
+    """ur_env_prefilter: the top level of an HDR cube (six RGBA16F faces of a power-of-two edge: a device tensor of 6 * base_size^2 * 8
+    bytes, or an array or bytes, uploaded here; assets.load_env_cube_top_level) becomes the prefiltered chain of log2(base_size) + 1 levels
+    on the device. Returns the payload, a device tensor in DDS order: what build_env_cube takes as
+    lib.UR_ENV_SOURCE_RGBA16F. table: hostmath.env_prefilter_table(base_size, sample_count) on the device (made and uploaded here when
+    None); out, scratch: device tensors to write into, else allocated. Nothing is synchronised or read back."""
+    base, samples = int(base_size), int(sample_count)
+    table_bytes = int(self._L.ur_env_prefilter_table_bytes(base, samples))
+    if table_bytes == 0:
+        raise ValueError(f"no prefilter: base size {base}, {samples} samples (powers of two, 1..2048 and 16..4096)")
+    need, mips = 48 * base * base, base.bit_length()
+    dst_bytes, scratch_bytes = int(self._L.ur_env_cube_source_bytes(_lib.UR_ENV_SOURCE_RGBA16F, base, mips)), int(self._L.ur_env_prefilter_scratch_bytes(base))
+    if not isinstance(src, torch.Tensor):
+        src = np.frombuffer(bytes(src), np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+    have = src.numel() * src.element_size() if isinstance(src, torch.Tensor) else src.size
+    if have != need:  # (refused before any upload)
+        raise ValueError(f"the top level of a cube of base size {base} is {need} bytes, the source has {have}")
+    if not isinstance(src, torch.Tensor):
+        src = to_device(src.copy(), self.device)
+    if table is None:
+        from . import hostmath
+        table = to_device(hostmath.env_prefilter_table(base, samples).copy(), self.device)
+    dst = out if out is not None else torch.empty((dst_bytes // 8, 4), dtype=torch.int16, device=src.device)
+    scratch = scratch if scratch is not None else torch.empty(scratch_bytes, dtype=torch.uint8, device=src.device)
+    size = lambda t: t.numel() * t.element_size()  # noqa: E731
+    _lib.check(self._L.ur_env_prefilter(self._ctx, _ptr(src), need, base, samples, _ptr(table), size(table), _ptr(dst), size(dst), _ptr(scratch), size(scratch)),
+               "ur_env_prefilter")
+    dst._keep = (src, table, scratch)  # (the launches are still in flight)
+    return dst
+
+
+def _bake_env_cube(self, src, base_size: int, sample_count: int = 1024, *, table=None, out=None) -> torch.Tensor:
+    """prefilter_env_cube chained into build_env_cube: the top level of an HDR cube becomes the staged cube make_tables takes, with
+    log2(base_size) + 1 mips, all on the device. out: as in build_env_cube."""
+    payload = self.prefilter_env_cube(src, base_size, sample_count, table=table)
+    return self.build_env_cube(payload.view(torch.uint8).reshape(-1), _lib.UR_ENV_SOURCE_RGBA16F, int(base_size), int(base_size).bit_length(), out=out)
+
+
+HotPath.prefilter_env_cube = _prefilter_env_cube
+HotPath.bake_env_cube = _bake_env_cube
 HotPath.build_scene = _build_scene
 HotPath.build_mesh = _build_mesh
 HotPath.transcode_texture = _transcode_texture

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_host.h).
+"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_env_prefilter.h, include/ur_host.h).
 
 The shared library is the product; there is no Python or CPU fallback. If it is missing, importing the compute
 entry points raises — build it with `python -m unclerenderer_amd.build` (hipcc, gfx950).
@@ -245,6 +245,9 @@ UR_SCENE_BUILD_MAX_DRAWS = 1 << 24
 UR_ENV_SOURCE_RGBA16F, UR_ENV_SOURCE_BC6H_UF16, UR_ENV_SOURCE_BC6H_SF16 = 10, 95, 96
 UR_ENV_CUBE_BUILD_MAX_STREAM_OPS = 3
 UR_ENV_CUBE_MAX_BASE_SIZE = 16384
+# ur_env_prefilter.h
+UR_ENV_PREFILTER_MAX_BASE_SIZE, UR_ENV_PREFILTER_MIN_SAMPLES, UR_ENV_PREFILTER_MAX_SAMPLES = 2048, 16, 4096
+UR_ENV_PREFILTER_MAX_STREAM_OPS = 15
 
 
 class DdsInfo(C.Structure):
@@ -455,6 +458,10 @@ SIGNATURES = {
     # ur_env_cube.h
     "ur_env_cube_source_bytes": (C.c_size_t, [_U32, _U32, _U32]),
     "ur_env_cube_build": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _U32, _VP, C.c_size_t, _VP]),
+    # ur_env_prefilter.h
+    "ur_env_prefilter_table_bytes": (C.c_size_t, [_U32, _U32]),
+    "ur_env_prefilter_scratch_bytes": (C.c_size_t, [_U32]),
+    "ur_env_prefilter": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t, _VP, C.c_size_t]),
     # ur_assets.h
     "ur_dds_parse":(C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
@@ -521,6 +528,8 @@ SIGNATURES = {
     "ur_host_mesh_build": (C.c_int, [_VP, C.c_uint64, C.POINTER(MeshPrimitive), _U32, _VP, _VP, C.POINTER(MeshSection), C.POINTER(MeshInfo)]),
     "ur_host_scene_build": (C.c_int, [C.POINTER(SceneBuildTables), C.POINTER(SceneConstants), C.POINTER(SceneBuildOutputs), C.c_uint64, _U32]),
     "ur_host_env_cube_build": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _U32, _VP, C.c_size_t, _VP]),
+    "ur_host_env_prefilter_table": (C.c_int, [_U32, _U32, _VP, C.c_size_t]),
+    "ur_host_env_prefilter": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
