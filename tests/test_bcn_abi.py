@@ -169,7 +169,7 @@ def test_load_texture_dds_from_a_path(urlib, tmp_path):
 
 def test_pack_texture_bc_checks_the_length_before_it_touches_a_device(urlib, monkeypatch):
     from unclerenderer_amd import hotpath
-    monkeypatch.setattr(hotpath, "to_device", lambda a: pytest.fail("a refused payload must not be uploaded"))
+    monkeypatch.setattr(hotpath.tensors, "to_device", lambda *args: pytest.fail("a refused payload must not be uploaded"))
     good = R.random_chain(R.BC3, 20, 12, 5, seed=3)
     for payload in (good[:-1], np.concatenate([good, good[:16]]), good[:16], b""):
         with pytest.raises(ValueError, match="bytes"):

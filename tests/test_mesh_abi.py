@@ -206,7 +206,7 @@ def test_build_refusals_that_need_no_device(urlib):
 def test_python_routing(urlib, monkeypatch):
     from unclerenderer_amd import assets, hostmath, hotpath
     # a refused mesh is refused before anything is uploaded
-    monkeypatch.setattr(hotpath, "to_device", lambda a: pytest.fail("a refused mesh must not be uploaded"))
+    monkeypatch.setattr(hotpath.tensors, "to_device", lambda *args: pytest.fail("a refused mesh must not be uploaded"))
 
     class NoDevice(hotpath.HotPath):
         def __init__(self):

@@ -168,14 +168,14 @@ def test_what_keeps_refusing_the_new_formats(urlib, monkeypatch):
     for fourcc in ("DXT3", "ATI1", "BC4U"):
         data = _dds(16, 16, 5, good, fourcc=fourcc)
         assert urlib.ur_dds_parse_texture2d(data, len(data), C.byref(info)) == ASSET_EUNSUPPORTED, fourcc
-    monkeypatch.setattr(hotpath, "to_device", lambda a: pytest.fail("a refused payload must not be uploaded"))
+    monkeypatch.setattr(hotpath.tensors, "to_device", lambda *args: pytest.fail("a refused payload must not be uploaded"))
     for fmt in (S.BC7, S.BC2, S.BC4):
         with pytest.raises(ValueError, match="no BC chain"):
             hotpath.pack_texture_bc(good, 16, 16, 5, fmt)
     # transcode_texture checks the length before it touches a device
     class NoDevice(hotpath.HotPath):
         def __init__(self):
-            self._L = urlib
+            self._L, self._ctx, self.device = urlib, None, 0  # (the payload path is told the context's device)
     for payload in (good[:-1], np.concatenate([good, good[:16]]), b""):
         with pytest.raises(ValueError, match="bytes"):
             NoDevice().transcode_texture(payload, 16, 16, 5, S.BC7)

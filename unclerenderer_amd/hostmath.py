@@ -12,6 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import lib as _lib
+from .payload import host_bytes
 
 
 def _f(*v) -> np.ndarray:
@@ -92,7 +93,7 @@ def bc_chain_bytes(format: int, width: int, height: int, mips: int) -> int:
 def bc_decode_level(format: int, blocks, level_width: int, level_height: int) -> np.ndarray:
     """ur_host_bc_decode_level: one level of ((w + 3) >> 2) x ((h + 3) >> 2) blocks (bytes or a uint8 array) -> its (h, w, 4) uint8 RGBA8 code
     words, by the functions the kernels decode with (csrc/bc_decode.h)."""
-    data = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8).reshape(-1)
+    data = host_bytes(blocks)
     per = 8 if format in (_lib.UR_TEXTURE_BC1_UNORM, _lib.UR_TEXTURE_BC1_UNORM_SRGB) else 16
     need = ((level_width + 3) >> 2) * ((level_height + 3) >> 2) * per
     if level_width < 1 or level_height < 1 or data.size < need:
@@ -113,7 +114,7 @@ def texture_chain_bytes(format: int, width: int, height: int, mips: int) -> int:
 def texture_decode_level(format: int, blocks, level_width: int, level_height: int) -> np.ndarray:
     """ur_host_texture_decode_level: bc_decode_level over the ten source formats, by the functions the transcode kernel decodes with
     (csrc/bc_wide_decode.h)."""
-    data = np.ascontiguousarray(np.frombuffer(bytes(blocks), np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8).reshape(-1)
+    data = host_bytes(blocks)
     need = texture_chain_bytes(format, max(level_width, 1), max(level_height, 1), 1)
     if level_width < 1 or level_height < 1 or need == 0 or data.size < need:
         raise ValueError(f"a {level_width} x {level_height} level of format {format} needs {need} bytes of blocks, got {data.size}")
@@ -311,7 +312,7 @@ def mesh_build(buffer, primitives):
     the .bin's bytes. Returns (vertices uint32[V, 16], indices uint32[I], sections, lib.MeshInfo): the bytes HotPath.build_mesh leaves on
     the device."""
     primitives = list(primitives)
-    data = np.ascontiguousarray(np.frombuffer(bytes(buffer), np.uint8) if isinstance(buffer, (bytes, bytearray, memoryview)) else buffer, np.uint8).reshape(-1)
+    data = host_bytes(buffer)
     layout, sections = mesh_layout(primitives, data.size)
     vertices, indices, info = np.zeros((layout.vertex_count, 16), np.uint32), np.zeros(layout.index_count, np.uint32), _lib.MeshInfo()
     rc = _lib.load().ur_host_mesh_build(data.ctypes.data_as(C.c_void_p), data.size, mesh_primitive_array(primitives), len(primitives),
@@ -329,7 +330,7 @@ def scene_build(nodes, meshes, mesh_infos, materials, draws, frame, slot_count: 
     lib.SceneBuildSummary) - the bytes HotPath.build_scene leaves on the device when its constants lie at constants_address. out: such a
     dict to write into (what a build leaves alone keeps its bytes), else zeroed arrays."""
     L = library if library is not None else _lib.load()
-    tables = [np.ascontiguousarray(t).view(np.uint8).reshape(-1) for t in (nodes, meshes, mesh_infos, materials, draws)]
+    tables = [host_bytes(t, reinterpret=True) for t in (nodes, meshes, mesh_infos, materials, draws)]
     counts = [t.size // C.sizeof(r) for t, r in zip(tables, (_lib.SceneNode, _lib.SceneMesh, _lib.MeshInfo, _lib.SceneMaterialFactors, _lib.SceneDraw))]
     if counts[1] != counts[2]:
         raise ValueError(f"{counts[1]} mesh records and {counts[2]} info records")
@@ -360,7 +361,7 @@ def env_cube_build(payload, format: int, base: int, mips: int, *, library=None):
     assets.load_env_cube_dds_source). Returns (the staged cube as uint16 [texels, 4] - the bytes HotPath.build_env_cube leaves on the
     device - and the number of reserved-mode blocks)."""
     L = library if library is not None else _lib.load()
-    data = np.frombuffer(bytes(payload), np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, np.uint8).reshape(-1)
+    data = host_bytes(payload)
     texels = int(_lib.load().ur_env_cube_texels(int(base), int(mips)))
     src = _aligned16(data.size)
     src[:] = data
@@ -394,7 +395,7 @@ def env_prefilter(src, base: int, sample_count: int = 1024, *, table=None, libra
     assets.load_env_cube_top_level). Returns the prefiltered chain as uint16 [texels, 4] in DDS order - the bytes
     HotPath.prefilter_env_cube leaves on the device, the UR_ENV_SOURCE_RGBA16F payload of env_cube_build with log2(base) + 1 mips."""
     L = library if library is not None else _lib.load()
-    data = np.frombuffer(bytes(src), np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+    data = host_bytes(src, reinterpret=True)
     if table is None:
         table = env_prefilter_table(base, sample_count, library=library)
     mips = int(base).bit_length()
@@ -402,7 +403,7 @@ def env_prefilter(src, base: int, sample_count: int = 1024, *, table=None, libra
     source = _aligned16(data.size)
     source[:] = data
     tab = _aligned16(table.size)
-    tab[:] = np.ascontiguousarray(table).view(np.uint8).reshape(-1)
+    tab[:] = host_bytes(table, reinterpret=True)
     dst = _aligned16(need)
     rc = L.ur_host_env_prefilter(C.c_void_p(source.ctypes.data), C.c_size_t(data.size), C.c_uint32(int(base)), C.c_uint32(int(sample_count)),
                                  C.c_void_p(tab.ctypes.data), C.c_size_t(tab.size), C.c_void_p(dst.ctypes.data), C.c_size_t(need))
