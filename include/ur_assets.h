@@ -58,6 +58,32 @@ int ur_bc6h_decode_block(const uint8_t block[16], int is_signed, ur_half4 out[16
  * [2],[3]; one-region modes leave [2],[3] zero) — what the decoder interpolates between; for tests and asset diagnostics */
 int ur_bc6h_block_endpoints(const uint8_t block[16], int is_signed, int32_t endpoints[12]);
 
+/* A Radiance .hdr panorama (csrc/hdr.cpp): the file's texels as they lie, four bytes R G B E each - what
+ * ur_env_panorama (include/ur_env_panorama.h) takes on the device. The rule is the one stb_image's HDR loader reads by. */
+#define UR_HDR_MAX_WIDTH 16384u
+#define UR_HDR_MAX_HEIGHT 8192u
+
+typedef struct ur_hdr_info {
+    uint32_t width, height;
+    uint32_t payload_offset; /* where the first scanline starts in the file */
+    uint32_t rle;            /* 1: scanlines are run-length coded (new-style RLE); 0: the payload is flat, 4 * width * height bytes */
+} ur_hdr_info;
+
+/* The header: a first line "#?RADIANCE" or "#?RGBE", header lines up to the empty line, "FORMAT=32-bit_rle_rgbe" among them, then the
+ * resolution line "-Y H +X W" with 1 <= W <= UR_HDR_MAX_WIDTH and 1 <= H <= UR_HDR_MAX_HEIGHT. The payload is run-length coded when
+ * 8 <= W < 32768 and it starts 02 02 hi lo with hi < 128, flat otherwise (the first scanline decides for the file).
+ * UR_EUNSUPPORTED for a resolution line of any other orientation; UR_EINVAL for a null argument, a file that is not Radiance, a header
+ * that ends early, a missing FORMAT line or a size out of range. ur_hdr_last_error has the text. */
+int ur_hdr_parse(const void* file, size_t size, ur_hdr_info* out);
+/* Writes 4 * width * height bytes, R G B E per texel, top row first. A flat payload is copied. A run-length coded one is expanded
+ * scanline by scanline: the marker 02 02 hi lo with (hi << 8 | lo) == width, then for each of the four channel planes count bytes - above
+ * 128 a run of count - 128 copies of the next byte, otherwise that many literal bytes. UR_EINVAL (ur_hdr_last_error has the text) for a
+ * null argument, an info that is not ur_hdr_parse's of this file, a count of 0, a run or literals past the width, a later scanline
+ * without the marker or with another length, and a truncated file; rgbe_out is then unspecified but never written outside its bytes. */
+int ur_hdr_unpack(const void* file, size_t size, const ur_hdr_info* info, uint8_t* rgbe_out);
+/* The text of the calling thread's last refusal by ur_hdr_parse or ur_hdr_unpack ("" before the first). */
+const char* ur_hdr_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

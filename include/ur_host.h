@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "ur_env_cube.h"
+#include "ur_env_panorama.h"
 #include "ur_env_prefilter.h"
 #include "ur_hotpath.h"
 #include "ur_mesh.h"
@@ -134,6 +135,17 @@ int ur_host_env_prefilter_table(uint32_t base_size, uint32_t sample_count, void*
  * All pointers are host memory; no GPU is needed. The same refusals as ur_env_prefilter but for the context and the scratch. */
 int ur_host_env_prefilter(const void* src_host, size_t src_bytes, uint32_t base_size, uint32_t sample_count, const void* table_host, size_t table_bytes,
                           void* dst_host, size_t dst_bytes);
+
+/* The taps a side ur_env_panorama (include/ur_env_panorama.h) is recommended to take for a width x height panorama and a
+ * cube of edge base_size: the smallest power of two K with 3 K base_size >= 2 width and 3 K base_size >= 4 height, at most 16 - sub-samples
+ * at most about half a panorama texel apart at a face's centre. 0 for sizes ur_env_panorama refuses. */
+uint32_t ur_host_env_panorama_taps(uint32_t width, uint32_t height, uint32_t base_size);
+
+/* ur_env_panorama on the host, serial: the CPU fallback and the byte reference, over csrc/env_panorama_rule.h, the very functions the
+ * kernel runs, every texel's taps summed in the rule's 64-lane order. All pointers are host memory; no GPU is needed. The same refusals
+ * as ur_env_panorama but for the context. */
+int ur_host_env_panorama(const void* rgbe_host, size_t rgbe_bytes, uint32_t width, uint32_t height, uint32_t base_size, uint32_t taps, void* dst_host,
+                         size_t dst_bytes);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

@@ -1,8 +1,9 @@
 """Asset loading. IBL: DDS (BC6H cube, RG16 LUT) -> host arrays ready for HotPath.stage_env_cube / make_tables; or the cube's payload as it
-lies (load_env_cube_dds_source) -> what HotPath.build_env_cube decodes and stages on the device. Material textures: DDS
+lies (load_env_cube_dds_source) -> what HotPath.build_env_cube decodes and stages on the device; or a Radiance .hdr panorama's texels
+(load_panorama_hdr) -> what environment.bake_panorama turns into the staged cube on the device. Material textures: DDS
 (RGBA8, BC1, BC3, BC5) -> what hotpath.pack_texture / pack_texture_bc take; BC blocks stay compressed, the sampler decodes them.
 BC2, BC4 and BC7 too (load_texture_dds_source) -> what HotPath.transcode_texture takes: decoded to RGBA8 once, on the device.
-All parsing and decoding happens in libur_hotpath.so (csrc/dds.cpp); this module only reads the file and marshals."""
+All parsing and decoding happens in libur_hotpath.so (csrc/dds.cpp, csrc/hdr.cpp); this module only reads the file and marshals."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,6 +43,31 @@ def load_env_cube_top_level(path) -> tuple[np.ndarray, int]:
     texels, base, mips, _ = load_env_cube_dds(path)
     per_face = sum(max(1, base >> m) ** 2 for m in range(mips))
     return np.ascontiguousarray(texels.reshape(6, per_face, 4)[:, :base * base]).reshape(6, base, base, 4), base
+
+
+def parse_panorama_hdr(data: bytes) -> _lib.HdrInfo:
+    """ur_hdr_parse: the header of a Radiance .hdr file (width, height, where the payload starts, whether it is run-length coded).
+    ValueError with the library's text for what it refuses."""
+    info = _lib.HdrInfo()
+    L = _lib.load()
+    rc = L.ur_hdr_parse(data, len(data), C.byref(info))
+    if rc != 0:
+        raise ValueError(f"ur_hdr_parse failed ({rc}): {L.ur_hdr_last_error().decode(errors='replace')}")
+    return info
+
+
+def load_panorama_hdr(path_or_bytes) -> np.ndarray:
+    """A lat-long Radiance .hdr panorama (a path, or the file's bytes) as its own texels: uint8 [height, width, 4], R G B E, top row first -
+    the source of environment.panorama_to_cube / bake_panorama and hostmath.env_panorama. Run-length coded scanlines are expanded here, on
+    the host (ur_hdr_unpack); the decode to numbers is the device's."""
+    data = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else Path(path_or_bytes).read_bytes()
+    info = parse_panorama_hdr(data)
+    out = np.zeros((int(info.height), int(info.width), 4), np.uint8)
+    L = _lib.load()
+    rc = L.ur_hdr_unpack(data, len(data), C.byref(info), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"ur_hdr_unpack failed ({rc}): {L.ur_hdr_last_error().decode(errors='replace')}")
+    return out
 
 
 def load_env_cube_dds_source(path_or_bytes) -> tuple[np.ndarray, int, int, int]:

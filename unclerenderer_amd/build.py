@@ -59,15 +59,18 @@ SOURCES = [
     ("scene_build.hip", EXACT),
     ("env_cube_build.hip", []),  # integer arithmetic alone: no flag changes its results
     ("env_prefilter.hip", EXACT),
+    ("env_panorama.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),
+    ("hdr.cpp", ["-x", "hip"]),  # host code only, bytes alone: no flag changes its results
     ("host_math.cpp", ["-x", "hip"] + EXACT),
     ("bc_host.cpp", ["-x", "hip"]),  # host code only, over csrc/bc_decode.h: integer arithmetic, so no flag changes its results
     ("mesh_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/mesh_rule.h: the rule the kernels of mesh_build.hip run
     ("scene_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/scene_rule.h: the rule the kernels of scene_build.hip run
     ("env_cube_host.cpp", ["-x", "hip"]),  # host code only, over csrc/bc6h_decode.h: the decoder the kernels of env_cube_build.hip run
     ("env_prefilter_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/env_prefilter_rule.h: the rule the kernels of env_prefilter.hip run
+    ("env_panorama_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/env_panorama_rule.h: the rule the kernel of env_panorama.hip runs
     ("lighting_plan.cpp", ["-x", "hip"] + EXACT),
     ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),

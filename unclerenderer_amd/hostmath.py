@@ -410,3 +410,32 @@ def env_prefilter(src, base: int, sample_count: int = 1024, *, table=None, libra
     if rc != 0:
         raise ValueError(f"ur_host_env_prefilter failed ({rc}): base size {base}, {sample_count} samples, {data.size} source bytes, {tab.size} table bytes")
     return dst.view(np.uint16).reshape(-1, 4)
+
+
+def env_panorama_taps(width: int, height: int, base: int) -> int:
+    """ur_host_env_panorama_taps: the taps a side recommended for a width x height panorama and a cube of edge `base`: the
+    smallest power of two K with 3 K base >= 2 width and 3 K base >= 4 height, at most 16. ValueError for sizes the build refuses."""
+    taps = int(_lib.load().ur_host_env_panorama_taps(int(width), int(height), int(base)))
+    if taps == 0:
+        raise ValueError(f"no panorama build: {width} x {height} to base size {base} (1..16384 x 1..8192; a power of two, 1..2048)")
+    return taps
+
+
+def env_panorama(rgbe, width: int, height: int, base: int, taps=None, *, library=None) -> np.ndarray:
+    """ur_host_env_panorama: the environment from a panorama on the host, serial, by the functions the kernel runs
+    (csrc/env_panorama_rule.h). rgbe: the panorama's texels, four bytes R G B E each, top row first (4 * width * height bytes:
+    assets.load_panorama_hdr). taps: the sub-samples a side, None for env_panorama_taps. Returns the cube's top level as uint16
+    [6, base, base, 4] - the bytes environment.panorama_to_cube leaves on the device, the source of env_prefilter."""
+    L = library if library is not None else _lib.load()
+    data = host_bytes(rgbe)
+    if taps is None:
+        taps = env_panorama_taps(width, height, base)
+    source = _aligned16(data.size)
+    source[:] = data
+    need = 48 * int(base) * int(base) if 0 < int(base) <= 2048 else 0
+    dst = _aligned16(need)
+    rc = L.ur_host_env_panorama(C.c_void_p(source.ctypes.data), C.c_size_t(data.size), C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_uint32(int(base)),
+                                C.c_uint32(int(taps)), C.c_void_p(dst.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_panorama failed ({rc}): {width} x {height} to base size {base}, {taps} taps a side, {data.size} source bytes")
+    return dst.view(np.uint16).reshape(6, int(base), int(base), 4)

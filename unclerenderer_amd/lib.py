@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_env_prefilter.h, include/ur_host.h).
+"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_env_prefilter.h, include/ur_env_panorama.h, include/ur_host.h).
 
 The shared library is the product; there is no Python or CPU fallback. If it is missing, importing the compute
 entry points raises — build it with `python -m unclerenderer_amd.build` (hipcc, gfx950).
@@ -248,11 +248,19 @@ UR_ENV_CUBE_MAX_BASE_SIZE = 16384
 # ur_env_prefilter.h
 UR_ENV_PREFILTER_MAX_BASE_SIZE, UR_ENV_PREFILTER_MIN_SAMPLES, UR_ENV_PREFILTER_MAX_SAMPLES = 2048, 16, 4096
 UR_ENV_PREFILTER_MAX_STREAM_OPS = 15
+# ur_env_panorama.h
+UR_ENV_PANORAMA_MAX_WIDTH, UR_ENV_PANORAMA_MAX_HEIGHT, UR_ENV_PANORAMA_MAX_BASE_SIZE, UR_ENV_PANORAMA_MAX_TAPS = 16384, 8192, 2048, 16
+UR_ENV_PANORAMA_MAX_STREAM_OPS = 1
 
 
 class DdsInfo(C.Structure):
     """ur_dds_info (include/ur_assets.h)."""
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "mip_count", "slices", "is_cube", "dxgi_format", "header_size", "block_dim", "bytes_per_block")]
+
+
+class HdrInfo(C.Structure):
+    """ur_hdr_info (include/ur_assets.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "payload_offset", "rle")]
 
 
 class SceneModel(C.Structure):
@@ -462,7 +470,12 @@ SIGNATURES = {
     "ur_env_prefilter_table_bytes": (C.c_size_t, [_U32, _U32]),
     "ur_env_prefilter_scratch_bytes": (C.c_size_t, [_U32]),
     "ur_env_prefilter": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t, _VP, C.c_size_t]),
+    # ur_env_panorama.h
+    "ur_env_panorama": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _U32, _U32, _VP, C.c_size_t]),
     # ur_assets.h
+    "ur_hdr_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(HdrInfo)]),
+    "ur_hdr_unpack": (C.c_int, [_VP, C.c_size_t, C.POINTER(HdrInfo), _VP]),
+    "ur_hdr_last_error": (C.c_char_p, []),
     "ur_dds_parse":(C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
     "ur_dds_parse_texture2d_source": (C.c_int, [_VP, C.c_size_t, C.POINTER(DdsInfo)]),
@@ -530,6 +543,8 @@ SIGNATURES = {
     "ur_host_env_cube_build": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _U32, _VP, C.c_size_t, _VP]),
     "ur_host_env_prefilter_table": (C.c_int, [_U32, _U32, _VP, C.c_size_t]),
     "ur_host_env_prefilter": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t]),
+    "ur_host_env_panorama_taps": (_U32, [_U32, _U32, _U32]),
+    "ur_host_env_panorama": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _U32, _U32, _VP, C.c_size_t]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
