@@ -8,9 +8,11 @@
 
 #include <stdint.h>
 
+#include "ur_brdf_lut.h"
 #include "ur_env_cube.h"
 #include "ur_env_panorama.h"
 #include "ur_env_prefilter.h"
+#include "ur_env_sky.h"
 #include "ur_hotpath.h"
 #include "ur_mesh.h"
 #include "ur_scene_build.h"
@@ -146,6 +148,30 @@ uint32_t ur_host_env_panorama_taps(uint32_t width, uint32_t height, uint32_t bas
  * as ur_env_panorama but for the context. */
 int ur_host_env_panorama(const void* rgbe_host, size_t rgbe_bytes, uint32_t width, uint32_t height, uint32_t base_size, uint32_t taps, void* dst_host,
                          size_t dst_bytes);
+
+/* The values ur_env_sky (include/ur_env_sky.h) folds the constants to, computed in double and each rounded once to fp32:
+ * out[0..2] the normalised LightDirection; out[3..5] rayleighColor * exp(-h / 8000) * 3 / (16 * 3.14159265) with h = max(0,
+ * CameraPosition[1]); out[6..8] LightColor * exp(-h / 1200) * 0.8 * (1 - 0.76^2) / (4 * 3.14159265); out[9] saturate(exp(-max(0, 1 - sun.y)
+ * * 2)). The shader's literals are the fp32 values, widened exactly. The device build and ur_host_env_sky use these very floats. UR_EINVAL
+ * for a null pointer, a CameraPosition[1], LightDirection or LightColor that is not finite, or a LightDirection of length zero. */
+int ur_host_env_sky_params(const ur_sky_constants* sky, float out[10]);
+
+/* ur_env_sky on the host, serial: the CPU fallback and the byte reference, over csrc/env_sky_rule.h, the very functions the kernel runs,
+ * every texel's taps summed in the rule's 64-lane order. All pointers are host memory; no GPU is needed. The same refusals as ur_env_sky
+ * but for the context. */
+int ur_host_env_sky(const ur_sky_constants* sky, uint32_t base_size, uint32_t taps, void* dst_host, size_t dst_bytes);
+
+/* The sample table of the BRDF LUT (include/ur_brdf_lut.h): for every row y of `height`, alpha = ((y + 0.5) / height)^2, the
+ * GGX importance half vectors of the sample_count Hammersley points of ur_host_env_prefilter_table, (sin cos phi, sin sin phi, cos) with
+ * cos^2 = (1 - xi2) / (1 + (alpha^2 - 1) xi2) and phi = 2 pi xi1, in double, each rounded to fp32: 16 bytes {hx, hy, hz, 0} a row and
+ * sample, rows outer. The device reads these very bytes. Writes ur_brdf_lut_table_bytes(height, sample_count) bytes; UR_EINVAL for a
+ * null out, numbers that function refuses or fewer out_bytes. */
+int ur_host_brdf_lut_table(uint32_t height, uint32_t sample_count, void* out, size_t out_bytes);
+
+/* ur_brdf_lut on the host, serial: the CPU fallback and the byte reference, over csrc/brdf_lut_rule.h, the very functions the kernel runs,
+ * every texel's samples summed in the rule's 64-lane order. All pointers are host memory; no GPU is needed. The same refusals as
+ * ur_brdf_lut but for the context. */
+int ur_host_brdf_lut(uint32_t width, uint32_t height, uint32_t sample_count, const void* table_host, size_t table_bytes, void* dst_host, size_t dst_bytes);
 
 /* A built-in debug-print font, so that ur_debug_print_draw / UR_FRAME_DEBUG_PRINT work with no asset (the reference bakes its atlas
  * from a font file with stb_truetype, DebugPrintFont.cpp; that stays the caller's). 5 x 7 dot-matrix glyphs of this repository's own

@@ -60,6 +60,8 @@ SOURCES = [
     ("env_cube_build.hip", []),  # integer arithmetic alone: no flag changes its results
     ("env_prefilter.hip", EXACT),
     ("env_panorama.hip", EXACT),
+    ("env_sky.hip", EXACT),
+    ("brdf_lut.hip", EXACT),
     ("stream_ceiling.hip", []),
     ("scene.cpp", ["-x", "hip"] + EXACT),
     ("dds.cpp", ["-x", "hip"] + EXACT),
@@ -71,6 +73,8 @@ SOURCES = [
     ("env_cube_host.cpp", ["-x", "hip"]),  # host code only, over csrc/bc6h_decode.h: the decoder the kernels of env_cube_build.hip run
     ("env_prefilter_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/env_prefilter_rule.h: the rule the kernels of env_prefilter.hip run
     ("env_panorama_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/env_panorama_rule.h: the rule the kernel of env_panorama.hip runs
+    ("env_sky_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/env_sky_rule.h: the rule the kernel of env_sky.hip runs
+    ("brdf_lut_host.cpp", ["-x", "hip"] + EXACT),  # host code only, over csrc/brdf_lut_rule.h: the rule the kernel of brdf_lut.hip runs
     ("lighting_plan.cpp", ["-x", "hip"] + EXACT),
     ("debug_font.cpp", ["-x", "hip"] + EXACT),
     ("rg/RenderGraph.cpp", ["-x", "hip"]),

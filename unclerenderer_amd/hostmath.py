@@ -439,3 +439,60 @@ def env_panorama(rgbe, width: int, height: int, base: int, taps=None, *, library
     if rc != 0:
         raise ValueError(f"ur_host_env_panorama failed ({rc}): {width} x {height} to base size {base}, {taps} taps a side, {data.size} source bytes")
     return dst.view(np.uint16).reshape(6, int(base), int(base), 4)
+
+
+def env_sky_params(sky) -> np.ndarray:
+    """ur_host_env_sky_params: the ten fp32 values the sky capture folds a lib.SkyConstants to, in float64 rounded once:
+    the normalised sun direction [0:3], the Rayleigh term [3:6], the Mie term [6:9], the sun attenuation [9]. ValueError for a
+    CameraPosition[1], LightDirection or LightColor that is not finite or a LightDirection of length zero."""
+    out = np.zeros(10, np.float32)
+    rc = _lib.load().ur_host_env_sky_params(C.byref(sky), _lib.fptr(out))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_sky_params failed ({rc}): CameraPosition.y, LightDirection and LightColor are finite, LightDirection is not zero")
+    return out
+
+
+def env_sky(sky, base: int, taps: int = 1, *, library=None) -> np.ndarray:
+    """ur_host_env_sky: the sky capture on the host, serial, by the functions the kernel runs (csrc/env_sky_rule.h). Returns
+    the cube's top level as uint16 [6, base, base, 4] - the bytes environment.sky_to_cube leaves on the device, the source of
+    env_prefilter."""
+    L = library if library is not None else _lib.load()
+    need = 48 * int(base) * int(base) if 0 < int(base) <= 2048 else 0
+    dst = _aligned16(need)
+    rc = L.ur_host_env_sky(C.byref(sky), C.c_uint32(int(base)), C.c_uint32(int(taps)), C.c_void_p(dst.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_env_sky failed ({rc}): base size {base}, {taps} taps a side")
+    return dst.view(np.uint16).reshape(6, int(base), int(base), 4)
+
+
+def brdf_lut_table(height: int, sample_count: int, *, library=None) -> np.ndarray:
+    """ur_host_brdf_lut_table: the sample table of the BRDF LUT for `height` rows and `sample_count` samples a texel, as
+    uint8 at a 16-byte aligned address - the bytes environment.brdf_lut uploads. ValueError for a height outside 1..256 or a sample count
+    that is no power of two in 16..4096."""
+    L = library if library is not None else _lib.load()
+    need = int(_lib.load().ur_brdf_lut_table_bytes(int(height), int(sample_count)))
+    if need == 0:
+        raise ValueError(f"no BRDF LUT table: {height} rows, {sample_count} samples (1..256; a power of two, 16..4096)")
+    out = _aligned16(need)
+    rc = L.ur_host_brdf_lut_table(C.c_uint32(int(height)), C.c_uint32(int(sample_count)), C.c_void_p(out.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_brdf_lut_table failed ({rc})")
+    return out
+
+
+def brdf_lut(width: int = 128, height: int = 32, sample_count: int = 1024, *, table=None, library=None) -> np.ndarray:
+    """ur_host_brdf_lut: the BRDF LUT on the host, serial, by the functions the kernel runs (csrc/brdf_lut_rule.h). Returns
+    uint16 [height, width, 2] (scale, bias) - the bytes environment.brdf_lut leaves on the device, what assets.load_brdf_lut_dds gives
+    for the shipped file."""
+    L = library if library is not None else _lib.load()
+    if table is None:
+        table = brdf_lut_table(height, sample_count, library=library)
+    tab = _aligned16(table.size)
+    tab[:] = host_bytes(table, reinterpret=True)
+    need = 4 * int(width) * int(height) if 0 < int(width) <= 1024 and 0 < int(height) <= 256 else 0
+    dst = _aligned16(need)
+    rc = L.ur_host_brdf_lut(C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_uint32(int(sample_count)), C.c_void_p(tab.ctypes.data), C.c_size_t(tab.size),
+                            C.c_void_p(dst.ctypes.data), C.c_size_t(need))
+    if rc != 0:
+        raise ValueError(f"ur_host_brdf_lut failed ({rc}): {width} x {height}, {sample_count} samples, {tab.size} table bytes")
+    return dst.view(np.uint16).reshape(int(height), int(width), 2)

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_env_prefilter.h, include/ur_env_panorama.h, include/ur_host.h).
+"""ctypes binding of the C-ABI (include/ur_hotpath.h, include/ur_raster.h, include/ur_mesh.h, include/ur_scene_build.h, include/ur_env_cube.h, include/ur_env_prefilter.h, include/ur_env_panorama.h, include/ur_env_sky.h, include/ur_brdf_lut.h, include/ur_host.h).
 
 The shared library is the product; there is no Python or CPU fallback. If it is missing, importing the compute
 entry points raises — build it with `python -m unclerenderer_amd.build` (hipcc, gfx950).
@@ -251,6 +251,11 @@ UR_ENV_PREFILTER_MAX_STREAM_OPS = 15
 # ur_env_panorama.h
 UR_ENV_PANORAMA_MAX_WIDTH, UR_ENV_PANORAMA_MAX_HEIGHT, UR_ENV_PANORAMA_MAX_BASE_SIZE, UR_ENV_PANORAMA_MAX_TAPS = 16384, 8192, 2048, 16
 UR_ENV_PANORAMA_MAX_STREAM_OPS = 1
+# ur_env_sky.h
+UR_ENV_SKY_MAX_BASE_SIZE, UR_ENV_SKY_MAX_TAPS, UR_ENV_SKY_MAX_STREAM_OPS = 2048, 16, 1
+# ur_brdf_lut.h
+UR_BRDF_LUT_MAX_WIDTH, UR_BRDF_LUT_MAX_HEIGHT, UR_BRDF_LUT_MIN_SAMPLES, UR_BRDF_LUT_MAX_SAMPLES = 1024, 256, 16, 4096
+UR_BRDF_LUT_MAX_STREAM_OPS = 1
 
 
 class DdsInfo(C.Structure):
@@ -472,6 +477,11 @@ SIGNATURES = {
     "ur_env_prefilter": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t, _VP, C.c_size_t]),
     # ur_env_panorama.h
     "ur_env_panorama": (C.c_int, [_VP, _VP, C.c_size_t, _U32, _U32, _U32, _U32, _VP, C.c_size_t]),
+    # ur_env_sky.h
+    "ur_env_sky": (C.c_int, [_VP, C.POINTER(SkyConstants), _U32, _U32, _VP, C.c_size_t]),
+    # ur_brdf_lut.h
+    "ur_brdf_lut_table_bytes": (C.c_size_t, [_U32, _U32]),
+    "ur_brdf_lut": (C.c_int, [_VP, _U32, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t]),
     # ur_assets.h
     "ur_hdr_parse": (C.c_int, [_VP, C.c_size_t, C.POINTER(HdrInfo)]),
     "ur_hdr_unpack": (C.c_int, [_VP, C.c_size_t, C.POINTER(HdrInfo), _VP]),
@@ -545,6 +555,10 @@ SIGNATURES = {
     "ur_host_env_prefilter": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t]),
     "ur_host_env_panorama_taps": (_U32, [_U32, _U32, _U32]),
     "ur_host_env_panorama": (C.c_int, [_VP, C.c_size_t, _U32, _U32, _U32, _U32, _VP, C.c_size_t]),
+    "ur_host_env_sky_params": (C.c_int, [C.POINTER(SkyConstants), _FP]),
+    "ur_host_env_sky": (C.c_int, [C.POINTER(SkyConstants), _U32, _U32, _VP, C.c_size_t]),
+    "ur_host_brdf_lut_table": (C.c_int, [_U32, _U32, _VP, C.c_size_t]),
+    "ur_host_brdf_lut": (C.c_int, [_U32, _U32, _U32, _VP, C.c_size_t, _VP, C.c_size_t]),
     "ur_host_debug_font": (C.c_int, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),
     "ur_host_direction_from_euler_degrees": (None, [_F, _F, _FP]),
     "ur_host_camera_forward_from_euler_degrees": (None, [_F, _F, _FP]),
