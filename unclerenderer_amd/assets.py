@@ -221,7 +221,8 @@ def load_gltf_meshes(path, hp):
     the glTF material index). Which model draws which mesh, and the pipeline keys, stay ur_scene_extract's."""
     from . import hotpath
     gltf, data = read_gltf(path)
-    buffer = hotpath.to_device(np.frombuffer(data, np.uint8).copy())
+    with hotpath.tensors.on_stream(hp):  # (the buffer is dropped at return, the builds that read it still in flight on the context's stream)
+        buffer = hotpath.tensors.to_device(np.frombuffer(data, np.uint8).copy(), hp.device)
     meshes = []
     for index in range(len(gltf.get("meshes", []))):
         primitives, materials = gltf_mesh_primitives(gltf, index)

@@ -30,15 +30,30 @@ using ur::set_error;
 
 namespace {
 
-// ur_create: a device table of `bytes` bytes with the contents of `host`, or zeroed when there are none. false: `what` is the error text
+// ur_create: a device table of `bytes` bytes with the contents of `host`, or zeroed when there are none, filled on the context's own
+// stream: everything the context launches is queued behind it, and creating a context waits for no other stream (a frame creates its
+// async lane's context inside its first UR_FRAME_ASYNC_COMPUTE render). `host` outlives the copy. false: `what` is the error text
 template <class T>
-bool upload_table(T** device, const T* host, size_t bytes, const char* what)
+bool upload_table(hipStream_t stream, T** device, const T* host, size_t bytes, const char* what)
 {
     if (hipMalloc(device, bytes) == hipSuccess &&
-        (host ? hipMemcpy(*device, host, bytes, hipMemcpyHostToDevice) : hipMemset(*device, 0, bytes)) == hipSuccess) return true;
+        (host ? hipMemcpyAsync(*device, host, bytes, hipMemcpyHostToDevice, stream) : hipMemsetAsync(*device, 0, bytes, stream)) == hipSuccess) return true;
     set_error("%s", what);
     return false;
 }
+
+// the three tables every context uploads, computed once
+struct HostTables {
+    float decode[256]; // sRGB8 -> linear (exact IEC 61966-2-1 curve, evaluated in double)
+    float encode[255];
+    float lod[127];
+    HostTables()
+    {
+        ur_host_srgb_decode_table(decode);
+        ur_host_srgb_encode_table(encode);
+        ur_host_lod_table(lod);
+    }
+};
 
 } // namespace
 
@@ -63,17 +78,11 @@ ur_ctx* ur_create(int device, void* stream)
     ctx->stream = static_cast<hipStream_t>(stream);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // sRGB8 -> linear (exact IEC 61966-2-1 curve, evaluated in double)
-    float table[256];
-    ur_host_srgb_decode_table(table);
-    float encode[255];
-    ur_host_srgb_encode_table(encode);
-    float lod[127];
-    ur_host_lod_table(lod);
-    if (!upload_table(&ctx->srgb_table, table, sizeof(table), "ur_create: sRGB table upload failed") ||
-        !upload_table(&ctx->srgb_encode_table, encode, sizeof(encode), "ur_create: sRGB encode table upload failed") ||
-        !upload_table(&ctx->lod_table, lod, sizeof(lod), "ur_create: level-of-detail table upload failed") ||
-        !upload_table<uint32_t>(&ctx->hzb_done, nullptr, 64, "ur_create: HZB arrival counter allocation failed")) {
+    static const HostTables tables; // (static: the copies below are asynchronous)
+    if (!upload_table<float>(ctx->stream, &ctx->srgb_table, tables.decode, sizeof(tables.decode), "ur_create: sRGB table upload failed") ||
+        !upload_table<float>(ctx->stream, &ctx->srgb_encode_table, tables.encode, sizeof(tables.encode), "ur_create: sRGB encode table upload failed") ||
+        !upload_table<float>(ctx->stream, &ctx->lod_table, tables.lod, sizeof(tables.lod), "ur_create: level-of-detail table upload failed") ||
+        !upload_table<uint32_t>(ctx->stream, &ctx->hzb_done, nullptr, 64, "ur_create: HZB arrival counter allocation failed")) {
         ur_destroy(ctx);
         return nullptr;
     }
@@ -93,7 +102,7 @@ ur_ctx* ur_create(int device, void* stream)
         ctx->claim_timed_out_dev = ctx->hzb_timed_out_dev + 1;
         *ctx->claim_timed_out = 0u;
     }
-    if (!upload_table<uint32_t>(&ctx->claim_words, nullptr, (ur::kClaimWords + 1u) * ur::kClaimWordStride * sizeof(uint32_t),
+    if (!upload_table<uint32_t>(ctx->stream, &ctx->claim_words, nullptr, (ur::kClaimWords + 1u) * ur::kClaimWordStride * sizeof(uint32_t),
                       "ur_create: tile-claim words allocation failed")) {
         ur_destroy(ctx);
         return nullptr;

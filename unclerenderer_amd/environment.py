@@ -38,8 +38,9 @@ def panorama_to_cube(hp, rgbe, width: int, height: int, base_size: int, taps=Non
     if int(hp._L.ur_host_env_panorama_taps(width, height, base)) == 0 or taps not in (1, 2, 4, 8, 16):
         raise ValueError(f"no panorama build: {width} x {height} to base size {base} with {taps} taps a side (1..16384 x 1..8192; powers of two, 1..2048 and 1..16)")
     need = 4 * width * height
-    src = tensors.device_bytes(rgbe, need, hp.device, lambda have: f"a panorama of {width} x {height} RGBE texels is {need} bytes, the source has {have}")
-    dst = out if out is not None else torch.empty((6, base, base, 4), dtype=torch.int16, device=src.device)
+    with tensors.on_stream(hp):
+        src = tensors.device_bytes(rgbe, need, hp.device, lambda have: f"a panorama of {width} x {height} RGBE texels is {need} bytes, the source has {have}")
+        dst = out if out is not None else torch.empty((6, base, base, 4), dtype=torch.int16, device=src.device)
     if nbytes(dst) != 48 * base * base:
         raise ValueError(f"the top level of a cube of base size {base} is {48 * base * base} bytes, out has {nbytes(dst)}")
     _lib.check(hp._L.ur_env_panorama(hp._ctx, _ptr(src), need, width, height, base, taps, _ptr(dst), nbytes(dst)), "ur_env_panorama")
@@ -67,7 +68,8 @@ def sky_to_cube(hp, sky, base_size: int, taps: int = 1, *, out=None) -> torch.Te
     if base < 1 or base > _lib.UR_ENV_SKY_MAX_BASE_SIZE or base & (base - 1) or taps not in (1, 2, 4, 8, 16):
         raise ValueError(f"no sky capture: base size {base} with {taps} taps a side (powers of two, 1..2048 and 1..16)")
     hostmath.env_sky_params(sky)  # (ValueError for constants the capture refuses)
-    dst = out if out is not None else torch.empty((6, base, base, 4), dtype=torch.int16, device=f"cuda:{hp.device}")
+    with tensors.on_stream(hp):
+        dst = out if out is not None else torch.empty((6, base, base, 4), dtype=torch.int16, device=f"cuda:{hp.device}")
     if nbytes(dst) != 48 * base * base:
         raise ValueError(f"the top level of a cube of base size {base} is {48 * base * base} bytes, out has {nbytes(dst)}")
     _lib.check(hp._L.ur_env_sky(hp._ctx, C.byref(sky), base, taps, _ptr(dst), nbytes(dst)), "ur_env_sky")
@@ -90,8 +92,9 @@ def brdf_lut(hp, width: int = 128, height: int = 32, sample_count: int = 1024, *
     width, height, samples = int(width), int(height), int(sample_count)
     if not 1 <= width <= _lib.UR_BRDF_LUT_MAX_WIDTH or int(hp._L.ur_brdf_lut_table_bytes(height, samples)) == 0:
         raise ValueError(f"no BRDF LUT: {width} x {height} with {samples} samples (1..1024 x 1..256; a power of two, 16..4096)")
-    table = tensors.to_device(hostmath.brdf_lut_table(height, samples).copy(), hp.device)
-    dst = out if out is not None else torch.empty((height, width, 2), dtype=torch.uint16, device=table.device)
+    with tensors.on_stream(hp):
+        table = tensors.to_device(hostmath.brdf_lut_table(height, samples).copy(), hp.device)
+        dst = out if out is not None else torch.empty((height, width, 2), dtype=torch.uint16, device=table.device)
     if nbytes(dst) != 4 * width * height:
         raise ValueError(f"a BRDF LUT of {width} x {height} is {4 * width * height} bytes, out has {nbytes(dst)}")
     _lib.check(hp._L.ur_brdf_lut(hp._ctx, width, height, samples, _ptr(table), nbytes(table), _ptr(dst), nbytes(dst)), "ur_brdf_lut")

@@ -90,10 +90,11 @@ class AssetBuilds:
         need = hostmath.texture_chain_bytes(format, width, height, mips)
         if need == 0:
             raise ValueError(f"no source chain: format {format}, {width} x {height}, {mips} mips (71, 72, 74, 75, 77, 78, 80, 83, 98, 99; sizes 1..65535, mips 1..255)")
-        blocks = tensors.device_bytes(data_or_tensor, need, self.device,
-                                      lambda have: f"a {width} x {height} chain of {mips} mips in format {format} is {need} bytes, the payload has {have}")
-        assert blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.is_cuda
-        out = torch.empty(self._L.ur_texture_transcode_bytes(int(width), int(height), int(mips)) // 4, dtype=torch.int32, device=blocks.device)
+        with tensors.on_stream(self):
+            blocks = tensors.device_bytes(data_or_tensor, need, self.device,
+                                          lambda have: f"a {width} x {height} chain of {mips} mips in format {format} is {need} bytes, the payload has {have}")
+            assert blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.is_cuda
+            out = torch.empty(self._L.ur_texture_transcode_bytes(int(width), int(height), int(mips)) // 4, dtype=torch.int32, device=blocks.device)
         desc = _lib.Texture2D()
         _lib.check(self._L.ur_texture_transcode(self._ctx, int(format), blocks.data_ptr(), int(width), int(height), int(mips), out.data_ptr(), C.byref(desc)),
                    "ur_texture_transcode")
@@ -112,14 +113,15 @@ class AssetBuilds:
             buffer = tensors.host_bytes(buffer)
         size = buffer.numel() if tensor else buffer.size
         layout, sections = hostmath.mesh_layout(primitives, size)  # (its own refusals, not a size to compare: before anything is uploaded)
-        if not tensor:
-            buffer = tensors.to_device(buffer.copy(), self.device)
-        assert buffer.is_cuda
-        vertices = torch.empty((layout.vertex_count, 16), dtype=torch.int32, device=buffer.device)
-        indices = torch.empty(layout.index_count, dtype=torch.int32, device=buffer.device)
-        info = torch.empty(C.sizeof(_lib.MeshInfo) // 4, dtype=torch.int32, device=buffer.device)
-        if scratch is None:
-            scratch = torch.empty(int(layout.scratch_bytes), dtype=torch.uint8, device=buffer.device)
+        with tensors.on_stream(self):
+            if not tensor:
+                buffer = tensors.to_device(buffer.copy(), self.device)
+            assert buffer.is_cuda
+            vertices = torch.empty((layout.vertex_count, 16), dtype=torch.int32, device=buffer.device)
+            indices = torch.empty(layout.index_count, dtype=torch.int32, device=buffer.device)
+            info = torch.empty(C.sizeof(_lib.MeshInfo) // 4, dtype=torch.int32, device=buffer.device)
+            if scratch is None:
+                scratch = torch.empty(int(layout.scratch_bytes), dtype=torch.uint8, device=buffer.device)
         assert scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= layout.scratch_bytes
         _lib.check(self._L.ur_mesh_build(self._ctx, buffer.data_ptr(), size, hostmath.mesh_primitive_array(primitives), len(primitives), vertices.data_ptr(),
                                          indices.data_ptr(), scratch.data_ptr(), scratch.numel(), info.data_ptr()), "ur_mesh_build")
@@ -140,10 +142,11 @@ class AssetBuilds:
             need = int(self._L.ur_scene_build_scratch_bytes(D))
             if need == 0:
                 raise ValueError(f"build_scene: {D} draws (1 .. 2^24 - 1)")
-            out = BuiltScene(torch.empty((D, 2, 4), dtype=torch.float32, device=dev), torch.empty((D, 16), dtype=torch.int32, device=dev),
-                             torch.zeros((tables.slot_count, tables.constants_stride), dtype=torch.uint8, device=dev),
-                             torch.empty((D, 4), dtype=torch.float32, device=dev), torch.empty(12, dtype=torch.int32, device=dev),
-                             torch.empty(need, dtype=torch.uint8, device=dev))
+            with tensors.on_stream(self):  # (the fill of the constants is queued in front of the build that writes into them)
+                out = BuiltScene(torch.empty((D, 2, 4), dtype=torch.float32, device=dev), torch.empty((D, 16), dtype=torch.int32, device=dev),
+                                 torch.zeros((tables.slot_count, tables.constants_stride), dtype=torch.uint8, device=dev),
+                                 torch.empty((D, 4), dtype=torch.float32, device=dev), torch.empty(12, dtype=torch.int32, device=dev),
+                                 torch.empty(need, dtype=torch.uint8, device=dev))
         assert nbytes(out.constants) >= tables.slot_count * tables.constants_stride and nbytes(out.bounds) >= 32 * D
         assert nbytes(out.commands) >= 64 * D and (out.centers is None or nbytes(out.centers) >= 16 * D)
         outputs = _lib.SceneBuildOutputs(out.bounds.data_ptr(), out.commands.data_ptr(), out.constants.data_ptr(), out.centers.data_ptr() if out.centers is not None else None,
@@ -164,9 +167,10 @@ class AssetBuilds:
         texels = int(self._L.ur_env_cube_texels(int(base), int(mips)))
         if need == 0 or texels == 0:
             raise ValueError(f"no cube source: format {format}, base size {base}, {mips} mips (10, 95, 96; mips 1..16)")
-        src = tensors.device_bytes(payload, need, self.device,
-                                   lambda have: f"a cube of base size {base} with {mips} mips in format {format} is {need} bytes, the payload has {have}")
-        dst = out if out is not None else torch.empty((texels, 4), dtype=torch.int16, device=src.device)
+        with tensors.on_stream(self):
+            src = tensors.device_bytes(payload, need, self.device,
+                                       lambda have: f"a cube of base size {base} with {mips} mips in format {format} is {need} bytes, the payload has {have}")
+            dst = out if out is not None else torch.empty((texels, 4), dtype=torch.int16, device=src.device)
         if nbytes(dst) != 8 * texels:
             raise ValueError(f"a staged cube of base size {base} with {mips} mips is {8 * texels} bytes, out has {nbytes(dst)}")
         _lib.check(self._L.ur_env_cube_build(self._ctx, _ptr(src), need, int(format), int(base), int(mips), _ptr(dst), texels, _ptr(info)), "ur_env_cube_build")
@@ -185,12 +189,13 @@ class AssetBuilds:
             raise ValueError(f"no prefilter: base size {base}, {samples} samples (powers of two, 1..2048 and 16..4096)")
         need, mips = 48 * base * base, base.bit_length()
         dst_bytes, scratch_bytes = int(self._L.ur_env_cube_source_bytes(_lib.UR_ENV_SOURCE_RGBA16F, base, mips)), int(self._L.ur_env_prefilter_scratch_bytes(base))
-        src = tensors.device_bytes(src, need, self.device, lambda have: f"the top level of a cube of base size {base} is {need} bytes, the source has {have}",
-                                   reinterpret=True)
-        if table is None:
-            table = tensors.to_device(hostmath.env_prefilter_table(base, samples).copy(), self.device)
-        dst = out if out is not None else torch.empty((dst_bytes // 8, 4), dtype=torch.int16, device=src.device)
-        scratch = scratch if scratch is not None else torch.empty(scratch_bytes, dtype=torch.uint8, device=src.device)
+        with tensors.on_stream(self):
+            src = tensors.device_bytes(src, need, self.device, lambda have: f"the top level of a cube of base size {base} is {need} bytes, the source has {have}",
+                                       reinterpret=True)
+            if table is None:
+                table = tensors.to_device(hostmath.env_prefilter_table(base, samples).copy(), self.device)
+            dst = out if out is not None else torch.empty((dst_bytes // 8, 4), dtype=torch.int16, device=src.device)
+            scratch = scratch if scratch is not None else torch.empty(scratch_bytes, dtype=torch.uint8, device=src.device)
         _lib.check(self._L.ur_env_prefilter(self._ctx, _ptr(src), need, base, samples, _ptr(table), nbytes(table), _ptr(dst), nbytes(dst), _ptr(scratch), nbytes(scratch)),
                    "ur_env_prefilter")
         dst._keep = (src, table, scratch)  # (the launches are still in flight)

@@ -160,7 +160,8 @@ class Context:
         cptr = constants.ctypes.data_as(C.POINTER(C.c_uint32))
         mips = layout.mips if layout is not None else None
         n = int(constants[40])
-        arr = cull_views_array([v if isinstance(v, _lib.CullView) else cull_view(command_count=n, **v) for v in views]) if views else None
+        with tensors.on_stream(self):  # (a view's host draw offsets are uploaded by cull_view)
+            arr = cull_views_array([v if isinstance(v, _lib.CullView) else cull_view(command_count=n, **v) for v in views]) if views else None
         dr = None
         if draw_offsets is not None or draw_commands is not None or draw_counts is not None:
             if draw_offsets is None or draw_commands is None or draw_counts is None:
@@ -177,7 +178,8 @@ class Context:
     def draw_offsets_to_device(self, offsets, command_count: int) -> torch.Tensor:
         """Check the precondition of ur_draw_ranges.offsets on the host array (offsets[0] == 0, non-decreasing, last == command_count,
         at least one range), then upload it (uint32)."""
-        return tensors.to_device(check_draw_offsets(offsets, command_count), self.device)
+        with tensors.on_stream(self):
+            return tensors.to_device(check_draw_offsets(offsets, command_count), self.device)
 
     # ---- lighting tables ----
     def stage_env_cube(self, cube_dds_order: np.ndarray, base: int, mips: int) -> torch.Tensor:
@@ -187,7 +189,8 @@ class Context:
             raise ValueError("bad cube size")
         expect = 6 * sum(max(1, base >> m) ** 2 for m in range(mips))
         assert src.size == expect * 4, f"cube has {src.size // 4} texels, expected {expect}"
-        dst = torch.empty((n, 4), dtype=torch.int16, device=f"cuda:{self.device}")
+        with tensors.on_stream(self):
+            dst = torch.empty((n, 4), dtype=torch.int16, device=f"cuda:{self.device}")
         _lib.check(self._L.ur_stage_env_cube(self._ctx, src.ctypes.data_as(C.c_void_p), base, mips, _ptr(dst)), "ur_stage_env_cube")
         return dst
 

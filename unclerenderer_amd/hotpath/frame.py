@@ -9,6 +9,7 @@ import torch
 from .. import lib as _lib
 from .context import HzbLayout, _host_draw_offsets, cull_view, cull_views_array, draw_ranges
 from .raster import raster_draws
+from . import tensors
 from .tensors import _ptr
 
 
@@ -133,7 +134,8 @@ class Frame:
         if offsets is None or commands is None or counts is None:
             raise ValueError("offsets, commands and counts go together")
         if not isinstance(offsets, torch.Tensor):
-            offsets = _host_draw_offsets(offsets, command_count)
+            with tensors.on_stream(self._hp):
+                offsets = _host_draw_offsets(offsets, command_count)
         dr = draw_ranges(offsets, commands, counts)
         self._draws_keep = dr
         _lib.check(self._L.ur_frame_set_draw_ranges(self._f, C.byref(dr)), "ur_frame_set_draw_ranges")
@@ -141,7 +143,8 @@ class Frame:
     def set_cull_views(self, views=()):
         """ur_frame_set_cull_views: the "GPU Culling" pass of the frames rendered with UR_FRAME_CULL_VIEWS also culls these views
         (cull_view(...) results or dicts of its arguments; kept alive here). No views: clear."""
-        views = [v if isinstance(v, _lib.CullView) else cull_view(**v) for v in views]
+        with tensors.on_stream(self._hp):  # (a view's host draw offsets are uploaded by cull_view)
+            views = [v if isinstance(v, _lib.CullView) else cull_view(**v) for v in views]
         arr = cull_views_array(views) if views else None
         self._views_keep = arr
         _lib.check(self._L.ur_frame_set_cull_views(self._f, arr, len(views)), "ur_frame_set_cull_views")

@@ -252,8 +252,9 @@ class RasterPasses:
         rows = h - row0 if rows is None else rows
         assert depth.dtype == torch.float32 and depth.numel() >= w * h
         d = draws if isinstance(draws, _lib.RasterDraws) else raster_draws(draws)
-        object_id = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if object_id is None else object_id
-        keys = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if keys is None else keys
+        with tensors.on_stream(self):
+            object_id = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if object_id is None else object_id
+            keys = torch.empty((rows, w), dtype=torch.int32, device=depth.device) if keys is None else keys
         for t in (object_id, keys):
             assert t.dtype == torch.int32 and t.numel() >= w * rows
         v, p = _matrix16(view), _matrix16(projection)
@@ -269,7 +270,8 @@ class RasterPasses:
         n = int(pts.shape[0])
         assert depth.dtype == torch.float32 and depth.numel() >= w * h
         d = draws if isinstance(draws, _lib.RasterDraws) else raster_draws(draws)
-        results = torch.empty((n, 4), dtype=torch.int32, device=depth.device) if results is None else results
+        with tensors.on_stream(self):
+            results = torch.empty((n, 4), dtype=torch.int32, device=depth.device) if results is None else results
         assert results.dtype == torch.int32 and results.numel() >= 4 * n
         v, p = _matrix16(view), _matrix16(projection)
         _lib.check(self._L.ur_object_id_pick(self._ctx, _lib.fptr(v), _lib.fptr(p), C.byref(d), _ptr(depth), w, h, int(flags), int(key_triangle_bits),

@@ -1,6 +1,7 @@
 """The torch plumbing of the binding: addresses, sizes, host <-> device copies and the one path from a caller's payload to a device tensor."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -19,6 +20,17 @@ def _ptr(t):
 def nbytes(t) -> int:
     """Bytes of a tensor's elements."""
     return t.numel() * t.element_size()
+
+
+def on_stream(hp):
+    """`with on_stream(hp):` around the torch work a wrapper does on the caller's behalf - allocations, fills, uploads - so that it is
+    queued on the context's stream like the launches that use it, whatever torch's current stream is; and torch's allocator, which hands a
+    freed block out again in the order of the stream it was allocated on, then orders the reuse of a dropped scratch buffer behind the
+    launches still in flight. Nothing changes where the context's stream is the current one, or for a stand-in context without a stream."""
+    stream = getattr(hp, "stream", None)
+    if stream is None or stream == torch.cuda.current_stream(stream.device):
+        return contextlib.nullcontext()
+    return torch.cuda.stream(stream)
 
 
 def to_device(a: np.ndarray, device=0) -> torch.Tensor:
